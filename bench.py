@@ -1,6 +1,6 @@
 """bench.py -- Mfrag/s and frames/s of the rasterisation hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,9 +13,8 @@ the diablo configs.
 A frame is the whole hot path: per-frame constants in, vertex transform, face set-up, silhouette
 + shadow-quad set-up, binning, tile visibility (coverage, z, stencil), deferred shading and
 finalise to uint8, with the scene already resident in HBM and the frame left in HBM
-(``mr_render_device``).  A STEP is a batch of frames -- at least ``--frames-per-step`` (default 256), and as
-many as it takes for the K timed steps to last 3 s at the rate of a short calibration run (``frames_per_step``
-in the line says how many) -- so the timed region does not depend on --steps; successive frames use DIFFERENT per-frame
+(``mr_render_device``).  A STEP is a batch of ``--frames-per-step`` frames (default 256): W steps of
+warm-up, then K timed steps (``ms_per_step`` is one of them); successive frames use DIFFERENT per-frame
 constants (the camera swings through 8 slightly different views), and ``--frames-in-flight``
 (default 3) of them are in flight on separate HIP streams.  With N > 1 every rank renders its share
 of the screen tiles (contiguous row bands of equal modelled cost by default, ``--partition stripes`` for
@@ -23,7 +22,11 @@ interleaved tile rows, ``--partition bands`` for equal row bands) and ONE RCCL a
 
 value = reference-equivalent fragments per frame (2 x triangle fragments + shadow-quad fragments:
 the reference rasterises every triangle in two passes) / time, summed over the views.
-The same line also carries the other regimes: one frame at a time (``latency_ms_single``,
+
+A plain run measures only that.  ``--dump-outputs DIR`` then writes the last timed frame (what a caller of the
+timed path receives) as float32 ``.npy`` files.  With ``--full`` the run also checks the last frame against a
+single-device render and the line also carries per-kernel times, the roofline, the CPU baseline (the C oracle;
+``--no-cpu-baseline`` leaves it out) and the other regimes: one frame at a time (``latency_ms_single``,
 ``value_single_frame``), with the fragment counters on (``value_counters_on``: no depth cull of
 shadow quads) and the host-visible ``Scene.render()`` (``scene_render_ms_host``: packing, per-frame
 upload, render, device->host copy into a NumPy array; the camera is a NEW object on every call, as when it moves,
@@ -46,8 +49,8 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E peak 8 TB/s (spec)
 N_VIEWS = 8
-TIMED_SECONDS = 3.0          # the K timed steps together last at least this long
 N_SIMDS = 1024               # 256 CUs x 4 SIMDs
+DUMP_BYTES = 64 * 10 ** 6    # --dump-outputs writes at most this much in all
 
 
 def valu_roofline(config, launch_ms, solo_ms):
@@ -152,6 +155,23 @@ def swing_cameras(api, scene, n_views, offset=0):
     return pairs
 
 
+def dump_outputs(out_dir, frame):
+    """The last timed frame, as a caller of the timed path receives it (uint8, H x W x 3), written as float32:
+    ``frame.npy``.  A frame larger than DUMP_BYTES (c5, 3840x2160) is written as a fixed, seeded sample of its
+    pixels instead: ``frame_sample.npy`` (n x 3) and their flat pixel indices ``frame_sample_pixels.npy``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.cpu().numpy().astype(np.float32)
+    if img.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), img)
+        return
+    h, w, c = img.shape
+    n = (DUMP_BYTES - 4096) // (c * 4 + 8)           # 4 KB for the two files' headers
+    pixels = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), img.reshape(h * w, c)[pixels])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), pixels.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -165,7 +185,13 @@ def main():
                     help="successive frames rendered on this many HIP streams (1 = one frame at a time)")
     ap.add_argument("--partition", choices=("stripes", "bands", "weighted"), default="weighted",
                     help="screen-tile split for --gpus > 1: interleaved tile rows, contiguous row bands, or bands of equal cost")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the last frame against a single-device render and measure the other regimes, "
+                         "per-kernel times, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame to DIR as float32 .npy files")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -241,14 +267,15 @@ def main():
         frags_view.append(2 * st["frag_tri"] + st["frag_quad"])
         unique_view.append(st["frag_tri"] + st["frag_quad"])
     scene.camera, scene.debug_camera = base_cameras
-    backend.render(scene, shadows=shadows)
-    full = dict(backend.last_stats)                                  # the base view = BASELINE.md's frame
-    frags_base = 2 * full["frag_tri"] + full["frag_quad"]
-    # this rank's share of the base view, counted (for the roofline's algorithmic bytes)
-    backend.render(scene, shadows=shadows, row_band=br.band if br.stripe is None else None, stripe=br.stripe)
-    part_stats = dict(backend.last_stats)
-    part_px = W * (br.band[1] - br.band[0]) if br.stripe is None else sum(
-        W * min(16, H - 16 * g) for g in range(-(-H // 16)) if g % world == rank)
+    if args.full:
+        backend.render(scene, shadows=shadows)
+        full = dict(backend.last_stats)                              # the base view = BASELINE.md's frame
+        frags_base = 2 * full["frag_tri"] + full["frag_quad"]
+        # this rank's share of the base view, counted (for the roofline's algorithmic bytes)
+        backend.render(scene, shadows=shadows, row_band=br.band if br.stripe is None else None, stripe=br.stripe)
+        part_stats = dict(backend.last_stats)
+        part_px = W * (br.band[1] - br.band[0]) if br.stripe is None else sum(
+            W * min(16, H - 16 * g) for g in range(-(-H // 16)) if g % world == rank)
 
     br.set_descriptors(descriptors(False, not args.all_marks))
     fps = max(1, args.frames_per_step)
@@ -261,19 +288,6 @@ def main():
     if not br.verify():                  # a work list overflowed during warm-up: it has been grown, warm up again
         run(br, args.warmup * fps)
         assert br.verify(), "work lists kept overflowing"
-    # A step is a batch of frames, sized so that the K timed steps last at least ~3 s whatever the config and
-    # however fast a frame has become (long enough for an outside observer sampling the device once a second to
-    # land inside the timed region): the rate of a short calibration run (untimed as far as the result goes)
-    # decides, the same on every rank.
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    run(br, 256)
-    torch.cuda.synchronize()
-    est = torch.tensor([(time.perf_counter() - t0) / 256], dtype=torch.float64, device="cuda")
-    if world > 1:
-        dist.all_reduce(est, op=dist.ReduceOp.MAX)
-    need = int(TIMED_SECONDS / (max(args.steps, 1) * max(float(est.item()), 1e-6))) + 1
-    fps = max(fps, -(-need // 8) * 8)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -291,123 +305,114 @@ def main():
         elapsed = float(t.item())
     n_frames = args.steps * fps
     assert br.verify(), "a work list overflowed in the timed frames"
-    ktimes, n_avg = br.kernel_times(2048)            # every marked frame still in the streams' event rings (~40 each)
-    last_frame = br.frame
-
-    # the frame every rank now holds must be the frame a single device renders for that view
-    view_of_last = (br.count - 1) % N_VIEWS
-    if rank == 0:
-        scene.camera, scene.debug_camera = views[view_of_last]
-        want = backend.render(scene, shadows=shadows)
-        scene.camera, scene.debug_camera = base_cameras
-        assert np.array_equal(last_frame.cpu().numpy(), want), "assembled frame differs from the single-device frame"
+    if args.full:
+        ktimes, n_avg = br.kernel_times(2048)            # every marked frame still in the streams' event rings (~40 each)
+    if args.dump_outputs and rank == 0:     # every rank holds the same assembled frame
+        dump_outputs(args.dump_outputs, br.frame)
     total_frags = sum(frags_view[i % N_VIEWS] for i in range(n_frames))
     total_unique = sum(unique_view[i % N_VIEWS] for i in range(n_frames))
 
-    # ---- the other regimes, outside the timed region (fewer frames each)
-    def timed(brx, n):
-        run(brx, max(8, n // 8))
-        brx.synchronize()
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t0 = time.perf_counter()
-        run(brx, n)
-        brx.synchronize()
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        return (time.perf_counter() - t0) / n
+    if args.full:
+        last_frame = br.frame
 
-    n_side = max(64, min(n_frames // 4, 1024))
-    solo = renderer(1, False)                                        # one frame at a time, every stage marked
-    solo.set_descriptors(descriptors(False, False))
-    per_frame_solo = timed(solo, n_side)
-    ktimes_solo, _ = solo.kernel_times(64)
-    counted = renderer(args.frames_in_flight, True)                  # fragment counters on: no depth cull of quads
-    counted.set_descriptors(descriptors(True, True))
-    per_frame_counted = timed(counted, n_side)
-
-    host_ms = host_overlay_ms = host_same_ms = host_overlay_same_ms = pipe_ms = pipe_overlay_ms = None
-    protocol_ms = protocol_copy_ms = None
-    if rank == 0 and world == 1:
-        # the drop-in call as a user makes it: Scene.render() returning the uint8 ndarray (packing of the
-        # per-frame constants, upload, the three kernels, device->host copy into page-locked memory), first
-        # the way the hot path is defined (debug-frustum overlay off, like the parity captures), then with
-        # upstream's default (overlay on: obj/core.py:638)
-        scene.camera, scene.debug_camera = base_cameras
-
-        def host_median(moving, n=15):
-            # moving: new Camera objects for every call, as in a sequence whose camera moves -- nothing the host
-            # derives from the cameras (matrices, planes, the overlay's line lists) can come from a cache
-            def step(k):
-                if moving:
-                    scene.camera, scene.debug_camera = swing_cameras(api, scene_base, 1, offset=k)[0]
-                return scene.render(shadows=shadows)
-            for k in range(3):
-                step(1000 + k)
-            samples = []
-            for k in range(n):
-                if moving:
-                    scene.camera, scene.debug_camera = base_cameras
-                t0 = time.perf_counter()
-                step(k + 1)
-                samples.append(time.perf_counter() - t0)
+        # the frame every rank now holds must be the frame a single device renders for that view
+        view_of_last = (br.count - 1) % N_VIEWS
+        if rank == 0:
+            scene.camera, scene.debug_camera = views[view_of_last]
+            want = backend.render(scene, shadows=shadows)
             scene.camera, scene.debug_camera = base_cameras
-            return sorted(samples)[len(samples) // 2] * 1e3
+            assert np.array_equal(last_frame.cpu().numpy(), want), "assembled frame differs from the single-device frame"
 
-        def pipelined(n=48, depth=3):
-            # the same frames as a sequence: Scene.render_frames keeps `depth` frames in flight (mr_render_async), so the
-            # host copy of one frame runs beside the kernels of the next and the host's preparation of the one after
-            cams = lambda off: (swing_cameras(api, scene_base, 1, offset=off + k)[0] for k in range(n))
-            for _ in scene.render_frames((swing_cameras(api, scene_base, 1, offset=500 + k)[0] for k in range(6)), shadows=shadows, depth=depth):
-                pass
+        # ---- the other regimes, outside the timed region (fewer frames each)
+        def timed(brx, n):
+            run(brx, max(8, n // 8))
+            brx.synchronize()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
             t0 = time.perf_counter()
-            for _ in scene.render_frames(cams(0), shadows=shadows, depth=depth):
-                pass
-            dt = (time.perf_counter() - t0) / n
-            scene.camera, scene.debug_camera = base_cameras
-            return dt * 1e3
+            run(brx, n)
+            brx.synchronize()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            return (time.perf_counter() - t0) / n
 
-        scene_base = scene
-        scene.draw_debug_frustum = False
-        host_ms = host_median(True)
-        host_same_ms = host_median(False)
-        pipe_ms = pipelined()
-        scene.draw_debug_frustum = True
-        host_overlay_ms = host_median(True)
-        host_overlay_same_ms = host_median(False)
-        pipe_overlay_ms = pipelined()
-        scene.draw_debug_frustum = False
-        # SURVEY 8(d)'s protocol: one frame at a time, HIP events around the whole device section of mr_render
-        # (per-frame constants, the three kernels, the copy of the uint8 frame into page-locked host memory), median
-        spans = []
-        for k in range(40):
-            scene.camera, scene.debug_camera = swing_cameras(api, scene_base, 1, offset=k)[0]
-            backend.render(scene, shadows=shadows, counters=False, keep_buffers=False, timing=True)
-            st = backend.stats()
-            if k >= 8:
-                spans.append((st["gpu_ms_total"], st["gpu_ms_copy"]))
-        scene.camera, scene.debug_camera = base_cameras
-        spans.sort()
-        protocol_ms, protocol_copy_ms = spans[len(spans) // 2]
+        n_side = max(64, min(n_frames // 4, 1024))
+        solo = renderer(1, False)                                        # one frame at a time, every stage marked
+        solo.set_descriptors(descriptors(False, False))
+        per_frame_solo = timed(solo, n_side)
+        ktimes_solo, _ = solo.kernel_times(64)
+        counted = renderer(args.frames_in_flight, True)                  # fragment counters on: no depth cull of quads
+        counted.set_descriptors(descriptors(True, True))
+        per_frame_counted = timed(counted, n_side)
+
+        host_ms = host_overlay_ms = host_same_ms = host_overlay_same_ms = pipe_ms = pipe_overlay_ms = None
+        protocol_ms = protocol_copy_ms = None
+        if rank == 0 and world == 1:
+            # the drop-in call as a user makes it: Scene.render() returning the uint8 ndarray (packing of the
+            # per-frame constants, upload, the three kernels, device->host copy into page-locked memory), first
+            # the way the hot path is defined (debug-frustum overlay off, like the parity captures), then with
+            # upstream's default (overlay on: obj/core.py:638)
+            scene.camera, scene.debug_camera = base_cameras
+
+            def host_median(moving, n=15):
+                # moving: new Camera objects for every call, as in a sequence whose camera moves -- nothing the host
+                # derives from the cameras (matrices, planes, the overlay's line lists) can come from a cache
+                def step(k):
+                    if moving:
+                        scene.camera, scene.debug_camera = swing_cameras(api, scene_base, 1, offset=k)[0]
+                    return scene.render(shadows=shadows)
+                for k in range(3):
+                    step(1000 + k)
+                samples = []
+                for k in range(n):
+                    if moving:
+                        scene.camera, scene.debug_camera = base_cameras
+                    t0 = time.perf_counter()
+                    step(k + 1)
+                    samples.append(time.perf_counter() - t0)
+                scene.camera, scene.debug_camera = base_cameras
+                return sorted(samples)[len(samples) // 2] * 1e3
+
+            def pipelined(n=48, depth=3):
+                # the same frames as a sequence: Scene.render_frames keeps `depth` frames in flight (mr_render_async), so the
+                # host copy of one frame runs beside the kernels of the next and the host's preparation of the one after
+                cams = lambda off: (swing_cameras(api, scene_base, 1, offset=off + k)[0] for k in range(n))
+                for _ in scene.render_frames((swing_cameras(api, scene_base, 1, offset=500 + k)[0] for k in range(6)), shadows=shadows, depth=depth):
+                    pass
+                t0 = time.perf_counter()
+                for _ in scene.render_frames(cams(0), shadows=shadows, depth=depth):
+                    pass
+                dt = (time.perf_counter() - t0) / n
+                scene.camera, scene.debug_camera = base_cameras
+                return dt * 1e3
+
+            scene_base = scene
+            scene.draw_debug_frustum = False
+            host_ms = host_median(True)
+            host_same_ms = host_median(False)
+            pipe_ms = pipelined()
+            scene.draw_debug_frustum = True
+            host_overlay_ms = host_median(True)
+            host_overlay_same_ms = host_median(False)
+            pipe_overlay_ms = pipelined()
+            scene.draw_debug_frustum = False
+            # SURVEY 8(d)'s protocol: one frame at a time, HIP events around the whole device section of mr_render
+            # (per-frame constants, the three kernels, the copy of the uint8 frame into page-locked host memory), median
+            spans = []
+            for k in range(40):
+                scene.camera, scene.debug_camera = swing_cameras(api, scene_base, 1, offset=k)[0]
+                backend.render(scene, shadows=shadows, counters=False, keep_buffers=False, timing=True)
+                st = backend.stats()
+                if k >= 8:
+                    spans.append((st["gpu_ms_total"], st["gpu_ms_copy"]))
+            scene.camera, scene.debug_camera = base_cameras
+            spans.sort()
+            protocol_ms, protocol_copy_ms = spans[len(spans) // 2]
 
     if rank == 0:
         per_frame = elapsed / n_frames
-        alg_full = algorithmic_bytes(full, W * H, n_faces, skybox)
-        alg = algorithmic_bytes(part_stats, part_px, n_faces, skybox)
-        # k_tile does the reference's three loops (coverage + z, stencil, shading + finalise); the
-        # per-primitive attribute reads belong to k_setup
-        tile_alg = alg["visibility"] + alg["shading"]
-        k_ms = ktimes["tile"]
-        achieved = tile_alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "r03_traffic.json")
-        if not os.path.exists(tpath):
-            tpath = os.path.join(ROOT, "profiles", "r02_traffic.json")
-        if os.path.exists(tpath):
-            with open(tpath) as fh:
-                traffic = json.load(fh).get(args.config, {}).get("k_tile")
         mean_frags = total_frags / n_frames
         line = {
             "metric": "Mfrag/s (1920x1080, 200k tris + shadow volumes)" if args.config == "c4"
@@ -425,58 +430,76 @@ def main():
             "data": "synthetic",
             "config": {"workload": label, "name": args.config, "frames_per_step": fps, "timed_frames": n_frames,
                        "timed_seconds": round(elapsed, 4),
-                       "fragments_per_frame": frags_base, "fragments_per_frame_mean_over_views": round(mean_frags, 1),
-                       "unique_fragments_per_frame": full["frag_tri"] + full["frag_quad"],
+                       "fragments_per_frame_mean_over_views": round(mean_frags, 1),
                        "faces": n_faces, "views": N_VIEWS, "frames_in_flight": args.frames_in_flight,
                        "regime": "frames of a camera swing (8 views, 0.05 deg apart), per-frame constants new each frame, "
                                  "frame left in HBM, fragment counters off",
                        "parallelism": (f"screen tiles x{world} ({partition})" + (" + 1 RCCL all-gather" if world > 1 else ""))},
             "mfrag_unique_per_s": round(total_unique / elapsed / 1e6, 2),
-            "latency_ms_single": round(per_frame_solo * 1e3, 5),
-            "latency_ms_single_device": round(ktimes_solo["frame"], 5),
-            "value_single_frame": round(mean_frags / per_frame_solo / 1e6, 2),
-            "value_counters_on": round(mean_frags / per_frame_counted / 1e6, 2),
-            "scene_render_ms_host": None if host_ms is None else round(host_ms, 4),
-            "value_scene_render_host": None if host_ms is None else round(frags_base / host_ms / 1e3, 2),
-            "scene_render_ms_host_with_overlay": None if host_overlay_ms is None else round(host_overlay_ms, 4),
-            "scene_render_ms_host_same_camera": None if host_same_ms is None else round(host_same_ms, 4),
-            "scene_render_ms_host_with_overlay_same_camera": None if host_overlay_same_ms is None else round(host_overlay_same_ms, 4),
-            "scene_render_ms_pipelined": None if pipe_ms is None else round(pipe_ms, 4),
-            "scene_render_ms_pipelined_with_overlay": None if pipe_overlay_ms is None else round(pipe_overlay_ms, 4),
-            "value_protocol": None if not protocol_ms else round(frags_base / protocol_ms / 1e3, 2),
-            "protocol": None if not protocol_ms else {
-                "what": "SURVEY 8(d): one frame at a time, HIP events around mr_render's device section (three kernels + the "
-                        "copy of the uint8 frame into page-locked host memory), median of 32 frames of a moving camera",
-                "ms_per_frame": round(protocol_ms, 5), "ms_copy": round(protocol_copy_ms, 5),
-                "frames_per_s": round(1e3 / protocol_ms, 1)},
-            "reference_numpy_mfrag_s": REFERENCE_MFRAGS[args.config],
-            # unless --all-marks, the timed region marks only frame start / tile start / tile end (a mark costs ~5 us
-            # between two kernels) and the library files the span ahead of k_tile under its third slot
-            "gpu_ms_per_kernel": ({k: round(v, 5) for k, v in ktimes.items()} if args.all_marks else
-                                  {"setup_and_bin_work": round(ktimes["bin_work"], 5), "tile": round(ktimes["tile"], 5),
-                                   "frame": round(ktimes["frame"], 5)}),
-            "gpu_ms_per_kernel_solo": {k: round(v, 5) for k, v in ktimes_solo.items()},
-            "frame_algorithmic_gb": round(alg_full["total"] / 1e9, 4),
-            "frame_hbm_frac": round(alg_full["total"] / per_frame / 1e9 / HBM_PEAK_GBS, 5),
-            "frame_hbm_frac_single": round(alg_full["total"] / per_frame_solo / 1e9 / HBM_PEAK_GBS, 5),
-            "roofline": {"bound": "hbm", "kernel": "k_tile", "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "algorithmic_bytes_per_launch": int(tile_alg),
-                         "avg_launch_ms": round(k_ms, 5), "launches_averaged": n_avg,
-                         "frames_in_flight": args.frames_in_flight,
-                         "note": "avg_launch_ms is the HIP-event span of k_tile in the timed region, where it shares the "
-                                 "device with the kernels of the other frames in flight; solo_* is the same kernel with one "
-                                 "frame at a time, right after the timed region.  The kernel's arithmetic is float64 on the "
-                                 "vector pipe (the reference's dtype); DESIGN.md section 5 has its VALU-side bound next to this one",
-                         "solo_launch_ms": round(ktimes_solo["tile"], 5),
-                         "solo_achieved": round(tile_alg / (ktimes_solo["tile"] * 1e-3) / 1e9, 2),
-                         "solo_frac": round(tile_alg / (ktimes_solo["tile"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
-            "roofline_valu": valu_roofline(args.config, k_ms, ktimes_solo["tile"]),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            scene.camera, scene.debug_camera = base_cameras
-            line["cpu_baseline"] = cpu_baseline(scene, frags_base, args.config,
-                                                budget_s=25.0 if args.config == "c5" else 12.0)
+        if args.full:
+            alg_full = algorithmic_bytes(full, W * H, n_faces, skybox)
+            alg = algorithmic_bytes(part_stats, part_px, n_faces, skybox)
+            # k_tile does the reference's three loops (coverage + z, stencil, shading + finalise); the
+            # per-primitive attribute reads belong to k_setup
+            tile_alg = alg["visibility"] + alg["shading"]
+            k_ms = ktimes["tile"]
+            achieved = tile_alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "r03_traffic.json")
+            if not os.path.exists(tpath):
+                tpath = os.path.join(ROOT, "profiles", "r02_traffic.json")
+            if os.path.exists(tpath):
+                with open(tpath) as fh:
+                    traffic = json.load(fh).get(args.config, {}).get("k_tile")
+            line["config"].update(fragments_per_frame=frags_base,
+                                  unique_fragments_per_frame=full["frag_tri"] + full["frag_quad"])
+            line.update({
+                "latency_ms_single": round(per_frame_solo * 1e3, 5),
+                "latency_ms_single_device": round(ktimes_solo["frame"], 5),
+                "value_single_frame": round(mean_frags / per_frame_solo / 1e6, 2),
+                "value_counters_on": round(mean_frags / per_frame_counted / 1e6, 2),
+                "scene_render_ms_host": None if host_ms is None else round(host_ms, 4),
+                "value_scene_render_host": None if host_ms is None else round(frags_base / host_ms / 1e3, 2),
+                "scene_render_ms_host_with_overlay": None if host_overlay_ms is None else round(host_overlay_ms, 4),
+                "scene_render_ms_host_same_camera": None if host_same_ms is None else round(host_same_ms, 4),
+                "scene_render_ms_host_with_overlay_same_camera": None if host_overlay_same_ms is None else round(host_overlay_same_ms, 4),
+                "scene_render_ms_pipelined": None if pipe_ms is None else round(pipe_ms, 4),
+                "scene_render_ms_pipelined_with_overlay": None if pipe_overlay_ms is None else round(pipe_overlay_ms, 4),
+                "value_protocol": None if not protocol_ms else round(frags_base / protocol_ms / 1e3, 2),
+                "protocol": None if not protocol_ms else {
+                    "what": "SURVEY 8(d): one frame at a time, HIP events around mr_render's device section (three kernels + the "
+                            "copy of the uint8 frame into page-locked host memory), median of 32 frames of a moving camera",
+                    "ms_per_frame": round(protocol_ms, 5), "ms_copy": round(protocol_copy_ms, 5),
+                    "frames_per_s": round(1e3 / protocol_ms, 1)},
+                "reference_numpy_mfrag_s": REFERENCE_MFRAGS[args.config],
+                # unless --all-marks, the timed region marks only frame start / tile start / tile end (a mark costs ~5 us
+                # between two kernels) and the library files the span ahead of k_tile under its third slot
+                "gpu_ms_per_kernel": ({k: round(v, 5) for k, v in ktimes.items()} if args.all_marks else
+                                      {"setup_and_bin_work": round(ktimes["bin_work"], 5), "tile": round(ktimes["tile"], 5),
+                                       "frame": round(ktimes["frame"], 5)}),
+                "gpu_ms_per_kernel_solo": {k: round(v, 5) for k, v in ktimes_solo.items()},
+                "frame_algorithmic_gb": round(alg_full["total"] / 1e9, 4),
+                "frame_hbm_frac": round(alg_full["total"] / per_frame / 1e9 / HBM_PEAK_GBS, 5),
+                "frame_hbm_frac_single": round(alg_full["total"] / per_frame_solo / 1e9 / HBM_PEAK_GBS, 5),
+                "roofline": {"bound": "hbm", "kernel": "k_tile", "achieved": round(achieved, 2),
+                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                             "traffic": traffic, "algorithmic_bytes_per_launch": int(tile_alg),
+                             "avg_launch_ms": round(k_ms, 5), "launches_averaged": n_avg,
+                             "frames_in_flight": args.frames_in_flight,
+                             "note": "avg_launch_ms is the HIP-event span of k_tile in the timed region, where it shares the "
+                                     "device with the kernels of the other frames in flight; solo_* is the same kernel with one "
+                                     "frame at a time, right after the timed region.  The kernel's arithmetic is float64 on the "
+                                     "vector pipe (the reference's dtype); DESIGN.md section 5 has its VALU-side bound next to this one",
+                             "solo_launch_ms": round(ktimes_solo["tile"], 5),
+                             "solo_achieved": round(tile_alg / (ktimes_solo["tile"] * 1e-3) / 1e9, 2),
+                             "solo_frac": round(tile_alg / (ktimes_solo["tile"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
+                "roofline_valu": valu_roofline(args.config, k_ms, ktimes_solo["tile"]),
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                scene.camera, scene.debug_camera = base_cameras
+                line["cpu_baseline"] = cpu_baseline(scene, frags_base, args.config,
+                                                    budget_s=25.0 if args.config == "c5" else 12.0)
         print(json.dumps(line), flush=True)
 
     if world > 1:

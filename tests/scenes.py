@@ -18,7 +18,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ASSETS = os.path.join(HERE, "assets")
-GENERATED = os.path.join(tempfile.gettempdir(), "mi355rast_generated")
+# meshes written on first use, in a directory of the user's own: the checkout may be read-only, and a
+# directory that another user created under the system temp dir could not be written
+GENERATED = os.path.join(tempfile.gettempdir(), f"mi355rast_generated_{os.getuid()}")
 
 
 def product_api():

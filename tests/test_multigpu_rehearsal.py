@@ -1,7 +1,7 @@
 """The N-rank path of bench.py end to end on ONE GPU (``MR_BENCH_REHEARSE=1``: every rank on device 0, gloo
 instead of RCCL): launch under torch.distributed.run as the driver does, every rank renders its stripes or
 band with the HIP library, the collective assembles the frame, rank 0 compares it with a single-device render
-(an assert inside bench.py) and prints the JSON line.  Rates measured this way mean nothing and are not looked at."""
+(an assert inside bench.py, made with --full) and prints the JSON line.  Rates measured this way mean nothing and are not looked at."""
 import json
 import os
 import subprocess
@@ -19,7 +19,7 @@ def test_bench_multi_rank_path_on_one_gpu(ranks, config, partition):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
            "--master-addr", "127.0.0.1", "--master-port", str(29530 + ranks), os.path.join(ROOT, "bench.py"),
            "--gpus", str(ranks), "--config", config, "--partition", partition, "--steps", "1", "--warmup", "1",
-           "--frames-per-step", "24", "--no-cpu-baseline"]
+           "--frames-per-step", "24", "--no-cpu-baseline", "--full"]
     run = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]

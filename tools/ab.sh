@@ -7,7 +7,7 @@ for flags in "$@"; do
       -o py-numpy-renderer_amd/libmi355rast.so py-numpy-renderer_amd/csrc/mi355rast.hip || exit 1
   for c in ${CFGS:-c4}; do
     for rep in 1 ${REPS:-2}; do
-    timeout -k 10 300 python3 bench.py --config $c --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | FL="$flags" CFG=$c python3 -c "
+    timeout -k 10 300 python3 bench.py --config $c --no-cpu-baseline --full ${BENCH_ARGS} 2>/dev/null | FL="$flags" CFG=$c python3 -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['gpu_ms_per_kernel_solo']

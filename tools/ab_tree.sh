@@ -10,7 +10,7 @@ for dir in "$@"; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 $FLAGS \
       -o py-numpy-renderer_amd/libmi355rast.so $dir/mi355rast.hip || exit 1
   for c in ${CFGS:-c4}; do
-    timeout -k 10 300 python3 bench.py --config $c --no-cpu-baseline ${BENCH_ARGS} 2>/dev/null | DIR="$dir" CFG=$c python3 -c "
+    timeout -k 10 300 python3 bench.py --config $c --no-cpu-baseline --full ${BENCH_ARGS} 2>/dev/null | DIR="$dir" CFG=$c python3 -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['gpu_ms_per_kernel_solo']

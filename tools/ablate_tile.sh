@@ -13,7 +13,7 @@ f = sorted(glob.glob("gpurun_out/pmc/abl*/*/*_kernel_trace.csv"), key=lambda p: 
 d = [float(r["End_Timestamp"]) - float(r["Start_Timestamp"]) for r in csv.DictReader(open(f)) if __import__("os").environ.get("KERNEL", "k_tile") in r["Kernel_Name"]]
 print("kernel us:", [round(x / 1e3, 1) for x in d])
 PY
-  timeout -k 10 300 python3 bench.py --config ${CFG:-c4} --no-cpu-baseline 2>/dev/null | python3 -c "
+  timeout -k 10 300 python3 bench.py --config ${CFG:-c4} --no-cpu-baseline --full 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['gpu_ms_per_kernel_solo']
 print('bench ms/frame', d['ms_per_frame'], 'solo', d['latency_ms_single'], 'solo kernels us', round(k['setup']*1e3,1), round(k['bin_work']*1e3,1), round(k['tile']*1e3,1))"

@@ -4,8 +4,9 @@
 tag=$1; cfg=$2; shift 2
 out=$GRAFT_REPO_ROOT/gpurun_out/prof/$tag
 rm -rf $out; mkdir -p $out
+bench=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $GRAFT_REPO_ROOT/bench.py --config $cfg --no-cpu-baseline "$@" > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 "$bench" --config $cfg --no-cpu-baseline --full "$@" > $out/bench.json 2> $out/bench.err
 python3 - "$out" <<'PY'
 import csv, glob, sys
 f = sorted(glob.glob(sys.argv[1] + '/*/*_kernel_stats.csv'))[-1]

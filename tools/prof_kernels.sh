@@ -5,8 +5,9 @@ tag=${1:-x}; steps=${2:-100}; fif=${3:-1}
 fifarg="--frames-in-flight $fif"; [ "$fif" = 0 ] && fifarg=""
 out=$GRAFT_REPO_ROOT/gpurun_out/prof/$tag
 mkdir -p $out
+bench=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $GRAFT_REPO_ROOT/bench.py --steps $steps --warmup 10 --no-cpu-baseline $fifarg > $out/bench.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 "$bench" --steps $steps --warmup 10 --no-cpu-baseline --full $fifarg > $out/bench.log 2>&1
 grep metric $out/bench.log | cut -c1-200
 python3 - "$out" <<'PY'
 import csv, glob, sys

@@ -29,8 +29,8 @@ hipcc -O3 --offload-arch=gfx950 -o tools/micro/valu_f64_rate tools/micro/valu_f6
 bash tools/prof_scene_render.sh > $R/${rnd}_c4_scene_render_kernel_trace.txt 2>&1 || exit 1
 grep "c4_torus" gpurun_out/prof/scene_render/run.log > $R/${rnd}_c4_scene_render_host_breakdown.txt
 # bench lines without the profiler (c4 with the CPU baseline: the line the driver records)
-for c in c2 c3 c5; do timeout -k 10 600 python bench.py --config $c --no-cpu-baseline > $R/${rnd}_bench_$c.json 2> $R/bench_$c.err || exit 1; done
-timeout -k 10 900 python bench.py > $R/${rnd}_bench_c4.json 2> $R/bench_c4.err || exit 1
+for c in c2 c3 c5; do timeout -k 10 600 python bench.py --config $c --no-cpu-baseline --full > $R/${rnd}_bench_$c.json 2> $R/bench_$c.err || exit 1; done
+timeout -k 10 900 python bench.py --full > $R/${rnd}_bench_c4.json 2> $R/bench_c4.err || exit 1
 # what one rank of a split frame costs this device (no collective), per partition; and the atomics micro-benchmark
 python3 tools/time_band.py c4_torus200k_1080p 2 4 8 2>&1 | grep -v amdgpu.ids > $R/${rnd}_partition_per_rank_times.txt
 python3 tools/time_band.py c5_torus1m_4k_skybox 2 4 8 2>&1 | grep -v amdgpu.ids >> $R/${rnd}_partition_per_rank_times.txt
