@@ -61,6 +61,13 @@ enum {
                                  and MR_FRAME_KEEP_FLOAT.  On part of a frame (row band / stripes;
                                  mr_render_device only) the overlay is not drawn: the state it needs is appended to the
                                  rows for mr_overlay_apply, see there */
+    MR_FRAME_SUPERSAMPLE2 = 512,   /* ordered-grid supersampling, s = 2 or 4 samples per output pixel and axis (at most one of */
+    MR_FRAME_SUPERSAMPLE4 = 1024,  /* the two).  width / height, viewport, sky_* and row_begin / row_end then describe the
+                                 SAMPLE grid and must be multiples of s; stripe_count > 1 is refused.  Output pixel (x, y)
+                                 is the mean of samples (s x + i, s y + j), 0 <= i, j < s (rows counted from the bottom),
+                                 finalised once: the output buffer holds (row_end - row_begin) / s x width / s x 3 bytes.
+                                 The taps (mr_read_z / _stencil / _winner / _frame_f32) and the counters stay on the sample
+                                 grid.  With MR_FRAME_OVERLAY the lines are drawn on the sample grid too (whole frames only) */
     MR_FRAME_KEEP_BUFFERS = 64 /* also write the reference's working buffers (z_buffer, stencil_buffer, winner
                                  face per pixel; obj/core.py:588-591) to device memory for mr_read_z /
                                  mr_read_stencil / mr_read_winner.  Without it they only ever exist on chip,
@@ -223,7 +230,8 @@ int mr_scene_set_overlay_cameras(mr_scene *scene, const double *corners, const d
 
 /* Scene.render() -- obj/core.py:587-640: depth/ambient pass, shadow-volume stencil pass, lit
  * pass and finalise (flip, **0.8, *255, uint8) on the GPU.  out_rgb receives
- * (row_end - row_begin) x width x 3 bytes, row 0 = top row of the band.  stats may be NULL. */
+ * (row_end - row_begin) x width x 3 bytes, row 0 = top row of the band (divided by s twice with
+ * MR_FRAME_SUPERSAMPLE2/4, as for mr_render_async and mr_render_device).  stats may be NULL. */
 int mr_render(mr_scene *scene, const mr_frame_desc *frame, uint8_t *out_rgb, mr_stats *stats);
 
 /* The overlay on a frame split over several devices.  The lines test z at pixels other devices own, so a device that
@@ -308,7 +316,8 @@ int mr_get_kernel_times(mr_scene *scene, int n_frames, float *out_ms, int cap);
 int mr_get_stream_kernel_times(mr_scene *scene, void *stream, int n_frames, float *out_ms, int cap);
 
 /* Debug taps for parity tests: the reference's working buffers after the last render
- * (obj/core.py:588-591).  Row = screen y (not flipped), as in the reference. */
+ * (obj/core.py:588-591).  Row = screen y (not flipped), as in the reference.  (H, W) is the frame's
+ * width / height as passed, i.e. the sample grid of a supersampled frame. */
 /* z, stencil and winner need a frame rendered with MR_FRAME_KEEP_BUFFERS. */
 int mr_read_z(mr_scene *scene, double *out_hw);            /* z_buffer, float64 (H, W) */
 int mr_read_stencil(mr_scene *scene, int16_t *out_hw);     /* stencil_buffer, int16 (H, W) */

@@ -23,6 +23,8 @@ FRAME_SHADOWS, FRAME_KEEP_FLOAT, FRAME_FACE_STATUS, FRAME_LIGHT_TIMING, FRAME_SK
 FRAME_KEEP_BUFFERS = 64
 FRAME_NO_TIMING = 128
 FRAME_OVERLAY = 256
+FRAME_SUPERSAMPLE2, FRAME_SUPERSAMPLE4 = 512, 1024
+_SUPERSAMPLE_FLAGS = {1: 0, 2: FRAME_SUPERSAMPLE2, 4: FRAME_SUPERSAMPLE4}
 ABI_VERSION = 3
 TILE_RECORD_WORDS = 12
 
@@ -183,7 +185,10 @@ def fill_frame_desc(pf, row_band=None, keep_float=False, light_timing=False, fac
                | (FRAME_LIGHT_TIMING if light_timing else 0) | (FRAME_FACE_STATUS if face_status else 0)
                | (FRAME_COUNTERS if counters else 0) | (FRAME_KEEP_BUFFERS if keep_buffers else 0)
                | (FRAME_NO_TIMING if no_timing else 0) | (FRAME_OVERLAY if overlay else 0))
-    d.row_begin, d.row_end = (0, pf.height) if row_band is None else (int(row_band[0]), int(row_band[1]))
+    # a supersampled frame (pf is its sample grid): row_band counts OUTPUT rows, the descriptor sample rows
+    ss = int(getattr(pf, "supersample", 1))
+    d.flags |= _SUPERSAMPLE_FLAGS[ss]
+    d.row_begin, d.row_end = (0, pf.height) if row_band is None else (int(row_band[0]) * ss, int(row_band[1]) * ss)
     if stripe is not None:                      # (index, count): interleaved tile rows, see mi355rast.h
         d.stripe_index, d.stripe_count = int(stripe[0]), int(stripe[1])
     for name in ("mvp", "viewport", "debug_mvp", "frustum_planes", "camera_pos", "light_pos", "light_dir",
@@ -332,7 +337,7 @@ class DeviceRenderer:
         cam = scene.camera
         dbg = scene.debug_camera if scene.debug_camera is not None else cam
         key = (id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")), tuple(scene.resolution),
-               int(scene.system), int(scene.subsystem))
+               int(scene.system), int(scene.subsystem), getattr(scene, "supersample", 1))
         if getattr(self, "_overlay_key", None) == key or getattr(self, "_overlay_pinned", False):
             return
         # the key holds ids: keep the objects alive while it is cached, so that no other camera or matrix can
@@ -342,13 +347,16 @@ class DeviceRenderer:
         # them -- clipping, projection, DDA, dashes, the per-pixel lists and their upload -- is one call into the library
         corners, inside = frustum_corners(cam, dbg)
         f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-        corners, planes, mvp, viewport = f64(corners), f64(cam.frustum_planes), f64(cam.MVP), f64(cam.viewport)
-        height, width = (int(v) for v in scene.resolution)
+        corners, planes, mvp = f64(corners), f64(cam.frustum_planes), f64(cam.MVP)
+        # (a supersampled frame draws the lines on its sample grid, like the reference at that resolution)
+        from ._pack import sample_grid
+        _, height, width, viewport = sample_grid(scene)
+        viewport = f64(viewport)
         _check(self.lib.mr_scene_set_overlay_cameras(self.handle, corners.ctypes.data, planes.ctypes.data, mvp.ctypes.data,
                                                      viewport.ctypes.data, float(cam.near), float(cam.far), int(inside),
                                                      height, width), "mr_scene_set_overlay_cameras")
         self._overlay_key = (id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")),
-                             tuple(scene.resolution), int(scene.system), int(scene.subsystem))
+                             tuple(scene.resolution), int(scene.system), int(scene.subsystem), getattr(scene, "supersample", 1))
         self._overlay_refs = (cam, dbg, cam.__dict__.get("MVP"), dbg.__dict__.get("MVP"))
 
     def set_overlay_lists(self, ops, pin=True):
@@ -378,7 +386,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -439,9 +447,10 @@ class DeviceRenderer:
             self._desc_key = dkey
         desc = self._desc_cached
         self._n_faces = sum(len(m._faces) for m in scene.models)
-        rows = desc.row_end - desc.row_begin if stripe is None else stripe_out_rows(pf.height, stripe[1])
-        self._frame = (pf.height, pf.width)
-        return desc, self._pinned.array((rows, pf.width, 3))
+        ss = pf.supersample           # (the output of a supersampled frame: s x s samples per pixel)
+        rows = (desc.row_end - desc.row_begin) // ss if stripe is None else stripe_out_rows(pf.height, stripe[1])
+        self._frame = (pf.height, pf.width)          # the taps' shape: the sample grid
+        return desc, self._pinned.array((rows, pf.width // ss, 3))
 
     ASYNC_LANES = 4
 

@@ -70,6 +70,9 @@ class PackedFrame:
     background: np.ndarray
     sky_tri: Optional[np.ndarray] = None      # (2, 3, 2) int32, cubemap skybox only
     sky_rays: Optional[np.ndarray] = None     # (2, 3, 3) float64
+    # samples per output pixel and axis (Scene.supersample).  width / height / viewport / sky_* above are then the
+    # sample grid's: the frame of a twin scene at (s H, s W) with its camera's offsets times s
+    supersample: int = 1
 
 
 @dataclass
@@ -96,15 +99,38 @@ def _wrap(idx, n, what):
     return idx
 
 
+SUPERSAMPLE_FACTORS = (1, 2, 4)
+
+
+def check_supersample(value):
+    """``Scene.supersample``: 1, 2 or 4 samples per output pixel and axis (s divides the 16 x 16 tile, and s * s is a
+    power of two: a block of equal colours resolves to exactly that colour)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) not in SUPERSAMPLE_FACTORS:
+        raise ValueError(f"supersample must be one of {SUPERSAMPLE_FACTORS}, got {value!r}")
+    return int(value)
+
+
+def sample_grid(scene):
+    """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame."""
+    cam = scene.camera
+    s = check_supersample(getattr(scene, "supersample", 1))
+    height, width = (int(v) for v in scene.resolution)
+    if s == 1:
+        return 1, height, width, cam.viewport
+    from .transformation import ViewPort
+    return s, s * height, s * width, ViewPort((s * height, s * width), cam.far, cam.near,
+                                              x_offset=cam.x_offset * s, y_offset=cam.y_offset * s)
+
+
 def pack_frame(scene, shadows=True) -> PackedFrame:
     cam, light = scene.camera, scene.light
     dbg = scene.debug_camera if scene.debug_camera is not None else cam
-    height, width = (int(v) for v in scene.resolution)
+    ss, height, width, viewport = sample_grid(scene)
     sky = scene.skybox
     sky_tri = sky_rays = None
     if sky is not None and hasattr(sky, "textures"):
         from .cube_map import sky_frame_constants
-        sky_tri, sky_rays = sky_frame_constants(cam)
+        sky_tri, sky_rays = sky_frame_constants(cam, viewport)
         background = np.zeros(3, dtype=np.float32)          # uncovered pixels stay black (frame starts at 0)
     elif sky is not None:
         background = np.asarray(np.array(sky), dtype=np.float32).ravel()
@@ -117,7 +143,7 @@ def pack_frame(scene, shadows=True) -> PackedFrame:
         width=width, height=height, system=int(scene.system),
         backface_culling=bool(cam.backface_culling), light_type=kind, shadows=bool(shadows),
         mvp=np.ascontiguousarray(cam.MVP, dtype=np.float64),
-        viewport=np.ascontiguousarray(cam.viewport, dtype=np.float64),
+        viewport=np.ascontiguousarray(viewport, dtype=np.float64),
         debug_mvp=np.ascontiguousarray(dbg.MVP, dtype=np.float64),
         frustum_planes=np.ascontiguousarray(cam.frustum_planes, dtype=np.float64),
         z_near=float(cam.near), z_far=float(cam.far),
@@ -128,7 +154,7 @@ def pack_frame(scene, shadows=True) -> PackedFrame:
         att_constant=float(light.constant), att_linear=float(light.linear),
         att_quadratic=float(light.quadratic),
         spot_edge0=float(np.cos(np.deg2rad(20))), spot_edge1=float(np.cos(np.deg2rad(10))),
-        background=background, sky_tri=sky_tri, sky_rays=sky_rays)
+        background=background, sky_tri=sky_tri, sky_rays=sky_rays, supersample=ss)
 
 
 def _texture_id(tex, textures, seen):

@@ -418,6 +418,14 @@ class Scene:
       (``obj/triangular.py:39,83``); ``None`` means "same as ``camera``" (the reference raises).
     * ``shadows`` is accepted and ignored like upstream (``obj/core.py:568``): the stencil
       pass always runs.  Use ``render(shadows=False)`` to skip it explicitly.
+    * ``supersample`` (an addition; 1, 2 or 4, default 1): ordered-grid anti-aliasing.  With s > 1 the
+      frame is rendered on the sample grid ``(s*H, s*W)`` -- upstream's frame of the same scene at that
+      resolution, the camera's ``x_offset`` / ``y_offset`` times s, overlay included -- and output pixel
+      (x, y) is the mean of samples (s*x + i, s*y + j), 0 <= i, j < s (rows counted from the bottom like
+      the reference's buffers: the grid is anchored at the pixel's lower corner), finalised once.
+      ``resolution`` stays the OUTPUT size, ``render()`` returns ``uint8 (H, W, 3)``; the device taps
+      (``read_z`` ...), ``last_stats`` and the ``verbose`` face report count the sample grid.  Neither
+      ``resolution`` nor the camera is changed.  Split frames (``multigpu``) refuse s > 1.
     """
 
     camera = Bound()
@@ -426,7 +434,7 @@ class Scene:
 
     def __init__(self, camera=None, light=None, shadows=False, debug_camera=None,
                  resolution=(1500, 1500), system=SYSTEM.RH, subsystem=SUBSYSTEM.DIRECTX,
-                 skymap=None, device=None):
+                 skymap=None, device=None, supersample=1):
         self.system = system
         self.subsystem = subsystem
         self.models: List[Model] = []
@@ -434,12 +442,23 @@ class Scene:
         self.light = light if light is not None else Light(position=(1, 1, 1))
         self.debug_camera = debug_camera
         self.resolution = resolution
+        self.supersample = supersample
         self.skybox = skymap
         self.shadows = shadows
         self.device = device
         self.draw_debug_frustum = True      # like the reference, which always overlays it (core.py:638); switchable here
         self.verbose = False                # the reference always prints its face histogram (core.py:634-636)
         self._renderer = None
+
+    @property
+    def supersample(self):
+        """Samples per output pixel and axis: 1, 2 or 4 (see the class docstring)."""
+        return self._supersample
+
+    @supersample.setter
+    def supersample(self, value):
+        from ._pack import check_supersample
+        self._supersample = check_supersample(value)
 
     @property
     def last_stats(self):
@@ -464,7 +483,8 @@ class Scene:
         reference, the frame carries the debug camera's frustum as red lines (``obj/core.py:638``);
         ``scene.draw_debug_frustum = False`` leaves it out.  With ``scene.verbose`` (off by default)
         the three lines the reference prints per model after its lit pass (``obj/core.py:634-636``)
-        are reproduced from the device's per-face codes."""
+        are reproduced from the device's per-face codes.  With ``scene.supersample`` = s > 1 the frame is the
+        s x s box-filtered mean of the sample grid (class docstring); *row_band* counts output rows."""
         backend = self._backend()
         report = self.verbose and row_band is None
         # the debug camera's frustum, drawn by the device into its own frame and z-buffer right after the

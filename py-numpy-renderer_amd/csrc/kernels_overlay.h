@@ -38,7 +38,7 @@ struct OverlayArgs {
     double *st_z;                        // state: z ...
     float *st_f;                         // ... and float colour (3 per entry)
     const int32_t *pixel_of;             // null: a state index is the pixel row * W + col (row = screen y); else slot -> pixel
-    uint8_t *out;                        // the uint8 frame (row 0 = top), out_width x out_height
+    uint8_t *out;                        // the uint8 frame (row 0 = top), out_width x out_height; null: not finalised here
     int32_t out_width, out_height;
     const float *gamma_lut;
 };
@@ -83,6 +83,7 @@ k_overlay(const OverlayArgs a, const double sign)
         for (int kk = 1; kk < OVERLAY_TARGETS; ++kk)
             if (any & (1u << kk)) overlay_blend(f);
         a.st_f[3 * (size_t)x] = f[0]; a.st_f[3 * (size_t)x + 1] = f[1]; a.st_f[3 * (size_t)x + 2] = f[2];
+        if (!a.out) return;                 // a supersampled frame: the float frame only (k_resolve_touched finalises)
         const int t = a.pixel_of ? a.pixel_of[x] : x;
         const int py = t / a.out_width, px = t - py * a.out_width;
         uint8_t *o = a.out + ((size_t)(a.out_height - 1 - py) * a.out_width + px) * 3;

@@ -175,6 +175,48 @@ __device__ __forceinline__ int out_row(const FrameConst &fc, int py, int l)
     return fc.band_y1 - 1 - py;
 }
 
+// ---- supersampling (MR_FRAME_SUPERSAMPLE2/4; FrameConst::ss_mode): the tile works on the sample grid, and output
+// pixel (x, y) is the mean of samples (s x + i, s y + j), i, j < s.  s divides the tile, so every block of s x s samples
+// lies inside one tile, and width / band are multiples of s, so a block is entirely inside the band or entirely out.
+// The block's s * s colours are summed in ONE fixed order -- row-major from its bottom-left sample -- by the fused
+// resolve below, k_resolve_touched and k_resolve_full alike, so the three give the same bytes.
+// Output row of the block whose bottom-left sample is screen row py (band rows top first, like out_row).
+__device__ __forceinline__ uint8_t *ss_out_pixel(uint8_t *out, int width, int band_y1, int shift, int px, int py)
+{
+    return out + ((size_t)((band_y1 - 1 - py) >> shift) * (width >> shift) + (px >> shift)) * 3;
+}
+// mean of the block whose bottom-left sample is rgb[0]; rows `row` floats apart, samples 3 floats apart
+__device__ __forceinline__ void ss_block_mean(const float *rgb, int row, int shift, float m[3])
+{
+    const int s = 1 << shift;
+    float acc[3] = { 0.f, 0.f, 0.f };
+    for (int j = 0; j < s; ++j)
+        for (int i = 0; i < s; ++i) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += rgb[j * row + i * 3 + c];
+        }
+    const float inv = 1.0f / (float)(s * s);       // a power of two: exact, and a uniform block keeps its colour
+#pragma unroll
+    for (int c = 0; c < 3; ++c) m[c] = acc[c] * inv;
+}
+// The fused resolve: the tile's 256 sample colours are staged in LDS (s_rgb, 3 floats per sample, row-major from the
+// tile's bottom row); (16 / s)^2 threads each finalise one output pixel.  Call after the barrier behind the staging.
+__device__ __forceinline__ void ss_resolve_tile(const FrameConst &fc, const float *s_rgb, uint8_t *out, int gx, int gy, int tid,
+                                                const float *s_gamma)
+{
+    const int shift = fc.ss_mode & SS_SHIFT_MASK, n_log = 4 - shift;      // TILE_W == 16: (16 / s) blocks per side
+    static_assert(TILE_W == 16 && TILE_H == 16, "ss_resolve_tile");
+    if (tid >= 1 << (2 * n_log)) return;
+    const int bx = tid & ((1 << n_log) - 1), by = tid >> n_log;
+    const int px = gx + (bx << shift), py = gy + (by << shift);
+    if (px >= fc.width || py < fc.band_y0 || py >= fc.band_y1) return;
+    float m[3];
+    ss_block_mean(s_rgb + ((by << shift) * TILE_W + (bx << shift)) * 3, TILE_W * 3, shift, m);
+    uint8_t *o = ss_out_pixel(out, fc.width, fc.band_y1, shift, px, py);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = gamma_u8(m[c], s_gamma);
+}
+
 constexpr int QUAD_STAGE_U4 = 12;     // uint4 pieces staged per quad: 64-byte header + 4 edges
 static_assert(offsetof(QuadRec, e) == 64 && sizeof(QuadEdge) == 32, "QuadRec layout");
 static_assert(QUAD_BATCH == WAVE, "lane j of every wavefront classifies quad j of the batch");
@@ -268,7 +310,11 @@ struct TileKernArgs { FrameConst fc; TileArgs ta; ShadeArgs sh; };
 // row-major order, i.e. round-robin over the XCDs: heavy tiles cluster on the screen, and an
 // XCD-contiguous mapping (tried first) left six of the eight XCDs idle behind the two that
 // owned the mesh and its shadow.
-template <bool SPLIT>      // SPLIT: the heaviest tiles' shadow quads are shared out over HEAVY_SPLIT workgroups (see HEAVY_SPLIT)
+// SPLIT: the heaviest tiles' shadow quads are shared out over HEAVY_SPLIT workgroups (see HEAVY_SPLIT).
+// SS: a supersampled frame (FrameConst::ss_mode != 0; the host launches SS only then): the uint8 output is written by
+// the resolve of s x s samples, not per sample.  An instantiation of its own so that the plain frame's code is
+// untouched by it (a runtime branch on ss_mode cost the plain c4 frame 1.2 %).
+template <bool SPLIT, bool SS>
 __global__ void __launch_bounds__(TILE_PX, K_TILE_WAVES)
 k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), phase by phase
 {
@@ -364,15 +410,30 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             !taps) {
             if (part != 0) return;                        // (a tile that was heavy a frame ago: one part will do)
             uint8_t *o = sh.out + ((size_t)out_row(fc, py, ltr) * fc.width + px) * 3;
+            const int ss = SS ? fc.ss_mode : 0;           // (never SS_SEPARATE here: that frame writes every tile's float colour)
             if (sky_tile) {
                 s_gamma[tid] = sh.gamma_lut[tid];
                 if (tid == 0) s_gamma[GAMMA_LUT_SIZE - 1] = sh.gamma_lut[GAMMA_LUT_SIZE - 1];
                 float rgb[3] = { 0.f, 0.f, 0.f };
                 if (live) sky_color(fc, sh.sky, px, py, rgb);
+                if (ss) {                                 // the sky's samples, resolved like any tile's
+                    float *s_rgb = reinterpret_cast<float *>(s_quad);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) s_rgb[lp * 3 + j] = rgb[j];
+                }
                 __syncthreads();
-                if (live) {
+                if (ss) {
+                    ss_resolve_tile(fc, reinterpret_cast<const float *>(s_quad), sh.out, gx, gy, tid, s_gamma);
+                } else if (live) {
 #pragma unroll
                     for (int j = 0; j < 3; ++j) o[j] = gamma_u8(rgb[j], s_gamma);
+                }
+            } else if (ss) {                              // (16 / s)^2 output pixels of the finalised background
+                const int shift = ss & SS_SHIFT_MASK, n_log = 4 - shift;
+                const int bpx = gx + ((tid & ((1 << n_log) - 1)) << shift), bpy = gy + ((tid >> n_log) << shift);
+                if (tid < 1 << (2 * n_log) && bpx < fc.width && bpy >= fc.band_y0 && bpy < fc.band_y1) {
+                    uint8_t *ob = ss_out_pixel(sh.out, fc.width, fc.band_y1, shift, bpx, bpy);
+                    ob[0] = (uint8_t)fc.background_u8; ob[1] = (uint8_t)(fc.background_u8 >> 8); ob[2] = (uint8_t)(fc.background_u8 >> 16);
                 }
             } else if (live) {
                 o[0] = (uint8_t)fc.background_u8; o[1] = (uint8_t)(fc.background_u8 >> 8); o[2] = (uint8_t)(fc.background_u8 >> 16);
@@ -787,6 +848,10 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
 
     // ---- 4. deferred shading + finalise (kernels_shade.h; obj/core.py:640)
     const bool lit = (int16_t)sten == 0;                  // the reference's buffer is int16
+    // A supersampled frame's samples are staged in the quad area for the fused resolve at the end of this phase (see
+    // there): every wavefront must have left the last quad batch first.
+    const bool fused_ss = SS && !(kernargs<TileKernArgs>().fc.ss_mode & SS_SEPARATE);
+    if (fused_ss) __syncthreads();
     if (live) {
         const TileKernArgs &ka = kernargs<TileKernArgs>();
         const FrameConst &fc = ka.fc;
@@ -811,18 +876,36 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         }
         const size_t at_px = (size_t)py * fc.width + px;
         if (sh.frame && taps) { sh.frame[at_px * 3 + 0] = rgb[0]; sh.frame[at_px * 3 + 1] = rgb[1]; sh.frame[at_px * 3 + 2] = rgb[2]; }
-        uint8_t *o = sh.out + ((size_t)out_row(fc, py, ltr) * fc.width + px) * 3;
-        if (ready_u8) {
-            o[0] = (uint8_t)fc.background_u8; o[1] = (uint8_t)(fc.background_u8 >> 8); o[2] = (uint8_t)(fc.background_u8 >> 16);
-        } else {
+        if (SS) {                                         // (the output pixel is written by a resolve)
+            if (fused_ss) {
+                float *s_rgb = reinterpret_cast<float *>(s_quad);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) o[j] = gamma_u8(rgb[j], s_gamma);
+                for (int j = 0; j < 3; ++j) s_rgb[lp * 3 + j] = rgb[j];
+            }
+        } else {
+            uint8_t *o = sh.out + ((size_t)out_row(fc, py, ltr) * fc.width + px) * 3;
+            if (ready_u8) {
+                o[0] = (uint8_t)fc.background_u8; o[1] = (uint8_t)(fc.background_u8 >> 8); o[2] = (uint8_t)(fc.background_u8 >> 16);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) o[j] = gamma_u8(rgb[j], s_gamma);
+            }
         }
         if (ta.zbuf && taps) {                            // taps for the parity tests / per-face status / overlay
             ta.zbuf[at_px] = zbest;
             ta.winner[at_px] = best;
             ta.stencil[at_px] = sten;
         }
+    }
+    // Fused resolve of a supersampled frame: after shading, where the register pressure has fallen.  The live samples'
+    // colours are in the quad staging area (dead since phase 3; a dead sample's block is never read), and (16 / s)^2
+    // threads finalise the output pixels.  (Uncovered background samples resolve from the float background like any
+    // other: a uniform block keeps its colour exactly.)  SS_SEPARATE: k_resolve_full does it from the float frame.
+    static_assert(TILE_PX * 3 * sizeof(float) <= sizeof(s_quad), "resolve staging fits the quad area");
+    if (fused_ss) {
+        __syncthreads();
+        const TileKernArgs &ka = kernargs<TileKernArgs>();
+        ss_resolve_tile(ka.fc, reinterpret_cast<const float *>(s_quad), ka.sh.out, gx, gy, tid, s_gamma);
     }
 
     // ---- per-tile statistics and housekeeping
@@ -894,6 +977,44 @@ k_reduce_tile_stats(const uint32_t *__restrict__ tile_stats, int n_tiles, Counte
             atomicAdd(tid == TILE_STATS ? &ctr->tri_bin_total : &ctr->bin_total, (unsigned int)v);
         }
     }
+}
+
+// Supersampled frames, resolved from the sample grid's float frame (row = screen y) instead of inside k_tile.
+// k_resolve_touched: after k_overlay, which blended its lines into the float frame only, the output pixel that holds
+// each touched sample is resolved again.  Several samples of one block write the same bytes: no dedupe needed.  The
+// overlay's tile mask made k_tile write the float colour of every tile with a touched sample, and a block never
+// leaves its tile, so every sample read here is there.
+__global__ void __launch_bounds__(256)
+k_resolve_touched(const int32_t *__restrict__ touched, int n_slots, const float *__restrict__ frame, int width, int band_y1,
+                  int shift, const float *__restrict__ gamma_lut, uint8_t *__restrict__ out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n_slots) return;
+    const int t = touched[i];
+    const int py = (t / width) & ~((1 << shift) - 1), px = (t % width) & ~((1 << shift) - 1);
+    float m[3];
+    ss_block_mean(frame + ((size_t)py * width + px) * 3, width * 3, shift, m);
+    uint8_t *o = ss_out_pixel(out, width, band_y1, shift, px, py);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = gamma_u8(m[c], gamma_lut);
+}
+
+// k_resolve_full: every output pixel of the band [band_y0, band_y1) (sample rows) from the float frame
+// (MR_RESOLVE_PATH=separate: the yardstick of the fused resolve, and its A/B).  One thread per output pixel.
+__global__ void __launch_bounds__(256)
+k_resolve_full(const float *__restrict__ frame, int width, int band_y0, int band_y1, int shift,
+               const float *__restrict__ gamma_lut, uint8_t *__restrict__ out)
+{
+    const int ow = width >> shift, oh = (band_y1 - band_y0) >> shift;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)ow * oh) return;
+    const int orow = (int)(i / ow), ox = (int)(i - (long long)orow * ow);
+    const int py = band_y1 - ((orow + 1) << shift), px = ox << shift;
+    float m[3];
+    ss_block_mean(frame + ((size_t)py * width + px) * 3, width * 3, shift, m);
+    uint8_t *o = out + (size_t)i * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = gamma_u8(m[c], gamma_lut);
 }
 
 }  // namespace mr

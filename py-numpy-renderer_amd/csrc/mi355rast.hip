@@ -122,6 +122,7 @@ struct FrameSlot {
     int last_n_tiles = 0;
     bool last_ordered = false;               // the last frame's tile kernel followed the order buffer (else row-major)
     bool overlay_deferred = false;           // the last enqueue_frame left the overlay to finish_overlay
+    int last_ss_mode = 0;                    // FrameConst::ss_mode of the last frame (finish_overlay resolves after the overlay)
     bool have_frame = false, stats_reduced = false;
     bool last_copied = false;                // the last frame was followed by a timed device-to-host copy (mr_render, mr_render_async)
 
@@ -446,6 +447,21 @@ FrameSlot *slot_for(mr_scene *sc, hipStream_t stream)
     return sc->slots.back().get();
 }
 
+// samples per output pixel and axis (MR_FRAME_SUPERSAMPLE2/4), 1 without
+inline int ss_factor(const mr_frame_desc *fr)
+{
+    return (fr->flags & MR_FRAME_SUPERSAMPLE4) ? 4 : (fr->flags & MR_FRAME_SUPERSAMPLE2) ? 2 : 1;
+}
+inline int ss_shift(int s) { return s == 4 ? 2 : s == 2 ? 1 : 0; }
+
+// MR_RESOLVE_PATH=separate: a supersampled frame is resolved by k_resolve_full from the float frame instead of inside
+// k_tile (the yardstick of the fused resolve, and its A/B)
+bool resolve_separate()
+{
+    static const bool sep = [] { const char *e = getenv("MR_RESOLVE_PATH"); return e && !strcmp(e, "separate"); }();
+    return sep;
+}
+
 int validate_frame(const mr_frame_desc *fr)
 {
     if (!fr) return fail(MR_E_INVALID, "frame descriptor is NULL");
@@ -462,6 +478,14 @@ int validate_frame(const mr_frame_desc *fr)
             return fail(MR_E_INVALID, "a striped frame spans all rows: row_begin / row_end must be 0 / height");
     } else if (fr->stripe_count < 0) {
         return fail(MR_E_INVALID, "stripe_count must not be negative");
+    }
+    if ((fr->flags & MR_FRAME_SUPERSAMPLE2) && (fr->flags & MR_FRAME_SUPERSAMPLE4))
+        return fail(MR_E_INVALID, "MR_FRAME_SUPERSAMPLE2 and MR_FRAME_SUPERSAMPLE4 are exclusive");
+    const int s = ss_factor(fr);
+    if (s > 1) {
+        if (fr->width % s || fr->height % s) return fail(MR_E_INVALID, "supersampling: the sample grid's width and height must be multiples of s");
+        if (fr->row_begin % s || fr->row_end % s) return fail(MR_E_INVALID, "supersampling: row_begin / row_end must be multiples of s");
+        if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
     return MR_OK;
 }
@@ -562,19 +586,23 @@ mr::FrameConst make_const(const mr_scene *sc, const mr_frame_desc *fr)
     fc.specular_strength = fr->specular_strength;
     fc.att_constant = fr->att_constant; fc.att_linear = fr->att_linear; fc.att_quadratic = fr->att_quadratic;
     fc.spot_edge0 = fr->spot_edge0; fc.spot_edge1 = fr->spot_edge1;
+    const int s = ss_factor(fr);
+    fc.ss_mode = s > 1 ? ss_shift(s) | (resolve_separate() ? mr::SS_SEPARATE : 0) : 0;
     return fc;
 }
 
 inline unsigned blocks_for(long long n, int per_block) { return (unsigned)std::max<long long>(1, (n + per_block - 1) / per_block); }
 
-// bytes of the uint8 output of a frame: the band's rows, or the striped layout's blocks
+// bytes of the uint8 output of a frame: the band's rows, or the striped layout's blocks (a supersampled frame: its
+// output pixels, s x s samples each)
 size_t out_bytes(const mr_frame_desc *fr)
 {
     if (fr->stripe_count > 1) {
         const int rows = (fr->height + mr::TILE_H - 1) / mr::TILE_H;
         return (size_t)((rows + fr->stripe_count - 1) / fr->stripe_count) * mr::TILE_H * fr->width * 3;
     }
-    return (size_t)(fr->row_end - fr->row_begin) * fr->width * 3;
+    const int s = ss_factor(fr);
+    return (size_t)((fr->row_end - fr->row_begin) / s) * (fr->width / s) * 3;
 }
 
 // Builds the overlay's lists from the cameras mr_scene_set_overlay_cameras left (host_overlay.h: clipping, projection,
@@ -683,20 +711,47 @@ void launch_overlay(mr_scene *sc, FrameSlot *fs, uint8_t *d_out, int width, int 
     hipLaunchKernelGGL(mr::k_overlay, dim3(1), dim3(mr::OVERLAY_BLOCK), 0, stream, oa, (double)system);
 }
 
+// The output of a supersampled frame that k_tile did not finalise in full, after the overlay (which, on such a frame,
+// blends into the float frame only): the output pixels of the touched samples (k_resolve_touched), or with
+// MR_RESOLVE_PATH=separate every output pixel of the band (k_resolve_full).  Nothing to do for other frames.
+void launch_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, int ss_mode, bool overlay_drawn, uint8_t *d_out,
+                    hipStream_t stream)
+{
+    const int shift = ss_mode & mr::SS_SHIFT_MASK;
+    if (!shift) return;
+    const int band_y0 = fr.height - fr.row_end, band_y1 = fr.height - fr.row_begin;
+    if (ss_mode & mr::SS_SEPARATE) {
+        const long long n = (long long)(fr.width >> shift) * ((band_y1 - band_y0) >> shift);
+        hipLaunchKernelGGL(mr::k_resolve_full, dim3(blocks_for(n, 256)), dim3(256), 0, stream, fs->d_frame.as<float>(), fr.width,
+                           band_y0, band_y1, shift, sc->d_gamma.as<float>(), d_out);
+    } else if (overlay_drawn && !sc->ov_touched.empty()) {
+        const int n_slots = (int)sc->ov_touched.size();
+        hipLaunchKernelGGL(mr::k_resolve_touched, dim3(blocks_for(n_slots, 256)), dim3(256), 0, stream,
+                           reinterpret_cast<const int32_t *>(static_cast<const char *>(fs->ov.lists.p) + fs->ov.off[5]), n_slots,
+                           fs->d_frame.as<float>(), fr.width, band_y1, shift, sc->d_gamma.as<float>(), d_out);
+    }
+}
+
 // Second half of a frame whose overlay enqueue_frame left for later (may_defer_overlay): the device is busy with the
 // frame's three kernels, the host builds the lines' lists meanwhile, then the upload and the overlay kernel follow on the
-// frame's stream.
+// frame's stream (and, on a supersampled frame, the resolve that has to wait for it).
 int finish_overlay(mr_scene *sc, FrameSlot *fs, uint8_t *d_out)
 {
     if (!fs->overlay_deferred) return MR_OK;
     fs->overlay_deferred = false;
     realize_overlay(sc);
-    if (sc->ov_points == 0) return MR_OK;
     const mr_frame_desc &fr = fs->last_frame;
+    const int ss_mode = fs->last_ss_mode;
+    if (sc->ov_points == 0) {
+        launch_resolve(sc, fs, fr, ss_mode, false, d_out, fs->stream);
+        HIP_TRY(hipGetLastError());
+        return MR_OK;
+    }
     if (sc->ov_width != fr.width || sc->ov_height != fr.height) return fail(MR_E_INVALID, "overlay lists were built for a frame of another size");
-    int rc = sync_slot_overlay(sc, fs, false);
+    int rc = sync_slot_overlay(sc, fs, ss_mode != 0);
     if (rc) return rc;
-    launch_overlay(sc, fs, d_out, fr.width, fr.height, fr.system, fs->stream);
+    launch_overlay(sc, fs, ss_mode ? nullptr : d_out, fr.width, fr.height, fr.system, fs->stream);
+    launch_resolve(sc, fs, fr, ss_mode, true, d_out, fs->stream);
     HIP_TRY(hipGetLastError());
     return MR_OK;
 }
@@ -719,16 +774,20 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     const bool overlay = (fc.flags & MR_FRAME_OVERLAY) && sc->ov_points > 0 && !deferred;
     // did the caller ask for the z / stencil / winner / float-frame taps?  (The overlay needs z and colour too, but
     // only at the pixels its lines touch: then only the tiles that hold such a pixel write them, ov_off[7].)
+    // (a supersampled frame resolved by k_resolve_full needs every tile's float colour)
+    if (fc.ss_mode & SS_SEPARATE) fc.flags |= MR_FRAME_KEEP_FLOAT;
     const bool taps_asked = (fc.flags & (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT)) != 0;
     // a device that owns only part of the frame (a rank of a multi-GPU split) cannot replay the overlay: its lines test
     // z at pixels other devices own.  It appends the state of the touched pixels it owns to its rows instead
     // (k_overlay_export), and the overlay is replayed on the assembled frame (mr_overlay_apply).
     if (fc.flags & MR_FRAME_OVERLAY) {
+        if (partial && fc.ss_mode)
+            return fail(MR_E_INVALID, "the overlay of a supersampled frame is drawn on whole frames only");
         if (partial && fr->stripe_count <= 1 && (fr->height % (fr->row_end - fr->row_begin) || fr->row_begin % (fr->row_end - fr->row_begin)))
             return fail(MR_E_INVALID, "overlay on a row band: the bands of the split must be equal");
         if (!deferred && sc->ov_points > 0 && (sc->ov_width != fc.width || sc->ov_height != fc.height))
             return fail(MR_E_INVALID, "overlay lists were built for a frame of another size");
-        if (overlay && (rc = sync_slot_overlay(sc, fs, partial))) return rc;
+        if (overlay && (rc = sync_slot_overlay(sc, fs, partial || fc.ss_mode != 0))) return rc;
         fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     }
     const size_t npx = (size_t)fc.width * fc.height;
@@ -921,10 +980,15 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     static const unsigned split_max_big = [] { const char *e = getenv("MR_SPLIT_MAX"); return e ? (unsigned)atoi(e) : 64u; }();
     tka.ta.split_max = std::min<unsigned>(small_grid ? (unsigned)HEAVY0_MAX : split_max_big, (unsigned)HEAVY0_MAX);
     const bool split = split_mode < 0 ? (small_grid || ordered) : split_mode != 0;
-    if (n_tiles > 0 && split)
-        hipLaunchKernelGGL(k_tile<true>, dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
+    const bool ss = fc.ss_mode != 0;        // supersampled: the instantiations that resolve (see k_tile)
+    if (n_tiles > 0 && split && ss)
+        hipLaunchKernelGGL((k_tile<true, true>), dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
+    else if (n_tiles > 0 && split)
+        hipLaunchKernelGGL((k_tile<true, false>), dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
+    else if (n_tiles > 0 && ss)
+        hipLaunchKernelGGL((k_tile<false, true>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
     else if (n_tiles > 0)
-        hipLaunchKernelGGL(k_tile<false>, dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
+        hipLaunchKernelGGL((k_tile<false, false>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
     else          // nothing to draw on this device (a stripe beyond the frame): still hand the counters on
         HIP_TRY(hipMemsetAsync(next_ctr, 0, sizeof(Counters), stream));
     if (timing) HIP_TRY(hipEventRecord(fs->ev[4], stream));
@@ -941,9 +1005,11 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
                            reinterpret_cast<const int32_t *>(static_cast<const char *>(fs->ov.lists.p) + fs->ov.off[5]), n_slots,
                            fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, world, fr->stripe_count > 1 ? 1 : 0, rank, state);
     } else if (overlay) {                   // after the lit pass' per-face verdicts, as in obj/core.py:624-638
-        launch_overlay(sc, fs, d_out, fc.width, fc.height, fc.system, stream);
+        launch_overlay(sc, fs, fc.ss_mode ? nullptr : d_out, fc.width, fc.height, fc.system, stream);
     }
+    if (!deferred) launch_resolve(sc, fs, *fr, fc.ss_mode, overlay, d_out, stream);   // (deferred: finish_overlay's)
     HIP_TRY(hipGetLastError());
+    fs->last_ss_mode = fc.ss_mode;
     fs->last_frame = *fr;
     fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = n_tiles;

@@ -70,9 +70,11 @@ struct FrameConst {
     // device's rows; CC_CONE also the back-face cone, a face being culled when  s * n . (a - cull_eye) > 0  with
     // s = -1 if CC_NEGATIVE else +1; CC_COUNT count the culled clusters (a diagnostic)
     int32_t cluster_cull;
-    int32_t pad_cc;
+    int32_t ss_mode;             // supersampling: log2 s in SS_SHIFT_MASK (0 = off), SS_SEPARATE: k_tile leaves the resolve to k_resolve_full
     double cull_eye[3];          // the camera's centre of projection in world space (the null vector of MVP's x, y, w columns)
 };
+
+constexpr int SS_SHIFT_MASK = 0xff, SS_SEPARATE = 0x100;
 
 // Output of the optional stand-alone vertex kernel (k_vertex_mfma): everything
 // obj/triangular.py:36-45 derives per face corner, once per unique vertex.

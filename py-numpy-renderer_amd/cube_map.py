@@ -61,14 +61,16 @@ class CubeMap:
         return self.textures[side.astype(int), ij[0], ij[1]]
 
 
-def sky_frame_constants(camera):
+def sky_frame_constants(camera, viewport=None):
     """Per-frame constants of the skybox fill: for each of the two triangles its screen
     vertices truncated to int (``obj/cube_map.py:88-89``) and the three un-projected corner rays
-    ``face @ inv(view_without_translation @ projection)`` divided by w (``:95-98``)."""
+    ``face @ inv(view_without_translation @ projection)`` divided by w (``:95-98``).  *viewport*
+    defaults to ``camera.viewport``; a supersampled frame passes its sample grid's."""
     view = np.array(camera.lookat, dtype=np.float64, copy=True)
     view[3, :3] = 0
     unproject = np.linalg.inv(_fp.matmul_chain(view, camera.projection))
-    viewport = camera.viewport
+    if viewport is None:
+        viewport = camera.viewport
     tri_px = np.empty((2, 3, 2), dtype=np.int32)
     rays = np.empty((2, 3, 3), dtype=np.float64)
     for t, face in enumerate(SKY_TRIANGLES):

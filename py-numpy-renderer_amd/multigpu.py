@@ -208,6 +208,8 @@ class BandRenderer:
     def __init__(self, scene, rank=0, world=1, shadows=True, light_timing=False, frames_in_flight=1,
                  partition="bands", timing_every=1, overlay=False, streams=None):
         height, width = (int(v) for v in scene.resolution)
+        if getattr(scene, "supersample", 1) != 1:
+            raise ValueError("a frame split over devices does not support supersample > 1 (render it on one device)")
         if partition not in ("bands", "stripes", "weighted"):
             raise ValueError(f"unknown partition {partition!r}")
         self.rank, self.world, self.partition = rank, world, partition
