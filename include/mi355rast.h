@@ -346,6 +346,15 @@ int mr_debug_read_tile_records(mr_scene *scene, uint32_t *out, int32_t cap_tiles
  * on with the screen and row test only. */
 int mr_debug_clusters_culled(mr_scene *scene);
 
+/* Diagnostics of the silhouette cache: out[0] = the path the edge half of the most recently enqueued frame
+ * with shadows took (0 fused: every edge tested against the light; 1 fused, and captured into the cache; 2 read from the
+ * cache; -1 no such frame yet), out[1] = the entries that frame read from the cache (0 unless out[0] == 2), out[2] =
+ * captures started on this scene so far, out[3] = cache buffers that hold a usable silhouette.  A silhouette is captured
+ * when two consecutive frames have the same light (type, position and direction, compared bit for bit) and is dropped
+ * with the geometry; MR_SIL_CACHE=0 in the environment (looked up per frame) keeps every frame on the fused path.  The
+ * frames do not depend on it.  Does not wait for the device. */
+int mr_debug_sil_cache(mr_scene *scene, int32_t *out);
+
 /* Diagnostics: the order in which the most recent frame's tile kernel took its tiles (entry b = the tile
  * of workgroup b): heaviest first by the estimate the slot's previous frame left, row-major for a first
  * frame or a new tile grid.  Always a permutation of 0 .. n_tiles-1.  Returns the number of tiles. */

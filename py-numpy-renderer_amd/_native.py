@@ -114,6 +114,7 @@ _PROTOTYPES = {
     "mr_debug_clusters_culled": (C.c_int, [C.c_void_p]),
     "mr_host_camera_constants": (None, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3),
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -592,6 +593,13 @@ class DeviceRenderer:
     def clusters_culled(self):
         """Clusters of 64 faces the last frame's set-up dropped whole (counted only under MR_CLUSTER_CULL=count)."""
         return int(_check(self.lib.mr_debug_clusters_culled(self.handle), "mr_debug_clusters_culled"))
+
+    def sil_cache(self):
+        """Silhouette cache: (path of the last frame with shadows: 0 fused / 1 captured / 2 cached / -1 none, entries it
+        read from the cache, captures started so far, usable buffers); see mi355rast.h."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.mr_debug_sil_cache(self.handle, out), "mr_debug_sil_cache")
+        return tuple(int(x) for x in out)
 
     def read_tile_order(self):
         """The order in which the last frame's tile kernel took its tiles: (n_tiles,) uint32."""

@@ -313,7 +313,17 @@ struct SetupArgs {
 // k_setup's arguments in one block, read phase by phase through kernargs<>() (rast_math.h): the three 4x4 matrices,
 // the six planes and two dozen pointers do not fit the scalar registers at once, and read as plain arguments they
 // were all fetched at the top and parked in vector-register lanes.
-struct SetupKernArgs { FrameConst fc; SetupArgs sa; BinArgs bins; uint32_t face_blocks; uint32_t edge_spread; };
+// The silhouette cache (one per scene and light, see mi355rast.hip, SilCache): the extruded world-space quad (A, B, D, C) of
+// every silhouette edge and the packed (face << 2 | corner) that gave the edge its orientation.  Neither depends on the
+// camera, so a frame whose light and geometry are those of the frames before reads them back instead of testing every edge.
+struct SilQuad { double v[4][4]; };
+enum : uint32_t { SIL_FUSED = 0, SIL_CAPTURE = 1, SIL_CACHED = 2 };
+struct SilArgs {
+    SilQuad *quads;                  // SIL_CAPTURE: written at the silhouette index; SIL_CACHED: read
+    uint32_t *last;                  // (face << 2 | corner) per entry
+    uint32_t mode, count;            // SIL_*; SIL_CACHED: entries.  SIL_CAPTURE: capacity of the two arrays
+};
+struct SetupKernArgs { FrameConst fc; SetupArgs sa; BinArgs bins; uint32_t face_blocks; uint32_t edge_spread; SilArgs sil; };
 #define SETUP_ARGS() const SetupKernArgs &ka_ = kernargs<SetupKernArgs>(); const FrameConst &fc = ka_.fc; \
                      const SetupArgs &sa = ka_.sa; const BinArgs &bins = ka_.bins; (void)fc; (void)sa; (void)bins
 
@@ -695,44 +705,64 @@ __device__ __forceinline__ double plane_dot(const double *P, const double *q)
 // plane that keeps every vertex is skipped (the walk would copy the polygon verbatim).  The
 // arithmetic per vertex and per edge is exactly the sequential algorithm's, so the quads are
 // bit-identical.  `have`: this 16-lane group has an edge (face, corner = sil_f, sil_k; list slot
-// s_idx).  Every lane of the wavefront must call it; s_poly is the wavefront's scratch.
+// s_idx).  Every lane of the wavefront must call both halves; s_poly is the wavefront's scratch.
 constexpr int QS_LANES = 16;
 constexpr uint32_t EDGE_DENSE = 0xffu;       // SetupKernArgs::edge_spread: two edges per lane (see edge_block)
+constexpr uint32_t EDGE_CACHED = 0xfeu;      // SetupKernArgs::edge_spread: the edge workgroups are quad workgroups (see quad_block)
 static_assert(MAX_POLY <= QS_LANES, "one polygon vertex per lane");
 
-__device__ __forceinline__ void quad_setup_group(bool have, int sil_f, int sil_k, uint32_t s_base_raw, uint32_t s_rank,
-                                                 double (*s_poly)[MAX_POLY + 4][4])
+// The clipping scratch of wavefront wv of the workgroup (one array for the kernel, whichever path the workgroup takes)
+__device__ __forceinline__ double (*quad_scratch(int wv))[MAX_POLY + 4][4]
+{
+    __shared__ double s_poly[SETUP_BLOCK / WAVE][WAVE / QS_LANES][MAX_POLY + 4][4];
+    return s_poly[wv];
+}
+
+// Corner c (0..3 = A, B, D, C) of the shadow quad of the edge that starts at corner sil_k of face sil_f: the edge's two
+// ends, and the same two pushed away from the light (obj/core.py:612-621)
+__device__ __forceinline__ void quad_corner(const FrameConst &fc, const SetupArgs &sa, int sil_f, int sil_k, int c, double v[4])
+{
+    const int corner = (c == 0 || c == 3) ? sil_k : (sil_k + 1) % 3;       // A, B, D, C: the edge's first / second end
+    if (fc.pos32) {
+        const float *src = static_cast<const FacePos32 *>(sa.face_pos)[sil_f].v[corner];
+        for (int j = 0; j < 4; ++j) v[j] = (double)src[j];
+    } else {
+        const double *src = static_cast<const FacePos64 *>(sa.face_pos)[sil_f].v[corner];
+        for (int j = 0; j < 4; ++j) v[j] = src[j];
+    }
+    if (c >= 2) {
+        if (fc.light_type == MR_LIGHT_POINT) {
+            double d[4] = { v[0] - fc.light_pos[0], v[1] - fc.light_pos[1], v[2] - fc.light_pos[2], v[3] - 1.0 };
+            double l = sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]);
+            if (l == 0) l = 1;
+            for (int j = 0; j < 4; ++j) v[j] = v[j] + 1000 * (d[j] / l);
+        } else {
+            for (int j = 0; j < 3; ++j) v[j] = v[j] + fc.light_dir[j] * -1000;
+            v[3] = v[3] + 1.0;
+        }
+    }
+}
+
+// Front half: the edge's corners and their extrusion away from the light (obj/core.py:612-621).  quad = (A, B, D, C);
+// lanes 0..3 of the group receive A, B, D, C in v, the other lanes zeros.  Nothing here depends on the camera.
+__device__ __forceinline__ void quad_extrude_group(bool have, int sil_f, int sil_k, double v[4])
+{
+    const int gl = (threadIdx.x & (WAVE - 1)) % QS_LANES;
+    for (int j = 0; j < 4; ++j) v[j] = 0;
+    SETUP_ARGS();                                                // phase: the edge's corners, extrusion
+    if (have && gl < 4) {
+        quad_corner(fc, sa, sil_f, sil_k, gl, v);
+    }
+}
+
+// Back half: clipping, projection, plane, pixel box, work items and the record of the quad whose corners lanes 0..3 of the
+// group hold in v (from quad_extrude_group, or from the silhouette cache).
+__device__ __forceinline__ void quad_finish_group(bool have, double v[4], uint32_t s_base_raw, uint32_t s_rank,
+                                                  double (*s_poly)[MAX_POLY + 4][4])
 {
     const int lane = threadIdx.x & (WAVE - 1);
     const int grp = lane / QS_LANES, gl = lane % QS_LANES, g0 = grp * QS_LANES;
-
-    // ---- extrusion (obj/core.py:612-621): quad = (A, B, D, C); lanes 0..3 hold A, B, D, C
-    double v[4] = { 0, 0, 0, 0 };
     int n = have ? 4 : 0;
-    {
-    SETUP_ARGS();                                                // phase: the edge's corners, extrusion
-    if (have && gl < 4) {
-        const int corner = (gl == 0 || gl == 3) ? sil_k : (sil_k + 1) % 3;       // A, B, D, C: the edge's first / second end
-        if (fc.pos32) {
-            const float *src = static_cast<const FacePos32 *>(sa.face_pos)[sil_f].v[corner];
-            for (int j = 0; j < 4; ++j) v[j] = (double)src[j];
-        } else {
-            const double *src = static_cast<const FacePos64 *>(sa.face_pos)[sil_f].v[corner];
-            for (int j = 0; j < 4; ++j) v[j] = src[j];
-        }
-        if (gl >= 2) {
-            if (fc.light_type == MR_LIGHT_POINT) {
-                double d[4] = { v[0] - fc.light_pos[0], v[1] - fc.light_pos[1], v[2] - fc.light_pos[2], v[3] - 1.0 };
-                double l = sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]);
-                if (l == 0) l = 1;
-                for (int j = 0; j < 4; ++j) v[j] = v[j] + 1000 * (d[j] / l);
-            } else {
-                for (int j = 0; j < 3; ++j) v[j] = v[j] + fc.light_dir[j] * -1000;
-                v[3] = v[3] + 1.0;
-            }
-        }
-    }
-    }
 
     // ---- clipping, one plane at a time
     {
@@ -864,6 +894,29 @@ __device__ __forceinline__ void quad_setup_group(bool have, int sil_f, int sil_k
     }
 }
 
+// Quad workgroup of a frame that found its light's silhouette in the cache (these take the edge workgroups' place in
+// the grid, behind the faces): one entry per 16-lane group, the back half of the fused path from there.  Entry i is silhouette edge i of the frame (record, sil_edges and n_quads as edge_block
+// leaves them).
+__device__ __forceinline__ void quad_block(uint32_t block)
+{
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE, gl = lane % QS_LANES;
+    const uint32_t at = (block * blockDim.x + threadIdx.x) / QS_LANES;
+    double v[4] = { 0, 0, 0, 0 };
+    bool have;
+    {
+        const SetupKernArgs &ka = kernargs<SetupKernArgs>();
+        have = at < ka.sil.count;
+        if (have && gl < 4) for (int j = 0; j < 4; ++j) v[j] = ka.sil.quads[at].v[gl][j];
+        if (have && gl == 4 && at < ka.sa.quad_cap) {
+            const uint32_t ls = ka.sil.last[at];
+            ka.sa.sil_edges[at * 2 + 0] = (int32_t)(ls >> 2);
+            ka.sa.sil_edges[at * 2 + 1] = (int32_t)(ls & 3u);
+        }
+        if (block == 0 && threadIdx.x == 0) atomicAdd(&ka.sa.ctr->n_quads, ka.sil.count);
+    }
+    quad_finish_group(have, v, 0u, at, quad_scratch(wv));
+}
+
 // Edge workgroup: one unique undirected edge per lane.  An edge is on the silhouette when an odd
 // number of its incident light-facing faces toggled it; it keeps the orientation of the last
 // such face in face order (set add/discard semantics of obj/triangular.py:294-302).  The
@@ -875,7 +928,6 @@ __device__ __forceinline__ void quad_setup_group(bool have, int sil_f, int sil_k
 __device__ __forceinline__ void edge_block(uint32_t block)
 {
     SETUP_ARGS();
-    __shared__ double s_poly[SETUP_BLOCK / WAVE][WAVE / QS_LANES][MAX_POLY + 4][4];
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
     // How many edges a lane looks at.  A wavefront sets its silhouette edges up four at a time, one round of 10-15 us
     // after the other, so what matters is how many it FINDS:
@@ -887,6 +939,7 @@ __device__ __forceinline__ void edge_block(uint32_t block)
     //     start their chain late -- two edges per lane halve their number and still find five in one wavefront less
     //     than once per frame.
     const uint32_t spread = ka_.edge_spread;
+    if (spread == EDGE_CACHED) { quad_block(block); return; }      // (the frame found its silhouette in the cache)
     const bool dense = spread == EDGE_DENSE;
     const uint32_t slot_in_grid = block * blockDim.x + threadIdx.x;
     int e[2];
@@ -963,7 +1016,9 @@ __device__ __forceinline__ void edge_block(uint32_t block)
         const uint32_t l0 = (uint32_t)__shfl((int)last[0], from), l1 = (uint32_t)__shfl((int)last[1], from);
         const uint32_t r0 = (uint32_t)__shfl((int)my_rank0, from), r1 = (uint32_t)__shfl((int)my_rank1, from);
         const uint32_t ls = set ? l1 : l0, rank = set ? r1 : r0;
-        quad_setup_group(have, (int)(ls >> 2), (int)(ls & 3u), base_raw, rank, s_poly[wv]);
+        double v[4];
+        quad_extrude_group(have, (int)(ls >> 2), (int)(ls & 3u), v);
+        quad_finish_group(have, v, base_raw, rank, quad_scratch(wv));
     }
     const uint32_t base = (uint32_t)__shfl((int)base_raw, 0);
     const SetupArgs &sa2 = kernargs<SetupKernArgs>().sa;
@@ -973,6 +1028,22 @@ __device__ __forceinline__ void edge_block(uint32_t block)
         if (sil[i] && my_slot < sa2.quad_cap) {
             sa2.sil_edges[my_slot * 2 + 0] = (int32_t)(last[i] >> 2);      // the host maps the face back to its model
             sa2.sil_edges[my_slot * 2 + 1] = (int32_t)(last[i] & 3u);
+        }
+    }
+    // A capture frame leaves its silhouette in the cache as well (SilArgs), entry = silhouette index: here, behind the
+    // frame's own work and one edge per lane, so that the rounds above are the same code whether the frame captures or not.
+    if (kernargs<SetupKernArgs>().sil.mode != SIL_CAPTURE) return;
+#pragma unroll 1
+    for (int i = 0; i < 2; ++i) {
+        const SetupKernArgs &kc = kernargs<SetupKernArgs>();
+        const uint32_t at = base + (i ? my_rank1 : my_rank0);
+        if (!sil[i] || at >= kc.sil.count) continue;
+        kc.sil.last[at] = last[i];
+#pragma unroll 1
+        for (int c = 0; c < 4; ++c) {
+            double v[4];
+            quad_corner(kc.fc, kc.sa, (int)(last[i] >> 2), (int)(last[i] & 3u), c, v);
+            for (int j = 0; j < 4; ++j) kc.sil.quads[at].v[c][j] = v[j];
         }
     }
 }

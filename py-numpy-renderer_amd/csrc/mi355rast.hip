@@ -88,6 +88,7 @@ constexpr int EVENT_RING = 512, N_MARKS = 6;     // (bench.py marks one frame in
 // Everything one in-flight frame writes.
 struct FrameSlot {
     hipStream_t stream = nullptr;                 // the stream this slot serves
+    int id = 0;                                   // its index among the scene's slots
     DevBuf d_vout, d_vclip, d_tris, d_clips, d_status, d_count_list, d_quads, d_sil, d_counters;
     DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_work, d_tile_stats, d_hist, d_split;
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
@@ -150,6 +151,56 @@ struct FrameSlot {
 };
 
 constexpr int MAX_SLOTS = 32;
+
+// The silhouette cache of a scene (kernels_geometry.h, SilArgs).  Which edges are on the silhouette and where their shadow
+// quads stand in world space depends on the light and the geometry alone, so frames that only move the camera read both
+// back.  The key is every byte the two steps read of the frame: the light's type, position AND direction (the
+// light-facing test reads the position of a directional light too), compared as bytes.  The geometry is not in the
+// key: commit() drops the cache whenever it rebuilds the static records.
+//   * A key seen on two consecutive frames is captured: that frame's fused edge path also stores its entries, and its
+//     stream copies the count to pinned memory and records an event.  Nobody waits: enqueues poll the event while a
+//     capture is pending, and only a buffer whose event the HOST has seen complete is read -- so a reader on another
+//     stream needs no hipStreamWaitEvent.
+//   * Two buffers.  A buffer is captured into only when FREE: never read, or retired -- an event recorded on every
+//     stream that read it, behind its last reader -- and those events seen complete.  If none is free, no capture.
+struct SilKey { int32_t light_type, pad; double pos[3], dir[3]; };
+struct SilCache {
+    enum State { FREE, CAPTURING, VALID, RETIRING };
+    struct Buf {
+        DevBuf quads, last;
+        uint32_t cap = 0, count = 0;
+        State state = FREE;
+        SilKey key = {};
+        hipEvent_t captured = nullptr;
+        uint32_t *h_count = nullptr;              // pinned: the capture frame's silhouette count
+        uint32_t readers = 0;                     // bit per frame slot that has enqueued a frame reading it
+        uint64_t used = 0;                        // the scene's frame serial when it was last read
+        hipEvent_t retire[MAX_SLOTS] = {};
+        uint32_t retiring = 0;                    // RETIRING: the slots whose event is still awaited
+    } buf[2];
+    SilKey last_key = {};
+    bool have_last = false;
+    int pending = 0;                              // buffers CAPTURING or RETIRING: only then are events polled
+    int last_path = -1;                           // mr_debug_sil_cache: SIL_* of the last frame with shadows
+    uint32_t last_entries = 0, captures = 0;
+
+    void drop()                                   // (the device is idle: commit, mr_scene_clear)
+    {
+        for (Buf &b : buf) { b.state = FREE; b.readers = b.retiring = 0; b.count = 0; }
+        have_last = false; pending = 0;
+    }
+    void release()
+    {
+        drop();
+        for (Buf &b : buf) {
+            b.quads.release(); b.last.release(); b.cap = 0;
+            if (b.captured) (void)hipEventDestroy(b.captured);
+            if (b.h_count) (void)hipHostFree(b.h_count);
+            for (hipEvent_t &e : b.retire) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+            b.captured = nullptr; b.h_count = nullptr;
+        }
+    }
+};
 
 }  // namespace
 
@@ -215,6 +266,7 @@ struct mr_scene {
     uint64_t frame_serial = 0;               // frames enqueued on any stream
     mr_stats stats = {};
     int n_silhouette = 0;
+    SilCache sil;
     // Capacities of the per-frame work lists, shared by all slots: what one frame learnt (a tile with
     // a longer list, more silhouette edges) holds for the frames rendered on other streams too.
     uint32_t bin_cap[mr::BIN_CLASSES] = { 512u, 128u, 256u };   // entries per tile and class
@@ -369,6 +421,7 @@ int commit(mr_scene *sc)
 {
     if (!sc->dirty) return MR_OK;
     HIP_TRY(hipDeviceSynchronize());          // no frame may still be reading the old arrays
+    sc->sil.drop();                           // the silhouette belongs to the geometry that is about to be replaced
     if (!sc->d_gamma.p) {
         const std::vector<float> lut = gamma_thresholds();
         HIP_TRY(sc->d_gamma.ensure(lut.size() * sizeof(float)));
@@ -444,6 +497,7 @@ FrameSlot *slot_for(mr_scene *sc, hipStream_t stream)
     sc->slots.emplace_back(new (std::nothrow) FrameSlot());
     if (!sc->slots.back()) { sc->slots.pop_back(); return nullptr; }
     sc->slots.back()->stream = stream;
+    sc->slots.back()->id = (int)sc->slots.size() - 1;
     return sc->slots.back().get();
 }
 
@@ -756,6 +810,85 @@ int finish_overlay(mr_scene *sc, FrameSlot *fs, uint8_t *d_out)
     return MR_OK;
 }
 
+// Which path the edge half of this frame's k_setup takes (SilCache).  Returns the buffer the frame captures into, or
+// nullptr: the caller then copies the count out and records the buffer's event behind k_setup.
+SilCache::Buf *choose_silhouette_path(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, mr::SilArgs &sil)
+{
+    SilCache &c = sc->sil;
+    sil = mr::SilArgs{};
+    sil.mode = mr::SIL_FUSED;
+    {
+        const char *env = getenv("MR_SIL_CACHE");            // (looked up per frame: the tests switch it)
+        if (env && !strcmp(env, "0")) { c.last_path = mr::SIL_FUSED; c.last_entries = 0; c.have_last = false; return nullptr; }
+    }
+    SilKey key;
+    std::memset(&key, 0, sizeof key);
+    key.light_type = fc.light_type;
+    std::memcpy(key.pos, fc.light_pos, sizeof key.pos);
+    std::memcpy(key.dir, fc.light_dir, sizeof key.dir);
+    if (c.pending) {
+        for (SilCache::Buf &b : c.buf) {
+            if (b.state == SilCache::CAPTURING && hipEventQuery(b.captured) == hipSuccess) {
+                b.count = *b.h_count;
+                b.state = b.count <= b.cap ? SilCache::VALID : SilCache::FREE;    // (an overflowed capture is discarded)
+                b.readers = 0;
+                c.pending -= 1;
+            } else if (b.state == SilCache::RETIRING) {
+                for (int i = 0; i < MAX_SLOTS; ++i)
+                    if ((b.retiring >> i & 1u) && hipEventQuery(b.retire[i]) == hipSuccess) b.retiring &= ~(1u << i);
+                if (!b.retiring) { b.state = SilCache::FREE; c.pending -= 1; }
+            }
+        }
+    }
+    const bool repeat = c.have_last && !std::memcmp(&c.last_key, &key, sizeof key);
+    c.last_key = key; c.have_last = true;
+    c.last_path = mr::SIL_FUSED; c.last_entries = 0;
+    bool on_its_way = false;
+    for (SilCache::Buf &b : c.buf) {
+        if (b.state != SilCache::VALID && b.state != SilCache::CAPTURING) continue;
+        if (std::memcmp(&b.key, &key, sizeof key)) continue;
+        if (b.state == SilCache::CAPTURING) { on_its_way = true; continue; }
+        sil.mode = mr::SIL_CACHED; sil.count = b.count;
+        sil.quads = b.quads.as<mr::SilQuad>(); sil.last = b.last.as<uint32_t>();
+        b.readers |= 1u << fs->id;
+        b.used = sc->frame_serial;
+        c.last_path = mr::SIL_CACHED; c.last_entries = b.count;
+        return nullptr;
+    }
+    if (!repeat || on_its_way) return nullptr;
+    // a key worth keeping: into a free buffer; if there is none, the longest unused one starts to retire
+    SilCache::Buf *into = nullptr, *oldest = nullptr;
+    for (SilCache::Buf &b : c.buf) {
+        if (b.state == SilCache::FREE && !into) into = &b;
+        if (b.state == SilCache::VALID && (!oldest || b.used < oldest->used)) oldest = &b;
+    }
+    if (!into && oldest) {
+        oldest->retiring = 0;
+        for (auto &s : sc->slots) {
+            if (!(oldest->readers >> s->id & 1u)) continue;
+            hipEvent_t &e = oldest->retire[s->id];
+            if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
+            if (hipEventRecord(e, s->stream) != hipSuccess) return nullptr;
+            oldest->retiring |= 1u << s->id;
+        }
+        oldest->readers = 0;
+        if (oldest->retiring) { oldest->state = SilCache::RETIRING; c.pending += 1; }
+        else { oldest->state = SilCache::FREE; into = oldest; }
+    }
+    if (!into) return nullptr;
+    if (!into->captured && hipEventCreateWithFlags(&into->captured, hipEventDisableTiming) != hipSuccess) return nullptr;
+    if (!into->h_count && hipHostMalloc((void **)&into->h_count, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return nullptr;
+    const uint32_t cap = fs->quad_cap;
+    if (into->quads.ensure((size_t)cap * sizeof(mr::SilQuad)) != hipSuccess || into->last.ensure((size_t)cap * sizeof(uint32_t)) != hipSuccess)
+        return nullptr;
+    into->cap = cap; into->key = key;
+    sil.mode = mr::SIL_CAPTURE; sil.count = cap;
+    sil.quads = into->quads.as<mr::SilQuad>(); sil.last = into->last.as<uint32_t>();
+    c.last_path = mr::SIL_CAPTURE;
+    c.captures += 1;
+    return into;
+}
+
 int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t *d_out, bool may_defer_overlay = false)
 {
     using namespace mr;
@@ -898,14 +1031,26 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
         const bool dense = spread_env == -1 || (spread_env == -2 && fc.n_edges > (1 << 17));
         const unsigned spread = dense ? EDGE_DENSE : spread_env >= 0 ? (unsigned)std::min(spread_env, 4)
                               : fc.n_edges <= (1 << 15) ? 2u : 1u;
+        constexpr unsigned QS_PER_BLOCK = SETUP_BLOCK / QS_LANES;
+        SilArgs sil = {};
+        SilCache::Buf *capture = shadows && fc.n_edges > 0 ? choose_silhouette_path(sc, fs, fc, sil) : nullptr;
         const unsigned edge_blocks = !(shadows && fc.n_edges > 0) ? 0u
+                                   : sil.mode == SIL_CACHED ? (sil.count + QS_PER_BLOCK - 1) / QS_PER_BLOCK     // quad workgroups
                                    : dense ? blocks_for(fc.n_edges, 2 * SETUP_BLOCK) : blocks_for((long long)fc.n_edges << spread, SETUP_BLOCK);
         SetupKernArgs ska;
-        ska.fc = fc; ska.sa = sa; ska.bins = ba; ska.face_blocks = face_blocks; ska.edge_spread = spread;
+        ska.fc = fc; ska.sa = sa; ska.bins = ba; ska.face_blocks = face_blocks; ska.edge_spread = sil.mode == SIL_CACHED ? EDGE_CACHED : spread; ska.sil = sil;
         if (vertex_mfma)
             hipLaunchKernelGGL(k_setup<true>, dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
         else
             hipLaunchKernelGGL(k_setup<false>, dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
+        if (capture) {
+            // the count follows on this stream; the buffer is read once the host has seen the event complete
+            hipError_t e = hipMemcpyAsync(capture->h_count, &ctr->n_quads, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipEventRecord(capture->captured, stream);
+            if (e != hipSuccess) return fail(MR_E_DEVICE, std::string("silhouette capture: ") + hipGetErrorString(e));
+            capture->state = SilCache::CAPTURING;
+            sc->sil.pending += 1;
+        }
     }
     if (all_marks) HIP_TRY(hipEventRecord(fs->ev[2], stream));
 
@@ -1171,6 +1316,7 @@ int mr_scene_clear(mr_scene *sc)
     sc->edge_ids.clear(); sc->edge_raw.clear();
     sc->dirty = true;
     sc->last = nullptr;
+    sc->sil.drop();
     sc->reset_caps();
     for (auto &fs : sc->slots) fs->reset_caps();
     return MR_OK;
@@ -1197,6 +1343,7 @@ void mr_scene_destroy(mr_scene *sc)
                        };
     for (DevBuf *b : bufs) b->release();
     for (auto &fs : sc->slots) fs->release();
+    sc->sil.release();
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     delete sc;
 }
@@ -1766,6 +1913,15 @@ int mr_debug_clusters_culled(mr_scene *sc)
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(fs->stream));
     return (int)fs->h_counters->pad0[0];
+}
+
+int mr_debug_sil_cache(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    out[0] = sc->sil.last_path; out[1] = (int32_t)sc->sil.last_entries; out[2] = (int32_t)sc->sil.captures;
+    out[3] = 0;
+    for (const SilCache::Buf &b : sc->sil.buf) out[3] += b.state == SilCache::VALID ? 1 : 0;
+    return MR_OK;
 }
 
 int mr_debug_read_tile_order(mr_scene *sc, uint32_t *out, int32_t cap_tiles)

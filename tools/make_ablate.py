@@ -65,8 +65,16 @@ s = s.replace("namespace mr {\n", "#ifndef MR_ABLATE\n#define MR_ABLATE 0\n#endi
               "slot_[k] = (unsigned int)(__builtin_amdgcn_s_memrealtime() - dbg_t0_local) + 1u; if ((k) == 0) slot_[7] = (unsigned int)dbg_t0_local; } } while (0)\n", 1)
 # the stamps need the wave's start time in scope of both functions: a per-thread variable declared at file scope is not
 # possible on the device, so edge_block's start time is passed through a thread-local register variable
-s = s.replace("__device__ __forceinline__ void quad_setup_group(bool have,", "__device__ __forceinline__ void quad_setup_group(unsigned long long dbg_t0_local, bool have,")
-s = s.replace("        quad_setup_group(have, (int)(ls >> 2)", "        quad_setup_group(dbg_t0_local, have, (int)(ls >> 2)")
+# (the stamps [1]..[4] sit in the back half of the quad set-up, which the fused path and the cached one share: a quad
+# workgroup of a frame that reads the silhouette cache stamps [0] when its entry has been asked for and [5] at its end)
+for a, b in [
+    ("__device__ __forceinline__ void quad_finish_group(bool have,", "__device__ __forceinline__ void quad_finish_group(unsigned long long dbg_t0_local, bool have,"),
+    ("        quad_finish_group(have, v, base_raw,", "        quad_finish_group(dbg_t0_local, have, v, base_raw,"),
+    ("    quad_finish_group(have, v, 0u, at, quad_scratch(wv));\n", "    DBG_T(0);\n    quad_finish_group(dbg_t0_local, have, v, 0u, at, quad_scratch(wv));\n    __builtin_amdgcn_s_waitcnt(0); DBG_T(5);\n"),
+    ("__device__ __forceinline__ void quad_block(uint32_t block)\n{\n", "__device__ __forceinline__ void quad_block(uint32_t block)\n{\n    const unsigned long long dbg_t0_local = __builtin_amdgcn_s_memrealtime();\n"),
+]:
+    assert s.count(a) == 1, a
+    s = s.replace(a, b)
 s = s.replace("    g_dbg_t0 = __builtin_amdgcn_s_memrealtime();\n", "    const unsigned long long dbg_t0_local = __builtin_amdgcn_s_memrealtime();\n")
 s = s.replace("__device__ __forceinline__ void edge_block(uint32_t block)\n{\n", "__device__ __forceinline__ void edge_block(uint32_t block)\n{\n    const unsigned long long dbg_t_block = __builtin_amdgcn_s_memrealtime(); (void)dbg_t_block;\n")
 open(p, "w").write(s)
