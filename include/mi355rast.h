@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 3
+#define MR_ABI_VERSION 4
 
 enum {
     MR_OK = 0,
@@ -171,7 +171,7 @@ int mr_device_available(void);
 int mr_abi_version(void);
 
 /* sizeof() of the ABI structs as this build sees them (0 mr_frame_desc, 1 mr_material,
- * 2 mr_model_desc, 3 mr_stats, 4 mr_overlay_desc; -1 otherwise), so a binding can verify its own layout. */
+ * 2 mr_model_desc, 3 mr_stats, 4 mr_overlay_desc, 5 mr_light_desc; -1 otherwise), so a binding can verify its own layout. */
 int mr_abi_struct_size(int which);
 
 /* Scene() -- obj/core.py:563-582.  Returns NULL on failure. */
@@ -193,6 +193,29 @@ int mr_scene_add_model(mr_scene *scene, const mr_model_desc *model);
 
 /* Drops all models and textures (keeps device allocations for reuse). */
 int mr_scene_clear(mr_scene *scene);
+
+/* More than one light (an addition: the reference's Scene has exactly one).  The frame descriptor's light stays light 0;
+ * this sets lights 1 .. n of every frame enqueued afterwards (0 <= n <= MR_MAX_LIGHTS - 1; copied during the call;
+ * n = 0: plain frames again).  With L_0 .. L_n the frame's lights, F_k the float frame the same scene gives with L_k as
+ * its only light and W the winner map (which does not depend on the light), the frame is
+ *     F[p] = min(F_0[p] + F_1[p] + ... + F_n[p], 1)   (float32 adds in this order)   where a face covers p,
+ *     F[p] = F_0[p]                                    (background / skybox)           elsewhere,
+ * then overlay and finalise (or resolve) as for any frame.  Every F_k keeps the reference's clip(0.05, 1), so a pixel
+ * no light reaches shows 0.05 per light.  Visibility runs once; every light has its own silhouette, shadow quads and
+ * stencil count (mr_read_stencil_light / mr_read_silhouette_light).  mr_stats: frag_tri, covered_px, n_faces*,
+ * tri_bin_entries as for one light; frag_quad, stencil_updates, lit_px, n_quads, n_quads_drawn, quad_bin_entries are sums
+ * over the lights.  Frames of a scene with extra lights refuse MR_FRAME_FACE_STATUS and stripe_count > 1 (MR_E_INVALID)
+ * and neither read nor fill the silhouette cache. */
+#define MR_MAX_LIGHTS 4
+typedef struct mr_light_desc {
+    int32_t type;                   /* MR_LIGHT_* */
+    int32_t pad;
+    double pos[3], dir[3], color[3], ambient[3];   /* as light_pos / light_dir / light_color / light_ambient of mr_frame_desc */
+    double specular_strength;
+    double att_constant, att_linear, att_quadratic;
+    double spot_edge0, spot_edge1;
+} mr_light_desc;
+int mr_scene_set_extra_lights(mr_scene *scene, const mr_light_desc *lights, int32_t n);
 
 /* Tuning / test hook: capacities of the per-frame work lists -- entries per 16x16 tile for the small
  * triangle pairs, big triangle pairs and shadow quads, and entries of the large primitives' work list;
@@ -328,6 +351,10 @@ int mr_read_face_status(mr_scene *scene, uint8_t *out_faces);  /* MR_FACE_* per 
  * the reference's model.silhouette (obj/triangular.py:294-302).  Returns the number of edges
  * (may exceed cap; only cap are written) or a negative error. */
 int mr_read_silhouette(mr_scene *scene, int32_t *out_triples, int32_t cap);
+/* The same two taps for light k of the last frame (0 = the descriptor's light: what the two above read; 1.. = the
+ * lights of mr_scene_set_extra_lights).  A light's silhouette edges come in no particular order. */
+int mr_read_stencil_light(mr_scene *scene, int32_t light, int16_t *out_hw);
+int mr_read_silhouette_light(mr_scene *scene, int32_t light, int32_t *out_triples, int32_t cap);
 
 /* Diagnostics: the tile kernel's per-tile records of the last frame, MR_TILE_RECORD_WORDS uint32 per tile:
  * [0..4] triangle fragments, quad fragments, stencil updates, covered px, lit px (MR_FRAME_COUNTERS);

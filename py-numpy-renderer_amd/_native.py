@@ -25,7 +25,8 @@ FRAME_NO_TIMING = 128
 FRAME_OVERLAY = 256
 FRAME_SUPERSAMPLE2, FRAME_SUPERSAMPLE4 = 512, 1024
 _SUPERSAMPLE_FLAGS = {1: 0, 2: FRAME_SUPERSAMPLE2, 4: FRAME_SUPERSAMPLE4}
-ABI_VERSION = 3
+ABI_VERSION = 4
+MAX_LIGHTS = 4
 TILE_RECORD_WORDS = 12
 
 
@@ -42,6 +43,26 @@ class FrameDesc(C.Structure):
                 ("att_quadratic", C.c_double), ("spot_edge0", C.c_double), ("spot_edge1", C.c_double),
                 ("background", C.c_float * 3), ("background_u8", C.c_uint32),
                 ("sky_tri", C.c_int32 * 12), ("sky_rays", C.c_double * 18)]
+
+
+class LightDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("pad", C.c_int32),
+                ("pos", C.c_double * 3), ("dir", C.c_double * 3), ("color", C.c_double * 3), ("ambient", C.c_double * 3),
+                ("specular_strength", C.c_double), ("att_constant", C.c_double), ("att_linear", C.c_double),
+                ("att_quadratic", C.c_double), ("spot_edge0", C.c_double), ("spot_edge1", C.c_double)]
+
+
+def fill_light_desc(pl):
+    """``mr_light_desc`` of a ``_pack.PackedLight``."""
+    d = LightDesc()
+    d.type = int(pl.light_type)
+    for name, src in (("pos", pl.light_pos), ("dir", pl.light_dir), ("color", pl.light_color), ("ambient", pl.light_ambient)):
+        for i in range(3):
+            getattr(d, name)[i] = float(src[i])
+    d.specular_strength = pl.specular_strength
+    d.att_constant, d.att_linear, d.att_quadratic = pl.att_constant, pl.att_linear, pl.att_quadratic
+    d.spot_edge0, d.spot_edge1 = pl.spot_edge0, pl.spot_edge1
+    return d
 
 
 class MaterialDesc(C.Structure):
@@ -89,6 +110,9 @@ _PROTOTYPES = {
     "mr_scene_set_overlay_cameras": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                C.c_int32, C.c_int32, C.c_int32]),
     "mr_scene_set_list_capacities": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "mr_scene_set_extra_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "mr_read_stencil_light": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_read_silhouette_light": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "mr_render": (C.c_int, [C.c_void_p, C.POINTER(FrameDesc), C.c_void_p, C.POINTER(Stats)]),
     "mr_overlay_state_bytes": (C.c_int64, [C.c_void_p]),
     "mr_overlay_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -156,7 +180,7 @@ def load_library():
             fn.restype, fn.argtypes = res, args
         if lib.mr_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_NAME}: ABI version {lib.mr_abi_version()}, this binding speaks {ABI_VERSION}; rebuild")
-        for which, struct in enumerate((FrameDesc, MaterialDesc, ModelDesc, Stats, OverlayDesc)):
+        for which, struct in enumerate((FrameDesc, MaterialDesc, ModelDesc, Stats, OverlayDesc, LightDesc)):
             if lib.mr_abi_struct_size(which) != C.sizeof(struct):
                 raise RuntimeError(f"{LIB_NAME}: layout of {struct.__name__} differs from the binding "
                                    f"({lib.mr_abi_struct_size(which)} vs {C.sizeof(struct)} bytes); rebuild")
@@ -382,7 +406,11 @@ class DeviceRenderer:
 
         def vec(x):
             return tuple(np.asarray(x, dtype=np.float64).ravel().tolist())
-        return (id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")), tuple(scene.resolution),
+        # lights 1.. (Scene.add_light): everything pack_light reads of them, like the first light's below
+        extras = tuple((id(x), vec(x.position), vec(x.center), vec(x.color), vec(x.ambient), str(x.light_type),
+                        float(x.specular_strength), float(x.constant), float(x.linear), float(x.quadratic))
+                       for x in list(getattr(scene, "lights", [light]))[1:])
+        return (extras, id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")), tuple(scene.resolution),
                 int(scene.system), int(scene.subsystem), bool(shadows), bool(cam.backface_culling), float(cam.near),
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
@@ -401,8 +429,21 @@ class DeviceRenderer:
             # CPython cannot hand their addresses to the objects of a later frame
             cam = scene.camera
             dbg = scene.debug_camera if scene.debug_camera is not None else cam
-            self._packed_refs = (cam, dbg, cam.__dict__.get("MVP"), dbg.__dict__.get("MVP"), scene.light, scene.skybox)
+            self._packed_refs = (cam, dbg, cam.__dict__.get("MVP"), dbg.__dict__.get("MVP"), scene.light, scene.skybox,
+                                 tuple(getattr(scene, "lights", ())))
         return self._packed[1]
+
+    def sync_lights(self, pf):
+        """The scene's extra lights (``mr_scene_set_extra_lights``) for the frames enqueued from now on; handed over
+        again only when they changed."""
+        n = len(pf.extra_lights)
+        key, last = (getattr(self, "_pack_serial", 0), n), getattr(self, "_lights_key", None)
+        if last == key or (n == 0 and (last is None or last[1] == 0)):
+            self._lights_key = key
+            return
+        descs = (LightDesc * max(n, 1))(*[fill_light_desc(x) for x in pf.extra_lights])
+        _check(self.lib.mr_scene_set_extra_lights(self.handle, descs if n else None, n), "mr_scene_set_extra_lights")
+        self._lights_key = key
 
     def render(self, scene, shadows=True, row_band=None, keep_float=False, face_status=False, counters=True,
                keep_buffers=None, stripe=None, timing=True, overlay=False):
@@ -435,6 +476,11 @@ class DeviceRenderer:
         self.sync_scene(scene)
         self.sync_skybox(scene)
         pf = self.packed_frame(scene, shadows)
+        if pf.extra_lights and face_status:
+            raise ValueError("the per-face status is not available with more than one light")
+        if pf.extra_lights and stripe is not None:
+            raise ValueError("striped frames are not available with more than one light")
+        self.sync_lights(pf)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -492,6 +538,9 @@ class DeviceRenderer:
         self.sync_scene(scene)
         self.sync_skybox(scene)
         pf = self.packed_frame(scene, shadows)
+        if pf.extra_lights and stripe is not None:
+            raise ValueError("striped frames are not available with more than one light")
+        self.sync_lights(pf)
         if overlay:
             self.sync_overlay(scene)
         desc = fill_frame_desc(pf, row_band, False, light_timing, counters=counters, stripe=stripe, no_timing=no_timing,
@@ -573,8 +622,12 @@ class DeviceRenderer:
     def read_z(self):
         return self._tap(self.lib.mr_read_z, np.float64)
 
-    def read_stencil(self):
-        return self._tap(self.lib.mr_read_stencil, np.int16)
+    def read_stencil(self, light=0):
+        """The stencil buffer of light *light* of the last frame (0: ``scene.light``)."""
+        h, w = self._frame
+        out = np.empty((h, w), dtype=np.int16)
+        _check(self.lib.mr_read_stencil_light(self.handle, int(light), out.ctypes.data), "mr_read_stencil_light")
+        return out
 
     def read_winner(self):
         return self._tap(self.lib.mr_read_winner, np.int32)
@@ -614,10 +667,11 @@ class DeviceRenderer:
         _check(self.lib.mr_read_face_status(self.handle, out.ctypes.data), "mr_read_face_status")
         return out[:self._n_faces]
 
-    def read_silhouette(self):
-        n = _check(self.lib.mr_read_silhouette(self.handle, None, 0), "mr_read_silhouette")
+    def read_silhouette(self, light=0):
+        """Silhouette edges of light *light* of the last frame as (model, a, b) rows (0: ``scene.light``)."""
+        n = _check(self.lib.mr_read_silhouette_light(self.handle, int(light), None, 0), "mr_read_silhouette_light")
         out = np.empty((max(n, 1), 3), dtype=np.int32)
-        _check(self.lib.mr_read_silhouette(self.handle, out.ctypes.data, n), "mr_read_silhouette")
+        _check(self.lib.mr_read_silhouette_light(self.handle, int(light), out.ctypes.data, n), "mr_read_silhouette_light")
         return out[:n]
 
     def close(self):

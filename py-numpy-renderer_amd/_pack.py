@@ -43,6 +43,25 @@ class PackedModel:
 
 
 @dataclass
+class PackedLight:
+    """One light as the C ABI takes it (``mr_light_desc``; for ``scene.light`` the same fields of ``mr_frame_desc``)."""
+    light_type: int
+    light_pos: np.ndarray
+    light_dir: np.ndarray
+    light_color: np.ndarray
+    light_ambient: np.ndarray
+    specular_strength: float
+    att_constant: float
+    att_linear: float
+    att_quadratic: float
+    spot_edge0: float
+    spot_edge1: float
+
+
+MAX_LIGHTS = 4
+
+
+@dataclass
 class PackedFrame:
     width: int
     height: int
@@ -73,6 +92,8 @@ class PackedFrame:
     # samples per output pixel and axis (Scene.supersample).  width / height / viewport / sky_* above are then the
     # sample grid's: the frame of a twin scene at (s H, s W) with its camera's offsets times s
     supersample: int = 1
+    # lights 1.. of the frame (Scene.add_light), scene.light being light 0: the fields above
+    extra_lights: tuple = ()
 
 
 @dataclass
@@ -122,6 +143,18 @@ def sample_grid(scene):
                                               x_offset=cam.x_offset * s, y_offset=cam.y_offset * s)
 
 
+def pack_light(light) -> PackedLight:
+    kind = light.light_type.value if isinstance(light.light_type, Lightning) else int(light.light_type)
+    return PackedLight(
+        light_type=kind,
+        light_pos=_vec3(light.position), light_dir=_vec3(light.direction),
+        light_color=_vec3(light.color), light_ambient=_vec3(light.ambient),
+        specular_strength=float(light.specular_strength),
+        att_constant=float(light.constant), att_linear=float(light.linear),
+        att_quadratic=float(light.quadratic),
+        spot_edge0=float(np.cos(np.deg2rad(20))), spot_edge1=float(np.cos(np.deg2rad(10))))
+
+
 def pack_frame(scene, shadows=True) -> PackedFrame:
     cam, light = scene.camera, scene.light
     dbg = scene.debug_camera if scene.debug_camera is not None else cam
@@ -138,23 +171,25 @@ def pack_frame(scene, shadows=True) -> PackedFrame:
             raise ValueError("skymap colour must have 3 components")
     else:
         background = np.asarray(_DEFAULT_BACKGROUND, dtype=np.float32)
-    kind = light.light_type.value if isinstance(light.light_type, Lightning) else int(light.light_type)
+    first = pack_light(light)
+    extras = tuple(pack_light(x) for x in list(getattr(scene, "lights", [light]))[1:])
+    if len(extras) > MAX_LIGHTS - 1:
+        raise ValueError(f"a scene has at most {MAX_LIGHTS} lights")
     return PackedFrame(
         width=width, height=height, system=int(scene.system),
-        backface_culling=bool(cam.backface_culling), light_type=kind, shadows=bool(shadows),
+        backface_culling=bool(cam.backface_culling), light_type=first.light_type, shadows=bool(shadows),
         mvp=np.ascontiguousarray(cam.MVP, dtype=np.float64),
         viewport=np.ascontiguousarray(viewport, dtype=np.float64),
         debug_mvp=np.ascontiguousarray(dbg.MVP, dtype=np.float64),
         frustum_planes=np.ascontiguousarray(cam.frustum_planes, dtype=np.float64),
         z_near=float(cam.near), z_far=float(cam.far),
         camera_pos=_vec3(cam.position),
-        light_pos=_vec3(light.position), light_dir=_vec3(light.direction),
-        light_color=_vec3(light.color), light_ambient=_vec3(light.ambient),
-        specular_strength=float(light.specular_strength),
-        att_constant=float(light.constant), att_linear=float(light.linear),
-        att_quadratic=float(light.quadratic),
-        spot_edge0=float(np.cos(np.deg2rad(20))), spot_edge1=float(np.cos(np.deg2rad(10))),
-        background=background, sky_tri=sky_tri, sky_rays=sky_rays, supersample=ss)
+        light_pos=first.light_pos, light_dir=first.light_dir,
+        light_color=first.light_color, light_ambient=first.light_ambient,
+        specular_strength=first.specular_strength,
+        att_constant=first.att_constant, att_linear=first.att_linear, att_quadratic=first.att_quadratic,
+        spot_edge0=first.spot_edge0, spot_edge1=first.spot_edge1,
+        background=background, sky_tri=sky_tri, sky_rays=sky_rays, supersample=ss, extra_lights=extras)
 
 
 def _texture_id(tex, textures, seen):

@@ -426,6 +426,9 @@ class Scene:
       ``resolution`` stays the OUTPUT size, ``render()`` returns ``uint8 (H, W, 3)``; the device taps
       (``read_z`` ...), ``last_stats`` and the ``verbose`` face report count the sample grid.  Neither
       ``resolution`` nor the camera is changed.  Split frames (``multigpu``) refuse s > 1.
+    * ``add_light(light)`` (an addition; up to four lights with ``light``): further shadow-casting lights in the
+      same frame -- visibility once, a stencil pass and an additive lighting pass per light; see ``add_light``.
+      ``verbose`` and split frames (``multigpu``) refuse more than one light.
     """
 
     camera = Bound()
@@ -468,6 +471,39 @@ class Scene:
     def add_model(self, model):
         self.models.append(model)
 
+    # -- more than one light (an addition: upstream's Scene has exactly one) -------------------
+    MAX_LIGHTS = 4
+
+    def add_light(self, light):
+        """A further shadow-casting light, up to four in all.  ``scene.light`` stays light 0.  With F_k the float
+        frame the scene gives with light k alone, a frame shows ``min(F_0 + F_1 + ..., 1)`` where a face covers the
+        pixel (float32 adds, in the order of the lights) and F_0's background elsewhere; every F_k keeps upstream's
+        ``clip(0.05, 1)``, so a pixel no light reaches shows 0.05 per light.  Lights may be of different kinds and
+        are read again at every ``render()``.  A ``show=True`` light gets its gizmo like ``scene.light`` does."""
+        if not isinstance(light, Light):
+            raise TypeError(f"add_light expects a Light, got {type(light).__name__}")
+        extra = self.__dict__.setdefault("_extra_lights", [])
+        if 1 + len(extra) >= self.MAX_LIGHTS:
+            raise ValueError(f"a scene has at most {self.MAX_LIGHTS} lights")
+        light.scene = self
+        if getattr(light, "show", False):
+            self.add_model(_gizmo(light))
+        extra.append(light)
+
+    @property
+    def lights(self):
+        """``[scene.light, *extra lights]`` (a copy: change the set with ``add_light`` / ``clear_lights``)."""
+        return [self.light, *self.__dict__.get("_extra_lights", ())]
+
+    def clear_lights(self):
+        """Drops the lights added with ``add_light``; ``scene.light`` stays."""
+        self.__dict__["_extra_lights"] = []
+
+    def _check_lights(self):
+        if len(self.lights) > 1 and self.verbose:
+            raise ValueError("scene.verbose is not available with more than one light: upstream's per-face status "
+                             "depends on the one stencil buffer")
+
     # -- rendering ------------------------------------------------------------------------
     def _backend(self):
         if self._renderer is None:
@@ -485,6 +521,7 @@ class Scene:
         the three lines the reference prints per model after its lit pass (``obj/core.py:634-636``)
         are reproduced from the device's per-face codes.  With ``scene.supersample`` = s > 1 the frame is the
         s x s box-filtered mean of the sample grid (class docstring); *row_band* counts output rows."""
+        self._check_lights()
         backend = self._backend()
         report = self.verbose and row_band is None
         # the debug camera's frustum, drawn by the device into its own frame and z-buffer right after the
@@ -504,6 +541,7 @@ class Scene:
         ``render()`` would have returned).  Up to four frames may be pending on one scene; the copy of frame i
         (longer than the frame's kernels at 1080p) then runs beside the kernels of frame i + 1 and beside the
         host's preparation of frame i + 2.  The reference has no such call: it is an addition for sequences."""
+        self._check_lights()
         backend = self._backend()
         pending = self.__dict__.setdefault("_pending", {})
         lane = next((k for k in range(backend.ASYNC_LANES) if k not in pending), None)

@@ -323,7 +323,8 @@ struct SilArgs {
     uint32_t *last;                  // (face << 2 | corner) per entry
     uint32_t mode, count;            // SIL_*; SIL_CACHED: entries.  SIL_CAPTURE: capacity of the two arrays
 };
-struct SetupKernArgs { FrameConst fc; SetupArgs sa; BinArgs bins; uint32_t face_blocks; uint32_t edge_spread; SilArgs sil; };
+// (lights: behind everything else, read by the multi-light instantiation's edge workgroups only)
+struct SetupKernArgs { FrameConst fc; SetupArgs sa; BinArgs bins; uint32_t face_blocks; uint32_t edge_spread; SilArgs sil; FrameLights lights; };
 #define SETUP_ARGS() const SetupKernArgs &ka_ = kernargs<SetupKernArgs>(); const FrameConst &fc = ka_.fc; \
                      const SetupArgs &sa = ka_.sa; const BinArgs &bins = ka_.bins; (void)fc; (void)sa; (void)bins
 
@@ -720,7 +721,8 @@ __device__ __forceinline__ double (*quad_scratch(int wv))[MAX_POLY + 4][4]
 
 // Corner c (0..3 = A, B, D, C) of the shadow quad of the edge that starts at corner sil_k of face sil_f: the edge's two
 // ends, and the same two pushed away from the light (obj/core.py:612-621)
-__device__ __forceinline__ void quad_corner(const FrameConst &fc, const SetupArgs &sa, int sil_f, int sil_k, int c, double v[4])
+__device__ __forceinline__ void quad_corner(const FrameConst &fc, const SetupArgs &sa, int light_type, const double *light_pos,
+                                            const double *light_dir, int sil_f, int sil_k, int c, double v[4])
 {
     const int corner = (c == 0 || c == 3) ? sil_k : (sil_k + 1) % 3;       // A, B, D, C: the edge's first / second end
     if (fc.pos32) {
@@ -731,13 +733,13 @@ __device__ __forceinline__ void quad_corner(const FrameConst &fc, const SetupArg
         for (int j = 0; j < 4; ++j) v[j] = src[j];
     }
     if (c >= 2) {
-        if (fc.light_type == MR_LIGHT_POINT) {
-            double d[4] = { v[0] - fc.light_pos[0], v[1] - fc.light_pos[1], v[2] - fc.light_pos[2], v[3] - 1.0 };
+        if (light_type == MR_LIGHT_POINT) {
+            double d[4] = { v[0] - light_pos[0], v[1] - light_pos[1], v[2] - light_pos[2], v[3] - 1.0 };
             double l = sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]);
             if (l == 0) l = 1;
             for (int j = 0; j < 4; ++j) v[j] = v[j] + 1000 * (d[j] / l);
         } else {
-            for (int j = 0; j < 3; ++j) v[j] = v[j] + fc.light_dir[j] * -1000;
+            for (int j = 0; j < 3; ++j) v[j] = v[j] + light_dir[j] * -1000;
             v[3] = v[3] + 1.0;
         }
     }
@@ -751,14 +753,25 @@ __device__ __forceinline__ void quad_extrude_group(bool have, int sil_f, int sil
     for (int j = 0; j < 4; ++j) v[j] = 0;
     SETUP_ARGS();                                                // phase: the edge's corners, extrusion
     if (have && gl < 4) {
-        quad_corner(fc, sa, sil_f, sil_k, gl, v);
+        quad_corner(fc, sa, fc.light_type, fc.light_pos, fc.light_dir, sil_f, sil_k, gl, v);
+    }
+}
+// The same for light k of a frame with several (FrameLights); k is the same in every lane.
+__device__ __forceinline__ void quad_extrude_group_ml(bool have, int sil_f, int sil_k, int k, double v[4])
+{
+    const int gl = (threadIdx.x & (WAVE - 1)) % QS_LANES;
+    for (int j = 0; j < 4; ++j) v[j] = 0;
+    const SetupKernArgs &ka = kernargs<SetupKernArgs>();         // phase: the edge's corners, extrusion
+    if (have && gl < 4) {
+        const LightRec &l = ka.lights.l[k];
+        quad_corner(ka.fc, ka.sa, l.type, l.pos, l.dir, sil_f, sil_k, gl, v);
     }
 }
 
 // Back half: clipping, projection, plane, pixel box, work items and the record of the quad whose corners lanes 0..3 of the
 // group hold in v (from quad_extrude_group, or from the silhouette cache).
 __device__ __forceinline__ void quad_finish_group(bool have, double v[4], uint32_t s_base_raw, uint32_t s_rank,
-                                                  double (*s_poly)[MAX_POLY + 4][4])
+                                                  double (*s_poly)[MAX_POLY + 4][4], uint32_t light = 0u)
 {
     const int lane = threadIdx.x & (WAVE - 1);
     const int grp = lane / QS_LANES, gl = lane % QS_LANES, g0 = grp * QS_LANES;
@@ -890,7 +903,7 @@ __device__ __forceinline__ void quad_finish_group(bool have, double v[4], uint32
         q.n = n;
         q.edge = (int32_t)s_idx;                  // (the silhouette list's atomic has had the whole set-up to come back)
         q.x0 = (int16_t)bx0; q.x1 = (int16_t)bx1; q.y0 = (int16_t)by0; q.y1 = (int16_t)by1;
-        q.pad[0] = q.pad[1] = q.pad[2] = 0;
+        q.light = light; q.pad[0] = q.pad[1] = 0;
     }
 }
 
@@ -1042,8 +1055,124 @@ __device__ __forceinline__ void edge_block(uint32_t block)
 #pragma unroll 1
         for (int c = 0; c < 4; ++c) {
             double v[4];
-            quad_corner(kc.fc, kc.sa, (int)(last[i] >> 2), (int)(last[i] & 3u), c, v);
+            quad_corner(kc.fc, kc.sa, kc.fc.light_type, kc.fc.light_pos, kc.fc.light_dir, (int)(last[i] >> 2), (int)(last[i] & 3u), c, v);
             for (int j = 0; j < 4; ++j) kc.sil.quads[at].v[c][j] = v[j];
+        }
+    }
+}
+
+// Edge workgroup of a frame with several lights (FrameLights; k_setup<., true>): the edge records are loaded ONCE and
+// tested against every light -- per light and incident face one dot, what the records were laid out for -- and every
+// (silhouette edge, light) pair gets a shadow quad through the same two halves as above.  The lights take their turns
+// one after the other, each with the plain path's bookkeeping: one atomic on n_quads per wavefront and light, records
+// and sil_edges at the silhouette index, so a light's entries are scattered over the one list and carry its index (the
+// QuadRec's `light`, bits 2.. of the list's corner word).  Such frames neither read nor fill the silhouette cache.
+__device__ __forceinline__ void edge_block_ml(uint32_t block)
+{
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    int n_lights;
+    uint32_t lit_odd = 0;                            // bit 4 i + k: the lane's edge i is on light k's silhouette
+    uint32_t last[2][MAX_LIGHTS] = {};
+    {
+        const SetupKernArgs &ka = kernargs<SetupKernArgs>();
+        const FrameConst &fc = ka.fc;
+        const SetupArgs &sa = ka.sa;
+        n_lights = min(max(ka.lights.n, 1), MAX_LIGHTS);
+        const uint32_t spread = ka.edge_spread;
+        const bool dense = spread == EDGE_DENSE;
+        const uint32_t slot_in_grid = block * blockDim.x + threadIdx.x;
+        int e[2];
+        bool want[2];
+        if (dense) {
+            e[0] = (int)(block * 2u * blockDim.x + threadIdx.x); e[1] = e[0] + (int)blockDim.x;
+            want[0] = e[0] < fc.n_edges; want[1] = e[1] < fc.n_edges;
+        } else {
+            e[0] = (int)(slot_in_grid >> spread); e[1] = 0;
+            want[0] = (slot_in_grid & ((1u << spread) - 1u)) == 0 && e[0] < fc.n_edges; want[1] = false;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (!want[i]) continue;
+            EdgeRec r;
+            if (fc.edge_compact) {
+                const EdgeRec32 c = reinterpret_cast<const EdgeRec32 *>(sa.edges)[e[i]];
+                r.inc[0] = c.inc[0]; r.inc[1] = c.inc[1];
+                r.extra_off = r.extra_cnt = 0;
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) r.n[a][j] = (double)c.n[a][j];
+            } else {
+                r = sa.edges[e[i]];
+            }
+#pragma unroll
+            for (int k = 0; k < MAX_LIGHTS; ++k) {
+                if (k >= n_lights) break;
+                const double *lp = ka.lights.l[k].pos;
+                uint32_t cnt = 0;
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    if (r.inc[a] != 0xffffffffu && chain3(r.n[a][0], r.n[a][1], r.n[a][2], lp[0], lp[1], lp[2]) > 0) {
+                        ++cnt; last[i][k] = r.inc[a];
+                    }
+                }
+                for (uint32_t x = 0; x < r.extra_cnt; ++x) {
+                    const uint32_t inc = sa.edge_inc[r.extra_off + x];
+                    const double *fn = sa.face_n + (size_t)(inc >> 2) * 4;
+                    if (chain3(fn[0], fn[1], fn[2], lp[0], lp[1], lp[2]) > 0) { ++cnt; last[i][k] = inc; }
+                }
+                lit_odd |= (cnt & 1u) << (4 * i + k);
+            }
+        }
+    }
+    if (!__ballot(lit_odd != 0)) return;
+    const int grp = lane / QS_LANES;
+#pragma unroll
+    for (int k = 0; k < MAX_LIGHTS; ++k) {            // (unrolled: last[.][k] stays in registers)
+        if (k >= n_lights) break;
+        const bool sil[2] = { (lit_odd >> k & 1u) != 0, (lit_odd >> (4 + k) & 1u) != 0 };
+        unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);
+        if (!(todo0 | todo1)) continue;
+        const uint32_t found0 = (uint32_t)__popcll(todo0), found = found0 + (uint32_t)__popcll(todo1);
+        uint32_t base_raw = 0;
+        if (lane == 0) base_raw = atomicAdd(&kernargs<SetupKernArgs>().sa.ctr->n_quads, found);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const uint32_t my_rank0 = (uint32_t)__popcll(todo0 & below), my_rank1 = found0 + (uint32_t)__popcll(todo1 & below);
+        while (todo0 | todo1) {                       // four silhouette edges per round, as in edge_block
+            int src = -1, set = 0;
+            {
+                const int c0 = (int)__popcll(todo0);
+                unsigned long long t = grp < c0 ? todo0 : todo1;
+                const int nth = grp < c0 ? grp : grp - c0;
+                set = grp < c0 ? 0 : 1;
+                for (int g = 0; g <= nth && t; ++g) {
+                    const int b = __ffsll((long long)t) - 1;
+                    t &= t - 1;
+                    if (g == nth) src = b;
+                }
+            }
+            for (int g = 0; g < WAVE / QS_LANES; ++g) {
+                if (todo0) todo0 &= todo0 - 1;
+                else if (todo1) todo1 &= todo1 - 1;
+            }
+            const bool have = src >= 0;
+            const int from = have ? src : 0;
+            const uint32_t l0 = (uint32_t)__shfl((int)last[0][k], from), l1 = (uint32_t)__shfl((int)last[1][k], from);
+            const uint32_t r0 = (uint32_t)__shfl((int)my_rank0, from), r1 = (uint32_t)__shfl((int)my_rank1, from);
+            const uint32_t ls = set ? l1 : l0, rank = set ? r1 : r0;
+            double v[4];
+            quad_extrude_group_ml(have, (int)(ls >> 2), (int)(ls & 3u), k, v);
+            quad_finish_group(have, v, base_raw, rank, quad_scratch(wv), (uint32_t)k);
+        }
+        const uint32_t base = (uint32_t)__shfl((int)base_raw, 0);
+        const SetupArgs &sa2 = kernargs<SetupKernArgs>().sa;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t my_slot = base + (i ? my_rank1 : my_rank0);
+            if (sil[i] && my_slot < sa2.quad_cap) {
+                sa2.sil_edges[my_slot * 2 + 0] = (int32_t)(last[i][k] >> 2);
+                sa2.sil_edges[my_slot * 2 + 1] = (int32_t)((last[i][k] & 3u) | ((uint32_t)k << SIL_LIGHT_SHIFT));
+            }
         }
     }
 }
@@ -1053,7 +1182,9 @@ __device__ __forceinline__ void edge_block(uint32_t block)
 #ifndef MR_SETUP_WAVES
 #define MR_SETUP_WAVES 5
 #endif
-template <bool PRE_XFORM>
+// ML: a frame with several lights -- its edge workgroups are edge_block_ml's.  An instantiation of its own so that
+// the plain frame's kernel is the code it was.
+template <bool PRE_XFORM, bool ML>
 __global__ void __launch_bounds__(SETUP_BLOCK, MR_SETUP_WAVES)
 k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(), phase by phase
 {
@@ -1065,6 +1196,7 @@ k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(
     }
     const uint32_t b = blockIdx.x - 1;
     if (b < face_blocks) tri_setup_block<PRE_XFORM>(b);
+    else if (ML) edge_block_ml(b - face_blocks);
     else edge_block(b - face_blocks);
 }
 

@@ -165,6 +165,21 @@ __device__ __forceinline__ LightConst light_const(const FrameConst &fc)
     lc.light_type = fc.light_type;
     return lc;
 }
+// light k of a frame with several (the camera is not the light's: shade_light<true> does not read it)
+__device__ __forceinline__ LightConst light_const(const LightRec &l)
+{
+    LightConst lc;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        lc.camera_pos[j] = 0.0; lc.light_pos[j] = l.pos[j]; lc.light_dir[j] = l.dir[j];
+        lc.light_color[j] = l.color[j]; lc.light_ambient[j] = l.ambient[j];
+    }
+    lc.specular_strength = l.specular_strength;
+    lc.att_constant = l.att_constant; lc.att_linear = l.att_linear; lc.att_quadratic = l.att_quadratic;
+    lc.spot_edge0 = l.spot_edge0; lc.spot_edge1 = l.spot_edge1;
+    lc.light_type = l.type;
+    return lc;
+}
 
 __device__ __forceinline__ double clip01(double v) { return v < 0.05 ? 0.05 : (v > 1.0 ? 1.0 : v); }
 
@@ -194,8 +209,22 @@ __device__ __forceinline__ void load_shaded_face(const ShadeArgs &sh, bool pos32
     sf.attr = sh.face_attr + face;
 }
 
-__device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &t, const ShadedFace &sf, const Material &mat,
-                                            int px, int py, bool lit, float rgb[3])
+// Shading comes in two halves.  shade_surface: what does not depend on the light -- barycentrics, texture coordinates,
+// the (unnormalised) normal where some light will need it, the diffuse colour and the fragment's position.
+// shade_light: one light's contribution to it, the reference's clip(0.05, 1) included.  A plain frame runs one after the
+// other (shade_pixel); a frame with several lights runs the first once and the second once per light, with the three
+// things of the lit branch that do not depend on the light either -- unit normal, view vector, specular colour --
+// worked out once in between (shade_lit_surface) and handed in (PRE).
+struct Surface {
+    double tu, tv;
+    double raw[3];
+    bool raw_is_unit;
+    double color[3], pos[3];
+};
+struct LitSurface { double N[3], V[3], spec_light[3]; };
+
+__device__ __forceinline__ void shade_surface(const TriRec &t, const ShadedFace &sf, const Material &mat,
+                                              int px, int py, bool lit, Surface &s)
 {
     const FaceAttr &at = *sf.attr;
     const uint8_t ff = (uint8_t)(t.flags >> 8);
@@ -296,12 +325,53 @@ __device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &
     } else {
         color[0] = mat.kd[0]; color[1] = mat.kd[1]; color[2] = mat.kd[2];
     }
-    double pos[3], dl[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        pos[j] = chain3(p[0], p[1], p[2], wa[j], wb[j], wc[j]);
-        dl[j] = fc.light_pos[j] - pos[j];
+        s.pos[j] = chain3(p[0], p[1], p[2], wa[j], wb[j], wc[j]);
+        s.color[j] = color[j]; s.raw[j] = raw[j];
     }
+    s.tu = tu; s.tv = tv; s.raw_is_unit = raw_is_unit;
+}
+
+__device__ __forceinline__ void surface_normal(const Surface &s, double N[3])
+{
+    if (s.raw_is_unit) { N[0] = s.raw[0]; N[1] = s.raw[1]; N[2] = s.raw[2]; }
+    else c_normalize3(s.raw, N);
+}
+__device__ __forceinline__ void surface_view(const double camera_pos[3], const Surface &s, double V[3])
+{
+    double tmp[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) tmp[j] = camera_pos[j] - s.pos[j];
+    c_normalize3(tmp, V);
+}
+__device__ __forceinline__ void surface_specular(const Surface &s, const Material &mat, double spec_light[3])
+{
+    if (mat.map_ks.rgb) {
+        const float *tx = texel(mat.map_ks, s.tu, s.tv);
+        const float sp = tx[0] * 255.0f;              // float32 product (obj/core.py:149)
+        spec_light[0] = spec_light[1] = spec_light[2] = (double)sp;
+    } else {
+        spec_light[0] = mat.ks255[0]; spec_light[1] = mat.ks255[1]; spec_light[2] = mat.ks255[2];
+    }
+}
+__device__ __forceinline__ void shade_lit_surface(const double camera_pos[3], const Surface &s, const Material &mat, LitSurface &ls)
+{
+    surface_normal(s, ls.N);
+    surface_view(camera_pos, s, ls.V);
+    surface_specular(s, mat, ls.spec_light);
+}
+
+// PRE: `pre` holds the lit branch's light-independent values (else they are worked out here, where shade_pixel always did)
+template <bool PRE>
+__device__ __forceinline__ void shade_light(const LightConst &fc, const Surface &s, const Material &mat, bool lit,
+                                            const LitSurface *pre, float rgb[3])
+{
+    const double *pos = s.pos;
+    double color[3] = { s.color[0], s.color[1], s.color[2] };
+    double dl[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dl[j] = fc.light_pos[j] - pos[j];
     // Light.attenuation (obj/core.py:517-524)
     const double dl2 = (dl[0] * dl[0] + dl[1] * dl[1]) + dl[2] * dl[2];
     const double dist = dl2 > 0 ? dl2 * c_rsqrt(dl2) : 0.0;
@@ -313,8 +383,8 @@ __device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &
         return;
     }
     double N[3], L[3], V[3], Hh[3], tmp[3];
-    if (raw_is_unit) { N[0] = raw[0]; N[1] = raw[1]; N[2] = raw[2]; }
-    else c_normalize3(raw, N);
+    if (PRE) { N[0] = pre->N[0]; N[1] = pre->N[1]; N[2] = pre->N[2]; }
+    else surface_normal(s, N);
 
     // ---- Blinn-Phong (obj/triangular.py:151-171)
     if (fc.light_type == MR_LIGHT_DIRECTIONAL) {
@@ -322,9 +392,8 @@ __device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &
     } else {
         c_normalize3(dl, L);
     }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) tmp[j] = fc.camera_pos[j] - pos[j];
-    c_normalize3(tmp, V);
+    if (PRE) { V[0] = pre->V[0]; V[1] = pre->V[1]; V[2] = pre->V[2]; }
+    else surface_view(fc.camera_pos, s, V);
     if (fc.light_type == MR_LIGHT_SPOT) {
         double x = (sum3(fc.light_dir, L) - fc.spot_edge0) * c_rcp(fc.spot_edge1 - fc.spot_edge0);
         x = x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x);
@@ -333,13 +402,8 @@ __device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &
         for (int j = 0; j < 3; ++j) color[j] = color[j] * in_light;
     }
     double spec_light[3];
-    if (mat.map_ks.rgb) {
-        const float *tx = texel(mat.map_ks, tu, tv);
-        const float s = tx[0] * 255.0f;               // float32 product (obj/core.py:149)
-        spec_light[0] = spec_light[1] = spec_light[2] = (double)s;
-    } else {
-        spec_light[0] = mat.ks255[0]; spec_light[1] = mat.ks255[1]; spec_light[2] = mat.ks255[2];
-    }
+    if (PRE) { spec_light[0] = pre->spec_light[0]; spec_light[1] = pre->spec_light[1]; spec_light[2] = pre->spec_light[2]; }
+    else surface_specular(s, mat, spec_light);
 #pragma unroll
     for (int j = 0; j < 3; ++j) tmp[j] = L[j] + V[j];
     c_normalize3(tmp, Hh);
@@ -353,6 +417,14 @@ __device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &
         const double diff = nl * fc.light_color[j];
         rgb[j] = (float)clip01((att * color[j]) * ((fc.light_ambient[j] + diff) + spec));
     }
+}
+
+__device__ __forceinline__ void shade_pixel(const LightConst &fc, const TriRec &t, const ShadedFace &sf, const Material &mat,
+                                            int px, int py, bool lit, float rgb[3])
+{
+    Surface s;
+    shade_surface(t, sf, mat, px, py, lit, s);
+    shade_light<false>(fc, s, mat, lit, nullptr, rgb);
 }
 
 }  // namespace mr

@@ -21,6 +21,9 @@
 //      one pixel per thread: stencil +-1 in a register (obj/triangular.py:335-368);
 //   4. deferred shading of the winner (kernels_shade.h), finalise, uint8 store.
 //
+// A frame with several lights (k_tile<., ., true>) keeps one stencil count per light in phase 3 and adds the
+// lights' colours in phase 4; see the kernel's ML parameter.
+//
 //   k_reduce_tile_stats   sums the per-tile fragment counts (only when statistics are asked for)
 #pragma once
 
@@ -304,7 +307,13 @@ struct TileArgs {
     uint32_t split_max;                 // ... if no more than this many are (<= HEAVY0_MAX)
 };
 
-struct TileKernArgs { FrameConst fc; TileArgs ta; ShadeArgs sh; };
+// A frame with several lights (k_tile<., ., true>): the lights (all of them, FrameLights) and the stencil taps of
+// lights 1.. (light 0's is TileArgs::stencil).  Behind everything else, like SetupKernArgs::lights.
+struct TileLights {
+    FrameLights lights;
+    int32_t *stencil[MAX_LIGHTS - 1];
+};
+struct TileKernArgs { FrameConst fc; TileArgs ta; ShadeArgs sh; TileLights ml; };
 
 // One workgroup per tile, one pixel per thread.  Tiles are dealt to workgroups in plain
 // row-major order, i.e. round-robin over the XCDs: heavy tiles cluster on the screen, and an
@@ -314,10 +323,17 @@ struct TileKernArgs { FrameConst fc; TileArgs ta; ShadeArgs sh; };
 // SS: a supersampled frame (FrameConst::ss_mode != 0; the host launches SS only then): the uint8 output is written by
 // the resolve of s x s samples, not per sample.  An instantiation of its own so that the plain frame's code is
 // untouched by it (a runtime branch on ss_mode cost the plain c4 frame 1.2 %).
-template <bool SPLIT, bool SS>
+// ML: a frame with several lights (TileLights), an instantiation of its own for the same reason.  Coverage, z and
+// winner are the light's business nowhere, so phases 1 and 2 are the plain frame's; phase 3 walks the tile's ONE quad
+// list once and keeps one stencil count per light (a quad carries its light's index, the same in every lane while the
+// quad is walked); phase 4 works out what of a pixel does not depend on the light once and adds the lights'
+// contributions F_k in float32, in the order of the lights: F = min(F_0 + F_1 + ..., 1), every F_k clipped to
+// [0.05, 1] like the reference's one.  Such frames never split tiles.
+template <bool SPLIT, bool SS, bool ML>
 __global__ void __launch_bounds__(TILE_PX, K_TILE_WAVES)
 k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), phase by phase
 {
+    static_assert(!(SPLIT && ML), "frames with several lights do not split their heavy tiles");
     __shared__ unsigned long long s_key[TILE_PX];
     __shared__ int s_win[TILE_PX];
     __shared__ unsigned int s_cnt[TILE_STATS];
@@ -626,6 +642,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
     // broadcast read).  Adds commute, so the order of the quads never mattered
     // (obj/triangular.py:365-368); the count stays in this thread's register.
     int sten = 0;
+    int sten_x[MAX_LIGHTS - 1] = { 0, 0, 0 };             // ML: lights 1.. (always indexed by constants: registers)
     unsigned int qfrags = 0, qupd = 0;
     // without the counters only the frame is the contract: the stencil matters where a triangle was drawn
     if (n_quad && (counters || __syncthreads_or(covered))) {
@@ -667,6 +684,8 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                                      (uint32_t)__double2loint(b0), (uint32_t)__double2hiint(b0));
                 } else if (piece >= 5 && (piece & 1) && !src->is_front) {
                     val.y ^= 0x80000000u; val.w ^= 0x80000000u;
+                } else if (ML && piece == 2) {
+                    val.w |= src->light << 1;               // beside is_front (0 / 1): the header's last 16 bytes are overwritten above
                 }
                 s_quad[i] = val;
                 if (piece == 0) s_id[q] = id;
@@ -756,7 +775,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 const int x0 = (int)(int16_t)(hb.x & 0xffffu), x1 = (int)(int16_t)(hb.x >> 16);
                 const int y0 = (int)(int16_t)(hb.y & 0xffffu), y1 = (int)(int16_t)(hb.y >> 16);
                 const int nv = (int)hb.z;
-                const bool front = hb.w != 0;
+                const bool front = ML ? (hb.w & 1u) != 0 : hb.w != 0;
                 bool in = live & (px >= x0) & (px < x1) & (py >= y0) & (py < y1);
                 auto d2 = [](uint32_t lo, uint32_t hi) { return __hiloint2double((int)hi, (int)lo); };
                 auto inner = [&](const uint4 &a, const uint4 &b) {       // staged edges: inner side is > 0
@@ -811,7 +830,15 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 }
                 pass = pass && in;
                 qupd += (unsigned int)__popcll(__ballot(pass));
+                if (ML) {
+                    const int lt = __builtin_amdgcn_readfirstlane((int)(hb.w >> 1)), d = pass ? (front ? 1 : -1) : 0;
+                    if (lt == 0) sten += d;
+                    else if (lt == 1) sten_x[0] += d;
+                    else if (lt == 2) sten_x[1] += d;
+                    else sten_x[2] += d;
+                } else {
                 sten += pass ? (front ? 1 : -1) : 0;
+                }
             }
         }
     }
@@ -848,10 +875,32 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
 
     // ---- 4. deferred shading + finalise (kernels_shade.h; obj/core.py:640)
     const bool lit = (int16_t)sten == 0;                  // the reference's buffer is int16
+    unsigned int n_lit = lit ? 1u : 0u;                   // ML: over the frame's lights
     // A supersampled frame's samples are staged in the quad area for the fused resolve at the end of this phase (see
     // there): every wavefront must have left the last quad batch first.
     const bool fused_ss = SS && !(kernargs<TileKernArgs>().fc.ss_mode & SS_SEPARATE);
     if (fused_ss) __syncthreads();
+    // ML: which lights reach the pixel, and the taps of z, winner and the stencil counts right here -- shading then
+    // carries one mask instead of the four counts and the depth (with them it did not fit five wavefronts' registers)
+    unsigned int lit_mask = lit ? 1u : 0u;
+    if (ML) {
+        const TileKernArgs &ka = kernargs<TileKernArgs>();
+        const int n_lights = min(max(ka.ml.lights.n, 1), MAX_LIGHTS);
+#pragma unroll
+        for (int k = 1; k < MAX_LIGHTS; ++k)
+            if (k < n_lights && (int16_t)sten_x[k - 1] == 0) lit_mask |= 1u << k;
+        if (live && ka.ta.zbuf && taps) {
+            int px, py;
+            my_pixel(px, py);
+            const size_t at_px = (size_t)py * ka.fc.width + px;
+            ka.ta.zbuf[at_px] = zbest;
+            ka.ta.winner[at_px] = best;
+            ka.ta.stencil[at_px] = sten;
+#pragma unroll
+            for (int k = 1; k < MAX_LIGHTS; ++k)
+                if (k < n_lights) ka.ml.stencil[k - 1][at_px] = sten_x[k - 1];
+        }
+    }
     if (live) {
         const TileKernArgs &ka = kernargs<TileKernArgs>();
         const FrameConst &fc = ka.fc;
@@ -868,7 +917,27 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             load_shaded_face(sh, fc.pos32 != 0, best, sf);
             const Material *mp = mat_lds ? reinterpret_cast<const Material *>(s_mat) + t.material
                                          : sh.materials + t.material;
+            if (ML) {
+                const int n_lights = min(max(ka.ml.lights.n, 1), MAX_LIGHTS);
+                n_lit = (unsigned int)__popc(lit_mask);
+                Surface sp;
+                shade_surface(t, sf, *mp, px, py, lit_mask != 0, sp);
+                LitSurface ls = {};
+                if (lit_mask) shade_lit_surface(lc.camera_pos, sp, *mp, ls);
+                float acc[3] = { 0.f, 0.f, 0.f };
+#pragma unroll 1
+                for (int k = 0; k < n_lights; ++k) {
+                    const LightConst lk = light_const(ka.ml.lights.l[k]);
+                    float fk[3];
+                    shade_light<true>(lk, sp, *mp, (lit_mask >> k & 1u) != 0, &ls, fk);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) acc[j] = acc[j] + fk[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 3; ++j) rgb[j] = fminf(acc[j], 1.0f);
+            } else {
             shade_pixel(lc, t, sf, *mp, px, py, lit, rgb);
+            }
         } else if ((fc.flags & MR_FRAME_SKYBOX) && sh.sky) {
             sky_color(fc, sh.sky, px, py, rgb);
         } else if (fc.background_u8 >> 24) {
@@ -891,7 +960,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 for (int j = 0; j < 3; ++j) o[j] = gamma_u8(rgb[j], s_gamma);
             }
         }
-        if (ta.zbuf && taps) {                            // taps for the parity tests / per-face status / overlay
+        if (!ML && ta.zbuf && taps) {                     // taps for the parity tests / per-face status / overlay
             ta.zbuf[at_px] = zbest;
             ta.winner[at_px] = best;
             ta.stencil[at_px] = sten;
@@ -911,9 +980,15 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
     // ---- per-tile statistics and housekeeping
     if (counters) {
         const unsigned long long cov = __ballot(covered), litm = __ballot(covered && lit);
+        if (ML) {                                         // lit_px: the sum over the lights
+            unsigned int v = covered ? n_lit : 0u;
+#pragma unroll
+            for (int off = WAVE / 2; off; off >>= 1) v += (unsigned int)__shfl_xor((int)v, off);
+            if (lane == 0 && v) atomicAdd(&s_cnt[4], v);
+        }
         if (lane == 0) {
             if (cov) atomicAdd(&s_cnt[3], (unsigned int)__popcll(cov));
-            if (litm) atomicAdd(&s_cnt[4], (unsigned int)__popcll(litm));
+            if (!ML && litm) atomicAdd(&s_cnt[4], (unsigned int)__popcll(litm));
             if (qfrags) atomicAdd(&s_cnt[1], qfrags);
             if (qupd) atomicAdd(&s_cnt[2], qupd);
         }

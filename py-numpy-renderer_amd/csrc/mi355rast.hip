@@ -92,6 +92,8 @@ struct FrameSlot {
     DevBuf d_vout, d_vclip, d_tris, d_clips, d_status, d_count_list, d_quads, d_sil, d_counters;
     DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_work, d_tile_stats, d_hist, d_split;
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
+    DevBuf d_stencil_x[mr::MAX_LIGHTS - 1];       // stencil taps of lights 1.. of a frame with several lights
+    int last_n_lights = 1;                        // lights of the last frame
     // capacities this slot's buffers were last bound with (the scene holds the current ones)
     uint32_t bin_cap[mr::BIN_CLASSES] = { 0, 0, 0 }, work_cap = 0, quad_cap = 0;
     int bins_zeroed_for = 0;
@@ -132,7 +134,8 @@ struct FrameSlot {
     {
         DevBuf *bufs[] = { &d_vout, &d_vclip, &d_count_list, &d_tris, &d_clips, &d_status, &d_quads, &d_sil, &d_counters,
                            &d_bin_count, &d_items[0], &d_items[1], &d_items[2], &d_work, &d_tile_stats, &d_hist, &d_split,
-                           &d_z, &d_winner, &d_stencil, &d_frame, &d_out };
+                           &d_z, &d_winner, &d_stencil, &d_frame, &d_out, &d_stencil_x[0], &d_stencil_x[1], &d_stencil_x[2] };
+        static_assert(mr::MAX_LIGHTS == 4 && mr::MAX_LIGHTS == MR_MAX_LIGHTS, "d_stencil_x");
         for (DevBuf *b : bufs) b->release();
         ov.lists.release(); ov.scratch.release();
         if (ov.staging) (void)hipHostFree(ov.staging);
@@ -267,6 +270,9 @@ struct mr_scene {
     mr_stats stats = {};
     int n_silhouette = 0;
     SilCache sil;
+    // lights 1.. of the frames to come (mr_scene_set_extra_lights); light 0 is the frame descriptor's
+    int n_extra_lights = 0;
+    mr::LightRec extra_lights[mr::MAX_LIGHTS - 1] = {};
     // Capacities of the per-frame work lists, shared by all slots: what one frame learnt (a tile with
     // a longer list, more silhouette edges) holds for the frames rendered on other streams too.
     uint32_t bin_cap[mr::BIN_CLASSES] = { 512u, 128u, 256u };   // entries per tile and class
@@ -542,6 +548,39 @@ int validate_frame(const mr_frame_desc *fr)
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
     return MR_OK;
+}
+
+// validate_frame, and what a scene with extra lights (mr_scene_set_extra_lights) refuses
+int validate_frame_for(const mr_scene *sc, const mr_frame_desc *fr)
+{
+    const int rc = validate_frame(fr);
+    if (rc) return rc;
+    if (sc->n_extra_lights > 0) {
+        if (fr->flags & MR_FRAME_FACE_STATUS)
+            return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
+        if (fr->stripe_count > 1)
+            return fail(MR_E_INVALID, "striped frames are not available with extra lights");
+    }
+    return MR_OK;
+}
+
+// all the lights of a frame with several: the descriptor's, then the scene's extra ones
+mr::FrameLights make_lights(const mr_scene *sc, const mr_frame_desc *fr)
+{
+    mr::FrameLights fl;
+    std::memset(&fl, 0, sizeof fl);
+    fl.n = 1 + sc->n_extra_lights;
+    mr::LightRec &l = fl.l[0];
+    for (int j = 0; j < 3; ++j) {
+        l.pos[j] = fr->light_pos[j]; l.dir[j] = fr->light_dir[j];
+        l.color[j] = fr->light_color[j]; l.ambient[j] = fr->light_ambient[j];
+    }
+    l.specular_strength = fr->specular_strength;
+    l.att_constant = fr->att_constant; l.att_linear = fr->att_linear; l.att_quadratic = fr->att_quadratic;
+    l.spot_edge0 = fr->spot_edge0; l.spot_edge1 = fr->spot_edge1;
+    l.type = fr->light_type;
+    for (int k = 0; k < sc->n_extra_lights; ++k) fl.l[1 + k] = sc->extra_lights[k];
+    return fl;
 }
 
 mr::FrameConst make_const(const mr_scene *sc, const mr_frame_desc *fr)
@@ -932,7 +971,10 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     // its own in front of k_setup (same bits; for A/B timing and the MFMA counters)
     static const bool vertex_mfma = [] { const char *e = getenv("MR_VERTEX_PATH"); return e && !strcmp(e, "mfma"); }();
 
-    if (sc->quad_cap == 0) sc->quad_cap = (uint32_t)std::min<size_t>(std::max(fc.n_edges, 1), 1u << 17);
+    // several lights (mr_scene_set_extra_lights): the multi-light instantiations of k_setup and k_tile
+    const int n_lights = 1 + sc->n_extra_lights;
+    const bool ml = n_lights > 1;
+    if (sc->quad_cap == 0) sc->quad_cap = (uint32_t)std::min<size_t>((size_t)std::max(fc.n_edges, 1) * n_lights, 1u << 17);
     fs->quad_cap = sc->quad_cap; fs->work_cap = sc->work_cap;
     for (int c = 0; c < BIN_CLASSES; ++c) fs->bin_cap[c] = sc->bin_cap[c];
 
@@ -964,6 +1006,7 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
         HIP_TRY(fs->d_z.ensure(npx * sizeof(double)));
         HIP_TRY(fs->d_winner.ensure(npx * sizeof(int32_t)));
         HIP_TRY(fs->d_stencil.ensure(npx * sizeof(int32_t)));
+        for (int k = 1; k < n_lights; ++k) HIP_TRY(fs->d_stencil_x[k - 1].ensure(npx * sizeof(int32_t)));
     }
     if (fc.flags & MR_FRAME_KEEP_FLOAT) HIP_TRY(fs->d_frame.ensure(npx * 3 * sizeof(float)));
     if (!fs->events_ok) {
@@ -1033,16 +1076,23 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
                               : fc.n_edges <= (1 << 15) ? 2u : 1u;
         constexpr unsigned QS_PER_BLOCK = SETUP_BLOCK / QS_LANES;
         SilArgs sil = {};
-        SilCache::Buf *capture = shadows && fc.n_edges > 0 ? choose_silhouette_path(sc, fs, fc, sil) : nullptr;
+        // (a frame with several lights takes the fused edge path and leaves the cache, keyed on one light, as it is)
+        SilCache::Buf *capture = shadows && fc.n_edges > 0 && !ml ? choose_silhouette_path(sc, fs, fc, sil) : nullptr;
+        if (shadows && fc.n_edges > 0 && ml) { sc->sil.last_path = SIL_FUSED; sc->sil.last_entries = 0; }
         const unsigned edge_blocks = !(shadows && fc.n_edges > 0) ? 0u
                                    : sil.mode == SIL_CACHED ? (sil.count + QS_PER_BLOCK - 1) / QS_PER_BLOCK     // quad workgroups
                                    : dense ? blocks_for(fc.n_edges, 2 * SETUP_BLOCK) : blocks_for((long long)fc.n_edges << spread, SETUP_BLOCK);
         SetupKernArgs ska;
         ska.fc = fc; ska.sa = sa; ska.bins = ba; ska.face_blocks = face_blocks; ska.edge_spread = sil.mode == SIL_CACHED ? EDGE_CACHED : spread; ska.sil = sil;
-        if (vertex_mfma)
-            hipLaunchKernelGGL(k_setup<true>, dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
+        if (ml) ska.lights = make_lights(sc, fr); else ska.lights.n = 1;      // (only the ML instantiations read them)
+        if (vertex_mfma && ml)
+            hipLaunchKernelGGL((k_setup<true, true>), dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
+        else if (ml)
+            hipLaunchKernelGGL((k_setup<false, true>), dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
+        else if (vertex_mfma)
+            hipLaunchKernelGGL((k_setup<true, false>), dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
         else
-            hipLaunchKernelGGL(k_setup<false>, dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
+            hipLaunchKernelGGL((k_setup<false, false>), dim3(1 + face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
         if (capture) {
             // the count follows on this stream; the buffer is read once the host has seen the event complete
             hipError_t e = hipMemcpyAsync(capture->h_count, &ctr->n_quads, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
@@ -1113,6 +1163,12 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     sh.out = d_out;
     TileKernArgs tka;
     tka.fc = fc; tka.ta = ta; tka.sh = sh;
+    if (ml) {
+        tka.ml.lights = make_lights(sc, fr);
+        for (int k = 1; k < MAX_LIGHTS; ++k) tka.ml.stencil[k - 1] = keep && k < n_lights ? fs->d_stencil_x[k - 1].as<int32_t>() : nullptr;
+    } else {
+        tka.ml.lights.n = 1;
+    }
     // which tiles are shared out over HEAVY_SPLIT workgroups next frame: on a device whose tiles are all resident
     // at once every tile with a quad walk worth sharing; on a whole frame only the handful that outlast
     // everything else (the launch then ends with them).  MR_TILE_SPLIT=0 | 1 forces it off / on for every grid.
@@ -1124,16 +1180,20 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     tka.ta.split_quads = small_grid ? 32u : split_quads_big;
     static const unsigned split_max_big = [] { const char *e = getenv("MR_SPLIT_MAX"); return e ? (unsigned)atoi(e) : 64u; }();
     tka.ta.split_max = std::min<unsigned>(small_grid ? (unsigned)HEAVY0_MAX : split_max_big, (unsigned)HEAVY0_MAX);
-    const bool split = split_mode < 0 ? (small_grid || ordered) : split_mode != 0;
+    const bool split = !ml && (split_mode < 0 ? (small_grid || ordered) : split_mode != 0);
     const bool ss = fc.ss_mode != 0;        // supersampled: the instantiations that resolve (see k_tile)
-    if (n_tiles > 0 && split && ss)
-        hipLaunchKernelGGL((k_tile<true, true>), dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
+    if (n_tiles > 0 && ml && ss)
+        hipLaunchKernelGGL((k_tile<false, true, true>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
+    else if (n_tiles > 0 && ml)
+        hipLaunchKernelGGL((k_tile<false, false, true>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
+    else if (n_tiles > 0 && split && ss)
+        hipLaunchKernelGGL((k_tile<true, true, false>), dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
     else if (n_tiles > 0 && split)
-        hipLaunchKernelGGL((k_tile<true, false>), dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
+        hipLaunchKernelGGL((k_tile<true, false, false>), dim3((unsigned)(n_tiles + SPLIT_FRONT)), dim3(TILE_PX), 0, stream, tka);
     else if (n_tiles > 0 && ss)
-        hipLaunchKernelGGL((k_tile<false, true>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
+        hipLaunchKernelGGL((k_tile<false, true, false>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
     else if (n_tiles > 0)
-        hipLaunchKernelGGL((k_tile<false, false>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
+        hipLaunchKernelGGL((k_tile<false, false, false>), dim3((unsigned)n_tiles), dim3(TILE_PX), 0, stream, tka);
     else          // nothing to draw on this device (a stripe beyond the frame): still hand the counters on
         HIP_TRY(hipMemsetAsync(next_ctr, 0, sizeof(Counters), stream));
     if (timing) HIP_TRY(hipEventRecord(fs->ev[4], stream));
@@ -1158,6 +1218,7 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     fs->last_frame = *fr;
     fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = n_tiles;
+    fs->last_n_lights = n_lights;
     fs->have_frame = true;
     fs->stats_reduced = false;
     fs->last_copied = false;
@@ -1274,6 +1335,7 @@ int mr_abi_struct_size(int which)
     case 2: return (int)sizeof(mr_model_desc);
     case 3: return (int)sizeof(mr_stats);
     case 4: return (int)sizeof(mr_overlay_desc);
+    case 5: return (int)sizeof(mr_light_desc);
     default: return -1;
     }
 }
@@ -1319,6 +1381,27 @@ int mr_scene_clear(mr_scene *sc)
     sc->sil.drop();
     sc->reset_caps();
     for (auto &fs : sc->slots) fs->reset_caps();
+    return MR_OK;
+}
+
+int mr_scene_set_extra_lights(mr_scene *sc, const mr_light_desc *lights, int32_t n)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (n < 0 || n > MR_MAX_LIGHTS - 1) return fail(MR_E_INVALID, "a frame has at most MR_MAX_LIGHTS lights: 0 <= n <= 3 extra ones");
+    if (n > 0 && !lights) return fail(MR_E_INVALID, "lights is NULL");
+    for (int k = 0; k < n; ++k)
+        if (lights[k].type < 0 || lights[k].type > 2) return fail(MR_E_INVALID, "unknown light type");
+    for (int k = 0; k < n; ++k) {
+        const mr_light_desc &d = lights[k];
+        mr::LightRec &l = sc->extra_lights[k];
+        std::memset(&l, 0, sizeof l);
+        for (int j = 0; j < 3; ++j) { l.pos[j] = d.pos[j]; l.dir[j] = d.dir[j]; l.color[j] = d.color[j]; l.ambient[j] = d.ambient[j]; }
+        l.specular_strength = d.specular_strength;
+        l.att_constant = d.att_constant; l.att_linear = d.att_linear; l.att_quadratic = d.att_quadratic;
+        l.spot_edge0 = d.spot_edge0; l.spot_edge1 = d.spot_edge1;
+        l.type = d.type;
+    }
+    sc->n_extra_lights = n;
     return MR_OK;
 }
 
@@ -1515,7 +1598,7 @@ int mr_scene_add_model(mr_scene *sc, const mr_model_desc *m)
 int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats *stats)
 {
     if (!sc || !out_rgb) return fail(MR_E_INVALID, "NULL argument");
-    int rc = validate_frame(fr);
+    int rc = validate_frame_for(sc, fr);
     if (rc) return rc;
     if ((rc = ensure_init())) return rc;
     FrameSlot *fs = slot_for(sc, g_stream);
@@ -1549,7 +1632,7 @@ int mr_render_async(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, int
 {
     if (!sc || !out_rgb) return fail(MR_E_INVALID, "NULL argument");
     if (lane < 0 || lane >= MR_ASYNC_LANES) return fail(MR_E_INVALID, "lane out of range");
-    int rc = validate_frame(fr);
+    int rc = validate_frame_for(sc, fr);
     if (rc) return rc;
     if ((rc = ensure_init())) return rc;
     if ((fr->flags & MR_FRAME_OVERLAY) && (fr->row_begin != 0 || fr->row_end != fr->height || fr->stripe_count > 1))
@@ -1745,7 +1828,7 @@ void mr_host_free(void *p)
 int mr_render_device(mr_scene *sc, const mr_frame_desc *fr, void *d_out_rgb, void *stream)
 {
     if (!sc || !d_out_rgb) return fail(MR_E_INVALID, "NULL argument");
-    int rc = validate_frame(fr);
+    int rc = validate_frame_for(sc, fr);
     if (rc) return rc;
     if ((rc = ensure_init())) return rc;
     FrameSlot *fs = slot_for(sc, stream ? (hipStream_t)stream : g_stream);
@@ -1848,15 +1931,18 @@ int mr_read_z(mr_scene *sc, double *out)
     return read_back(fs->d_z, out, (size_t)fs->last_frame.width * fs->last_frame.height, "z");
 }
 
-int mr_read_stencil(mr_scene *sc, int16_t *out)
+int mr_read_stencil(mr_scene *sc, int16_t *out) { return mr_read_stencil_light(sc, 0, out); }
+
+int mr_read_stencil_light(mr_scene *sc, int32_t light, int16_t *out)
 {
     FrameSlot *fs = last_slot(sc);
     if (!fs) return MR_E_INVALID;
     if (!(fs->last_frame.flags & MR_FRAME_KEEP_BUFFERS))
         return fail(MR_E_INVALID, "the last frame was rendered without MR_FRAME_KEEP_BUFFERS");
+    if (light < 0 || light >= fs->last_n_lights) return fail(MR_E_INVALID, "the last frame had no such light");
     const size_t n = (size_t)fs->last_frame.width * fs->last_frame.height;
     std::vector<int32_t> wide(n);           // the device accumulates in 32 bits; the reference's buffer is int16
-    int rc = read_back(fs->d_stencil, wide.data(), n, "stencil");
+    int rc = read_back(light ? fs->d_stencil_x[light - 1] : fs->d_stencil, wide.data(), n, "stencil");
     if (rc) return rc;
     if (!out) return fail(MR_E_INVALID, "NULL argument");
     for (size_t i = 0; i < n; ++i) out[i] = (int16_t)wide[i];
@@ -1938,10 +2024,38 @@ int mr_debug_read_tile_order(mr_scene *sc, uint32_t *out, int32_t cap_tiles)
     return fs->last_n_tiles;
 }
 
+int mr_read_silhouette_light(mr_scene *sc, int32_t light, int32_t *out, int32_t cap)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (light < 0 || light >= fs->last_n_lights) return fail(MR_E_INVALID, "the last frame had no such light");
+    if (fs->last_n_lights == 1) return mr_read_silhouette(sc, out, cap);
+    // the lights' entries share the one list, each tagged with its light: pick this one's
+    const int listed = std::min(sc->n_silhouette, (int)fs->quad_cap);
+    std::vector<int32_t> raw((size_t)std::max(listed, 1) * 2);
+    HIP_TRY(hipDeviceSynchronize());
+    if (listed > 0) HIP_TRY(hipMemcpy(raw.data(), fs->d_sil.p, (size_t)listed * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int n = 0;
+    for (int i = 0; i < listed; ++i) {
+        const int face = raw[i * 2], word = raw[i * 2 + 1], k = word & 3;
+        if ((word >> mr::SIL_LIGHT_SHIFT) != light) continue;
+        if (out && n < cap) {
+            int model = 0;
+            while (model + 1 < (int)sc->models.size() && face >= sc->models[model + 1].face_off) ++model;
+            out[n * 3 + 0] = model;
+            out[n * 3 + 1] = sc->edge_raw[(size_t)face * 3 + k];
+            out[n * 3 + 2] = sc->edge_raw[(size_t)face * 3 + (k + 1) % 3];
+        }
+        ++n;
+    }
+    return n;
+}
+
 int mr_read_silhouette(mr_scene *sc, int32_t *out, int32_t cap)
 {
     FrameSlot *fs = last_slot(sc);
     if (!fs) return MR_E_INVALID;
+    if (fs->last_n_lights > 1) return mr_read_silhouette_light(sc, 0, out, cap);
     const int n = sc->n_silhouette;
     const int take = std::min(std::min(n, cap), (int)fs->quad_cap);
     if (take > 0 && out) {

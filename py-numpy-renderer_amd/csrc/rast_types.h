@@ -76,6 +76,24 @@ struct FrameConst {
 
 constexpr int SS_SHIFT_MASK = 0xff, SS_SEPARATE = 0x100;
 
+// A frame with more than one light (mr_scene_set_extra_lights): ALL its lights, light 0 -- the one FrameConst
+// describes -- included, so that the kernels' loops over the lights read one array.  It travels behind the other
+// kernel arguments of k_setup and k_tile and only their multi-light instantiations read it.
+constexpr int MAX_LIGHTS = 4;            // MR_MAX_LIGHTS
+struct LightRec {
+    double pos[3], dir[3], color[3], ambient[3];
+    double specular_strength, att_constant, att_linear, att_quadratic;
+    double spot_edge0, spot_edge1;
+    int32_t type, pad;
+};
+struct FrameLights {
+    int32_t n;                   // 2 .. MAX_LIGHTS (1: the frame is a plain one and nobody reads this)
+    int32_t pad;
+    LightRec l[MAX_LIGHTS];
+};
+// sil_edges[2 i + 1] of silhouette entry i: the corner in bits 0-1, the light above them
+constexpr int SIL_LIGHT_SHIFT = 2;
+
 // Output of the optional stand-alone vertex kernel (k_vertex_mfma): everything
 // obj/triangular.py:36-45 derives per face corner, once per unique vertex.
 struct alignas(16) VertexOut {
@@ -161,7 +179,8 @@ struct alignas(16) QuadRec {
     int32_t n;                   // vertex count (>= 3)
     int32_t is_front;
     int32_t edge;                // silhouette-list entry it came from
-    uint32_t pad[3];
+    uint32_t light;              // which of the frame's lights cast it (0 unless the frame has several, see FrameLights)
+    uint32_t pad[2];
     QuadEdge e[MAX_POLY];
 };
 static_assert(sizeof(QuadRec) == 64 + 32 * MAX_POLY, "QuadRec layout");

@@ -210,6 +210,8 @@ class BandRenderer:
         height, width = (int(v) for v in scene.resolution)
         if getattr(scene, "supersample", 1) != 1:
             raise ValueError("a frame split over devices does not support supersample > 1 (render it on one device)")
+        if len(getattr(scene, "lights", ())) > 1:
+            raise ValueError("a frame split over devices does not support more than one light (render it on one device)")
         if partition not in ("bands", "stripes", "weighted"):
             raise ValueError(f"unknown partition {partition!r}")
         self.rank, self.world, self.partition = rank, world, partition
