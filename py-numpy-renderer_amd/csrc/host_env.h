@@ -1,0 +1,53 @@
+// host_env.h -- the environment switches of the library, all of them.
+//
+//   name              default   meaning
+//   MR_VERTEX_PATH    (inline)  mfma: vertex transform once per unique vertex on the matrix cores, as a launch of its own
+//                               in front of k_setup (same bits; for A/B timing and the MFMA counters)
+//   MR_RESOLVE_PATH   (fused)   separate: a supersampled frame is resolved by k_resolve_full from the float frame instead
+//                               of inside k_tile (the yardstick of the fused resolve, and its A/B)
+//   MR_EDGE_SPREAD    -2        lanes per edge in k_setup's edge half, as a shift: -2 by the size of the mesh, -1 dense
+//                               (two edges per lane), 0 .. 4 forced
+//   MR_TILE_ORDER     (auto)    rowmajor | heaviest: the order k_tile takes the tiles in (auto: see launch_tile)
+//   MR_TILE_SPLIT     -1        0 | 1: sharing a heavy tile's quads out over HEAVY_SPLIT workgroups off / on for every grid
+//   MR_SPLIT_COST     400       a whole frame's tile is shared out from this estimated cost ...
+//   MR_SPLIT_QUADS    48        ... and this many shadow quads
+//   MR_CLUSTER_CULL   (auto)    0 | 1 | box | count: cluster culling off / on / boxes only / on and counted (auto: see
+//                               cluster_cull_mode)
+//   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
+//
+// MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
+// rest are read once per process.
+#pragma once
+
+namespace {
+
+struct Env {
+    bool vertex_mfma, resolve_separate, sil_cache;
+    int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
+    unsigned split_cost, split_quads;
+    const char *cluster_cull;                     // as set, or NULL
+};
+
+Env read_env()
+{
+    static const Env once = [] {
+        auto is = [](const char *name, const char *value) { const char *e = getenv(name); return e && !strcmp(e, value); };
+        auto number = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+        Env e = {};
+        e.vertex_mfma = is("MR_VERTEX_PATH", "mfma");
+        e.resolve_separate = is("MR_RESOLVE_PATH", "separate");
+        e.edge_spread = number("MR_EDGE_SPREAD", -2);
+        e.tile_order = is("MR_TILE_ORDER", "rowmajor") ? 1 : is("MR_TILE_ORDER", "heaviest") ? 2 : 0;
+        e.tile_split = number("MR_TILE_SPLIT", -1);
+        e.split_cost = (unsigned)number("MR_SPLIT_COST", 400);
+        e.split_quads = (unsigned)number("MR_SPLIT_QUADS", 48);
+        return e;
+    }();
+    Env e = once;
+    e.cluster_cull = getenv("MR_CLUSTER_CULL");
+    const char *sil = getenv("MR_SIL_CACHE");
+    e.sil_cache = !(sil && !strcmp(sil, "0"));
+    return e;
+}
+
+}  // namespace

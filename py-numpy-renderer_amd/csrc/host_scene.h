@@ -1,0 +1,277 @@
+// host_scene.h -- the static scene: what the caller's models become on the host (concatenated arrays, the unique-edge
+// table, the cluster records), their device copies, and commit(), which brings the device up to date.
+#pragma once
+
+namespace {
+
+struct FrameSlot;      // host_frame.h
+
+struct EdgeKey {
+    uint64_t key;      // (lo << 32) | hi of the two global vertex indices
+    uint32_t inc;      // face * 4 + corner
+};
+
+}  // namespace
+
+struct mr_scene {
+    // ---- host staging of the static scene (concatenated over models, indices made global)
+    std::vector<double> verts;
+    std::vector<float> uv, normals;
+    std::vector<int32_t> faces;
+    std::vector<uint8_t> face_flags;
+    std::vector<mr::Material> materials;
+    std::vector<mr::Texture> textures;       // device pointers
+    std::vector<void *> texture_allocs;
+    std::vector<int32_t> model_face_off;      // first face of every model
+    std::vector<int32_t> edge_ids;            // per face corner: raw vertex identity for silhouette edges (made unique per model)
+    std::vector<int32_t> edge_raw;            // the same as the caller passed it (for mr_read_silhouette)
+    std::vector<mr::EdgeRec> edges;           // unique undirected edges, scrambled order
+    std::vector<uint32_t> edge_inc;           // incidences beyond an edge's first two
+    bool dirty = true;
+
+    // ---- device copies of the static scene
+    DevBuf d_verts, d_uv, d_normals, d_faces, d_face_flags, d_materials, d_textures, d_edges, d_edge_inc, d_face_n;
+    DevBuf d_edges32;                        // the compact edge table, when the scene allows it
+    bool edge_compact = false;
+    DevBuf d_face_pos, d_face_attr;          // static per face (rast_types.h, FacePosT / FaceAttr), built by commit()
+    DevBuf d_clusters;                       // static per 64 faces (rast_types.h, ClusterRec), built by commit()
+    bool pos32 = false;                      // d_face_pos holds FacePos32 (every model's vertices are float32)
+    bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
+    DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
+    DevBuf d_gamma;                          // GAMMA_LUT_SIZE float32 thresholds of the finalise step function
+    int32_t sky_size = 0;
+
+    // ---- debug-frustum overlay: the lines' points as built on the host (five targets and a depth per point, segment by
+    // segment); every frame slot keeps its own device copy (FrameSlot::ov), brought up to date when a frame of that
+    // slot draws the overlay
+    int32_t ov_height = 0, ov_width = 0;     // the frame the lists were built for
+    int32_t ov_points = 0, ov_segments = 0;
+    uint64_t ov_serial = 0;                  // bumped whenever the lists change
+    std::vector<int32_t> ov_target;          // (5, n_points) pixel row * width + col of every target
+    std::vector<double> ov_z;
+    std::vector<int32_t> ov_seg;             // first point, number of points per segment
+    std::vector<uint8_t> ov_tile_mask;       // the 16x16 tiles that hold a target
+    // mr_scene_set_overlay_cameras only leaves its arguments here; the lists are built when first needed (realize_overlay)
+    // -- for mr_render / mr_render_async AFTER the frame's three kernels have been launched, so that the host walks the
+    // lines while the device renders (the lists' only early use, the tile kernel's tap mask, is given up for that frame)
+    struct OvPending {
+        bool set = false;
+        double corners[32], planes[24], mvp[16], viewport[16], near_ = 0, far_ = 0;
+        int32_t inside = 0, height = 0, width = 0;
+    } ov_pending;
+    // the same targets as slots of the list of touched pixels, for a frame assembled from several devices (built
+    // when first asked for: build_overlay_slots)
+    std::vector<int32_t> ov_slot_of, ov_touched;
+    uint64_t ov_slots_serial = 0;            // the ov_serial the slot lists were built for
+    mr_host::OverlaySlotWork ov_slot_work;
+
+    // ---- lanes of mr_render_async: a stream of the library's own each, and what is in flight on it
+    struct Lane { hipStream_t stream = nullptr; bool busy = false; } lanes[MR_ASYNC_LANES];
+
+    // ---- frame slots, one per stream that has rendered this scene
+    std::vector<std::unique_ptr<FrameSlot>> slots;
+    FrameSlot *last = nullptr;               // slot of the most recently enqueued frame
+    uint64_t frame_serial = 0;               // frames enqueued on any stream
+    mr_stats stats = {};
+    int n_silhouette = 0;
+    SilCache sil;
+    // lights 1.. of the frames to come (mr_scene_set_extra_lights); light 0 is the frame descriptor's
+    int n_extra_lights = 0;
+    mr::LightRec extra_lights[mr::MAX_LIGHTS - 1] = {};
+    // Capacities of the per-frame work lists, shared by all slots: what one frame learnt (a tile with
+    // a longer list, more silhouette edges) holds for the frames rendered on other streams too.
+    uint32_t bin_cap[mr::BIN_CLASSES] = { 512u, 128u, 256u };   // entries per tile and class
+    uint32_t work_cap = 1u << 18, quad_cap = 0;
+    void reset_caps() { bin_cap[0] = 512u; bin_cap[1] = 128u; bin_cap[2] = 256u; work_cap = 1u << 18; quad_cap = 0; }
+};
+
+namespace {
+
+// Unique undirected edges with their incident (face, corner) pairs in face order: what the
+// reference's per-model set of Edge objects (obj/triangular.py:286-302) reduces to.  An edge is
+// identified by the RAW vertex ids of its corners (mr_model_desc.edge_ids), as in the reference.
+// The table is stored in a scrambled order (sorted by a hash of the edge): silhouettes run along
+// consecutive vertex indices, and a wavefront of k_setup that found dozens of silhouette edges
+// among its 64 would set their quads up four at a time while the rest of the device idles.
+void build_edge_table(mr_scene *sc)
+{
+    const size_t nf = sc->faces.size() / 12;
+    std::vector<EdgeKey> keys;
+    keys.reserve(nf * 3);
+    for (size_t f = 0; f < nf; ++f) {
+        const int32_t *id = &sc->edge_ids[f * 3];
+        for (int k = 0; k < 3; ++k) {
+            uint32_t a = (uint32_t)id[k], b = (uint32_t)id[(k + 1) % 3];
+            uint32_t lo = std::min(a, b), hi = std::max(a, b);
+            keys.push_back({ ((uint64_t)lo << 32) | hi, (uint32_t)(f * 4 + k) });
+        }
+    }
+    auto scramble = [](uint64_t k) {                   // splitmix64 finaliser: a bijection
+        k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull; k ^= k >> 27; k *= 0x94d049bb133111ebull; k ^= k >> 31;
+        return k;
+    };
+    for (EdgeKey &e : keys) e.key = scramble(e.key);
+    std::sort(keys.begin(), keys.end(), [](const EdgeKey &x, const EdgeKey &y) {
+        return x.key != y.key ? x.key < y.key : x.inc < y.inc;
+    });
+    sc->edges.clear();
+    sc->edge_inc.clear();
+    for (size_t i = 0; i < keys.size();) {
+        size_t j = i;
+        while (j < keys.size() && keys[j].key == keys[i].key) ++j;
+        mr::EdgeRec r;
+        std::memset(&r, 0, sizeof r);
+        r.inc[0] = keys[i].inc;
+        r.inc[1] = j - i > 1 ? keys[i + 1].inc : 0xffffffffu;
+        r.extra_off = (uint32_t)sc->edge_inc.size();
+        r.extra_cnt = j - i > 2 ? (uint32_t)(j - i - 2) : 0u;
+        for (size_t k = i + 2; k < j; ++k) sc->edge_inc.push_back(keys[k].inc);
+        sc->edges.push_back(r);
+        i = j;
+    }
+}
+
+// Finalise is uint8(frame ** 0.8 * 255) in float32 (obj/core.py:640): a monotone step function
+// of the colour with 255 steps.  GAMMA_LUT[k] is the smallest float32 in [0, 1] whose step is
+// >= k, found by bisection over the bit patterns against the host's own powf, so that k_shade
+// can place a colour with one approximate exp2/log2 and two table compares and still return
+// exactly what powf would (k_shade's gamma_u8).
+std::vector<float> gamma_thresholds()
+{
+    auto step = [](float x) { return (int)(uint8_t)(powf(x, 0.8f) * 255.0f); };
+    std::vector<float> lut(mr::GAMMA_LUT_SIZE);
+    lut[0] = 0.0f;
+    for (int k = 1; k < 256; ++k) {
+        uint32_t lo = 0, hi = 0x3f800000u;      // step(0) = 0 < k <= 255 = step(1)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            float x;
+            memcpy(&x, &mid, 4);
+            if (step(x) >= k) hi = mid; else lo = mid;
+        }
+        memcpy(&lut[k], &hi, 4);
+    }
+    lut[256] = INFINITY;
+    return lut;
+}
+
+// The static cluster records (rast_types.h, ClusterRec): bounding box and normal cone of every 64 consecutive faces.
+std::vector<mr::ClusterRec> build_clusters(const mr_scene *sc)
+{
+    const size_t nf = sc->faces.size() / 12, nc = (nf + mr::CLUSTER_FACES - 1) / mr::CLUSTER_FACES;
+    std::vector<mr::ClusterRec> out(nc);
+    auto down = [](double x) { float f = (float)x; return (double)f > x ? std::nextafter(f, -INFINITY) : f; };
+    auto up = [](double x) { float f = (float)x; return (double)f < x ? std::nextafter(f, INFINITY) : f; };
+    for (size_t c = 0; c < nc; ++c) {
+        mr::ClusterRec r;
+        std::memset(&r, 0, sizeof r);
+        double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY }, sum[3] = { 0, 0, 0 };
+        bool boxed = true, coned = true;
+        const size_t f0 = c * mr::CLUSTER_FACES, f1 = std::min(nf, f0 + mr::CLUSTER_FACES);
+        std::vector<std::array<double, 3>> normals;
+        normals.reserve(f1 - f0);
+        for (size_t f = f0; f < f1; ++f) {
+            const double *v[3];
+            for (int k = 0; k < 3; ++k) {
+                v[k] = &sc->verts[(size_t)sc->faces[f * 12 + k * 4] * 4];
+                if (!(v[k][3] == 1.0)) boxed = false;                     // (a homogeneous coordinate other than 1: no box)
+                for (int j = 0; j < 3; ++j) { lo[j] = std::min(lo[j], v[k][j]); hi[j] = std::max(hi[j], v[k][j]); if (!std::isfinite(v[k][j])) boxed = false; }
+            }
+            const double a[3] = { v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2] };
+            const double b[3] = { v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2] };
+            double n[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
+            const double l = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            if (!(l > 0) || !std::isfinite(l)) { coned = false; continue; }
+            for (int j = 0; j < 3; ++j) { n[j] /= l; sum[j] += n[j]; }
+            normals.push_back({ n[0], n[1], n[2] });
+        }
+        if (boxed) {
+            for (int j = 0; j < 3; ++j) { r.lo[j] = down(lo[j]); r.hi[j] = up(hi[j]); }
+        } else {
+            for (int j = 0; j < 3; ++j) { r.lo[j] = NAN; r.hi[j] = NAN; }      // never culled: every comparison fails
+        }
+        r.cos_half = -2.f; r.sin_half = 1.f;
+        const double sl = std::sqrt(sum[0] * sum[0] + sum[1] * sum[1] + sum[2] * sum[2]);
+        if (coned && sl > 1e-6 * (double)(f1 - f0)) {
+            double least = 1.0;
+            for (const auto &n : normals) least = std::min(least, (n[0] * sum[0] + n[1] * sum[1] + n[2] * sum[2]) / sl);
+            least -= 1e-6;
+            if (least > 0.05) {                                             // a cone wider than ~87 degrees never culls anything
+                for (int j = 0; j < 3; ++j) r.axis[j] = (float)(sum[j] / sl);
+                // the axis as stored (float32) is not the axis the dots were taken with: 1e-6 covers it
+                r.cos_half = (float)(least - 1e-6);
+                r.sin_half = (float)std::min(1.0, std::sqrt(std::max(0.0, 1.0 - (double)r.cos_half * (double)r.cos_half)) + 1e-6);
+            }
+        }
+        out[c] = r;
+    }
+    return out;
+}
+
+int commit(mr_scene *sc)
+{
+    if (!sc->dirty) return MR_OK;
+    HIP_TRY(hipDeviceSynchronize());          // no frame may still be reading the old arrays
+    sc->sil.drop();                           // the silhouette belongs to the geometry that is about to be replaced
+    if (!sc->d_gamma.p) {
+        const std::vector<float> lut = gamma_thresholds();
+        HIP_TRY(sc->d_gamma.ensure(lut.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(sc->d_gamma.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    build_edge_table(sc);
+    for (mr::Material &m : sc->materials) {
+        const mr::Texture none = { nullptr, 0, 0 };
+        auto header = [&](int32_t id) { return id >= 0 && id < (int32_t)sc->textures.size() ? sc->textures[id] : none; };
+        m.map_kd = header(m.tex_kd); m.map_norm = header(m.tex_norm); m.map_ks = header(m.tex_ks);
+    }
+    int rc = MR_OK;
+    auto up = [&](DevBuf &buf, const auto &v) { if (!rc) rc = upload(buf, v, g_stream); };
+    up(sc->d_verts, sc->verts); up(sc->d_uv, sc->uv); up(sc->d_normals, sc->normals); up(sc->d_faces, sc->faces);
+    up(sc->d_face_flags, sc->face_flags); up(sc->d_materials, sc->materials); up(sc->d_textures, sc->textures);
+    up(sc->d_edges, sc->edges); up(sc->d_edge_inc, sc->edge_inc);
+    if (rc) return rc;
+    // static per scene: the faces' unit normals (light-facing test), copied into the edge records
+    const int nf = (int)(sc->faces.size() / 12), ne = (int)sc->edges.size();
+    HIP_TRY(sc->d_face_n.ensure(std::max<size_t>((size_t)nf * 4 * sizeof(double), 16)));
+    if (nf > 0)
+        hipLaunchKernelGGL(mr::k_face_normals, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
+                           sc->d_face_flags.as<uint8_t>(), sc->d_verts.as<double>(), sc->d_face_n.as<double>());
+    if (ne > 0)
+        hipLaunchKernelGGL(mr::k_edge_normals, dim3((ne + 255) / 256), dim3(256), 0, g_stream, ne, sc->d_edges.as<mr::EdgeRec>(),
+                           sc->d_face_n.as<double>());
+    // the static face records: float32 corners when every model's vertices are float32
+    sc->pos32 = true;
+    sc->has_no_depth = false;
+    for (uint8_t ff : sc->face_flags) {
+        if (!(ff & mr::FF_VERTS_F32)) sc->pos32 = false;
+        if (ff & mr::FF_NO_DEPTH) sc->has_no_depth = true;
+    }
+    HIP_TRY(sc->d_face_pos.ensure(std::max<size_t>((size_t)nf * (sc->pos32 ? sizeof(mr::FacePos32) : sizeof(mr::FacePos64)), 16)));
+    HIP_TRY(sc->d_face_attr.ensure(std::max<size_t>((size_t)nf * sizeof(mr::FaceAttr), 16)));
+    {
+        const std::vector<mr::ClusterRec> clusters = build_clusters(sc);
+        HIP_TRY(sc->d_clusters.ensure(std::max<size_t>(clusters.size() * sizeof(mr::ClusterRec), 64)));
+        if (!clusters.empty())
+            HIP_TRY(hipMemcpyAsync(sc->d_clusters.p, clusters.data(), clusters.size() * sizeof(mr::ClusterRec), hipMemcpyHostToDevice, g_stream));
+        HIP_TRY(hipStreamSynchronize(g_stream));            // (the vector goes out of scope)
+    }
+    auto face_static = [&](auto kernel, auto *face_pos) {
+        hipLaunchKernelGGL(kernel, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(), sc->d_face_flags.as<uint8_t>(),
+                           sc->d_verts.as<double>(), sc->d_uv.as<float>(), sc->d_normals.as<float>(), face_pos, sc->d_face_attr.as<mr::FaceAttr>());
+    };
+    if (nf > 0 && sc->pos32) face_static(mr::k_face_static<float>, sc->d_face_pos.as<mr::FacePos32>());
+    else if (nf > 0) face_static(mr::k_face_static<double>, sc->d_face_pos.as<mr::FacePos64>());
+    // compact edge records when every model's vertices are float32 and no edge has more than two faces
+    sc->edge_compact = ne > 0 && sc->edge_inc.empty() && sc->pos32;
+    if (sc->edge_compact) {
+        HIP_TRY(sc->d_edges32.ensure((size_t)ne * sizeof(mr::EdgeRec32)));
+        hipLaunchKernelGGL(mr::k_edge_compact, dim3((ne + 255) / 256), dim3(256), 0, g_stream, ne, sc->d_edges.as<mr::EdgeRec>(),
+                           sc->d_edges32.as<mr::EdgeRec32>());
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    sc->dirty = false;
+    return MR_OK;
+}
+
+}  // namespace
