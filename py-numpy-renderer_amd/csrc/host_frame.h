@@ -178,13 +178,12 @@ mr::LightRec light_rec(int32_t type, const double *pos, const double *dir, const
     return l;
 }
 
-// all the lights of a frame with several: the descriptor's, then the scene's extra ones
-void make_lights(const mr_scene *sc, const mr_frame_desc *fr, mr::FrameLights &fl)
+// all the lights of a frame with several: the frame's own (FrameConst::light), then the scene's extra ones
+void make_lights(const mr_scene *sc, const mr::FrameConst &fc, mr::FrameLights &fl)
 {
     std::memset(&fl, 0, sizeof fl);
     fl.n = 1 + sc->n_extra_lights;
-    fl.l[0] = light_rec(fr->light_type, fr->light_pos, fr->light_dir, fr->light_color, fr->light_ambient, fr->specular_strength,
-                        fr->att_constant, fr->att_linear, fr->att_quadratic, fr->spot_edge0, fr->spot_edge1);
+    fl.l[0] = fc.light;
     for (int k = 0; k < sc->n_extra_lights; ++k) fl.l[1 + k] = sc->extra_lights[k];
 }
 
@@ -240,7 +239,7 @@ mr::FrameConst make_const(const mr_scene *sc, const mr_frame_desc *fr, const Env
     mr::FrameConst fc;
     std::memset(&fc, 0, sizeof fc);
     fc.width = fr->width; fc.height = fr->height; fc.system = fr->system;
-    fc.backface_culling = fr->backface_culling; fc.light_type = fr->light_type; fc.flags = fr->flags;
+    fc.backface_culling = fr->backface_culling; fc.flags = fr->flags;
     // output rows count from the top, the reference's buffers from the bottom (obj/core.py:640 flips)
     fc.band_y0 = fr->height - fr->row_end;
     fc.band_y1 = fr->height - fr->row_begin;
@@ -271,10 +270,10 @@ mr::FrameConst make_const(const mr_scene *sc, const mr_frame_desc *fr, const Env
     fc.f_minus_n = fr->z_far - fr->z_near;
     for (int j = 0; j < 3; ++j) {
         fc.camera_pos[j] = fr->camera_pos[j];
-        fc.light_pos[j] = fr->light_pos[j]; fc.light_dir[j] = fr->light_dir[j];
-        fc.light_color[j] = fr->light_color[j]; fc.light_ambient[j] = fr->light_ambient[j];
         fc.background[j] = fr->background[j];
     }
+    fc.light = light_rec(fr->light_type, fr->light_pos, fr->light_dir, fr->light_color, fr->light_ambient, fr->specular_strength,
+                         fr->att_constant, fr->att_linear, fr->att_quadratic, fr->spot_edge0, fr->spot_edge1);
     fc.background_u8 = (uint32_t)fr->background_u8;
     std::memcpy(fc.sky_tri, fr->sky_tri, sizeof fc.sky_tri);
     std::memcpy(fc.sky_rays, fr->sky_rays, sizeof fc.sky_rays);
@@ -284,9 +283,6 @@ mr::FrameConst make_const(const mr_scene *sc, const mr_frame_desc *fr, const Env
     fc.edge_compact = sc->edge_compact ? 1 : 0;
     fc.pos32 = sc->pos32 ? 1 : 0;
     fc.cluster_cull = cluster_cull_mode(fr, env.cluster_cull, fc.cull_eye);
-    fc.specular_strength = fr->specular_strength;
-    fc.att_constant = fr->att_constant; fc.att_linear = fr->att_linear; fc.att_quadratic = fr->att_quadratic;
-    fc.spot_edge0 = fr->spot_edge0; fc.spot_edge1 = fr->spot_edge1;
     const int s = ss_factor(fr);
     fc.ss_mode = s > 1 ? ss_shift(s) | (env.resolve_separate ? mr::SS_SEPARATE : 0) : 0;
     return fc;
@@ -498,7 +494,7 @@ int launch_setup(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fr
 
     const bool edges = p.shadows && fc.n_edges > 0;
     ska.sil = SilArgs{};
-    if (edges) sc->sil.choose_path(p.env.sil_cache, p.n_lights, fs->id, stream, fs->quad_cap, sc->frame_serial, fc, ska.sil);
+    if (edges) sc->sil.choose_path(p.env.sil_cache, p.n_lights, fs->id, stream, fs->quad_cap, sc->frame_serial, fc.light, ska.sil);
     constexpr unsigned QS_PER_BLOCK = SETUP_BLOCK / QS_LANES;
     const unsigned edge_blocks = !edges ? 0u
                                : ska.sil.mode == SIL_CACHED ? (ska.sil.count + QS_PER_BLOCK - 1) / QS_PER_BLOCK     // quad workgroups
@@ -621,7 +617,7 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     if ((rc = grow_tile_state(fs, p))) return rc;
     // several lights (mr_scene_set_extra_lights): the multi-light instantiations of k_setup and k_tile read them all
     mr::FrameLights lights;
-    if (p.ml) make_lights(sc, fr, lights);
+    if (p.ml) make_lights(sc, fc, lights);
     if ((rc = launch_setup(sc, fs, fc, p, lights))) return rc;
     if (p.all_marks) HIP_TRY(hipEventRecord(fs->ev[2], stream));
     launch_bin_work(fs, fc, p);

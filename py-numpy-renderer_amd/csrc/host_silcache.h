@@ -18,6 +18,15 @@
 namespace {
 
 struct SilKey { int32_t light_type, pad; double pos[3], dir[3]; };
+inline SilKey sil_key(const mr::LightRec &l)
+{
+    SilKey key;
+    std::memset(&key, 0, sizeof key);
+    key.light_type = l.type;
+    std::memcpy(key.pos, l.pos, sizeof key.pos);
+    std::memcpy(key.dir, l.dir, sizeof key.dir);
+    return key;
+}
 
 struct SilCache {
     enum State { FREE, CAPTURING, VALID, RETIRING };
@@ -86,7 +95,7 @@ struct SilCache {
     // Which path the edge half of this frame's k_setup takes: fills `sil`.  `enabled` is the frame's MR_SIL_CACHE; a frame
     // with several lights takes the fused edge path and leaves the cache, keyed on one light, as it is.
     void choose_path(bool enabled, int n_lights, int slot, hipStream_t stream, uint32_t quad_cap, uint64_t frame_serial,
-                     const mr::FrameConst &fc, mr::SilArgs &sil)
+                     const mr::LightRec &light, mr::SilArgs &sil)
     {
         sil = mr::SilArgs{};
         sil.mode = mr::SIL_FUSED;
@@ -95,11 +104,7 @@ struct SilCache {
         if (n_lights > 1) return;
         if (!enabled) { have_last = false; return; }
         slot_stream[slot] = stream;
-        SilKey key;
-        std::memset(&key, 0, sizeof key);
-        key.light_type = fc.light_type;
-        std::memcpy(key.pos, fc.light_pos, sizeof key.pos);
-        std::memcpy(key.dir, fc.light_dir, sizeof key.dir);
+        const SilKey key = sil_key(light);
         // what the host has seen complete since the last look: a capture becomes VALID, a retired buffer FREE
         if (pending) {
             for (Buf &b : buf) {

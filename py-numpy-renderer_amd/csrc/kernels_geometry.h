@@ -127,17 +127,11 @@ k_face_static(int n_faces, const int32_t *__restrict__ faces, const uint8_t *__r
 __device__ __forceinline__ void load_face_pos(const void *face_pos, bool pos32, int f, double va[4], double vb[4], double vc[4],
                                               int32_t &material, uint8_t &ff)
 {
-    if (pos32) {
-        const FacePos32 p = static_cast<const FacePos32 *>(face_pos)[f];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { va[j] = (double)p.v[0][j]; vb[j] = (double)p.v[1][j]; vc[j] = (double)p.v[2][j]; }
-        material = p.material; ff = (uint8_t)p.flags;
-    } else {
-        const FacePos64 p = static_cast<const FacePos64 *>(face_pos)[f];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { va[j] = p.v[0][j]; vb[j] = p.v[1][j]; vc[j] = p.v[2][j]; }
-        material = p.material; ff = (uint8_t)p.flags;
-    }
+    auto take = [&](auto *p) {      // (ONE branch on pos32: three calls of the dispatching face_corner spill 20 bytes)
+        face_corner(p, f, 0, va); face_corner(p, f, 1, vb); face_corner(p, f, 2, vc);
+        material = p[f].material; ff = (uint8_t)p[f].flags;
+    };
+    if (pos32) take(static_cast<const FacePos32 *>(face_pos)); else take(static_cast<const FacePos64 *>(face_pos));
 }
 
 // One face corner through obj/triangular.py:36-45: clip = v @ MVP (and @ debug MVP), depth =
@@ -157,6 +151,18 @@ __device__ __forceinline__ void clip_coords(const FrameConst &fc, const double v
     }
 }
 
+// Strictly inside both cameras' clip volumes with a relative margin of 1e-12.  A fragment's clip coordinates are a
+// non-negative combination of the corners' (weights u*dp/wc, all >= 0 when u,v,w >= 0 and every w > 0), evaluated with
+// a few ulp (1e-16) of rounding, so when all three corners carry this flag the strict test of obj/triangular.py:85-87
+// cannot fail for any fragment of the face and need not be evaluated.
+__device__ __forceinline__ bool clip_safe(const double clip[4], const double clipd[4])
+{
+    const double k = 1.0 - 1e-12;
+    const double wl = clip[3] * k, wd = clipd[3] * k;
+    return fabs(clip[0]) < wl && fabs(clip[1]) < wl && fabs(clip[2]) < wl &&
+           fabs(clipd[0]) < wd && fabs(clipd[1]) < wd && fabs(clipd[2]) < wd;
+}
+
 __device__ __forceinline__ void xform_vertex(const FrameConst &fc, const double v[4], CornerOut &o)
 {
     // the clip-space coordinates are not kept: the few faces that need them for the per-fragment
@@ -171,15 +177,7 @@ __device__ __forceinline__ void xform_vertex(const FrameConst &fc, const double 
     o.sy = row_times_col(ndc, fc.viewport, 1);
     o.sz = row_times_col(ndc, fc.viewport, 2);
     o.zlin = linearize_z(fc, o.sz);
-    // Strictly inside both cameras' clip volumes with a relative margin of 1e-12.  A fragment's
-    // clip coordinates are a non-negative combination of the corners' (weights u*dp/wc, all
-    // >= 0 when u,v,w >= 0 and every w > 0), evaluated with a few ulp (1e-16) of rounding, so
-    // when all three corners carry this flag the strict test of obj/triangular.py:85-87 cannot
-    // fail for any fragment of the face and need not be evaluated.
-    const double k = 1.0 - 1e-12;
-    const double wl = clip[3] * k, wd = clipd[3] * k;
-    o.safe = fabs(clip[0]) < wl && fabs(clip[1]) < wl && fabs(clip[2]) < wl &&
-             fabs(clipd[0]) < wd && fabs(clipd[1]) < wd && fabs(clipd[2]) < wd;
+    o.safe = clip_safe(clip, clipd);
 }
 
 // The vertex stage on the matrix cores, once per unique vertex.  The two products of
@@ -240,10 +238,7 @@ k_vertex_mfma(const FrameConst fc, const double *__restrict__ verts, VertexOut *
         o.sx = s_scr[wv][v][0]; o.sy = s_scr[wv][v][1]; o.sz = s_scr[wv][v][2];
         o.depth = 1.0 / oc.clip[3];
         o.zlin = linearize_z(fc, o.sz);
-        const double kk = 1.0 - 1e-12;                  // "safely inside" flag: see xform_vertex
-        const double wl = oc.clip[3] * kk, wd = oc.clipd[3] * kk;
-        o.safe = (fabs(oc.clip[0]) < wl && fabs(oc.clip[1]) < wl && fabs(oc.clip[2]) < wl &&
-                  fabs(oc.clipd[0]) < wd && fabs(oc.clipd[1]) < wd && fabs(oc.clipd[2]) < wd) ? 1 : 0;
+        o.safe = clip_safe(oc.clip, oc.clipd) ? 1 : 0;
         o.pad = 0;
         out[base + v] = o;
         out_clip[base + v] = oc;
@@ -310,10 +305,7 @@ struct SetupArgs {
     uint32_t quad_cap;
 };
 
-// k_setup's arguments in one block, read phase by phase through kernargs<>() (rast_math.h): the three 4x4 matrices,
-// the six planes and two dozen pointers do not fit the scalar registers at once, and read as plain arguments they
-// were all fetched at the top and parked in vector-register lanes.
-// The silhouette cache (one per scene and light, see mi355rast.hip, SilCache): the extruded world-space quad (A, B, D, C) of
+// The silhouette cache (one per scene and light, see host_silcache.h, SilCache): the extruded world-space quad (A, B, D, C) of
 // every silhouette edge and the packed (face << 2 | corner) that gave the edge its orientation.  Neither depends on the
 // camera, so a frame whose light and geometry are those of the frames before reads them back instead of testing every edge.
 struct SilQuad { double v[4][4]; };
@@ -323,17 +315,20 @@ struct SilArgs {
     uint32_t *last;                  // (face << 2 | corner) per entry
     uint32_t mode, count;            // SIL_*; SIL_CACHED: entries.  SIL_CAPTURE: capacity of the two arrays
 };
+// k_setup's arguments in one block, read phase by phase through kernargs<>() (rast_math.h): the three 4x4 matrices,
+// the six planes and two dozen pointers do not fit the scalar registers at once, and read as plain arguments they
+// were all fetched at the top and parked in vector-register lanes.
 // (lights: behind everything else, read by the multi-light instantiation's edge workgroups only)
 struct SetupKernArgs { FrameConst fc; SetupArgs sa; BinArgs bins; uint32_t face_blocks; uint32_t edge_spread; SilArgs sil; FrameLights lights; };
 #define SETUP_ARGS() const SetupKernArgs &ka_ = kernargs<SetupKernArgs>(); const FrameConst &fc = ka_.fc; \
                      const SetupArgs &sa = ka_.sa; const BinArgs &bins = ka_.bins; (void)fc; (void)sa; (void)bins
+// light k of the frame as the edge workgroups of k_setup<., ML> see it (k is 0 in a plain frame)
+template <bool ML>
+__device__ __forceinline__ const LightRec &setup_light(const SetupKernArgs &ka, int k) { return ML ? ka.lights.l[k] : ka.fc.light; }
 
-struct CornerOut;
 template <bool PRE_XFORM>
-__device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t ff,
-                                                const double va[4], const double vb[4], const double vc[4],
-                                                const CornerOut &A, const CornerOut &B, const CornerOut &C,
-                                                unsigned int &covered, PrimBox &pb, bool &clip);
+__device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t ff, const CornerOut &A, const CornerOut &B,
+                                                const CornerOut &C, unsigned int &covered, PrimBox &pb, bool &clip);
 
 // One face: status, TriRec / TriAttr / TriClip.  Returns bit 0 = the face goes on to the tile
 // kernel, bit 1 = its survivor count is left to k_bin_work; `covered` receives the fragments of a
@@ -380,15 +375,13 @@ __device__ __forceinline__ int tri_setup_one(int f, unsigned int &covered, PrimB
         if (cull) { status[f] = FACE_BACK_FACE_CULLING; return 0; }
     }
 
-    return tri_setup_record<PRE_XFORM>(f, material, ff, va, vb, vc, A, B, C, covered, pb, clip);
+    return tri_setup_record<PRE_XFORM>(f, material, ff, A, B, C, covered, pb, clip);
 }
 
 // second half of tri_setup_one: the faces that survive the cull (its own view of the arguments: phase 2)
 template <bool PRE_XFORM>
-__device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t ff,
-                                                const double va[4], const double vb[4], const double vc[4],
-                                                const CornerOut &A, const CornerOut &B, const CornerOut &C,
-                                                unsigned int &covered, PrimBox &pb, bool &clip)
+__device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t ff, const CornerOut &A, const CornerOut &B,
+                                                const CornerOut &C, unsigned int &covered, PrimBox &pb, bool &clip)
 {
     SETUP_ARGS();
     uint8_t *status = sa.status;
@@ -721,51 +714,34 @@ __device__ __forceinline__ double (*quad_scratch(int wv))[MAX_POLY + 4][4]
 
 // Corner c (0..3 = A, B, D, C) of the shadow quad of the edge that starts at corner sil_k of face sil_f: the edge's two
 // ends, and the same two pushed away from the light (obj/core.py:612-621)
-__device__ __forceinline__ void quad_corner(const FrameConst &fc, const SetupArgs &sa, int light_type, const double *light_pos,
-                                            const double *light_dir, int sil_f, int sil_k, int c, double v[4])
+__device__ __forceinline__ void quad_corner(const FrameConst &fc, const SetupArgs &sa, const LightRec &light, int sil_f, int sil_k,
+                                            int c, double v[4])
 {
     const int corner = (c == 0 || c == 3) ? sil_k : (sil_k + 1) % 3;       // A, B, D, C: the edge's first / second end
-    if (fc.pos32) {
-        const float *src = static_cast<const FacePos32 *>(sa.face_pos)[sil_f].v[corner];
-        for (int j = 0; j < 4; ++j) v[j] = (double)src[j];
-    } else {
-        const double *src = static_cast<const FacePos64 *>(sa.face_pos)[sil_f].v[corner];
-        for (int j = 0; j < 4; ++j) v[j] = src[j];
-    }
+    face_corner(sa.face_pos, fc.pos32 != 0, sil_f, corner, v);
     if (c >= 2) {
-        if (light_type == MR_LIGHT_POINT) {
-            double d[4] = { v[0] - light_pos[0], v[1] - light_pos[1], v[2] - light_pos[2], v[3] - 1.0 };
+        if (light.type == MR_LIGHT_POINT) {
+            double d[4] = { v[0] - light.pos[0], v[1] - light.pos[1], v[2] - light.pos[2], v[3] - 1.0 };
             double l = sqrt(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]);
             if (l == 0) l = 1;
             for (int j = 0; j < 4; ++j) v[j] = v[j] + 1000 * (d[j] / l);
         } else {
-            for (int j = 0; j < 3; ++j) v[j] = v[j] + light_dir[j] * -1000;
+            for (int j = 0; j < 3; ++j) v[j] = v[j] + light.dir[j] * -1000;
             v[3] = v[3] + 1.0;
         }
     }
 }
 
-// Front half: the edge's corners and their extrusion away from the light (obj/core.py:612-621).  quad = (A, B, D, C);
-// lanes 0..3 of the group receive A, B, D, C in v, the other lanes zeros.  Nothing here depends on the camera.
-__device__ __forceinline__ void quad_extrude_group(bool have, int sil_f, int sil_k, double v[4])
-{
-    const int gl = (threadIdx.x & (WAVE - 1)) % QS_LANES;
-    for (int j = 0; j < 4; ++j) v[j] = 0;
-    SETUP_ARGS();                                                // phase: the edge's corners, extrusion
-    if (have && gl < 4) {
-        quad_corner(fc, sa, fc.light_type, fc.light_pos, fc.light_dir, sil_f, sil_k, gl, v);
-    }
-}
-// The same for light k of a frame with several (FrameLights); k is the same in every lane.
-__device__ __forceinline__ void quad_extrude_group_ml(bool have, int sil_f, int sil_k, int k, double v[4])
+// Front half: the edge's corners and their extrusion away from light k of the frame (obj/core.py:612-621; k is the same
+// in every lane).  quad = (A, B, D, C); lanes 0..3 of the group receive A, B, D, C in v, the other lanes zeros.  Nothing
+// here depends on the camera.
+template <bool ML>
+__device__ __forceinline__ void quad_extrude_group(bool have, int sil_f, int sil_k, int k, double v[4])
 {
     const int gl = (threadIdx.x & (WAVE - 1)) % QS_LANES;
     for (int j = 0; j < 4; ++j) v[j] = 0;
     const SetupKernArgs &ka = kernargs<SetupKernArgs>();         // phase: the edge's corners, extrusion
-    if (have && gl < 4) {
-        const LightRec &l = ka.lights.l[k];
-        quad_corner(ka.fc, ka.sa, l.type, l.pos, l.dir, sil_f, sil_k, gl, v);
-    }
+    if (have && gl < 4) quad_corner(ka.fc, ka.sa, setup_light<ML>(ka, k), sil_f, sil_k, gl, v);
 }
 
 // Back half: clipping, projection, plane, pixel box, work items and the record of the quad whose corners lanes 0..3 of the
@@ -873,7 +849,6 @@ __device__ __forceinline__ void quad_finish_group(bool have, double v[4], uint32
     // (tools/micro/atomic_same_addr.hip) -- up to 14 us at the end of every chain.  Its work items of 64 tiles
     // (kernels_bin.h; all lanes take part) take one more returning atomic per wavefront, on one of WORK_SHARDS cursors.
     const uint32_t s_idx = (uint32_t)__shfl((int)s_base_raw, 0) + s_rank;
-    const uint32_t slot = s_idx;
     const uint32_t chunks = (boxed && gl == 0) ? quad_chunks(fc, bx0, bx1, by0, by1) : 0u;
     WorkSlot ws;
     const bool any_work = reserve_work_items(bins, chunks, ws);
@@ -881,11 +856,11 @@ __device__ __forceinline__ void quad_finish_group(bool have, double v[4], uint32
         const unsigned long long drawn = __ballot(boxed && gl == 0);           // (a statistic: nobody waits for it)
         if (lane == 0 && drawn) atomicAdd(&sa.ctr->n_quads_drawn, (uint32_t)__popcll(drawn));
     }
-    if (any_work) fill_work_items(bins, ws, slot < sa.quad_cap ? (WORK_QUAD | slot) : WORK_NONE, chunks);
+    if (any_work) fill_work_items(bins, ws, s_idx < sa.quad_cap ? (WORK_QUAD | s_idx) : WORK_NONE, chunks);
     if (!boxed) return;
-    if (slot >= sa.quad_cap) { if (gl == 0) atomicOr(&sa.ctr->overflow, 16u); return; }
+    if (s_idx >= sa.quad_cap) { if (gl == 0) atomicOr(&sa.ctr->overflow, 16u); return; }
 
-    QuadRec &q = sa.quads[slot];
+    QuadRec &q = sa.quads[s_idx];
     if (gl < MAX_POLY) {
         QuadEdge e;
         e.sx = used ? sx : 0.0; e.sy = used ? sy : 0.0;
@@ -907,9 +882,18 @@ __device__ __forceinline__ void quad_finish_group(bool have, double v[4], uint32
     }
 }
 
+// Entry `slot` of the frame's silhouette list: the (face << 2 | corner) that gave the edge its orientation, unpacked (the
+// host maps the face back to its model), with the light that cast it in bits SIL_LIGHT_SHIFT and up of the corner word.
+__device__ __forceinline__ void write_sil_edge(const SetupArgs &sa, uint32_t slot, uint32_t last, uint32_t light)
+{
+    if (slot >= sa.quad_cap) return;
+    sa.sil_edges[slot * 2 + 0] = (int32_t)(last >> 2);
+    sa.sil_edges[slot * 2 + 1] = (int32_t)((last & 3u) | (light << SIL_LIGHT_SHIFT));
+}
+
 // Quad workgroup of a frame that found its light's silhouette in the cache (these take the edge workgroups' place in
-// the grid, behind the faces): one entry per 16-lane group, the back half of the fused path from there.  Entry i is silhouette edge i of the frame (record, sil_edges and n_quads as edge_block
-// leaves them).
+// the grid, behind the faces): one entry per 16-lane group, the back half of the fused path from there.  Entry i is
+// silhouette edge i of the frame (record, sil_edges and n_quads as edge_block leaves them).
 __device__ __forceinline__ void quad_block(uint32_t block)
 {
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE, gl = lane % QS_LANES;
@@ -920,270 +904,187 @@ __device__ __forceinline__ void quad_block(uint32_t block)
         const SetupKernArgs &ka = kernargs<SetupKernArgs>();
         have = at < ka.sil.count;
         if (have && gl < 4) for (int j = 0; j < 4; ++j) v[j] = ka.sil.quads[at].v[gl][j];
-        if (have && gl == 4 && at < ka.sa.quad_cap) {
-            const uint32_t ls = ka.sil.last[at];
-            ka.sa.sil_edges[at * 2 + 0] = (int32_t)(ls >> 2);
-            ka.sa.sil_edges[at * 2 + 1] = (int32_t)(ls & 3u);
-        }
+        if (have && gl == 4) write_sil_edge(ka.sa, at, ka.sil.last[at], 0u);
         if (block == 0 && threadIdx.x == 0) atomicAdd(&ka.sa.ctr->n_quads, ka.sil.count);
     }
     quad_finish_group(have, v, 0u, at, quad_scratch(wv));
 }
 
-// Edge workgroup: one unique undirected edge per lane.  An edge is on the silhouette when an odd
-// number of its incident light-facing faces toggled it; it keeps the orientation of the last
-// such face in face order (set add/discard semantics of obj/triangular.py:294-302).  The
-// incident faces' normals sit in the edge record, so the test is one 64-byte load and two dots.
-// The scene's edges are stored in a scrambled order (host, build_edge_table): the silhouette of a
-// mesh runs along consecutive vertex indices, and without that a wavefront would find dozens
-// of silhouette edges among its 64 and set their quads up four at a time while the rest of the
-// device idles.
-__device__ __forceinline__ void edge_block(uint32_t block)
+// Which edges a lane of edge workgroup `block` looks at (want[i]: it has an i-th edge, e[i]).  A wavefront sets its
+// silhouette edges up four at a time, one round of 10-15 us after the other, so what matters is how many it FINDS:
+//   small scenes (spread s > 0): a mesh of a few thousand edges of which one in ten is on the silhouette (c3: 7 500 edges,
+//     120 wavefronts with five or six each) spent two or three rounds -- only every (1 << s)-th lane takes an edge, and
+//     there are that many more wavefronts;
+//   large scenes (EDGE_DENSE): one edge in 250 is on the silhouette, the launch holds more wavefronts than fit at once
+//     (c4: 3 128 of faces + 4 688 of edges against 5 120 places) and the edge wavefronts that wait for a place start their
+//     chain late -- two edges per lane, a workgroup apart, halve their number and still find five in one wavefront less
+//     than once per frame.
+__device__ __forceinline__ void lane_edges(uint32_t block, uint32_t spread, int n_edges, int e[2], bool want[2])
 {
-    SETUP_ARGS();
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    // How many edges a lane looks at.  A wavefront sets its silhouette edges up four at a time, one round of 10-15 us
-    // after the other, so what matters is how many it FINDS:
-    //   small scenes (edge_spread s > 0): a mesh of a few thousand edges of which one in ten is on the silhouette (c3:
-    //     7 500 edges, 120 wavefronts with five or six each) spent two or three rounds -- only every (1 << s)-th lane
-    //     takes an edge, and there are that many more wavefronts;
-    //   large scenes (EDGE_DENSE): one edge in 250 is on the silhouette, the launch holds more wavefronts than fit at
-    //     once (c4: 3 128 of faces + 4 688 of edges against 5 120 places) and the edge wavefronts that wait for a place
-    //     start their chain late -- two edges per lane halve their number and still find five in one wavefront less
-    //     than once per frame.
-    const uint32_t spread = ka_.edge_spread;
-    if (spread == EDGE_CACHED) { quad_block(block); return; }      // (the frame found its silhouette in the cache)
-    const bool dense = spread == EDGE_DENSE;
     const uint32_t slot_in_grid = block * blockDim.x + threadIdx.x;
-    int e[2];
-    bool want[2];
-    if (dense) {
+    if (spread == EDGE_DENSE) {
         e[0] = (int)(block * 2u * blockDim.x + threadIdx.x); e[1] = e[0] + (int)blockDim.x;
-        want[0] = e[0] < fc.n_edges; want[1] = e[1] < fc.n_edges;
+        want[0] = e[0] < n_edges; want[1] = e[1] < n_edges;
     } else {
         e[0] = (int)(slot_in_grid >> spread); e[1] = 0;
-        want[0] = (slot_in_grid & ((1u << spread) - 1u)) == 0 && e[0] < fc.n_edges; want[1] = false;
+        want[0] = (slot_in_grid & ((1u << spread) - 1u)) == 0 && e[0] < n_edges; want[1] = false;
     }
-    bool sil[2] = { false, false };
-    uint32_t last[2] = { 0, 0 };
+}
+
+// Edge e of the scene's table from either layout (EdgeRec32[] when `compact`, which has no extra incidences), widened
+__device__ __forceinline__ EdgeRec load_edge(const EdgeRec *edges, bool compact, int e)
+{
+    if (!compact) return edges[e];
+    const EdgeRec32 c = reinterpret_cast<const EdgeRec32 *>(edges)[e];
+    EdgeRec r;
+    r.inc[0] = c.inc[0]; r.inc[1] = c.inc[1]; r.extra_off = r.extra_cnt = 0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        if (!want[i]) continue;
-        EdgeRec r;
-        if (fc.edge_compact) {
-            const EdgeRec32 c = reinterpret_cast<const EdgeRec32 *>(sa.edges)[e[i]];
-            r.inc[0] = c.inc[0]; r.inc[1] = c.inc[1];
-            r.extra_off = r.extra_cnt = 0;
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int a = 0; a < 2; ++a)
+        for (int j = 0; j < 3; ++j) r.n[a][j] = (double)c.n[a][j];
+    return r;
+}
+
+// Is edge r on the silhouette of the light at lp?  It is when an odd number of its incident light-facing faces toggled
+// it; `last` receives the last such (face << 2 | corner) in face order, which gives the edge its orientation (set
+// add / discard semantics of obj/triangular.py:294-302).  The first two incident faces' normals sit in the record; the
+// rare further incidences are walked through the spill array.
+__device__ __forceinline__ bool edge_on_silhouette(const SetupArgs &sa, const EdgeRec &r, const double *lp, uint32_t &last)
+{
+    uint32_t cnt = 0;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) r.n[a][j] = (double)c.n[a][j];
-        } else {
-            r = sa.edges[e[i]];
-        }
-        uint32_t cnt = 0;
+    for (int a = 0; a < 2; ++a) {
+        if (r.inc[a] != 0xffffffffu && chain3(r.n[a][0], r.n[a][1], r.n[a][2], lp[0], lp[1], lp[2]) > 0) { ++cnt; last = r.inc[a]; }
+    }
+    for (uint32_t x = 0; x < r.extra_cnt; ++x) {
+        const uint32_t inc = sa.edge_inc[r.extra_off + x];
+        const double *fn = sa.face_n + (size_t)(inc >> 2) * 4;
+        if (chain3(fn[0], fn[1], fn[2], lp[0], lp[1], lp[2]) > 0) { ++cnt; last = inc; }
+    }
+    return (cnt & 1u) != 0;
+}
+
+// One round of the quad set-up serves four silhouette edges of the wavefront, one per 16-lane group: the lanes' first
+// edges (the set bits of todo0, in lane order), then their second (todo1).  Returns the lane whose edge group `grp`
+// serves in this round (-1: none is left for it) and in `set` which of that lane's two edges, and retires the round's
+// (up to) four from the lists.
+__device__ __forceinline__ int take_round(int grp, unsigned long long &todo0, unsigned long long &todo1, int &set)
+{
+    int src = -1;
+    const int c0 = (int)__popcll(todo0);
+    unsigned long long t = grp < c0 ? todo0 : todo1;
+    const int nth = grp < c0 ? grp : grp - c0;
+    set = grp < c0 ? 0 : 1;
+    for (int g = 0; g <= nth && t; ++g) {                        // this group takes the nth set bit
+        const int b = __ffsll((long long)t) - 1;
+        t &= t - 1;
+        if (g == nth) src = b;
+    }
+    unsigned long long t0 = todo0, t1 = todo1;                   // (copies: conditional writes through the references cost scratch)
+    for (int g = 0; g < WAVE / QS_LANES; ++g) {                  // the round's (up to) four leave the lists
+        if (t0) t0 &= t0 - 1;
+        else if (t1) t1 &= t1 - 1;
+    }
+    todo0 = t0; todo1 = t1;
+    return src;
+}
+
+// Edge workgroup: one unique undirected edge per lane (lane_edges).  The incident faces' normals sit in the edge record,
+// so the light-facing test is one 64-byte load and two dots.  The scene's edges are stored in a scrambled order (host,
+// build_edge_table): the silhouette of a mesh runs along consecutive vertex indices, and without that a wavefront would
+// find dozens of silhouette edges among its 64 and set their quads up four at a time while the rest of the device idles.
+// ML, a frame with several lights (FrameLights; k_setup<., true>): the edge records are loaded ONCE and tested against
+// every light -- per light and incident face one dot, what the records were laid out for -- and every (silhouette edge,
+// light) pair gets a shadow quad through the same two halves.  The lights take their turns one after the other, each
+// with the plain frame's bookkeeping: one atomic on n_quads per wavefront and light, records and sil_edges at the
+// silhouette index, so a light's entries are scattered over the one list and carry its index (the QuadRec's `light`,
+// write_sil_edge).  Such frames neither read nor fill the silhouette cache.  A plain frame's loops over the lights are
+// compiled away.
+template <bool ML>
+__device__ __forceinline__ void edge_block(uint32_t block)
+{
+    constexpr int NL = ML ? MAX_LIGHTS : 1;
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    int n_lights = 1;
+    uint32_t lit_odd = 0;                            // bit 4 i + k: the lane's edge i is on light k's silhouette
+    uint32_t last[2][NL] = {};
+    {
+        const SetupKernArgs &ka = kernargs<SetupKernArgs>();     // phase: the edge records against the lights
+        const uint32_t spread = ka.edge_spread;
+        if (!ML && spread == EDGE_CACHED) { quad_block(block); return; }      // (the frame found its silhouette in the cache)
+        if (ML) n_lights = min(max(ka.lights.n, 1), MAX_LIGHTS);
+        int e[2];
+        bool want[2];
+        lane_edges(block, spread, ka.fc.n_edges, e, want);
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            if (r.inc[a] != 0xffffffffu &&
-                chain3(r.n[a][0], r.n[a][1], r.n[a][2], fc.light_pos[0], fc.light_pos[1], fc.light_pos[2]) > 0) {
-                ++cnt; last[i] = r.inc[a];
+        for (int i = 0; i < 2; ++i) {
+            if (!want[i]) continue;
+            const EdgeRec r = load_edge(ka.sa.edges, ka.fc.edge_compact != 0, e[i]);
+#pragma unroll
+            for (int k = 0; k < NL; ++k) {
+                if (k >= n_lights) break;
+                if (edge_on_silhouette(ka.sa, r, setup_light<ML>(ka, k).pos, last[i][k])) lit_odd |= 1u << (4 * i + k);
             }
         }
-        for (uint32_t k = 0; k < r.extra_cnt; ++k) {
-            const uint32_t inc = sa.edge_inc[r.extra_off + k];
-            const double *fn = sa.face_n + (size_t)(inc >> 2) * 4;
-            if (chain3(fn[0], fn[1], fn[2], fc.light_pos[0], fc.light_pos[1], fc.light_pos[2]) > 0) { ++cnt; last[i] = inc; }
-        }
-        sil[i] = (cnt & 1u) != 0;
     }
-    unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);
-    if (!(todo0 | todo1)) return;
-    // the wavefront's silhouette edges get consecutive list slots with one atomic; its answer is first needed
-    // at the end of the quad set-up (the records' slots), so it is not waited for here
-    const uint32_t found0 = (uint32_t)__popcll(todo0), found = found0 + (uint32_t)__popcll(todo1);
-    uint32_t base_raw = 0;
-    if (lane == 0) base_raw = atomicAdd(&sa.ctr->n_quads, found);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const uint32_t my_rank0 = (uint32_t)__popcll(todo0 & below), my_rank1 = found0 + (uint32_t)__popcll(todo1 & below);
-    // quad set-up, four silhouette edges per round (one per 16-lane group): the lanes' first edges, then their second
+    if (ML && !__ballot(lit_odd != 0)) return;
     const int grp = lane / QS_LANES;
-    while (todo0 | todo1) {
-        int src = -1, set = 0;
-        {
-            const int c0 = (int)__popcll(todo0);
-            unsigned long long t = grp < c0 ? todo0 : todo1;
-            const int nth = grp < c0 ? grp : grp - c0;
-            set = grp < c0 ? 0 : 1;
-            for (int g = 0; g <= nth && t; ++g) {                   // this group takes the nth set bit
-                const int b = __ffsll((long long)t) - 1;
-                t &= t - 1;
-                if (g == nth) src = b;
-            }
-        }
-        for (int g = 0; g < WAVE / QS_LANES; ++g) {                  // the round's (up to) four leave the lists
-            if (todo0) todo0 &= todo0 - 1;
-            else if (todo1) todo1 &= todo1 - 1;
-        }
-        const bool have = src >= 0;
-        const int from = have ? src : 0;
-        const uint32_t l0 = (uint32_t)__shfl((int)last[0], from), l1 = (uint32_t)__shfl((int)last[1], from);
-        const uint32_t r0 = (uint32_t)__shfl((int)my_rank0, from), r1 = (uint32_t)__shfl((int)my_rank1, from);
-        const uint32_t ls = set ? l1 : l0, rank = set ? r1 : r0;
-        double v[4];
-        quad_extrude_group(have, (int)(ls >> 2), (int)(ls & 3u), v);
-        quad_finish_group(have, v, base_raw, rank, quad_scratch(wv));
-    }
-    const uint32_t base = (uint32_t)__shfl((int)base_raw, 0);
-    const SetupArgs &sa2 = kernargs<SetupKernArgs>().sa;
+    uint32_t base = 0, rank[2] = { 0, 0 };
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const uint32_t my_slot = base + (i ? my_rank1 : my_rank0);
-        if (sil[i] && my_slot < sa2.quad_cap) {
-            sa2.sil_edges[my_slot * 2 + 0] = (int32_t)(last[i] >> 2);      // the host maps the face back to its model
-            sa2.sil_edges[my_slot * 2 + 1] = (int32_t)(last[i] & 3u);
+    for (int k = 0; k < NL; ++k) {                    // (unrolled: last[.][k] stays in registers)
+        if (k >= n_lights) break;
+        const bool sil[2] = { (lit_odd >> k & 1u) != 0, (lit_odd >> (4 + k) & 1u) != 0 };
+        unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);
+        if (!(todo0 | todo1)) { if (ML) continue; else return; }
+        // the wavefront's silhouette edges get consecutive list slots with one atomic; its answer is first needed
+        // at the end of the quad set-up (the records' slots), so it is not waited for here
+        const uint32_t found0 = (uint32_t)__popcll(todo0), found = found0 + (uint32_t)__popcll(todo1);
+        uint32_t base_raw = 0;
+        if (lane == 0) base_raw = atomicAdd(&kernargs<SetupKernArgs>().sa.ctr->n_quads, found);
+        const unsigned long long below = (1ull << lane) - 1ull;
+        rank[0] = (uint32_t)__popcll(todo0 & below); rank[1] = found0 + (uint32_t)__popcll(todo1 & below);
+        while (todo0 | todo1) {                       // quad set-up, four silhouette edges per round (take_round)
+            int set;
+            const int src = take_round(grp, todo0, todo1, set);
+            const bool have = src >= 0;
+            const int from = have ? src : 0;
+            const uint32_t l0 = (uint32_t)__shfl((int)last[0][k], from), l1 = (uint32_t)__shfl((int)last[1][k], from);
+            const uint32_t r0 = (uint32_t)__shfl((int)rank[0], from), r1 = (uint32_t)__shfl((int)rank[1], from);
+            const uint32_t ls = set ? l1 : l0;
+            double v[4];
+            quad_extrude_group<ML>(have, (int)(ls >> 2), (int)(ls & 3u), k, v);
+            quad_finish_group(have, v, base_raw, set ? r1 : r0, quad_scratch(wv), (uint32_t)k);
         }
+        base = (uint32_t)__shfl((int)base_raw, 0);
+        const SetupArgs &sa2 = kernargs<SetupKernArgs>().sa;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (sil[i]) write_sil_edge(sa2, base + rank[i], last[i][k], (uint32_t)k);
     }
     // A capture frame leaves its silhouette in the cache as well (SilArgs), entry = silhouette index: here, behind the
     // frame's own work and one edge per lane, so that the rounds above are the same code whether the frame captures or not.
-    if (kernargs<SetupKernArgs>().sil.mode != SIL_CAPTURE) return;
+    if (ML || kernargs<SetupKernArgs>().sil.mode != SIL_CAPTURE) return;
 #pragma unroll 1
     for (int i = 0; i < 2; ++i) {
         const SetupKernArgs &kc = kernargs<SetupKernArgs>();
-        const uint32_t at = base + (i ? my_rank1 : my_rank0);
-        if (!sil[i] || at >= kc.sil.count) continue;
-        kc.sil.last[at] = last[i];
+        const uint32_t at = base + (i ? rank[1] : rank[0]), ls = i ? last[1][0] : last[0][0];
+        if (!(lit_odd >> (4 * i) & 1u) || at >= kc.sil.count) continue;
+        kc.sil.last[at] = ls;
 #pragma unroll 1
         for (int c = 0; c < 4; ++c) {
             double v[4];
-            quad_corner(kc.fc, kc.sa, kc.fc.light_type, kc.fc.light_pos, kc.fc.light_dir, (int)(last[i] >> 2), (int)(last[i] & 3u), c, v);
+            quad_corner(kc.fc, kc.sa, kc.fc.light, (int)(ls >> 2), (int)(ls & 3u), c, v);
             for (int j = 0; j < 4; ++j) kc.sil.quads[at].v[c][j] = v[j];
         }
     }
 }
 
-// Edge workgroup of a frame with several lights (FrameLights; k_setup<., true>): the edge records are loaded ONCE and
-// tested against every light -- per light and incident face one dot, what the records were laid out for -- and every
-// (silhouette edge, light) pair gets a shadow quad through the same two halves as above.  The lights take their turns
-// one after the other, each with the plain path's bookkeeping: one atomic on n_quads per wavefront and light, records
-// and sil_edges at the silhouette index, so a light's entries are scattered over the one list and carry its index (the
-// QuadRec's `light`, bits 2.. of the list's corner word).  Such frames neither read nor fill the silhouette cache.
-__device__ __forceinline__ void edge_block_ml(uint32_t block)
-{
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    int n_lights;
-    uint32_t lit_odd = 0;                            // bit 4 i + k: the lane's edge i is on light k's silhouette
-    uint32_t last[2][MAX_LIGHTS] = {};
-    {
-        const SetupKernArgs &ka = kernargs<SetupKernArgs>();
-        const FrameConst &fc = ka.fc;
-        const SetupArgs &sa = ka.sa;
-        n_lights = min(max(ka.lights.n, 1), MAX_LIGHTS);
-        const uint32_t spread = ka.edge_spread;
-        const bool dense = spread == EDGE_DENSE;
-        const uint32_t slot_in_grid = block * blockDim.x + threadIdx.x;
-        int e[2];
-        bool want[2];
-        if (dense) {
-            e[0] = (int)(block * 2u * blockDim.x + threadIdx.x); e[1] = e[0] + (int)blockDim.x;
-            want[0] = e[0] < fc.n_edges; want[1] = e[1] < fc.n_edges;
-        } else {
-            e[0] = (int)(slot_in_grid >> spread); e[1] = 0;
-            want[0] = (slot_in_grid & ((1u << spread) - 1u)) == 0 && e[0] < fc.n_edges; want[1] = false;
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (!want[i]) continue;
-            EdgeRec r;
-            if (fc.edge_compact) {
-                const EdgeRec32 c = reinterpret_cast<const EdgeRec32 *>(sa.edges)[e[i]];
-                r.inc[0] = c.inc[0]; r.inc[1] = c.inc[1];
-                r.extra_off = r.extra_cnt = 0;
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) r.n[a][j] = (double)c.n[a][j];
-            } else {
-                r = sa.edges[e[i]];
-            }
-#pragma unroll
-            for (int k = 0; k < MAX_LIGHTS; ++k) {
-                if (k >= n_lights) break;
-                const double *lp = ka.lights.l[k].pos;
-                uint32_t cnt = 0;
-#pragma unroll
-                for (int a = 0; a < 2; ++a) {
-                    if (r.inc[a] != 0xffffffffu && chain3(r.n[a][0], r.n[a][1], r.n[a][2], lp[0], lp[1], lp[2]) > 0) {
-                        ++cnt; last[i][k] = r.inc[a];
-                    }
-                }
-                for (uint32_t x = 0; x < r.extra_cnt; ++x) {
-                    const uint32_t inc = sa.edge_inc[r.extra_off + x];
-                    const double *fn = sa.face_n + (size_t)(inc >> 2) * 4;
-                    if (chain3(fn[0], fn[1], fn[2], lp[0], lp[1], lp[2]) > 0) { ++cnt; last[i][k] = inc; }
-                }
-                lit_odd |= (cnt & 1u) << (4 * i + k);
-            }
-        }
-    }
-    if (!__ballot(lit_odd != 0)) return;
-    const int grp = lane / QS_LANES;
-#pragma unroll
-    for (int k = 0; k < MAX_LIGHTS; ++k) {            // (unrolled: last[.][k] stays in registers)
-        if (k >= n_lights) break;
-        const bool sil[2] = { (lit_odd >> k & 1u) != 0, (lit_odd >> (4 + k) & 1u) != 0 };
-        unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);
-        if (!(todo0 | todo1)) continue;
-        const uint32_t found0 = (uint32_t)__popcll(todo0), found = found0 + (uint32_t)__popcll(todo1);
-        uint32_t base_raw = 0;
-        if (lane == 0) base_raw = atomicAdd(&kernargs<SetupKernArgs>().sa.ctr->n_quads, found);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const uint32_t my_rank0 = (uint32_t)__popcll(todo0 & below), my_rank1 = found0 + (uint32_t)__popcll(todo1 & below);
-        while (todo0 | todo1) {                       // four silhouette edges per round, as in edge_block
-            int src = -1, set = 0;
-            {
-                const int c0 = (int)__popcll(todo0);
-                unsigned long long t = grp < c0 ? todo0 : todo1;
-                const int nth = grp < c0 ? grp : grp - c0;
-                set = grp < c0 ? 0 : 1;
-                for (int g = 0; g <= nth && t; ++g) {
-                    const int b = __ffsll((long long)t) - 1;
-                    t &= t - 1;
-                    if (g == nth) src = b;
-                }
-            }
-            for (int g = 0; g < WAVE / QS_LANES; ++g) {
-                if (todo0) todo0 &= todo0 - 1;
-                else if (todo1) todo1 &= todo1 - 1;
-            }
-            const bool have = src >= 0;
-            const int from = have ? src : 0;
-            const uint32_t l0 = (uint32_t)__shfl((int)last[0][k], from), l1 = (uint32_t)__shfl((int)last[1][k], from);
-            const uint32_t r0 = (uint32_t)__shfl((int)my_rank0, from), r1 = (uint32_t)__shfl((int)my_rank1, from);
-            const uint32_t ls = set ? l1 : l0, rank = set ? r1 : r0;
-            double v[4];
-            quad_extrude_group_ml(have, (int)(ls >> 2), (int)(ls & 3u), k, v);
-            quad_finish_group(have, v, base_raw, rank, quad_scratch(wv), (uint32_t)k);
-        }
-        const uint32_t base = (uint32_t)__shfl((int)base_raw, 0);
-        const SetupArgs &sa2 = kernargs<SetupKernArgs>().sa;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t my_slot = base + (i ? my_rank1 : my_rank0);
-            if (sil[i] && my_slot < sa2.quad_cap) {
-                sa2.sil_edges[my_slot * 2 + 0] = (int32_t)(last[i][k] >> 2);
-                sa2.sil_edges[my_slot * 2 + 1] = (int32_t)((last[i][k] & 3u) | ((uint32_t)k << SIL_LIGHT_SHIFT));
-            }
-        }
-    }
-}
-
-// First launch of the frame: workgroup 0 puts the frame's tiles in order (a serial walk of some microseconds,
-// hidden behind the others), workgroups [1, 1 + face_blocks) set faces up, the rest look at edges.
 #ifndef MR_SETUP_WAVES
 #define MR_SETUP_WAVES 5
 #endif
-// ML: a frame with several lights -- its edge workgroups are edge_block_ml's.  An instantiation of its own so that
-// the plain frame's kernel is the code it was.
+// First launch of the frame: workgroup 0 puts the frame's tiles in order (a serial walk of some microseconds, hidden
+// behind the others), workgroups [1, 1 + face_blocks) set faces up, the rest look at edges.  ML: a frame with several
+// lights -- an instantiation of its own so that the plain frame's kernel is the code it was.
 template <bool PRE_XFORM, bool ML>
 __global__ void __launch_bounds__(SETUP_BLOCK, MR_SETUP_WAVES)
 k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(), phase by phase
@@ -1196,8 +1097,7 @@ k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(
     }
     const uint32_t b = blockIdx.x - 1;
     if (b < face_blocks) tri_setup_block<PRE_XFORM>(b);
-    else if (ML) edge_block_ml(b - face_blocks);
-    else edge_block(b - face_blocks);
+    else edge_block<ML>(b - face_blocks);
 }
 
 // Second launch: the leftover survivor counts (a few workgroups, first so that their

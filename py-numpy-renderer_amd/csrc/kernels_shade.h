@@ -151,21 +151,7 @@ struct LightConst {
     double specular_strength, att_constant, att_linear, att_quadratic, spot_edge0, spot_edge1;
     int32_t light_type;
 };
-__device__ __forceinline__ LightConst light_const(const FrameConst &fc)
-{
-    LightConst lc;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        lc.camera_pos[j] = fc.camera_pos[j]; lc.light_pos[j] = fc.light_pos[j]; lc.light_dir[j] = fc.light_dir[j];
-        lc.light_color[j] = fc.light_color[j]; lc.light_ambient[j] = fc.light_ambient[j];
-    }
-    lc.specular_strength = fc.specular_strength;
-    lc.att_constant = fc.att_constant; lc.att_linear = fc.att_linear; lc.att_quadratic = fc.att_quadratic;
-    lc.spot_edge0 = fc.spot_edge0; lc.spot_edge1 = fc.spot_edge1;
-    lc.light_type = fc.light_type;
-    return lc;
-}
-// light k of a frame with several (the camera is not the light's: shade_light<true> does not read it)
+// a light's view, without a camera: light k of a frame with several (shade_light<true> does not read the camera)
 __device__ __forceinline__ LightConst light_const(const LightRec &l)
 {
     LightConst lc;
@@ -178,6 +164,14 @@ __device__ __forceinline__ LightConst light_const(const LightRec &l)
     lc.att_constant = l.att_constant; lc.att_linear = l.att_linear; lc.att_quadratic = l.att_quadratic;
     lc.spot_edge0 = l.spot_edge0; lc.spot_edge1 = l.spot_edge1;
     lc.light_type = l.type;
+    return lc;
+}
+// the plain frame's view: its own light, seen from its camera
+__device__ __forceinline__ LightConst frame_light(const FrameConst &fc)
+{
+    LightConst lc = light_const(fc.light);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) lc.camera_pos[j] = fc.camera_pos[j];
     return lc;
 }
 

@@ -906,7 +906,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         const FrameConst &fc = ka.fc;
         const TileArgs &ta = ka.ta;
         const ShadeArgs &sh = ka.sh;
-        const LightConst lc = light_const(fc);
+        const LightConst lc = frame_light(fc);
         int px, py;
         my_pixel(px, py);
         float rgb[3] = { fc.background[0], fc.background[1], fc.background[2] };

@@ -172,4 +172,18 @@ __device__ __forceinline__ bool bound_box(const double *xs, const double *ys, in
     return true;
 }
 
+// Corner c of face f from the scene's static face records (FacePos32[] or FacePos64[]), as float64
+template <class T>
+__device__ __forceinline__ void face_corner(const FacePosT<T> *recs, int f, int c, double v[4])
+{
+    const T *src = recs[f].v[c];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (double)src[j];
+}
+__device__ __forceinline__ void face_corner(const void *face_pos, bool pos32, int f, int c, double v[4])
+{
+    if (pos32) face_corner(static_cast<const FacePos32 *>(face_pos), f, c, v);
+    else face_corner(static_cast<const FacePos64 *>(face_pos), f, c, v);
+}
+
 }  // namespace mr

@@ -38,12 +38,19 @@ enum : uint32_t {
     TF_SINGLE_Z = 4       // exactly one fragment survives coverage + clip -> z is a dot
 };
 
+// A light as the kernels read it: the frame's own (FrameConst::light) and every one of a frame with several (FrameLights).
+struct LightRec {
+    double pos[3], dir[3], color[3], ambient[3];
+    double specular_strength, att_constant, att_linear, att_quadratic;
+    double spot_edge0, spot_edge1;
+    int32_t type, pad;
+};
+
 // Per-frame constants, passed to every kernel by value (kernarg segment, scalar loads).
 struct FrameConst {
     int32_t width, height;
     int32_t system;              // +1 RH, -1 LH
     int32_t backface_culling;
-    int32_t light_type;
     int32_t flags;
     int32_t band_y0, band_y1;    // screen rows [band_y0, band_y1) this device owns (y up, unflipped)
     int32_t tiles_x, tiles_y;    // tile grid this device owns: tiles_y local tile rows
@@ -57,9 +64,7 @@ struct FrameConst {
     double planes[24];
     double two_nf, f_plus_n, f_minus_n;      // linearize_z constants (obj/core.py:226-228)
     double camera_pos[3];
-    double light_pos[3], light_dir[3], light_color[3], light_ambient[3];
-    double specular_strength, att_constant, att_linear, att_quadratic;
-    double spot_edge0, spot_edge1;
+    LightRec light;              // light 0, the frame descriptor's own
     float background[3];
     uint32_t background_u8;      // finalised background r | g << 8 | b << 16 | 1 << 24 (0 = not given)
     int32_t sky_tri[12];         // skybox triangles' integer screen vertices [t][v][xy]
@@ -76,16 +81,10 @@ struct FrameConst {
 
 constexpr int SS_SHIFT_MASK = 0xff, SS_SEPARATE = 0x100;
 
-// A frame with more than one light (mr_scene_set_extra_lights): ALL its lights, light 0 -- the one FrameConst
-// describes -- included, so that the kernels' loops over the lights read one array.  It travels behind the other
+// A frame with more than one light (mr_scene_set_extra_lights): ALL its lights, light 0 -- FrameConst::light --
+// included, so that the kernels' loops over the lights read one array.  It travels behind the other
 // kernel arguments of k_setup and k_tile and only their multi-light instantiations read it.
 constexpr int MAX_LIGHTS = 4;            // MR_MAX_LIGHTS
-struct LightRec {
-    double pos[3], dir[3], color[3], ambient[3];
-    double specular_strength, att_constant, att_linear, att_quadratic;
-    double spot_edge0, spot_edge1;
-    int32_t type, pad;
-};
 struct FrameLights {
     int32_t n;                   // 2 .. MAX_LIGHTS (1: the frame is a plain one and nobody reads this)
     int32_t pad;

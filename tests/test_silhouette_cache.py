@@ -1,4 +1,4 @@
-"""GPU: the silhouette cache (mi355rast.hip, SilCache; kernels_geometry.h, quad_block).
+"""GPU: the silhouette cache (host_silcache.h, SilCache; kernels_geometry.h, quad_block and the capture epilogue of edge_block).
 
 A frame whose light and geometry are those of the frames before reads its silhouette edges and their extruded
 world-space quads back instead of testing every edge against the light.  Both paths run the same arithmetic, so

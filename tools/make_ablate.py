@@ -43,15 +43,15 @@ edits = [
     ("    bin_triangles(fc, bins, (r & 1) != 0, (uint32_t)f, pb, clip);", "    if (MR_ABLATE != 7) bin_triangles(fc, bins, (r & 1) != 0, (uint32_t)f, pb, clip);"),
     ("    sa.tris[f] = t;        // (shading", "    if (MR_ABLATE != 8) sa.tris[f] = t;        // (shading"),
     ("    if (b < face_blocks) tri_setup_block<PRE_XFORM>(b);", "    if (b < face_blocks) { if (MR_ABLATE != 10 && MR_ABLATE != 17) tri_setup_block<PRE_XFORM>(b); }"),
-    ("    else edge_block(b - face_blocks);", "    else if (MR_ABLATE != 11 && MR_ABLATE != 17) edge_block(b - face_blocks);"),
+    ("    else edge_block<ML>(b - face_blocks);", "    else if (MR_ABLATE != 11 && MR_ABLATE != 17) edge_block<ML>(b - face_blocks);"),
     # 60: time stamps along the chain of a wavefront that has silhouette edges (lane 0; sums, maxima and the count in the
     #     counters' padding words, printed by the host when MR_SETUP_TIMES is set): stage k = DBG_T(k)
-    ("\n    unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);\n", "\n    g_dbg_t0 = __builtin_amdgcn_s_memrealtime();\n    unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);\n    if (todo0 | todo1) { DBG_T(0); }\n"),
+    ("\n        unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);\n", "\n        g_dbg_t0 = __builtin_amdgcn_s_memrealtime();\n        unsigned long long todo0 = __ballot(sil[0]), todo1 = __ballot(sil[1]);\n        if (todo0 | todo1) { DBG_T(0); }\n"),
     ("    // ---- clipping, one plane at a time\n", "    DBG_T(1);\n    // ---- clipping, one plane at a time\n"),
     ("    const bool alive = n >= 3;                           // obj/triangular.py:322-323\n", "    DBG_T(2);\n    const bool alive = n >= 3;                           // obj/triangular.py:322-323\n"),
     ("    double xs[2] = { lo_x, hi_x }, ys[2] = { lo_y, hi_y };\n", "    DBG_T(3);\n    double xs[2] = { lo_x, hi_x }, ys[2] = { lo_y, hi_y };\n"),
-    ("    if (!boxed) return;\n    if (slot >= sa.quad_cap)", "    DBG_T(4);\n    if (!boxed) return;\n    if (slot >= sa.quad_cap)"),
-    ("\n    const uint32_t base = (uint32_t)__shfl((int)base_raw, 0);\n", "\n    __builtin_amdgcn_s_waitcnt(0); DBG_T(5);\n    const uint32_t base = (uint32_t)__shfl((int)base_raw, 0);\n"),
+    ("    if (!boxed) return;\n    if (s_idx >= sa.quad_cap)", "    DBG_T(4);\n    if (!boxed) return;\n    if (s_idx >= sa.quad_cap)"),
+    ("\n        base = (uint32_t)__shfl((int)base_raw, 0);\n", "\n        __builtin_amdgcn_s_waitcnt(0); DBG_T(5);\n        base = (uint32_t)__shfl((int)base_raw, 0);\n"),
 ]
 for a, b in edits:
     assert s.count(a) == 1, a
@@ -69,15 +69,14 @@ s = s.replace("namespace mr {\n", "#ifndef MR_ABLATE\n#define MR_ABLATE 0\n#endi
 # workgroup of a frame that reads the silhouette cache stamps [0] when its entry has been asked for and [5] at its end)
 for a, b in [
     ("__device__ __forceinline__ void quad_finish_group(bool have,", "__device__ __forceinline__ void quad_finish_group(unsigned long long dbg_t0_local, bool have,"),
-    ("\n        quad_finish_group(have, v, base_raw,", "\n        quad_finish_group(dbg_t0_local, have, v, base_raw,"),
-    ("\n            quad_finish_group(have, v, base_raw,", "\n            quad_finish_group(0ull, have, v, base_raw,"),      # (several lights: no stamps)
+    ("\n            quad_finish_group(have, v, base_raw,", "\n            quad_finish_group(dbg_t0_local, have, v, base_raw,"),   # (several lights: every light's turn stamps)
     ("    quad_finish_group(have, v, 0u, at, quad_scratch(wv));\n", "    DBG_T(0);\n    quad_finish_group(dbg_t0_local, have, v, 0u, at, quad_scratch(wv));\n    __builtin_amdgcn_s_waitcnt(0); DBG_T(5);\n"),
     ("__device__ __forceinline__ void quad_block(uint32_t block)\n{\n", "__device__ __forceinline__ void quad_block(uint32_t block)\n{\n    const unsigned long long dbg_t0_local = __builtin_amdgcn_s_memrealtime();\n"),
+    ("        g_dbg_t0 = __builtin_amdgcn_s_memrealtime();\n", "        const unsigned long long dbg_t0_local = __builtin_amdgcn_s_memrealtime();\n"),
+    ("template <bool ML>\n__device__ __forceinline__ void edge_block(uint32_t block)\n{\n", "template <bool ML>\n__device__ __forceinline__ void edge_block(uint32_t block)\n{\n    const unsigned long long dbg_t_block = __builtin_amdgcn_s_memrealtime(); (void)dbg_t_block;\n"),
 ]:
     assert s.count(a) == 1, a
     s = s.replace(a, b)
-s = s.replace("    g_dbg_t0 = __builtin_amdgcn_s_memrealtime();\n", "    const unsigned long long dbg_t0_local = __builtin_amdgcn_s_memrealtime();\n")
-s = s.replace("__device__ __forceinline__ void edge_block(uint32_t block)\n{\n", "__device__ __forceinline__ void edge_block(uint32_t block)\n{\n    const unsigned long long dbg_t_block = __builtin_amdgcn_s_memrealtime(); (void)dbg_t_block;\n")
 open(p, "w").write(s)
 # host: print the stamps
 p = os.path.join(dst, "host_frame.h")         # collect()
