@@ -254,7 +254,7 @@ def main():
     if args.loader:
         loader_kat(api)
         return
-    small = list(scenes.SMALL) + ["diablo_small_noshadow"] + list(scenes.OVERLAY)
+    small = list(scenes.SMALL) + list(scenes.BEHIND_CAMERA) + ["diablo_small_noshadow"] + list(scenes.OVERLAY)
     names = args.names or (small + (list(scenes.FULL) if args.full else []))
     for name in names:
         shadows = name not in scenes.NO_SHADOW

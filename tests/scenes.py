@@ -277,6 +277,249 @@ def neg_uv_obj():
     return _write_if_changed(os.path.join(GENERATED, "neg_uv.obj"), "\n".join(lines) + "\n")
 
 
+# --------------------------------------------------------------------------- adversarial meshes
+# Seeded meshes built to put counts and pixel boxes on either side of the rasteriser's limits (a pair's 24 box
+# pixels, a face's 4 tiles and 64-tile work items, a tile's rounds of 64 records), with the faces a clean mesh
+# never has: without area, listed twice, listed twice with opposite winding, edges with many faces.  They are
+# placed through the frame of the standard camera of _std_cameras: eye (0.5, 1, 2) looking at the origin, fovy 60.
+ADVERSARIAL_RESOLUTION = (136, 152)      # no multiple of 16 either way; 9 x 10 tiles: a whole-frame face needs two work items
+_EYE = np.array([0.5, 1.0, 2.0])
+_FWD = -_EYE / np.linalg.norm(_EYE)
+_RIGHT = np.cross(_FWD, [0.0, 1.0, 0.0]) / np.linalg.norm(np.cross(_FWD, [0.0, 1.0, 0.0]))
+_UP = np.cross(_RIGHT, _FWD)
+_PX = 2 * math.tan(math.radians(30)) / ADVERSARIAL_RESOLUTION[0]      # world units per pixel and unit of distance
+
+
+_PIVOT = -_EYE / 32                      # on the camera's axis, exact in float32 and in six decimals: see _dense_tile
+
+
+def _at(px, py, d):
+    """World point that the standard camera sees at pixel (px, py) of the 136 x 152 frame (x to the right, y upwards
+    like the reference's buffer rows), *d* world units in front of the camera plane."""
+    h, w = ADVERSARIAL_RESOLUTION
+    return _EYE + d * (_FWD + (px - w / 2) * _PX * _RIGHT + (py - h / 2) * _PX * _UP)
+
+
+class _ObjWriter:
+    """``v/vt/`` faces like bare_tetra_obj: uv, no normals.  Corners are (vertex, uv) pairs of 1-based indices."""
+
+    def __init__(self, rng):
+        self.rng, self.v, self.vt, self.f = rng, [], [], []
+        self.group, self.groups = "", []                 # the label of every face written, in file order
+
+    def vertex(self, p):
+        self.v.append("v %.6f %.6f %.6f" % tuple(p))
+        return len(self.v)
+
+    def uv(self):
+        """A texture coordinate outside [0, 1] on either side: u from -0.95 to 2.5, v from -1.5 to 1.95.  Below 0 a
+        texel index wraps from the far side, above 1 it clips (obj/core.py:138-143); u below -1 or v above 2 would
+        index past the far side, and upstream raises IndexError there."""
+        self.vt.append("vt %.6f %.6f" % (self.rng.uniform(-0.95, 2.5), self.rng.uniform(-1.5, 1.95)))
+        return len(self.vt)
+
+    def face(self, vi, ti=None):
+        ti = ti if ti is not None else [self.uv() for _ in vi]
+        self.f.append("f " + " ".join("%d/%d/" % c for c in zip(vi, ti)))
+        self.groups.append(self.group)
+        return list(vi), list(ti)
+
+    def triangle(self, a, b, c):
+        """An isolated triangle: three vertices and three uv of its own."""
+        return self.face([self.vertex(a), self.vertex(b), self.vertex(c)])
+
+    def text(self):
+        return "\n".join(self.v + self.vt + self.f) + "\n"
+
+
+def _backdrop(obj, d):
+    """One face over the whole frame, *d* in front of the camera, listed with both windings on vertices of its own:
+    its pixel box is the frame (90 tiles, two 64-tile work items), its corners lie outside the frustum."""
+    a, b, c = _at(-190, -40, d), _at(342, -40, d), _at(76, 330, d)
+    obj.triangle(a, b, c)
+    obj.triangle(a, c, b)
+
+
+def _soup_triangles(obj, rng, n):
+    """*n* isolated triangles of four sizes from half a world unit down to sub-pixel, three quarters of them facing
+    the camera, then the kinds without area and the repeats."""
+    made = []
+    for i in range(n):
+        size = (0.5, 0.12, 0.03, 0.004)[i % 4]
+        d = rng.uniform(1.5, 4.0)
+        centre = _at(rng.uniform(5, 147), rng.uniform(5, 131), d)
+        ang = np.sort(rng.uniform(0, 2 * np.pi, 3))
+        if i % 4 == 3 and rng.random() < 0.5:
+            ang = ang[::-1]
+        pts = [centre + size * rng.uniform(0.3, 1.0) * (math.cos(t) * _RIGHT + math.sin(t) * _UP)
+               + size * rng.uniform(-0.3, 0.3) * _FWD for t in ang]
+        obj.triangle(*pts)
+        made.append(pts)
+    for k in range(3):                                   # two equal corners, in every position
+        a, b = made[k][0], made[k][1] + 0.05 * _UP
+        obj.triangle(*[(a, a, b), (a, b, a), (b, a, a)][k])
+    for k in range(3):                                   # collinear corners; a near-collinear sliver
+        a, b = made[3 + k][0], made[3 + k][1]
+        obj.triangle(a, a + 0.5 * (b - a), b)
+        obj.triangle(a, a + 0.5 * (b - a) + 2e-4 * _UP, b)
+    for k in range(0, n, 5):                             # exact repeats of an earlier face, some with the winding turned
+        a, b, c = made[k]
+        obj.triangle(*((a, b, c) if k % 10 else (a, c, b)))
+    return made
+
+
+def soup_obj(seed, behind=False):
+    """Triangle soup: isolated triangles from sub-pixel to half the frame, faces with two equal corners, collinear
+    corners, a sliver, exact repeats with the same and the opposite winding, and one face over the whole frame.
+    Every vertex lies in front of the camera plane -- unless *behind*: then three large faces with one or two corners
+    behind it (clip-space w < 0) come FIRST in the file, so that no earlier face has coloured the pixels they own."""
+    rng = np.random.default_rng(20261018 + seed)
+    obj = _ObjWriter(rng)
+    if behind:
+        for k, (px, py, back) in enumerate(((20, 30, 1), (125, 95, 1), (80, 125, 2))):
+            # three world units across, straddling the camera plane: corners at d = 2.5 and at d = -0.5
+            a = _at(px, py, 2.5)
+            b = _at(px + 40, py + 10, 2.5) if back == 1 else _EYE - 0.5 * _FWD + 0.4 * _RIGHT + 0.2 * k * _UP
+            c = _EYE - 0.5 * _FWD - 0.3 * _RIGHT - 0.5 * _UP + 0.3 * k * _RIGHT
+            obj.triangle(a, b, c)
+    _soup_triangles(obj, rng, 48)
+    _backdrop(obj, 6.0)
+    name = f"soup_{'behind_' if behind else ''}{seed}.obj"
+    return _write_if_changed(os.path.join(GENERATED, name), obj.text())
+
+
+def welded_obj(seed):
+    """70 faces drawn from a pool of 14 vertices and 9 uv: many edges with three and more faces (the edge stage's
+    extra-incidence lists), one edge with seven, an index used twice in a face, faces repeated with the same and
+    with the opposite winding."""
+    rng = np.random.default_rng(20261019 + seed)
+    obj = _ObjWriter(rng)
+    pool = [obj.vertex(rng.uniform(-0.65, 0.65, 3) * (1.0, 0.8, 1.0)) for _ in range(14)]
+    uvs = [obj.uv() for _ in range(9)]
+    faces = []
+
+    def add(vi):
+        faces.append(obj.face(list(vi), [uvs[int(t)] for t in rng.integers(0, 9, 3)]))
+
+    for k in range(2, 9):                                # seven faces on the edge (pool[0], pool[1]), windings mixed
+        add((pool[0], pool[1], pool[k]) if k % 3 else (pool[1], pool[0], pool[k]))
+    while len(faces) < 58:
+        add(rng.choice(pool, 3, replace=False))
+    for k in range(4):                                   # an index used twice in a face
+        a, b = rng.choice(pool, 2, replace=False)
+        add([(a, a, b), (a, b, a), (b, a, a), (a, b, b)][k])
+    for k in range(8):                                   # repeats: the same corners again, every other one turned
+        vi, ti = faces[3 + 5 * k]
+        obj.face(vi if k % 2 else [vi[0], vi[2], vi[1]], ti if k % 2 else [ti[0], ti[2], ti[1]])
+    return _write_if_changed(os.path.join(GENERATED, f"welded_{seed}.obj"), obj.text())
+
+
+def _dense_tile(seed):
+    """The writer behind dense_tile_obj, with every face labelled (``groups``)."""
+    rng = np.random.default_rng(20261020 + seed)
+    obj = _ObjWriter(rng)
+
+    def tiny(cx, cy, spread, lo, hi, count, d_lo=2.38, d_hi=2.5):        # on both sides of the stack's plane
+        for i in range(count):
+            d = rng.uniform(d_lo, d_hi)
+            px, py = cx + rng.uniform(-spread, spread), cy + rng.uniform(-spread, spread)
+            r = rng.uniform(lo, hi) / 2
+            ang = np.sort(rng.uniform(0, 2 * np.pi, 3))
+            if i % 4 == 3:
+                ang = ang[::-1]                          # a quarter face away from the camera
+            obj.triangle(*[_at(px + r * math.cos(t), py + r * math.sin(t), d) for t in ang])
+
+    # (a face whose box holds no sample of it never reaches a tile: of these about half do)
+    obj.group = "tiny"
+    tiny(76, 68, 2.5, 1.5, 4, 520)                       # more than 128 small pairs in the centre tile
+    tiny(108, 68, 2.5, 1.5, 3.5, 240)                    # 65 to 128 in the tile two to the right
+    tiny(76, 68, 24, 1, 8, 200)                          # small and big pairs side by side in the tiles around
+    obj.group = "tile_sized"
+    for i in range(12):
+        px, py = rng.uniform(20, 132), rng.uniform(20, 116)
+        obj.triangle(_at(px, py, 2.6), _at(px + 16, py + rng.uniform(-3, 3), 2.6), _at(px + rng.uniform(0, 16), py + 16, 2.6))
+    # the stack: nine faces on 12 coplanar points around the centre tile, in the plane 2.44 in front of the camera, each
+    # listed eight times, copy k of every face before copy k + 1 of any: 72 big pairs in that tile, and at every
+    # pixel the nearest face ties with its seven copies -- the last of them wins, in whatever order the tile's list was filled
+    obj.group = "stack"
+    pix = np.array([(76 + 14 * math.cos(t) + rng.uniform(-2, 2), 68 + 14 * math.sin(t) + rng.uniform(-2, 2))
+                    for t in np.linspace(0, 2 * np.pi, 12, endpoint=False)])
+    pts = [_at(px, py, 2.44) for px, py in pix]
+    ids = [obj.vertex(p) for p in pts]
+    uvs = [obj.uv() for _ in ids]
+    stack = [tuple(int(t) for t in np.sort(rng.choice(12, 3, replace=False))) for _ in range(9)]     # ascending: towards the camera
+    for _ in range(8):
+        for tri in stack:
+            obj.face([ids[t] for t in tri], [uvs[t] for t in tri])
+    # tiny faces in the stack's plane: convex combinations of a stack face's corners, shrunk until the pixel box is at
+    # most 4 x 4, and copies of one of them.  Their z is the stack's to about 1e-7 and never to the bit (the corners' z
+    # differ after rounding to six decimals, and so do the roundings of two faces' barycentrics): the copies tie with each
+    # other, small pair against small pair, and none of them with the stack.
+    obj.group = "in_plane"
+    copies = None
+    for k in range(24):
+        tri = list(stack[k % 9])
+        extent = float((pix[tri].max(axis=0) - pix[tri].min(axis=0)).max())
+        share = min(0.5, 3.9 / extent)
+        w = (1 - share) * rng.dirichlet((1, 1, 1)) + share * np.eye(3)
+        sub = [w[j, 0] * pts[tri[0]] + w[j, 1] * pts[tri[1]] + w[j, 2] * pts[tri[2]] for j in range(3)]
+        obj.triangle(*sub)
+        copies = sub if copies is None else copies
+    for _ in range(3):
+        obj.triangle(*copies)
+    # the pivot: where a small and a big pair do tie to the bit.  _PIVOT lies on the camera's axis and has coordinates
+    # that are powers of two, so it lands on the sample of pixel (76, 68), the frame's centre, exactly: its clip-space x
+    # and y vanish, and its w is one of the doubles for which w * (1 / w) rounds to 1 (the origin's is not).  A face whose
+    # FIRST corner it is has the barycentrics (1, 0, 0) there, and its z at that pixel is the corner's own, whatever
+    # the other two corners are.  Six faces with a box of at most 4 x 4 pixels and four that reach 9 to 11.5 pixels
+    # into the tile, in seeded order, in front of everything else at that pixel: ten pairs of both classes tie there,
+    # and the last in the file wins.  (A pixel box is half open: the sample is in it because the other corners lie to
+    # its right and above.  The vertex lies beyond the origin, where the orthographic camera's near plane is.  No tie
+    # under the f64 variant: its rotation takes the vertex off the axis.)
+    obj.group = "pivot"
+    d = float(np.dot(_PIVOT - _EYE, _FWD))
+    for big in rng.permutation([False] * 6 + [True] * 4):
+        if big:
+            r, t1, t2 = rng.uniform(9, 11.5, 2), rng.uniform(20, 50), rng.uniform(100, 150)
+        else:
+            r, t1, t2 = rng.uniform(2, 3.8, 2), rng.uniform(-15, 30), rng.uniform(60, 105)
+        t1, t2 = math.radians(t1), math.radians(t2)
+        da, db = d + rng.uniform(0.004, 0.008, 2)
+        obj.triangle(_PIVOT, _at(76 + r[0] * math.cos(t1), 68 + r[0] * math.sin(t1), da), _at(76 + r[1] * math.cos(t2), 68 + r[1] * math.sin(t2), db))
+    # the fan: 80 faces on the edge (p, q), every one wound to face the light at (2, 3, 4), so that each throws two quads
+    obj.group = "fan"
+    p, q = _at(20, 118, 2.0), _at(52, 100, 2.2)
+    ip, iq, tp, tq = obj.vertex(p), obj.vertex(q), obj.uv(), obj.uv()
+    axis = (q - p) / np.linalg.norm(q - p)
+    side = np.cross(axis, _FWD) / np.linalg.norm(np.cross(axis, _FWD))
+    light = np.array([2.0, 3.0, 4.0])
+    for k in range(80):
+        t = 2 * np.pi * k / 80
+        tip = 0.5 * (p + q) + 0.25 * (math.cos(t) * side + math.sin(t) * np.cross(axis, side)) + 0.002 * k * axis
+        it, tt = obj.vertex(tip), obj.uv()
+        lit = np.dot(np.cross(q - p, tip - p), light) > 0
+        obj.face([ip, iq, it] if lit else [iq, ip, it], [tp, tq, tt] if lit else [tq, tp, tt])
+    obj.group = "backdrop"
+    _backdrop(obj, 5.0)
+    return obj
+
+
+def dense_tile_obj(seed):
+    """Hundreds of triangles of 1 to 8 pixels inside a few tiles, a dozen tile-sized ones, a stack of 72 coplanar,
+    partly overlapping faces (nine, each listed eight times) over the tile at the frame's centre with tiny faces in its
+    plane, ten faces of both pair classes that tie to the bit at the frame's centre, a fan of 80 faces on one long edge
+    whose shadow quads run through the same tiles, and a face over the whole frame behind them all.  Pixel (76, 68), the
+    frame's centre, lies 4 pixels or more inside its tile in both directions: a cluster within 3 pixels of it falls into
+    one tile."""
+    return _write_if_changed(os.path.join(GENERATED, f"dense_tile_{seed}.obj"), _dense_tile(seed).text())
+
+
+def dense_tile_groups(seed):
+    """The label of every face of dense_tile_obj(seed), in file order: tiny, tile_sized, stack, in_plane, pivot, fan,
+    backdrop."""
+    return np.array(_dense_tile(seed).groups)
+
+
 # --------------------------------------------------------------------------- building blocks
 def _std_cameras(api, **over):
     kw = dict(fovy=60, near=0.1, far=20, backface_culling=True)
@@ -525,6 +768,84 @@ def quad_negative_uv(api, resolution=(150, 200)):
     return _scene(api, cam, dbg, _std_light(api), resolution, [quad, _floor(api)])
 
 
+VARIANTS = ("std", "noclip", "f64", "textured", "lh_gl_ortho", "cull_off")
+
+
+def _adversarial(api, path, variant, resolution, floor=False):
+    """A generated mesh under one of VARIANTS: the standard camera; ``Model.clip = False``; float64 vertices
+    (``Model @`` a float64 rotation); a ``map_Kd`` texture under the mesh's uv (u from -0.95 to 2.5, v from -1.5 to 1.95:
+    _ObjWriter.uv); LH/OpenGL with
+    tetra_ortho's orthographic camera; culling off.  (No normal map: upstream's ``inv`` raises on a face without area.)"""
+    assert variant in VARIANTS, variant
+    system = {}
+    if variant == "lh_gl_ortho":
+        kw = dict(projection_type=api.PROJECTION_TYPE.ORTHOGRAPHIC, fovy=35, far=20, backface_culling=True)
+        cam, dbg = api.Camera((0.5, 1, 2), (0, 0, 0), **kw), api.Camera((0.5, 1, 2), (0, 0, 0), **kw)
+        system = dict(system=api.SYSTEM.LH, subsystem=api.SUBSYSTEM.OPENGL)
+    else:
+        cam, dbg = _std_cameras(api, backface_culling=variant != "cull_off")
+    m = api.Model.load_model(path)
+    if variant == "noclip":
+        m.clip = False
+    elif variant == "f64":
+        m = m @ (api.rotate_xyz((3.0, -2.0, 1.5)) @ api.scale(1.0))
+        assert m.vertices.dtype == np.float64
+    elif variant == "textured":
+        m.textures.register("diffuse", os.path.join(ASSETS, "grid.tga"), normalize=False)
+    models = [m, _floor(api, textured=False)] if floor else [m]
+    return _scene(api, cam, dbg, _std_light(api), resolution, models, **system)
+
+
+def soup(api, seed=0, variant="std", resolution=ADVERSARIAL_RESOLUTION):
+    """Triangle soup (soup_obj): sizes from sub-pixel to the whole frame, faces without area, repeats."""
+    return _adversarial(api, soup_obj(seed), variant, resolution)
+
+
+def soup_behind_camera(api, seed=0, variant="std", resolution=ADVERSARIAL_RESOLUTION):
+    """The soup after three large faces with corners behind the camera plane (clip-space w < 0).  Upstream writes
+    their z and no colour (every fragment fails the ``>= 0`` row filter of obj/triangular.py:139-141); the oracle and
+    the kernels shade them.  Parity is defined in front of the camera plane: see DESIGN.md."""
+    return _adversarial(api, soup_obj(seed, behind=True), variant, resolution)
+
+
+def welded(api, seed=0, variant="std", resolution=ADVERSARIAL_RESOLUTION):
+    """70 faces on 14 vertices (welded_obj) over the floor that catches their shadow volumes."""
+    return _adversarial(api, welded_obj(seed), variant, resolution, floor=True)
+
+
+def dense_tile(api, seed=0, variant="std", resolution=ADVERSARIAL_RESOLUTION):
+    """Hundreds of tiny faces, a coplanar stack and a fan of shadow casters in a few tiles (dense_tile_obj)."""
+    return _adversarial(api, dense_tile_obj(seed), variant, resolution)
+
+
+def face_geometry(scene):
+    """Per face of the scene, models in order: clip-space w of its corners (F, 3), whether upstream's cull drops it, and
+    its pixel box (x0, x1, y0, y1) as obj/transformation.py:35-43 cuts it (ceil, clamped to the frame; no box -> zeros),
+    from the vertices through ``camera.MVP`` and ``camera.viewport``."""
+    cam = scene.camera
+    h, w = scene.resolution
+    ws, culled, boxes = [], [], []
+    for model in scene.models:
+        corners = np.asarray(model._faces)[:, :, 0]
+        clip = np.asarray(model.vertices, dtype=np.float64)[corners] @ cam.MVP              # (F, 3, 4)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            screen = (clip / clip[..., 3:4]) @ cam.viewport
+        n_z = np.cross(screen[:, 1, :3] - screen[:, 0, :3], screen[:, 2, :3] - screen[:, 0, :3])[:, 2]
+        lo_x, hi_x = np.maximum(screen[..., 0].min(axis=1), 0), np.minimum(screen[..., 0].max(axis=1), w)
+        lo_y, hi_y = np.maximum(screen[..., 1].min(axis=1), 0), np.minimum(screen[..., 1].max(axis=1), h)
+        box = np.ceil(np.stack([lo_x, hi_x, lo_y, hi_y], axis=1))
+        box[~np.isfinite(box).all(axis=1) | (lo_x > hi_x) | (lo_y > hi_y)] = 0
+        ws.append(clip[..., 3]), culled.append(bool(cam.backface_culling) & (n_z < 0)), boxes.append(box.astype(np.int64))
+    return np.concatenate(ws), np.concatenate(culled), np.concatenate(boxes)
+
+
+def behind_camera_pixels(scene, winner):
+    """Pixels of a winner map whose face has a corner on or behind the camera plane (clip-space w <= 0)."""
+    w, _, _ = face_geometry(scene)
+    behind = (w <= 0).any(axis=1)
+    return (winner >= 0) & behind[np.maximum(winner, 0)]
+
+
 # name -> (builder, kwargs); the small ones have full golden buffers committed
 SMALL = {
     "cube_small": (cube_small, {}),
@@ -546,6 +867,14 @@ SMALL = {
     "fins_nonmanifold": (fins_nonmanifold, {}),
     "wall_nine_materials": (wall_nine_materials, {}),
     "quad_negative_uv": (quad_negative_uv, {}),
+    "soup_s0": (soup, {"seed": 0}),
+    "welded_s0": (welded, {"seed": 0}),
+    "dense_tile_s0": (dense_tile, {"seed": 0}),
+    "welded_s4_ortho": (welded, {"seed": 4, "variant": "lh_gl_ortho"}),
+}
+# a full capture too, but outside SMALL: its frame is the reference's only in front of the camera plane
+BEHIND_CAMERA = {
+    "soup_behind_camera_s0": (soup_behind_camera, {"seed": 0}),
 }
 
 # BASELINE.json configs at full size: only the uint8 frame, winner map, stencil and z row sums are kept
@@ -567,5 +896,5 @@ OVERLAY = ["diablo_small_overlay", "diablo_floor_lh_gl_overlay", "cube_outward_o
 def build(api, name):
     if name == "diablo_small_noshadow":
         return diablo_small(api)
-    fn, kw = {**SMALL, **FULL, **HUGE}[name]
+    fn, kw = {**SMALL, **BEHIND_CAMERA, **FULL, **HUGE}[name]
     return fn(api, **kw)
