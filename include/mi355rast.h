@@ -387,6 +387,36 @@ int mr_debug_sil_cache(mr_scene *scene, int32_t *out);
  * frame or a new tile grid.  Always a permutation of 0 .. n_tiles-1.  Returns the number of tiles. */
 int mr_debug_read_tile_order(mr_scene *scene, uint32_t *out, int32_t cap_tiles);
 
+/* A model's pose: the model (index as mr_scene_add_model returned it) renders as if its vertices were the float64 array
+ * V' = vertices @ m16, every element rn(v[0] * m[0][j]) followed by fma steps in ascending k (mr_host_matmul_chain) --
+ * the reference's `Model @ M` with the product's rounding pinned.  m16 is a row-major 4 x 4 in the row-vector
+ * convention; NULL removes the pose.  Vertices only: vertex normals, uv, materials and topology stay.  The pose is
+ * absolute (it replaces the one before) and the vertices passed to mr_scene_add_model are never changed.  V' is float64,
+ * so a posed model behaves as one with vertices_are_f32 == 0.
+ * The call copies m16 and launches nothing.  The next frame applies what changed in one pass on the device (vertices,
+ * face normals, edge records, per-face and per-cluster records); that pass waits for the device before and after, like
+ * a commit.  When a model with vertices_are_f32 != 0 goes from un-posed to posed or back, one ordinary commit of the
+ * scene comes first.  MR_E_INVALID for a model index out of range or an entry that is not finite. */
+int mr_scene_set_model_pose(mr_scene *scene, int32_t model, const double *m16);
+
+/* Diagnostics of the pose pass: out[0] = full commits of this scene so far, out[1] = pose passes so far, out[2] = models
+ * that have a pose now, out[3] = vertices the last pass wrote.  Does not wait for the device. */
+int mr_debug_pose(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds (HIP events on the library's stream) of the five steps of the last pose pass:
+ *   [0] k_pose_vertices (with the copies that give un-posed models their vertices back)   [1] k_face_normals
+ *   [2] k_edge_normals   [3] k_face_static   [4] k_clusters
+ * MR_E_INVALID before the first pass.  The pass has waited for its kernels: this call does not wait. */
+#define MR_N_POSE_TIMES 5
+int mr_debug_pose_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
+ * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
+ * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;
+ * cos_half < -1 = no cone), 5 pad words.  Copies at most cap_clusters records; returns the number of clusters of the
+ * last commit or a negative error.  Synchronises the device. */
+int mr_debug_read_clusters(mr_scene *scene, void *out, int32_t cap_clusters);
+
 /* Human-readable description of the last error on this thread ("" if none). */
 const char *mr_last_error(void);
 

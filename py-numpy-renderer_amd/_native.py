@@ -139,6 +139,10 @@ _PROTOTYPES = {
     "mr_host_camera_constants": (None, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3),
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_scene_set_model_pose": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_debug_pose": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_pose_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_read_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -281,6 +285,7 @@ class DeviceRenderer:
         if not self.handle:
             raise RuntimeError("mr_scene_create failed: " + self.lib.mr_last_error().decode())
         self._signature = None
+        self._pose_keys = []                 # per model: the bytes of the pose the library holds, or None
         self._sky_key = None
         self._last_stats = {}
         self._frame = None
@@ -311,9 +316,28 @@ class DeviceRenderer:
             for m in scene.models)
 
     def sync_scene(self, scene):
+        """The library's scene in step with the Python one: everything again when a model, texture or material changed
+        (``_scene_signature``), and the models' poses, which are no part of that signature, beside it."""
         sig = self._scene_signature(scene)
-        if sig == self._signature:
-            return
+        if sig != self._signature:
+            self._upload_scene(scene)
+            self._signature = sig
+            self._pose_keys = [None] * len(scene.models)        # (mr_scene_clear dropped the poses)
+        self.sync_poses(scene)
+
+    def sync_poses(self, scene):
+        """``mr_scene_set_model_pose`` for every model whose ``pose`` is not the one the library holds."""
+        keys = self._pose_keys
+        for index, model in enumerate(scene.models):
+            pose = getattr(model, "pose", None)
+            key = None if pose is None else pose.tobytes()
+            if key == keys[index]:
+                continue
+            _check(self.lib.mr_scene_set_model_pose(self.handle, index, None if pose is None else pose.ctypes.data),
+                   "mr_scene_set_model_pose")
+            keys[index] = key
+
+    def _upload_scene(self, scene):
         _check(self.lib.mr_scene_clear(self.handle), "mr_scene_clear")
         textures, seen, uploaded = [], {}, 0
         for model in scene.models:
@@ -342,7 +366,6 @@ class DeviceRenderer:
             d.n_faces, d.n_materials = len(pm.faces), len(pm.materials)
             d.vertices_are_f32, d.clip, d.depth_test = int(pm.vertices_are_f32), int(pm.clip), int(pm.depth_test)
             _check(self.lib.mr_scene_add_model(self.handle, C.byref(d)), "mr_scene_add_model")
-        self._signature = sig
 
     def sync_skybox(self, scene):
         sky = scene.skybox if hasattr(scene.skybox, "texels") else None
@@ -653,6 +676,31 @@ class DeviceRenderer:
         out = (C.c_int32 * 4)()
         _check(self.lib.mr_debug_sil_cache(self.handle, out), "mr_debug_sil_cache")
         return tuple(int(x) for x in out)
+
+    def pose_counters(self):
+        """``mr_debug_pose``: (full commits of the scene so far, pose passes so far, posed models, vertices the last
+        pass wrote)."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.mr_debug_pose(self.handle, out), "mr_debug_pose")
+        return tuple(int(x) for x in out)
+
+    POSE_TIME_NAMES = ("pose_vertices", "face_normals", "edge_normals", "face_static", "clusters")
+
+    def pose_times(self):
+        """Device milliseconds of the five kernels of the last pose pass (``mr_debug_pose_times``)."""
+        buf = (C.c_float * 5)()
+        _check(self.lib.mr_debug_pose_times(self.handle, buf), "mr_debug_pose_times")
+        return dict(zip(self.POSE_TIME_NAMES, (float(v) for v in buf)))
+
+    def read_clusters(self):
+        """The per-cluster records of the scene (``mr_debug_read_clusters``): a structured array with ``lo``, ``hi``,
+        ``axis`` (3 float32 each), ``cos_half``, ``sin_half``."""
+        dtype = np.dtype([("lo", np.float32, 3), ("hi", np.float32, 3), ("axis", np.float32, 3), ("cos_half", np.float32),
+                          ("sin_half", np.float32), ("pad", np.uint32, 5)])
+        n = _check(self.lib.mr_debug_read_clusters(self.handle, (C.c_uint32 * 16)(), 0), "mr_debug_read_clusters")
+        out = np.zeros(max(n, 1), dtype=dtype)
+        _check(self.lib.mr_debug_read_clusters(self.handle, out.ctypes.data, n), "mr_debug_read_clusters")
+        return out[:n]
 
     def read_tile_order(self):
         """The order in which the last frame's tile kernel took its tiles: (n_tiles,) uint32."""

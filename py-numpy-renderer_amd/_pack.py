@@ -143,6 +143,38 @@ def sample_grid(scene):
                                               x_offset=cam.x_offset * s, y_offset=cam.y_offset * s)
 
 
+def check_pose(value):
+    """``Model.pose``: ``None``, or a finite 4x4 matrix, returned as a read-only float64 copy.  ``TypeError`` for what
+    is no array of numbers, ``ValueError`` for a wrong shape or an entry that is not finite."""
+    if value is None:
+        return None
+    if isinstance(value, (str, bytes)):
+        raise TypeError(f"pose must be None or a 4x4 matrix, got {type(value).__name__}")
+    try:
+        m = np.array(value, dtype=np.float64)
+    except TypeError as exc:
+        raise TypeError(f"pose must be None or a 4x4 matrix of numbers: {exc}") from None
+    except ValueError as exc:
+        raise ValueError(f"pose must be None or a 4x4 matrix of numbers: {exc}") from None
+    if m.shape != (4, 4):
+        raise ValueError(f"pose must be 4x4, got shape {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError("pose must be finite")
+    m = np.ascontiguousarray(m)
+    m.setflags(write=False)
+    return m
+
+
+def posed_vertices(model):
+    """The vertices a model renders with: ``model.vertices``, or with a pose the float64 array
+    ``matmul_chain(float64(vertices), pose)`` (``Model.pose``)."""
+    pose = getattr(model, "pose", None)
+    if pose is None:
+        return np.asarray(model.vertices)
+    from ._fp import matmul_chain
+    return matmul_chain(np.asarray(model.vertices).astype(np.float64), pose)
+
+
 def pack_light(light) -> PackedLight:
     kind = light.light_type.value if isinstance(light.light_type, Lightning) else int(light.light_type)
     return PackedLight(
@@ -203,8 +235,10 @@ def _texture_id(tex, textures, seen):
     return seen[key]
 
 
-def pack_model(model, textures, seen) -> PackedModel:
-    verts = np.asarray(model.vertices)
+def pack_model(model, textures, seen, posed=False) -> PackedModel:
+    """*posed*: pack the vertices the model renders with (``posed_vertices``) instead of ``model.vertices`` -- what the
+    oracle needs; the device gets the vertices as they are and the pose beside them (``mr_scene_set_model_pose``)."""
+    verts = posed_vertices(model) if posed else np.asarray(model.vertices)
     if verts.ndim != 2 or verts.shape[1] != 4:
         raise ValueError(f"Model.vertices must be (V, 4), got {verts.shape}")
     faces = np.asarray(model._faces)
@@ -253,5 +287,5 @@ def pack_model(model, textures, seen) -> PackedModel:
 
 def pack_scene(scene, shadows=True) -> PackedScene:
     textures, seen = [], {}
-    models = [pack_model(m, textures, seen) for m in scene.models]
+    models = [pack_model(m, textures, seen, posed=True) for m in scene.models]
     return PackedScene(frame=pack_frame(scene, shadows), models=models, textures=textures)

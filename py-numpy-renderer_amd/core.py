@@ -63,7 +63,17 @@ class TextureMaps:
 
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
-    (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices."""
+    (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
+
+    ``pose`` (an addition; ``None`` by default, or a 4x4 matrix in the row-vector convention) moves the model
+    between frames without a re-upload.  A model with ``pose = M`` renders as the reference renders the same model
+    with its ``vertices`` replaced by the float64 array ``_fp.matmul_chain(float64(vertices), float64(M))`` -- every
+    element ``rn(v[0] * M[0][j])`` followed by ``fma`` steps in ascending k.  That is upstream's ``Model @ M`` with the
+    product's rounding pinned to the one order this package uses for its 4x4 products.  Like ``Model @ M`` it moves
+    ``vertices`` only (vertex normals are not transformed), and its result is float64: a posed float32 model behaves
+    as a float64 model (face normals, edge vectors and silhouette normals in float64).  ``vertices`` itself is never
+    modified and the pose is absolute, not cumulative: ``pose = None`` gives the un-posed model back.  A scene whose
+    models all have ``pose = None`` is exactly the scene without this attribute."""
 
     def __init__(self, vertices, uv, normals, faces, shadowing=False, materials=None,
                  material_group=None, clip=True, depth_test=True):
@@ -80,6 +90,7 @@ class Model:
         self.shape = None
         self.silhouette = set()             # filled by Scene.render with the last frame's edges
         self._revision = 0                  # bumped whenever device copies go stale
+        self._pose = None
 
     # -- ingest ---------------------------------------------------------------------------
     @classmethod
@@ -152,6 +163,17 @@ class Model:
                 else:
                     setattr(material, key, val)
         return library
+
+    @property
+    def pose(self):
+        """``None`` or the 4x4 float64 pose matrix (read-only: assign a new matrix to move the model); see the class
+        docstring."""
+        return getattr(self, "_pose", None)
+
+    @pose.setter
+    def pose(self, value):
+        from ._pack import check_pose
+        self._pose = check_pose(value)
 
     def __matmul__(self, other):
         self.vertices = self.vertices @ other

@@ -606,6 +606,7 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
 {
     int rc = commit(sc);
     if (rc) return rc;
+    if ((rc = apply_poses(sc))) return rc;
     hipStream_t stream = fs->stream;
     mr::FrameConst fc;
     FramePlan p;

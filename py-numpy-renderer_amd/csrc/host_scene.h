@@ -28,6 +28,17 @@ struct mr_scene {
     std::vector<mr::EdgeRec> edges;           // unique undirected edges, scrambled order
     std::vector<uint32_t> edge_inc;           // incidences beyond an edge's first two
     bool dirty = true;
+    // a model's place in the arrays above and its pose (mr_scene_set_model_pose; host_pose.h)
+    struct ModelPose {
+        int32_t vert_off = 0, n_verts = 0;
+        bool verts_f32 = false;               // as the caller passed it: a posed model's faces lose FF_VERTS_F32
+        bool posed = false;
+        bool on_device = false;               // d_verts holds posed vertices in this model's range
+        double m[16] = {};
+    };
+    std::vector<ModelPose> poses;             // one per model
+    bool pose_dirty = false;                  // a pose changed: apply_poses() has work
+    int32_t commits = 0, pose_passes = 0, pose_written = 0;      // mr_debug_pose
 
     // ---- device copies of the static scene
     DevBuf d_verts, d_uv, d_normals, d_faces, d_face_flags, d_materials, d_textures, d_edges, d_edge_inc, d_face_n;
@@ -35,6 +46,12 @@ struct mr_scene {
     bool edge_compact = false;
     DevBuf d_face_pos, d_face_attr;          // static per face (rast_types.h, FacePosT / FaceAttr), built by commit()
     DevBuf d_clusters;                       // static per 64 faces (rast_types.h, ClusterRec), built by commit()
+    int32_t n_clusters = 0;
+    // the pose pass: the vertices as the caller passed them (d_verts holds what the kernels read) and the pass's two tables
+    DevBuf d_verts0, d_pose_rows, d_pose_blocks;
+    bool verts0_valid = false;
+    hipEvent_t pose_ev[6] = {};               // marks of the last pass (mr_debug_pose_times)
+    int pose_marks = 0;
     bool pos32 = false;                      // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
     DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
@@ -250,6 +267,7 @@ int commit(mr_scene *sc)
     HIP_TRY(sc->d_face_attr.ensure(std::max<size_t>((size_t)nf * sizeof(mr::FaceAttr), 16)));
     {
         const std::vector<mr::ClusterRec> clusters = build_clusters(sc);
+        sc->n_clusters = (int32_t)clusters.size();
         HIP_TRY(sc->d_clusters.ensure(std::max<size_t>(clusters.size() * sizeof(mr::ClusterRec), 64)));
         if (!clusters.empty())
             HIP_TRY(hipMemcpyAsync(sc->d_clusters.p, clusters.data(), clusters.size() * sizeof(mr::ClusterRec), hipMemcpyHostToDevice, g_stream));
@@ -271,6 +289,13 @@ int commit(mr_scene *sc)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));
     sc->dirty = false;
+    // d_verts holds the vertices as they were passed: the poses are applied next (apply_poses)
+    sc->commits += 1;
+    sc->verts0_valid = false;
+    for (mr_scene::ModelPose &mp : sc->poses) {
+        mp.on_device = false;
+        if (mp.posed) sc->pose_dirty = true;
+    }
     return MR_OK;
 }
 

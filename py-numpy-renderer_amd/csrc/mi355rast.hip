@@ -6,6 +6,7 @@
 //   host_silcache.h     the silhouette cache
 //   host_scene.h        the static scene and commit()
 //   host_overlay_dev.h  the debug-frustum overlay's device plumbing (host_overlay.h builds its lists)
+//   host_pose.h         a model's pose, applied on the device in front of the frame
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //
 // One process drives one GPU.  A scene keeps its static arrays (vertices, attributes, index arrays, textures, the
@@ -47,11 +48,13 @@
 #include "kernels_geometry.h"
 #include "kernels_tile.h"
 #include "kernels_overlay.h"
+#include "kernels_pose.h"
 
 #include "host_device.h"
 #include "host_env.h"
 #include "host_silcache.h"
 #include "host_scene.h"
+#include "host_pose.h"
 #include "host_overlay_dev.h"
 #include "host_frame.h"
 
@@ -106,6 +109,7 @@ int mr_scene_clear(mr_scene *sc)
     sc->verts.clear(); sc->uv.clear(); sc->normals.clear(); sc->faces.clear(); sc->face_flags.clear();
     sc->materials.clear(); sc->model_face_off.clear(); sc->edges.clear(); sc->edge_inc.clear();
     sc->edge_ids.clear(); sc->edge_raw.clear();
+    sc->poses.clear(); sc->pose_dirty = false;
     sc->dirty = true;
     sc->last = nullptr;
     sc->sil.drop();
@@ -146,11 +150,13 @@ void mr_scene_destroy(mr_scene *sc)
     if (!sc) return;
     mr_scene_clear(sc);
     for (DevBuf *b : { &sc->d_verts, &sc->d_uv, &sc->d_normals, &sc->d_faces, &sc->d_face_flags, &sc->d_materials, &sc->d_textures, &sc->d_edges,
-                       &sc->d_edges32, &sc->d_edge_inc, &sc->d_face_n, &sc->d_face_pos, &sc->d_face_attr, &sc->d_clusters, &sc->d_sky, &sc->d_gamma })
+                       &sc->d_edges32, &sc->d_edge_inc, &sc->d_face_n, &sc->d_face_pos, &sc->d_face_attr, &sc->d_clusters, &sc->d_sky, &sc->d_gamma,
+                       &sc->d_verts0, &sc->d_pose_rows, &sc->d_pose_blocks })
         b->release();
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
+    for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
     delete sc;
 }
 
@@ -304,11 +310,25 @@ int mr_scene_add_model(mr_scene *sc, const mr_model_desc *m)
         sc->edge_ids.push_back(raw + m->n_vertices + 2 * vert_off);
     }
     sc->model_face_off.push_back(face_off);
+    mr_scene::ModelPose mp;
+    mp.vert_off = vert_off; mp.n_verts = m->n_vertices; mp.verts_f32 = m->vertices_are_f32 != 0;
+    sc->poses.push_back(mp);
     sc->dirty = true;
     sc->last = nullptr;
     sc->quad_cap = 0;
     for (auto &fs : sc->slots) fs->reset_caps();
     return (int)sc->model_face_off.size() - 1;
+}
+
+int mr_scene_set_model_pose(mr_scene *sc, int32_t model, const double *m16)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    if (m16)
+        for (int i = 0; i < 16; ++i)
+            if (!std::isfinite(m16[i])) return fail(MR_E_INVALID, "a pose matrix must be finite");
+    set_model_pose(sc, model, m16);
+    return MR_OK;
 }
 
 int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats *stats)
@@ -672,6 +692,34 @@ int mr_debug_sil_cache(mr_scene *sc, int32_t *out)
     out[0] = sc->sil.last_path; out[1] = (int32_t)sc->sil.last_entries; out[2] = (int32_t)sc->sil.captures;
     out[3] = sc->sil.valid_buffers();
     return MR_OK;
+}
+
+int mr_debug_pose(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    int32_t posed = 0;
+    for (const mr_scene::ModelPose &mp : sc->poses) posed += mp.posed ? 1 : 0;
+    out[0] = sc->commits; out[1] = sc->pose_passes; out[2] = posed; out[3] = sc->pose_written;
+    return MR_OK;
+}
+
+int mr_debug_pose_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (sc->pose_marks != 6) return fail(MR_E_INVALID, "no pose pass over faces yet");
+    for (int k = 0; k < MR_N_POSE_TIMES; ++k) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->pose_ev[k], sc->pose_ev[k + 1]));
+    return MR_OK;
+}
+
+int mr_debug_read_clusters(mr_scene *sc, void *out, int32_t cap_clusters)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    if (sc->dirty || !sc->d_clusters.p) return fail(MR_E_INVALID, "clusters: nothing rendered since the scene changed");
+    static_assert(sizeof(mr::ClusterRec) == 64, "the cluster record's layout is documented in the header");
+    const int n = std::min(sc->n_clusters, cap_clusters);
+    HIP_TRY(hipDeviceSynchronize());
+    if (n > 0) HIP_TRY(hipMemcpy(out, sc->d_clusters.p, (size_t)n * sizeof(mr::ClusterRec), hipMemcpyDeviceToHost));
+    return sc->n_clusters;
 }
 
 int mr_debug_read_tile_order(mr_scene *sc, uint32_t *out, int32_t cap_tiles)
