@@ -384,9 +384,11 @@ class DeviceRenderer:
         resolution only (a camera's MVP is cached for life), so they are built and uploaded once."""
         cam = scene.camera
         dbg = scene.debug_camera if scene.debug_camera is not None else cam
-        key = (id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")), tuple(scene.resolution),
-               int(scene.system), int(scene.subsystem), getattr(scene, "supersample", 1))
-        if getattr(self, "_overlay_key", None) == key or getattr(self, "_overlay_pinned", False):
+        # (the lines go through camera.viewport: its offsets and depth range may be reassigned on a camera that stays)
+        key = lambda: (id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")), tuple(scene.resolution),
+                       int(scene.system), int(scene.subsystem), getattr(scene, "supersample", 1),
+                       cam.x_offset, cam.y_offset, float(cam.near), float(cam.far))
+        if getattr(self, "_overlay_key", None) == key() or getattr(self, "_overlay_pinned", False):
             return
         # the key holds ids: keep the objects alive while it is cached, so that no other camera or matrix can
         # be given a recycled address and pass for them
@@ -403,8 +405,7 @@ class DeviceRenderer:
         _check(self.lib.mr_scene_set_overlay_cameras(self.handle, corners.ctypes.data, planes.ctypes.data, mvp.ctypes.data,
                                                      viewport.ctypes.data, float(cam.near), float(cam.far), int(inside),
                                                      height, width), "mr_scene_set_overlay_cameras")
-        self._overlay_key = (id(cam), id(dbg), id(cam.__dict__.get("MVP")), id(dbg.__dict__.get("MVP")),
-                             tuple(scene.resolution), int(scene.system), int(scene.subsystem), getattr(scene, "supersample", 1))
+        self._overlay_key = key()                    # the MVPs exist (and are cached) now
         self._overlay_refs = (cam, dbg, cam.__dict__.get("MVP"), dbg.__dict__.get("MVP"))
 
     def set_overlay_lists(self, ops, pin=True):

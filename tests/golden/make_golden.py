@@ -166,8 +166,11 @@ def save_small(name, r):
     np.savez_compressed(os.path.join(HERE, f"{name}.npz"),
                         out=r.out, frame=r.frame, z=r.z, stencil=r.stencil, winner=r.winner,
                         face_status=r.status, silhouette=r.silhouette, **{f"host_{k}": v for k, v in r.host.items()})
+    import scenes
+    # the generated textures of the recipe, if it has any: shape and CRC32 of the texels each file decodes to
+    textures = {label: scenes.texture_record(path) for label, path in sorted(scenes.TEXTURED.get(name, {}).items())}
     with open(os.path.join(HERE, f"{name}.json"), "w") as fh:
-        json.dump(dict(counts=r.counts, stdout=r.stdout), fh, indent=1)
+        json.dump(dict(counts=r.counts, stdout=r.stdout, **({"textures": textures} if textures else {})), fh, indent=1)
 
 
 def save_overlay(name, r):

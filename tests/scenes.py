@@ -277,6 +277,66 @@ def neg_uv_obj():
     return _write_if_changed(os.path.join(GENERATED, "neg_uv.obj"), "\n".join(lines) + "\n")
 
 
+# --------------------------------------------------------------------------- generated textures
+# Non-square maps whose texels are unrelated to their neighbours: a swapped height and width, a wrong row stride or a
+# wrap by the wrong dimension moves nearly every sample to a texel of another colour.  Every texel is a closed-form
+# integer hash of (row, column, channel, texture id) in uint32 arithmetic: the same bytes on every host and under every
+# NumPy, with no random generator whose stream could change between versions.
+def hash_u32(a, b, c, d):
+    """murmur3's 32-bit finaliser over four mixed-in words; arrays broadcast, arithmetic wraps at 2^32."""
+    u = lambda v: np.atleast_1d(v).astype(np.uint32)            # (arrays wrap silently, scalars would warn)
+    shape = np.broadcast_shapes(*(np.shape(v) for v in (a, b, c, d)))
+    x = (u(a) * np.uint32(0x9E3779B1)) ^ (u(b) * np.uint32(0x85EBCA77)) ^ (u(c) * np.uint32(0xC2B2AE3D)) ^ (u(d) * np.uint32(0x27D4EB2F))
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x85EBCA6B)
+    x = x ^ (x >> np.uint32(13))
+    x = x * np.uint32(0xC2B2AE35)
+    return (x ^ (x >> np.uint32(16))).reshape(shape)
+
+
+def hash_texels(h, w, tex_id, normal_map=False):
+    """uint8 (h, w, 3).  A colour map takes the top byte of the hash per channel.  A normal map is the unit vector
+    (x, y, 1) / |.| with x and y from two hash bytes in [-0.75, 0.75] -- +z dominates -- encoded as
+    ``rint((n + 1) / 2 * 255)``, what ``register(..., normalize=True)`` undoes."""
+    row, col, ch = np.arange(h)[:, None, None], np.arange(w)[None, :, None], np.arange(3)[None, None, :]
+    top = (hash_u32(row, col, ch, tex_id) >> np.uint32(24)).astype(np.int64)
+    if not normal_map:
+        return top.astype(np.uint8)
+    n = np.empty((h, w, 3), dtype=np.float64)
+    n[..., :2] = (top[..., :2] - 127.5) / 170.0
+    n[..., 2] = 1.0
+    n /= np.sqrt((n * n).sum(axis=-1, keepdims=True))
+    return np.rint((n + 1.0) / 2.0 * 255.0).astype(np.uint8)
+
+
+def hash_texture(h, w, tex_id, normal_map=False):
+    """The lossless PNG of hash_texels under GENERATED, written on first use (and again if its texels differ)."""
+    from PIL import Image
+    path = os.path.join(GENERATED, f"hash_{'nm' if normal_map else 'rgb'}_{tex_id}_{h}x{w}.png")
+    texels = hash_texels(h, w, tex_id, normal_map)
+    if os.path.exists(path):
+        try:
+            with Image.open(path) as im:
+                if np.array_equal(np.asarray(im.convert("RGB")), texels):
+                    return path
+        except OSError:
+            pass
+    os.makedirs(GENERATED, exist_ok=True)
+    tmp = f"{path}.{os.getpid()}.tmp"
+    Image.fromarray(texels, "RGB").save(tmp, format="PNG")
+    os.replace(tmp, path)
+    return path
+
+
+def texture_record(path):
+    """What pins a texture file: the (h, w) of the decoded image and the CRC32 of its RGB bytes."""
+    import zlib
+    from PIL import Image
+    with Image.open(path) as im:
+        texels = np.ascontiguousarray(np.asarray(im.convert("RGB")))
+    return dict(shape=[int(texels.shape[0]), int(texels.shape[1])], crc32=int(zlib.crc32(texels.tobytes())))
+
+
 # --------------------------------------------------------------------------- adversarial meshes
 # Seeded meshes built to put counts and pixel boxes on either side of the rasteriser's limits (a pair's 24 box
 # pixels, a face's 4 tiles and 64-tile work items, a tile's rounds of 64 records), with the faces a clean mesh
@@ -768,6 +828,128 @@ def quad_negative_uv(api, resolution=(150, 200)):
     return _scene(api, cam, dbg, _std_light(api), resolution, [quad, _floor(api)])
 
 
+# --------------------------------------------------------------------------- shading inputs
+# Recipes for what the captures above hold constant: texture shapes (every file under assets/ is square), the light's
+# colour, attenuation and ambient strength, a colour sky and the cameras' viewport offsets.
+TEXTURED = {}                  # recipe name -> {label: texture file}, filled in when the recipe is built
+
+
+def _register_hash_maps(model, recipe, prefix, diffuse=None, normals=None, specular=None, tangent=True):
+    """Hash textures of the given (h, w, texture id) on a model; the files are noted under TEXTURED[recipe]."""
+    files = TEXTURED.setdefault(recipe, {})
+    if diffuse is not None:
+        files[f"{prefix}_diffuse"] = hash_texture(*diffuse)
+        model.textures.register("diffuse", files[f"{prefix}_diffuse"], normalize=False)
+    if normals is not None:
+        files[f"{prefix}_normals"] = hash_texture(*normals, normal_map=True)
+        model.textures.register("normals", files[f"{prefix}_normals"], tangent=tangent)
+    if specular is not None:
+        files[f"{prefix}_specular"] = hash_texture(*specular)
+        model.textures.register("specular", files[f"{prefix}_specular"], normalize=False)
+    return model
+
+
+def torus_rect_maps(api, resolution=(150, 200), name="torus_rect_maps"):
+    """Three maps of different non-square shapes on one material -- diffuse 40 x 96 (h x w), tangent-space normal map
+    96 x 40, specular map 33 x 57 -- and a 64 x 31 floor, under a coloured point light close to the torus whose
+    ``constant`` is below 1: the attenuation exceeds 1 on the near side and some channels end at the upper clip."""
+    cam, dbg = _std_cameras(api)
+    light = api.Light((0.9, 1.5, 1.3), color=(1.0, 0.7, 0.4), ambient_strength=0.25, specular_strength=0.6,
+                      constant=0.6, linear=0.3, quadratic=0.02)
+    torus = _register_hash_maps(api.Model.load_model(torus_obj(40, 25)), name, "torus",
+                                diffuse=(40, 96, 1), normals=(96, 40, 2), specular=(33, 57, 3))
+    floor = _register_hash_maps(api.Model.load_model(floor_obj()), name, "floor", diffuse=(64, 31, 4))
+    return _scene(api, cam, dbg, light, resolution, [torus, floor])
+
+
+def quad_rect_object_nm(api, resolution=(150, 200), name="quad_rect_object_nm"):
+    """neg_uv_obj's quad (uv from -0.6 to 1.4: rows and columns wrap from the far side) with a 24 x 80 diffuse map, an
+    80 x 24 OBJECT-space normal map and a specular map one texel wide (5 x 1: ``w - 1 == 0``, every column index is 0),
+    LH/OpenGL, culling off, under a coloured directional light with an attenuation of its own."""
+    cam, dbg = _std_cameras(api, backface_culling=False)
+    light = api.Light((-0.5, 1.0, 1.5), light_type=api.Lightning.DIRECTIONAL_LIGHTNING, center=(0, 0, 0),
+                      color=(0.5, 0.9, 1.0), ambient_strength=0.3, specular_strength=0.4,
+                      constant=1.2, linear=0.05, quadratic=0.25)
+    quad = _register_hash_maps(api.Model.load_model(neg_uv_obj()), name, "quad",
+                               diffuse=(24, 80, 5), normals=(80, 24, 6), specular=(5, 1, 7), tangent=False)
+    floor = _register_hash_maps(api.Model.load_model(floor_obj()), name, "floor", diffuse=(64, 31, 4))
+    return _scene(api, cam, dbg, light, resolution, [quad, floor], system=api.SYSTEM.LH, subsystem=api.SUBSYSTEM.OPENGL)
+
+
+def _shift(scene, x_offset, y_offset):
+    for cam in (scene.camera, scene.debug_camera):
+        cam.x_offset, cam.y_offset = x_offset, y_offset
+    return scene
+
+
+def cube_skybox_offset(api, resolution=(135, 240), offsets=(13, 52)):
+    """cube_skybox with both cameras' viewport shifted: the scene and the cubemap's two screen triangles move."""
+    return _shift(cube_skybox(api, resolution=resolution), *offsets)
+
+
+def torus_spot_offset_sky(api, resolution=(180, 320), offsets=(-45, -9), sky=(0.9, 0.3, 0.1), nu=40, nv=25):
+    """torus_spot shifted so that part of the scene leaves the frame on two sides, under a coloured spot light, in
+    front of a colour sky (``Scene(skymap=<colour>)``, obj/core.py:597-598)."""
+    cam, dbg = _std_cameras(api)
+    light = api.Light((2, 3, 4), light_type=api.Lightning.SPOT_LIGHTNING, color=(0.9, 1.0, 0.5),
+                      ambient_strength=0.1, specular_strength=0.1)
+    sc = _scene(api, cam, dbg, light, resolution, [_torus(api, nu, nv), _floor(api)], skymap=sky)
+    return _shift(sc, *offsets)
+
+
+def _unit(seed, k):
+    """The k-th draw of a sweep seed: a float in [0, 1) from the integer hash (no random generator)."""
+    return float(hash_u32(seed, k, 0x5EED, 0xD1CE)) / 2.0 ** 32
+
+
+def shading_sweep_parameters(seed, resolution=ADVERSARIAL_RESOLUTION):
+    """What seed *seed* of the shading-input sweep draws: four map shapes with 2 to 97 rows and 1 to 97 columns (seeds 1,
+    2, 3 and 5 mod 8 force a 2 x N, an N x 1 and two 2 x 1 maps), a light kind, colour and attenuation, viewport offsets
+    within half the frame either way, and a sky colour in [0, 1] (one component of seed 4 mod 8 is exactly 0, one of seed
+    6 exactly 1).  No map is one texel HIGH: upstream's ``Material.__setattr__`` (obj/materials.py:57-60) takes an array
+    whose first axis has length 1 for a one-entry ``.mtl`` value and raises on it, and so does this package's."""
+    draws = iter(range(64))
+    u = lambda: _unit(seed, next(draws))
+    shapes = {key: (2 + int(u() * 96), 1 + int(u() * 97)) for key in ("torus_diffuse", "torus_normals", "torus_specular", "floor_diffuse")}
+    forced = {1: ("torus_diffuse", (2, None)), 2: ("torus_normals", (None, 1)), 3: ("torus_specular", (2, 1)),
+              5: ("floor_diffuse", (2, 1))}.get(seed % 8)
+    if forced:
+        key, (fh, fw) = forced
+        shapes[key] = (fh or shapes[key][0], fw or shapes[key][1])
+    h, w = resolution
+    sky = [round(u(), 3) for _ in range(3)]
+    if seed % 8 == 4:
+        sky[seed // 8 % 3] = 0.0
+    if seed % 8 == 6:
+        sky[seed // 8 % 3] = 1.0
+    return dict(shapes=shapes, kind=seed % 3, position=(4 * u() - 2, 1.5 + 2.5 * u(), 4 * u() - 2),
+                color=tuple(round(0.2 + 0.8 * u(), 3) for _ in range(3)),
+                ambient_strength=round(0.4 * u(), 3), specular_strength=round(0.7 * u(), 3),
+                constant=round(0.5 + u(), 3), linear=round(0.4 * u(), 3), quadratic=round(0.4 * u(), 3),
+                offsets=(int((2 * u() - 1) * (w // 2)), int((2 * u() - 1) * (h // 2))), sky=tuple(sky),
+                tangent=bool(seed % 2 == 0), lh_gl=bool(seed % 4 == 3))
+
+
+def shading_sweep(api, seed, resolution=ADVERSARIAL_RESOLUTION):
+    """One seed of the sweep: a 24 x 16 torus with three hash maps and the floor with one, under what
+    shading_sweep_parameters draws.  An object-space normal map on odd seeds, LH/OpenGL on every fourth."""
+    p = shading_sweep_parameters(seed, resolution)
+    name = f"shading_sweep_{seed}"
+    kinds = (api.Lightning.POINT_LIGHTNING, api.Lightning.SPOT_LIGHTNING, api.Lightning.DIRECTIONAL_LIGHTNING)
+    cam, dbg = _std_cameras(api)
+    light = api.Light(p["position"], light_type=kinds[p["kind"]], center=(0, 0, 0), color=p["color"],
+                      ambient_strength=p["ambient_strength"], specular_strength=p["specular_strength"],
+                      constant=p["constant"], linear=p["linear"], quadratic=p["quadratic"])
+    s = p["shapes"]
+    torus = _register_hash_maps(api.Model.load_model(torus_obj(24, 16)), name, "torus",
+                                diffuse=(*s["torus_diffuse"], 100 + seed), normals=(*s["torus_normals"], 200 + seed),
+                                specular=(*s["torus_specular"], 300 + seed), tangent=p["tangent"])
+    floor = _register_hash_maps(api.Model.load_model(floor_obj()), name, "floor", diffuse=(*s["floor_diffuse"], 400 + seed))
+    system = dict(system=api.SYSTEM.LH, subsystem=api.SUBSYSTEM.OPENGL) if p["lh_gl"] else {}
+    sc = _scene(api, cam, dbg, light, resolution, [torus, floor], skymap=p["sky"], **system)
+    return _shift(sc, *p["offsets"])
+
+
 VARIANTS = ("std", "noclip", "f64", "textured", "lh_gl_ortho", "cull_off")
 
 
@@ -871,6 +1053,10 @@ SMALL = {
     "welded_s0": (welded, {"seed": 0}),
     "dense_tile_s0": (dense_tile, {"seed": 0}),
     "welded_s4_ortho": (welded, {"seed": 4, "variant": "lh_gl_ortho"}),
+    "torus_rect_maps": (torus_rect_maps, {}),
+    "quad_rect_object_nm": (quad_rect_object_nm, {}),
+    "cube_skybox_offset": (cube_skybox_offset, {}),
+    "torus_spot_offset_sky": (torus_spot_offset_sky, {}),
 }
 # a full capture too, but outside SMALL: its frame is the reference's only in front of the camera plane
 BEHIND_CAMERA = {
@@ -890,7 +1076,7 @@ HUGE = {
 }
 NO_SHADOW = {"c1_diablo_800x600", "c2_diablo_1080p", "diablo_small_noshadow"}
 # the same scenes with upstream's debug-frustum overlay left on (obj/core.py:638)
-OVERLAY = ["diablo_small_overlay", "diablo_floor_lh_gl_overlay", "cube_outward_overlay"]
+OVERLAY = ["diablo_small_overlay", "diablo_floor_lh_gl_overlay", "cube_outward_overlay", "torus_spot_offset_sky_overlay"]
 
 
 def build(api, name):
