@@ -390,7 +390,7 @@ int mr_debug_read_tile_order(mr_scene *scene, uint32_t *out, int32_t cap_tiles);
 /* A model's pose: the model (index as mr_scene_add_model returned it) renders as if its vertices were the float64 array
  * V' = vertices @ m16, every element rn(v[0] * m[0][j]) followed by fma steps in ascending k (mr_host_matmul_chain) --
  * the reference's `Model @ M` with the product's rounding pinned.  m16 is a row-major 4 x 4 in the row-vector
- * convention; NULL removes the pose.  Vertices only: vertex normals, uv, materials and topology stay.  The pose is
+ * convention; NULL removes the pose.  Vertices only: vertex normals (but see mr_scene_set_model_pose_normals), uv, materials and topology stay.  The pose is
  * absolute (it replaces the one before) and the vertices passed to mr_scene_add_model are never changed.  V' is float64,
  * so a posed model behaves as one with vertices_are_f32 == 0.
  * The call copies m16 and launches nothing.  The next frame applies what changed in one pass on the device (vertices,
@@ -398,6 +398,17 @@ int mr_debug_read_tile_order(mr_scene *scene, uint32_t *out, int32_t cap_tiles);
  * a commit.  When a model with vertices_are_f32 != 0 goes from un-posed to posed or back, one ordinary commit of the
  * scene comes first.  MR_E_INVALID for a model index out of range or an entry that is not finite. */
 int mr_scene_set_model_pose(mr_scene *scene, int32_t model, const double *m16);
+
+/* A posed model's normal matrix: with g9 = G (row-major 3 x 3, row vectors; the caller passes the inverse transpose of the
+ * pose's upper-left 3 x 3) the model renders as if its vertex normals were float32(normals @ G) and every object-space
+ * normal map of its materials (tex_norm >= 0, norm_tangent == 0) held float32(texel @ G) -- every component
+ * rn(n[0] * G[0][j]) followed by fma steps in ascending k, in float64, rounded to float32 once; nothing is re-normalised.
+ * Tangent-space maps, tex_kd and tex_ks are not touched, and a texture shared with another model stays what it was for
+ * that model.  NULL: the normals stay as they were passed (the default).  Valid only for a model that has a pose;
+ * removing the pose removes the matrix.  The call copies g9 and launches nothing: the next frame's pose pass does the
+ * work (a matrix alone, the pose as it was, leaves the vertices' part of the pass out).
+ * MR_E_INVALID for a model index out of range, a model without a pose or an entry that is not finite. */
+int mr_scene_set_model_pose_normals(mr_scene *scene, int32_t model, const double *g9);
 
 /* Diagnostics of the pose pass: out[0] = full commits of this scene so far, out[1] = pose passes so far, out[2] = models
  * that have a pose now, out[3] = vertices the last pass wrote.  Does not wait for the device. */
@@ -409,6 +420,11 @@ int mr_debug_pose(mr_scene *scene, int32_t *out);
  * MR_E_INVALID before the first pass.  The pass has waited for its kernels: this call does not wait. */
 #define MR_N_POSE_TIMES 5
 int mr_debug_pose_times(mr_scene *scene, float *out_ms);
+
+/* The same for the two kernels of the last pass that had normal matrices to apply: [0] k_pose_normals  [1] k_pose_texels
+ * (0 for one that pass did not launch: no normals, or no object-space map).  MR_E_INVALID before the first such pass. */
+#define MR_N_POSE_NORMALS_TIMES 2
+int mr_debug_pose_normals_times(mr_scene *scene, float *out_ms);
 
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit

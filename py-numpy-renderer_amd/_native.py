@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import pack_frame, pack_model
+from ._pack import pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -140,6 +140,8 @@ _PROTOTYPES = {
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_scene_set_model_pose": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_scene_set_model_pose_normals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_debug_pose_normals_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_pose": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_pose_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_read_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
@@ -285,7 +287,7 @@ class DeviceRenderer:
         if not self.handle:
             raise RuntimeError("mr_scene_create failed: " + self.lib.mr_last_error().decode())
         self._signature = None
-        self._pose_keys = []                 # per model: the bytes of the pose the library holds, or None
+        self._pose_keys = []                 # per model: (bytes of the pose, bytes of the normal matrix or None) the library holds, or None
         self._sky_key = None
         self._last_stats = {}
         self._frame = None
@@ -326,15 +328,21 @@ class DeviceRenderer:
         self.sync_poses(scene)
 
     def sync_poses(self, scene):
-        """``mr_scene_set_model_pose`` for every model whose ``pose`` is not the one the library holds."""
+        """``mr_scene_set_model_pose`` for every model whose ``pose`` is not the one the library holds, and
+        ``mr_scene_set_model_pose_normals`` after it where the normal matrix (``Model.pose_normals``) is not."""
         keys = self._pose_keys
         for index, model in enumerate(scene.models):
             pose = getattr(model, "pose", None)
-            key = None if pose is None else pose.tobytes()
+            g = None if pose is None else pose_normal_matrix(model)
+            key = None if pose is None else (pose.tobytes(), None if g is None else g.tobytes())
             if key == keys[index]:
                 continue
             _check(self.lib.mr_scene_set_model_pose(self.handle, index, None if pose is None else pose.ctypes.data),
                    "mr_scene_set_model_pose")
+            held = None if keys[index] is None else keys[index][1]
+            if key is not None and key[1] != held:            # (the library lets go of the matrix with the pose)
+                _check(self.lib.mr_scene_set_model_pose_normals(self.handle, index, None if g is None else g.ctypes.data),
+                       "mr_scene_set_model_pose_normals")
             keys[index] = key
 
     def _upload_scene(self, scene):
@@ -692,6 +700,15 @@ class DeviceRenderer:
         buf = (C.c_float * 5)()
         _check(self.lib.mr_debug_pose_times(self.handle, buf), "mr_debug_pose_times")
         return dict(zip(self.POSE_TIME_NAMES, (float(v) for v in buf)))
+
+    POSE_NORMALS_TIME_NAMES = ("pose_normals", "pose_texels")
+
+    def pose_normals_times(self):
+        """Device milliseconds of the two kernels of the last pose pass that had normal matrices to apply
+        (``mr_debug_pose_normals_times``)."""
+        buf = (C.c_float * 2)()
+        _check(self.lib.mr_debug_pose_normals_times(self.handle, buf), "mr_debug_pose_normals_times")
+        return dict(zip(self.POSE_NORMALS_TIME_NAMES, (float(v) for v in buf)))
 
     def read_clusters(self):
         """The per-cluster records of the scene (``mr_debug_read_clusters``): a structured array with ``lo``, ``hi``,

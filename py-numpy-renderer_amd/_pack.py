@@ -175,6 +175,67 @@ def posed_vertices(model):
     return matmul_chain(np.asarray(model.vertices).astype(np.float64), pose)
 
 
+def check_pose_normals(value):
+    """``Model.pose_normals``: ``True`` / ``False`` (``bool``, ``np.bool_``) or the integers 0 / 1, returned as a
+    ``bool``; ``TypeError`` for anything else."""
+    if isinstance(value, (bool, np.bool_)):
+        return bool(value)
+    if isinstance(value, (int, np.integer)) and int(value) in (0, 1):
+        return bool(value)
+    raise TypeError(f"pose_normals must be True or False, got {value!r}")
+
+
+def normal_matrix(pose):
+    """The 3x3 float64 matrix G that takes a posed model's normals along: the inverse transpose of ``pose[:3, :3]`` in
+    the row-vector convention (``n' = n @ G``), formed as the cofactor matrix divided by the determinant.  Plain float64
+    operations in the order written here, no LAPACK: ``C[i][j] = a[i+1][j+1] * a[i+2][j+2] - a[i+1][j+2] * a[i+2][j+1]``
+    (indices mod 3), ``det = (a[0][0] * C[0][0] + a[0][1] * C[0][1]) + a[0][2] * C[0][2]``, ``G[i][j] = C[i][j] / det``.
+    ``ValueError`` when the determinant is 0 or an entry of G is not finite."""
+    a = [[float(x) for x in row[:3]] for row in np.asarray(pose, dtype=np.float64)[:3]]
+    c = [[a[(i + 1) % 3][(j + 1) % 3] * a[(i + 2) % 3][(j + 2) % 3] - a[(i + 1) % 3][(j + 2) % 3] * a[(i + 2) % 3][(j + 1) % 3]
+          for j in range(3)] for i in range(3)]
+    det = (a[0][0] * c[0][0] + a[0][1] * c[0][1]) + a[0][2] * c[0][2]
+    if det == 0 or det != det:
+        raise ValueError("pose_normals needs an invertible pose")
+    g = np.array([[c[i][j] / det for j in range(3)] for i in range(3)], dtype=np.float64)
+    if not np.isfinite(g).all():
+        raise ValueError("pose_normals needs an invertible pose")
+    g.setflags(write=False)
+    return g
+
+
+def pose_normal_matrix(model):
+    """G of a model whose normals follow its pose (``pose`` set and ``pose_normals`` on), else ``None``."""
+    pose = getattr(model, "pose", None)
+    if pose is None or not getattr(model, "pose_normals", False):
+        return None
+    g = model.__dict__.get("_normal_matrix")
+    return g if g is not None else normal_matrix(pose)
+
+
+def _chain_f32(vectors, g):
+    """``float32(matmul_chain(float64(float32(vectors)), g))`` of an (..., 3) array: rounded once, not re-normalised."""
+    from ._fp import matmul_chain
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    return matmul_chain(v.reshape(-1, 3).astype(np.float64), g).astype(np.float32).reshape(v.shape)
+
+
+def posed_normals(model):
+    """The vertex normals a model renders with: ``model.normals``, or with ``pose_normals`` and a pose the float32 array
+    ``float32(matmul_chain(float64(float32(normals)), G))``, ``G = normal_matrix(pose)``."""
+    g = pose_normal_matrix(model)
+    if g is None or model.normals is None:
+        return model.normals
+    return _chain_f32(model.normals, g)
+
+
+def posed_normal_map(texels, g):
+    """An object-space normal map under the normal matrix *g*: ``float32(matmul_chain(float64(texels), g))`` texel by
+    texel, the shape kept."""
+    arr = np.asarray(texels)
+    return _chain_f32(arr[..., :3], g)
+
+
 def pack_light(light) -> PackedLight:
     kind = light.light_type.value if isinstance(light.light_type, Lightning) else int(light.light_type)
     return PackedLight(
@@ -235,10 +296,26 @@ def _texture_id(tex, textures, seen):
     return seen[key]
 
 
+def _posed_map_id(tex, g, model, textures, seen):
+    """A texture of its own for *model*'s re-baked copy of the object-space normal map *tex*: another model that
+    registered the same array keeps the original, or gets a copy with its own matrix."""
+    key = ("posed", id(model), id(tex))
+    if key not in seen:
+        arr = np.asarray(tex)
+        if arr.ndim != 3 or arr.shape[2] < 3:
+            raise ValueError(f"texture must be (h, w, 3), got {arr.shape}")
+        seen[key] = len(textures)
+        textures.append(np.ascontiguousarray(posed_normal_map(arr, g)))
+    return seen[key]
+
+
 def pack_model(model, textures, seen, posed=False) -> PackedModel:
-    """*posed*: pack the vertices the model renders with (``posed_vertices``) instead of ``model.vertices`` -- what the
-    oracle needs; the device gets the vertices as they are and the pose beside them (``mr_scene_set_model_pose``)."""
+    """*posed*: pack the arrays the model renders with -- ``posed_vertices`` and, with ``pose_normals``, ``posed_normals``
+    and re-baked object-space normal maps -- instead of ``model.vertices`` / ``normals`` / the maps as registered: what
+    the oracle needs; the device gets the arrays as they are and the matrices beside them (``mr_scene_set_model_pose``,
+    ``mr_scene_set_model_pose_normals``)."""
     verts = posed_vertices(model) if posed else np.asarray(model.vertices)
+    nmat = pose_normal_matrix(model) if posed else None
     if verts.ndim != 2 or verts.shape[1] != 4:
         raise ValueError(f"Model.vertices must be (V, 4), got {verts.shape}")
     faces = np.asarray(model._faces)
@@ -247,6 +324,8 @@ def pack_model(model, textures, seen, posed=False) -> PackedModel:
                          f"(got {faces.shape})")
     uv = None if model.uv is None else np.ascontiguousarray(model.uv, dtype=np.float32)
     normals = None if model.normals is None else np.ascontiguousarray(model.normals, dtype=np.float32)
+    if nmat is not None and normals is not None:
+        normals = np.ascontiguousarray(posed_normals(model))
     if uv is not None and (uv.ndim != 2 or uv.shape[1] < 2):
         raise ValueError(f"Model.uv must be (T, 3), got {uv.shape}")
     if uv is not None and uv.shape[1] != 3:
@@ -261,8 +340,11 @@ def pack_model(model, textures, seen, posed=False) -> PackedModel:
         if hasattr(mat, "map_Kd"):
             rec.tex_kd = _texture_id(mat.map_Kd, textures, seen)
         if hasattr(mat, "norm"):
-            rec.tex_norm = _texture_id(mat.norm, textures, seen)
             rec.norm_tangent = mat.is_tangent_space("norm")
+            if nmat is not None and not rec.norm_tangent:
+                rec.tex_norm = _posed_map_id(mat.norm, nmat, model, textures, seen)
+            else:
+                rec.tex_norm = _texture_id(mat.norm, textures, seen)
         if hasattr(mat, "map_Ks"):
             rec.tex_ks = _texture_id(mat.map_Ks, textures, seen)
         mats.append(rec)

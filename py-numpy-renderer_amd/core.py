@@ -73,7 +73,19 @@ class Model:
     ``vertices`` only (vertex normals are not transformed), and its result is float64: a posed float32 model behaves
     as a float64 model (face normals, edge vectors and silhouette normals in float64).  ``vertices`` itself is never
     modified and the pose is absolute, not cumulative: ``pose = None`` gives the un-posed model back.  A scene whose
-    models all have ``pose = None`` is exactly the scene without this attribute."""
+    models all have ``pose = None`` is exactly the scene without this attribute.
+
+    ``pose_normals`` (an addition; ``False`` by default; ``True`` / ``False`` / 0 / 1, anything else ``TypeError``)
+    makes the shading follow the pose.  With ``pose = M`` and ``pose_normals = True`` the model renders as the model above
+    with two further replacements, both made with ``G = _pack.normal_matrix(M)``, the inverse transpose of ``M[:3, :3]``
+    (cofactors over determinant in plain float64): ``normals`` by ``float32(matmul_chain(float64(float32(normals)), G))``
+    and every object-space normal map (``norm`` registered with ``tangent=False``) of its materials by
+    ``float32(matmul_chain(float64(texels), G))``, neither re-normalised (the reference normalises per fragment).
+    Tangent-space maps follow by themselves (their frame is built from the posed corners and these normals); ``map_Kd``
+    and ``map_Ks`` are never touched, and a texture array that another model holds too stays what it was for that model.
+    A pose that cannot be inverted raises ``ValueError`` at whichever of the two assignments completes the pair, and
+    the attribute keeps its value; without ``pose_normals`` such a pose stays legal.  With ``pose_normals = False`` or
+    ``pose = None`` everything is exactly as without this attribute."""
 
     def __init__(self, vertices, uv, normals, faces, shadowing=False, materials=None,
                  material_group=None, clip=True, depth_test=True):
@@ -91,6 +103,8 @@ class Model:
         self.silhouette = set()             # filled by Scene.render with the last frame's edges
         self._revision = 0                  # bumped whenever device copies go stale
         self._pose = None
+        self._pose_normals = False
+        self._normal_matrix = None          # normal_matrix(pose) while pose_normals is on and a pose is set
 
     # -- ingest ---------------------------------------------------------------------------
     @classmethod
@@ -172,8 +186,23 @@ class Model:
 
     @pose.setter
     def pose(self, value):
-        from ._pack import check_pose
-        self._pose = check_pose(value)
+        from ._pack import check_pose, normal_matrix
+        pose = check_pose(value)
+        # (a pose that cannot carry the normals is refused here, and the last one stays)
+        g = normal_matrix(pose) if pose is not None and self.pose_normals else None
+        self._pose, self._normal_matrix = pose, g
+
+    @property
+    def pose_normals(self):
+        """``False`` (the default) or ``True``: the shading normals follow ``pose``; see the class docstring."""
+        return getattr(self, "_pose_normals", False)
+
+    @pose_normals.setter
+    def pose_normals(self, value):
+        from ._pack import check_pose_normals, normal_matrix
+        on = check_pose_normals(value)
+        g = normal_matrix(self.pose) if on and self.pose is not None else None
+        self._pose_normals, self._normal_matrix = on, g
 
     def __matmul__(self, other):
         self.vertices = self.vertices @ other

@@ -1,10 +1,12 @@
 // host_pose.h -- the pose pass: a model's pose (mr_scene_set_model_pose) applied on the device, in front of the frame.
 //
-// A pose changes vertex positions and nothing else, so what a commit builds from positions is rebuilt where it lives:
+// A pose changes vertex positions, so what a commit builds from positions is rebuilt where it lives:
 // the posed vertices (k_pose_vertices, from the pristine copy d_verts0 into d_verts, which is what every kernel reads),
 // the face normals and their copies in the edge records, the static face records and the cluster records (k_clusters:
 // commit() keeps the host builder, so a scene without poses is what it always was).  Topology, attributes, materials,
 // tile histories and list capacities stay; the silhouette cache goes, it belongs to the geometry.
+// A model that also has a normal matrix (mr_scene_set_model_pose_normals) gets its vertex normals and its object-space
+// normal maps transformed in the same pass (apply_pose_normals), in front of the kernels above.
 // The pass is synchronous: it waits for the device before it starts (frames in flight on other streams read the static
 // records: the rule of commit() and mr_scene_add_model) and for its own kernels before it returns.
 #pragma once
@@ -21,6 +23,10 @@ void set_model_pose(mr_scene *sc, int32_t model, const double *m16)
     const bool was = mp.posed;
     mp.posed = m16 != nullptr;
     if (m16) std::memcpy(mp.m, m16, sizeof mp.m);
+    if (!mp.posed && mp.has_g) {                     // the normal matrix goes with the pose
+        mp.has_g = false;
+        sc->pose_g_dirty = true;
+    }
     if (was != mp.posed && mp.verts_f32) {
         // posed vertices are float64 (the product of float64 matrices): the model's faces lose FF_VERTS_F32, or get it back
         const size_t f0 = (size_t)sc->model_face_off[model];
@@ -29,18 +35,145 @@ void set_model_pose(mr_scene *sc, int32_t model, const double *m16)
             sc->face_flags[f] = (uint8_t)(mp.posed ? sc->face_flags[f] & ~mr::FF_VERTS_F32 : sc->face_flags[f] | mr::FF_VERTS_F32);
         sc->dirty = true;
     }
-    sc->pose_dirty = true;
+    sc->pose_dirty = sc->pose_geom_dirty = true;
 }
 
-// Runs where commit() runs, right after it.
+// mr_scene_set_model_pose_normals behind its argument checks
+void set_model_pose_normals(mr_scene *sc, int32_t model, const double *g9)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    if (!g9 && !mp.has_g) return;
+    if (g9 && mp.has_g && !std::memcmp(mp.g, g9, sizeof mp.g)) return;
+    mp.has_g = g9 != nullptr;
+    if (g9) std::memcpy(mp.g, g9, sizeof mp.g);
+    sc->pose_dirty = sc->pose_g_dirty = true;
+}
+
+// a material's object-space normal map, if it has one
+inline bool object_space_map(const mr_scene *sc, const mr::Material &m)
+{
+    return m.tex_norm >= 0 && m.tex_norm < (int32_t)sc->textures.size() && !m.norm_tangent;
+}
+
+// The normals' part of the pass, in front of the vertices' (k_face_static copies d_normals into the face records): runs
+// when a normal matrix was set, changed or removed, for every model that has one.  Vertex normals go from the pristine
+// d_normals0 into d_normals; every (model, object-space normal map) pair gets a re-baked copy of the map in d_rebaked,
+// and that model's materials -- the host's records, then their range on the device -- point at the copy.  A model whose
+// matrix is gone gets its normals and its materials' headers back.  The caller has waited for the device.
+struct NormalTables {                                    // (the caller keeps them until it has waited for the stream)
+    std::vector<mr::Vec3Row> nrows, trows;
+    std::vector<int32_t> nblocks, tblocks;
+};
+
+int apply_pose_normals(mr_scene *sc, NormalTables &tables)
+{
+    auto &[nrows, trows, nblocks, tblocks] = tables;
+    std::vector<size_t> toff;                            // of every texel row: its copy's first float in d_rebaked
+    std::vector<std::pair<int32_t, size_t>> mat_row;     // (material, the texel row of its map's copy)
+    size_t rebaked = 0;
+    for (const mr_scene::ModelPose &mp : sc->poses) {
+        if (!mp.has_g) continue;
+        mr::Vec3Row r;
+        std::memset(&r, 0, sizeof r);
+        std::memcpy(r.g, mp.g, sizeof r.g);
+        if (mp.n_normals > 0) {
+            r.first = mp.normal_off; r.count = mp.n_normals; r.block0 = (int32_t)nblocks.size();
+            nblocks.insert(nblocks.end(), (size_t)blocks_for(mp.n_normals, mr::POSE_BLOCK), (int32_t)nrows.size());
+            nrows.push_back(r);
+        }
+        const size_t own = mat_row.size();               // two materials of one model with one map share its copy
+        for (int32_t k = mp.mat_off; k < mp.mat_off + mp.n_mats; ++k) {
+            const mr::Material &m = sc->materials[k];
+            if (!object_space_map(sc, m)) continue;
+            size_t row = trows.size();
+            for (size_t j = own; j < mat_row.size(); ++j)
+                if (sc->materials[mat_row[j].first].tex_norm == m.tex_norm) row = mat_row[j].second;
+            if (row == trows.size()) {
+                const mr::Texture &t = sc->textures[m.tex_norm];
+                r.first = 0; r.src = t.rgb; r.count = (int64_t)t.h * t.w; r.block0 = (int32_t)tblocks.size();
+                tblocks.insert(tblocks.end(), (size_t)blocks_for(r.count, mr::POSE_BLOCK), (int32_t)row);
+                trows.push_back(r);
+                toff.push_back(rebaked);
+                rebaked += (size_t)r.count * 3;
+            }
+            mat_row.push_back({ k, row });
+        }
+    }
+    HIP_TRY(sc->d_rebaked.ensure(std::max<size_t>(rebaked * sizeof(float), 16)));
+    for (size_t k = 0; k < trows.size(); ++k) trows[k].dst = sc->d_rebaked.as<float>() + toff[k];
+    for (const auto &[k, row] : mat_row) sc->materials[k].map_norm.rgb = trows[row].dst;      // (h and w stay)
+    if (!nrows.empty() && !sc->normals0_valid) {
+        if (int rc = upload(sc->d_normals0, sc->normals, g_stream)) return rc;
+        sc->normals0_valid = true;
+    }
+    auto upload_materials = [&](const mr_scene::ModelPose &mp) -> int {
+        HIP_TRY(hipMemcpyAsync(sc->d_materials.as<mr::Material>() + mp.mat_off, sc->materials.data() + mp.mat_off,
+                               (size_t)mp.n_mats * sizeof(mr::Material), hipMemcpyHostToDevice, g_stream));
+        return MR_OK;
+    };
+    size_t next = 0;                                     // (mat_row lists the models' materials in model order)
+    for (mr_scene::ModelPose &mp : sc->poses) {
+        if (mp.has_g) {
+            const size_t first = next;
+            while (next < mat_row.size() && mat_row[next].first < mp.mat_off + mp.n_mats) ++next;
+            if (next > first)
+                if (int rc = upload_materials(mp)) return rc;
+            mp.maps_on_device = next > first;
+            mp.normals_on_device = mp.n_normals > 0;
+            continue;
+        }
+        if (mp.normals_on_device) {                      // a model whose matrix is gone gets its own normals back
+            const size_t off = (size_t)mp.normal_off * 3 * sizeof(float), bytes = (size_t)mp.n_normals * 3 * sizeof(float);
+            HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_normals.p) + off, static_cast<const char *>(sc->d_normals0.p) + off, bytes,
+                                   hipMemcpyDeviceToDevice, g_stream));
+            mp.normals_on_device = false;
+        }
+        if (mp.maps_on_device) {                         // ... and its materials the maps as they were added
+            for (int32_t k = mp.mat_off; k < mp.mat_off + mp.n_mats; ++k)
+                if (object_space_map(sc, sc->materials[k])) sc->materials[k].map_norm = sc->textures[sc->materials[k].tex_norm];
+            if (int rc = upload_materials(mp)) return rc;
+            mp.maps_on_device = false;
+        }
+    }
+    if (nrows.empty() && trows.empty()) return MR_OK;
+    // three marks round the two kernels (mr_debug_pose_normals_times)
+    for (hipEvent_t &e : sc->pose_n_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(sc->pose_n_ev[0], g_stream));
+    if (!nrows.empty()) {
+        if (int rc = upload(sc->d_normal_rows, nrows, g_stream)) return rc;
+        if (int rc = upload(sc->d_normal_blocks, nblocks, g_stream)) return rc;
+        hipLaunchKernelGGL(mr::k_pose_normals, dim3((unsigned)nblocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
+                           sc->d_normal_rows.as<mr::Vec3Row>(), sc->d_normal_blocks.as<int32_t>(), sc->d_normals0.as<float>(),
+                           sc->d_normals.as<float>());
+    }
+    HIP_TRY(hipEventRecord(sc->pose_n_ev[1], g_stream));
+    if (!trows.empty()) {
+        if (int rc = upload(sc->d_texel_rows, trows, g_stream)) return rc;
+        if (int rc = upload(sc->d_texel_blocks, tblocks, g_stream)) return rc;
+        hipLaunchKernelGGL(mr::k_pose_texels, dim3((unsigned)tblocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
+                           sc->d_texel_rows.as<mr::Vec3Row>(), sc->d_texel_blocks.as<int32_t>());
+    }
+    HIP_TRY(hipEventRecord(sc->pose_n_ev[2], g_stream));
+    sc->pose_n_marks = 3;
+    sc->pose_n_ran[0] = !nrows.empty(); sc->pose_n_ran[1] = !trows.empty();
+    return MR_OK;
+}
+
+// Runs where commit() runs, right after it.  What a pass does depends on what changed: a pose brings all of it, a
+// normal matrix alone (the pose as it was) the normals' part and k_face_static -- vertices, face and edge normals, the
+// cluster records and the silhouette cache stay.
 int apply_poses(mr_scene *sc)
 {
     if (!sc->pose_dirty) return MR_OK;
+    const bool geom = sc->pose_geom_dirty;
     std::vector<mr::PoseRow> rows;
     std::vector<int32_t> block_row;
-    bool restore = false;
+    bool restore = false, normals = false;
     int64_t written = 0;
     for (const mr_scene::ModelPose &mp : sc->poses) {
+        normals = normals || (sc->pose_g_dirty && (mp.has_g || mp.normals_on_device || mp.maps_on_device));
+        if (!geom) continue;
         if (!mp.posed) { restore = restore || mp.on_device; continue; }
         mr::PoseRow r;
         std::memset(&r, 0, sizeof r);
@@ -50,12 +183,30 @@ int apply_poses(mr_scene *sc)
         rows.push_back(r);
         written += mp.n_verts;
     }
-    if (rows.empty() && !restore) {                  // (a commit has just uploaded the pristine vertices)
-        sc->pose_dirty = false;
+    if (rows.empty() && !restore && !normals) {      // (a commit has just uploaded the pristine vertices)
+        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
         return MR_OK;
     }
     if (sc->pos32) return fail(MR_E_INVALID, "pose pass on a scene of float32 face records");   // (set_model_pose leaves such a scene dirty)
     HIP_TRY(hipDeviceSynchronize());                 // no frame may still be reading the records about to be rewritten
+    NormalTables normal_tables;
+    if (normals)
+        if (int rc = apply_pose_normals(sc, normal_tables)) return rc;
+    const int nf = (int)(sc->faces.size() / 12), ne = (int)sc->edges.size();
+    auto face_static = [&] {
+        hipLaunchKernelGGL(mr::k_face_static<double>, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
+                           sc->d_face_flags.as<uint8_t>(), sc->d_verts.as<double>(), sc->d_uv.as<float>(), sc->d_normals.as<float>(),
+                           sc->d_face_pos.as<mr::FacePos64>(), sc->d_face_attr.as<mr::FaceAttr>());
+    };
+    if (rows.empty() && !restore) {                  // normal matrices alone: the face records take the new normals
+        if (nf > 0) face_static();
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g_stream));     // (the tables go out of scope)
+        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
+        sc->pose_passes += 1;
+        sc->pose_written = 0;
+        return MR_OK;
+    }
     if (!sc->verts0_valid) {
         if (int rc = upload(sc->d_verts0, sc->verts, g_stream)) return rc;
         sc->verts0_valid = true;
@@ -83,7 +234,6 @@ int apply_poses(mr_scene *sc)
         for (mr_scene::ModelPose &mp : sc->poses) mp.on_device = mp.posed;
     }
     HIP_TRY(hipEventRecord(sc->pose_ev[mark++], g_stream));
-    const int nf = (int)(sc->faces.size() / 12), ne = (int)sc->edges.size();
     if (nf > 0) {
         hipLaunchKernelGGL(mr::k_face_normals, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
                            sc->d_face_flags.as<uint8_t>(), sc->d_verts.as<double>(), sc->d_face_n.as<double>());
@@ -92,9 +242,7 @@ int apply_poses(mr_scene *sc)
             hipLaunchKernelGGL(mr::k_edge_normals, dim3((ne + 255) / 256), dim3(256), 0, g_stream, ne, sc->d_edges.as<mr::EdgeRec>(),
                                sc->d_face_n.as<double>());
         HIP_TRY(hipEventRecord(sc->pose_ev[mark++], g_stream));
-        hipLaunchKernelGGL(mr::k_face_static<double>, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
-                           sc->d_face_flags.as<uint8_t>(), sc->d_verts.as<double>(), sc->d_uv.as<float>(), sc->d_normals.as<float>(),
-                           sc->d_face_pos.as<mr::FacePos64>(), sc->d_face_attr.as<mr::FaceAttr>());
+        face_static();
         HIP_TRY(hipEventRecord(sc->pose_ev[mark++], g_stream));
         const int nc = (nf + mr::CLUSTER_FACES - 1) / mr::CLUSTER_FACES;
         hipLaunchKernelGGL(mr::k_clusters, dim3((nc + 3) / 4), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
@@ -104,8 +252,8 @@ int apply_poses(mr_scene *sc)
     sc->pose_marks = mark;
     sc->sil.drop();                                  // the silhouette belongs to the geometry
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(g_stream));         // (the two tables go out of scope)
-    sc->pose_dirty = false;
+    HIP_TRY(hipStreamSynchronize(g_stream));         // (the tables go out of scope)
+    sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
     sc->pose_passes += 1;
     sc->pose_written = (int32_t)written;
     return MR_OK;

@@ -35,9 +35,18 @@ struct mr_scene {
         bool posed = false;
         bool on_device = false;               // d_verts holds posed vertices in this model's range
         double m[16] = {};
+        // the normal matrix (mr_scene_set_model_pose_normals): the model's vertex normals (an OBJ file counts its vn
+        // apart from its v) and its materials' object-space normal maps follow the pose
+        int32_t normal_off = 0, n_normals = 0, mat_off = 0, n_mats = 0;
+        bool has_g = false;
+        bool normals_on_device = false;       // d_normals holds transformed normals in this model's range
+        bool maps_on_device = false;          // this model's materials point at re-baked copies of their maps
+        double g[9] = {};
     };
     std::vector<ModelPose> poses;             // one per model
-    bool pose_dirty = false;                  // a pose changed: apply_poses() has work
+    bool pose_dirty = false;                  // a pose or a normal matrix changed: apply_poses() has work
+    bool pose_geom_dirty = false;             // ... and a pose among them: vertices and what is built from them
+    bool pose_g_dirty = false;                // ... and a normal matrix among them: normals and re-baked maps
     int32_t commits = 0, pose_passes = 0, pose_written = 0;      // mr_debug_pose
 
     // ---- device copies of the static scene
@@ -52,6 +61,13 @@ struct mr_scene {
     bool verts0_valid = false;
     hipEvent_t pose_ev[6] = {};               // marks of the last pass (mr_debug_pose_times)
     int pose_marks = 0;
+    // the same for normal matrices: the normals as the caller passed them, the tables of k_pose_normals and
+    // k_pose_texels, and the re-baked copies of object-space normal maps, one after the other
+    DevBuf d_normals0, d_normal_rows, d_normal_blocks, d_texel_rows, d_texel_blocks, d_rebaked;
+    bool normals0_valid = false;
+    hipEvent_t pose_n_ev[3] = {};             // marks round the two kernels (mr_debug_pose_normals_times)
+    int pose_n_marks = 0;
+    bool pose_n_ran[2] = {};                  // which of the two the last such pass launched
     bool pos32 = false;                      // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
     DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
@@ -292,9 +308,11 @@ int commit(mr_scene *sc)
     // d_verts holds the vertices as they were passed: the poses are applied next (apply_poses)
     sc->commits += 1;
     sc->verts0_valid = false;
+    sc->normals0_valid = false;               // (and the normals and the materials' map headers)
     for (mr_scene::ModelPose &mp : sc->poses) {
-        mp.on_device = false;
-        if (mp.posed) sc->pose_dirty = true;
+        mp.on_device = mp.normals_on_device = mp.maps_on_device = false;
+        if (mp.posed) sc->pose_dirty = sc->pose_geom_dirty = true;
+        if (mp.has_g) sc->pose_g_dirty = true;
     }
     return MR_OK;
 }

@@ -1,8 +1,11 @@
-// kernels_pose.h -- the two kernels only the pose pass runs (host_pose.h, apply_poses): a model's pose changes vertex
-// positions and nothing else, so the records that depend on positions are rebuilt on the device, in front of the frame.
+// kernels_pose.h -- the kernels only the pose pass runs (host_pose.h, apply_poses): a model's pose changes vertex
+// positions -- and, where the caller asked for it (mr_scene_set_model_pose_normals), the shading normals -- so the records
+// that depend on them are rebuilt on the device, in front of the frame.
 //
 //   k_pose_vertices   vertices of the posed models: pristine vertex @ pose, the ascending fma chain of
 //                     mr_host_matmul_chain, bit for bit
+//   k_pose_normals    vertex normals of the models that have a normal matrix G: float32(pristine normal @ G), the same chain
+//   k_pose_texels     the same for the texels of those models' object-space normal maps, into copies of the maps
 //   k_clusters        the per-cluster records (rast_types.h, ClusterRec) from the posed vertices: what build_clusters
 //                     (host_scene.h) builds on the host at commit time, one wavefront per cluster
 //
@@ -38,6 +41,53 @@ k_pose_vertices(const PoseRow *__restrict__ rows, const int32_t *__restrict__ bl
     o.z = chain4(v.x, v.y, v.z, v.w, r.m[2], r.m[6], r.m[10], r.m[14]);
     o.w = chain4(v.x, v.y, v.z, v.w, r.m[3], r.m[7], r.m[11], r.m[15]);
     verts[(size_t)r.first + i] = o;
+}
+
+// One model's vertex normals (k_pose_normals: first / count index the scene's normal array) or one object-space normal
+// map of one model (k_pose_texels: src / dst are the map and its re-baked copy, count its texels), the 3 x 3 matrix G
+// (row-major, row vectors) and the first of the workgroups that cover the range.
+struct alignas(8) Vec3Row {
+    const float *src;
+    float *dst;
+    int64_t count;
+    int32_t first, block0;
+    double g[9];
+};
+static_assert(sizeof(Vec3Row) == 104, "Vec3Row layout");
+
+// float32(v @ G) of one float32 3-vector: widened, every component rn(v0 * G0j) followed by fma steps in ascending k,
+// rounded to float32 once (_pack.posed_normals, bit for bit: the library is built with -ffp-contract=off).  A lane
+// reads and writes its 12 bytes, consecutive lanes consecutive vectors; G is uniform over the workgroup.
+__device__ __forceinline__ void pose_vec3(const Vec3Row &r, const float *__restrict__ src, float *__restrict__ dst, int64_t i)
+{
+    const float3 v = *reinterpret_cast<const float3 *>(src + i * 3);
+    const double x = (double)v.x, y = (double)v.y, z = (double)v.z;
+    float3 o;
+    o.x = (float)chain3(x, y, z, r.g[0], r.g[3], r.g[6]);
+    o.y = (float)chain3(x, y, z, r.g[1], r.g[4], r.g[7]);
+    o.z = (float)chain3(x, y, z, r.g[2], r.g[5], r.g[8]);
+    *reinterpret_cast<float3 *>(dst + i * 3) = o;
+}
+
+// One normal per thread, the scheme of k_pose_vertices: block_row[b] is the row workgroup b works for.
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_pose_normals(const Vec3Row *__restrict__ rows, const int32_t *__restrict__ block_row, const float *__restrict__ normals0,
+               float *__restrict__ normals)
+{
+    const Vec3Row &r = rows[block_row[blockIdx.x]];
+    const int64_t i = (int64_t)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int64_t)threadIdx.x;
+    if (i >= r.count) return;
+    pose_vec3(r, normals0 + (size_t)r.first * 3, normals + (size_t)r.first * 3, i);
+}
+
+// One texel per thread of every (model with G, object-space normal map) pair, the same two tables.
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_pose_texels(const Vec3Row *__restrict__ rows, const int32_t *__restrict__ block_row)
+{
+    const Vec3Row &r = rows[block_row[blockIdx.x]];
+    const int64_t i = (int64_t)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int64_t)threadIdx.x;
+    if (i >= r.count) return;
+    pose_vec3(r, r.src, r.dst, i);
 }
 
 __device__ __forceinline__ double shfl_xor_d(double v, int mask)

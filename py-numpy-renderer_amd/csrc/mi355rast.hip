@@ -109,7 +109,7 @@ int mr_scene_clear(mr_scene *sc)
     sc->verts.clear(); sc->uv.clear(); sc->normals.clear(); sc->faces.clear(); sc->face_flags.clear();
     sc->materials.clear(); sc->model_face_off.clear(); sc->edges.clear(); sc->edge_inc.clear();
     sc->edge_ids.clear(); sc->edge_raw.clear();
-    sc->poses.clear(); sc->pose_dirty = false;
+    sc->poses.clear(); sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
     sc->dirty = true;
     sc->last = nullptr;
     sc->sil.drop();
@@ -151,12 +151,14 @@ void mr_scene_destroy(mr_scene *sc)
     mr_scene_clear(sc);
     for (DevBuf *b : { &sc->d_verts, &sc->d_uv, &sc->d_normals, &sc->d_faces, &sc->d_face_flags, &sc->d_materials, &sc->d_textures, &sc->d_edges,
                        &sc->d_edges32, &sc->d_edge_inc, &sc->d_face_n, &sc->d_face_pos, &sc->d_face_attr, &sc->d_clusters, &sc->d_sky, &sc->d_gamma,
-                       &sc->d_verts0, &sc->d_pose_rows, &sc->d_pose_blocks })
+                       &sc->d_verts0, &sc->d_pose_rows, &sc->d_pose_blocks, &sc->d_normals0, &sc->d_normal_rows, &sc->d_normal_blocks,
+                       &sc->d_texel_rows, &sc->d_texel_blocks, &sc->d_rebaked })
         b->release();
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
     delete sc;
 }
 
@@ -312,6 +314,8 @@ int mr_scene_add_model(mr_scene *sc, const mr_model_desc *m)
     sc->model_face_off.push_back(face_off);
     mr_scene::ModelPose mp;
     mp.vert_off = vert_off; mp.n_verts = m->n_vertices; mp.verts_f32 = m->vertices_are_f32 != 0;
+    mp.normal_off = normal_off; mp.n_normals = m->normals ? m->n_normals : 0;
+    mp.mat_off = mat_off; mp.n_mats = m->n_materials;
     sc->poses.push_back(mp);
     sc->dirty = true;
     sc->last = nullptr;
@@ -328,6 +332,18 @@ int mr_scene_set_model_pose(mr_scene *sc, int32_t model, const double *m16)
         for (int i = 0; i < 16; ++i)
             if (!std::isfinite(m16[i])) return fail(MR_E_INVALID, "a pose matrix must be finite");
     set_model_pose(sc, model, m16);
+    return MR_OK;
+}
+
+int mr_scene_set_model_pose_normals(mr_scene *sc, int32_t model, const double *g9)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    if (!sc->poses[model].posed) return fail(MR_E_INVALID, "a normal matrix needs a model that has a pose");
+    if (g9)
+        for (int i = 0; i < 9; ++i)
+            if (!std::isfinite(g9[i])) return fail(MR_E_INVALID, "a normal matrix must be finite");
+    set_model_pose_normals(sc, model, g9);
     return MR_OK;
 }
 
@@ -708,6 +724,17 @@ int mr_debug_pose_times(mr_scene *sc, float *out_ms)
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
     if (sc->pose_marks != 6) return fail(MR_E_INVALID, "no pose pass over faces yet");
     for (int k = 0; k < MR_N_POSE_TIMES; ++k) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->pose_ev[k], sc->pose_ev[k + 1]));
+    return MR_OK;
+}
+
+int mr_debug_pose_normals_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (sc->pose_n_marks != 3) return fail(MR_E_INVALID, "no pose pass over normals yet");
+    for (int k = 0; k < MR_N_POSE_NORMALS_TIMES; ++k) {
+        out_ms[k] = 0.f;                             // (a kernel that was not launched: not the empty span between two marks)
+        if (sc->pose_n_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->pose_n_ev[k], sc->pose_n_ev[k + 1]));
+    }
     return MR_OK;
 }
 

@@ -8,6 +8,12 @@ minimum / median of --reps runs:
                  there on this one.
   (b) pose       Model.pose assigned on every frame: the pose pass in front of every frame.
   (c) pass       the device time of the pass's five kernels (HIP events, mean over the frames of (b)'s last run).
+  (a') both      new float64 vertices AND new float32 normals assigned on every frame (formed before the clock starts): what
+                 a caller without Model.pose_normals does to have the shading normals follow -- run this tool on the
+                 commit before that feature for the parent's figure.  Like (a) it uploads and commits the scene again.
+  (b') normals   Model.pose assigned on every frame with Model.pose_normals on: the pose pass with its two further
+                 kernels; (b') - (b) is what the normals cost.
+  (c') kernels   the device time of k_pose_normals and k_pose_texels (HIP events, mean over frames of (b')).
   (d) standing   frames with nothing changing: the un-posed scene (float32 records), the scene with a pose left alone
                  and the same model committed as float64 -- the cost of float64 face and edge records, which the
                  definition of a pose accepts.
@@ -61,6 +67,7 @@ def runs(fn, frames):
 
 def measure(api, name):
     has_pose = hasattr(api.Model, "pose")
+    has_normals = hasattr(api.Model, "pose_normals")
     scene = scenes.build(api, name)
     scene.draw_debug_frustum = False
     model = scene.models[0]
@@ -83,6 +90,18 @@ def measure(api, name):
     model.vertices = own
     scene.render()
     emit(f"{name:22s} (a) new vertices on every frame   {a[0]:9.3f} / {a[1]:9.3f} ms per frame")
+    if model.normals is not None:
+        own_normals = model.normals
+        turned = [_fp.matmul_chain(np.asarray(own_normals, dtype=np.float32).astype(np.float64), turn(api, i)[:3, :3]).astype(np.float32)
+                  for i in range(args.commit_frames + 1)]                  # (a rotation is its own normal matrix)
+
+        def by_both(i):
+            model.vertices, model.normals = arrays[i % len(arrays)], turned[i % len(turned)]
+            scene.render()
+        a2 = runs(by_both, args.commit_frames)
+        model.vertices, model.normals = own, own_normals
+        scene.render()
+        emit(f"{name:22s} (a') new vertices and normals     {a2[0]:9.3f} / {a2[1]:9.3f} ms per frame")
     if has_pose:
         def by_pose(i):
             model.pose = turn(api, i)
@@ -96,6 +115,18 @@ def measure(api, name):
                 acc[k] += v / 16
         emit(f"{name:22s} (c) the pass, device us           " + "  ".join(f"k_{k} {v * 1e3:.1f}" for k, v in acc.items())
              + f"  sum {sum(acc.values()) * 1e3:.1f}")
+        if has_normals:
+            model.pose_normals = True
+            b2 = runs(by_pose, args.frames)
+            emit(f"{name:22s} (b') ... with pose_normals        {b2[0]:9.3f} / {b2[1]:9.3f} ms per frame     (b') - (b) = "
+                 f"{b2[0] - b[0]:.3f} / {b2[1] - b[1]:.3f}")
+            acc = dict.fromkeys(backend.POSE_NORMALS_TIME_NAMES, 0.0)
+            for i in range(1, 17):
+                by_pose(i)
+                for k, v in backend.pose_normals_times().items():
+                    acc[k] += v / 16
+            emit(f"{name:22s} (c') its two kernels, device us   " + "  ".join(f"k_{k} {v * 1e3:.1f}" for k, v in acc.items()))
+            model.pose_normals = False
         model.pose = turn(api, 1)
         scene.render()
         standing["posed"] = runs(lambda i: scene.render(), args.frames)
