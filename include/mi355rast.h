@@ -426,6 +426,51 @@ int mr_debug_pose_times(mr_scene *scene, float *out_ms);
 #define MR_N_POSE_NORMALS_TIMES 2
 int mr_debug_pose_normals_times(mr_scene *scene, float *out_ms);
 
+/* A model's skin (linear-blend skinning): joints and weights are (n_vertices, 4), row-major -- vertex i follows the bones
+ * joints[i][0..3] by the weights weights[i][0..3], used as given (not normalised; a slot may repeat a joint or weigh 0).
+ * Every joint lies in [0, n_bones).  normal_owner is (n_normals) -- for every vertex normal of the model the index of the
+ * vertex whose blend matrix it takes, -1 for a normal that stays -- or NULL when the normals do not follow the skin (it
+ * is ignored for a model without normals).  joints == NULL removes the skin and its bones.  Everything is copied during
+ * the call and nothing is launched; a skin alone changes no frame.  Setting a skin puts the model in the rest position
+ * (no bones).  MR_E_INVALID for a model index out of range, missing weights, n_bones <= 0, a joint or an owner out of
+ * range or a weight that is not finite. */
+int mr_scene_set_model_skin(mr_scene *scene, int32_t model, const int32_t *joints, const double *weights, int32_t n_bones,
+                            const int32_t *normal_owner);
+
+/* The bones of a model that has a skin: bones16 is (n_bones, 4, 4), row-major, row-vector convention like a pose; NULL is
+ * the rest position (the model as it was added).  With bones B the model renders as if its vertices were the float64 array
+ *   S_i[r][c] = rn(w[i][0] * B[j[i][0]][r][c]) followed by fma steps over slots 1, 2, 3        (the blend matrix of vertex i)
+ *   V'[i]     = vertices[i] @ S_i, the chain of mr_scene_set_model_pose
+ * and, where the skin has a normal_owner table, its vertex normals float32(float64(normal) @ S_owner[:3][:3]) (the same
+ * chain over three terms; not re-normalised, not the inverse transpose: exact in direction for bones that rotate,
+ * translate and scale uniformly).  A pose set as well follows the skin: V' @ m16, and normals @ G before the one rounding
+ * to float32.  Object-space normal maps do not follow a skin.  V' is float64: the model behaves as one with
+ * vertices_are_f32 == 0, as a posed one does.  The call copies the matrices and launches nothing; the next frame's pose
+ * pass does the work (k_skin_vertices, k_skin_normals, then the kernels of every pose pass).
+ * MR_E_INVALID for a model index out of range, a model without a skin, n_bones other than the skin's, or an entry that
+ * is not finite. */
+int mr_scene_set_model_bones(mr_scene *scene, int32_t model, const double *bones16, int32_t n_bones);
+
+/* Host arithmetic, no device needed: V' of mr_scene_set_model_bones for n vertices -- verts and out are (n, 4) float64,
+ * joints (n, 4) int32, weights (n, 4) float64, bones (any, 4, 4) float64 -- in the chains the device uses, bit for bit. */
+void mr_host_skin_chain(const double *verts, const int32_t *joints, const double *weights, const double *bones, int32_t n, double *out);
+
+/* The same for n 3-vectors (normals, already widened to float64): out[i] = vectors[i] @ S[:3][:3] of vertex owner[i],
+ * or vectors[i] itself where owner[i] < 0.  joints and weights are the model's (n_vertices, 4) tables.  Not rounded to
+ * float32: out is (n, 3) float64. */
+void mr_host_skin_chain3(const double *vectors, const int32_t *owner, const int32_t *joints, const double *weights, const double *bones,
+                         int32_t n, double *out);
+
+/* Diagnostics of the skin: out[0] = models that have bones now, out[1] = bone matrices the last pose pass uploaded,
+ * out[2] = vertices and out[3] = normals the last pose pass skinned.  Does not wait for the device. */
+int mr_debug_skin(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds of the two skin kernels of the last pose pass that had a skin to apply:
+ * [0] k_skin_vertices  [1] k_skin_normals (0 for one that pass did not launch).  k_skin_vertices runs inside span [0]
+ * of mr_debug_pose_times.  MR_E_INVALID before the first such pass. */
+#define MR_N_SKIN_TIMES 2
+int mr_debug_skin_times(mr_scene *scene, float *out_ms);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_skin, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -145,6 +145,12 @@ _PROTOTYPES = {
     "mr_debug_pose": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_pose_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_read_clusters": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "mr_scene_set_model_skin": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_scene_set_model_bones": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "mr_host_skin_chain": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_host_skin_chain3": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_debug_skin": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_skin_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -288,6 +294,7 @@ class DeviceRenderer:
             raise RuntimeError("mr_scene_create failed: " + self.lib.mr_last_error().decode())
         self._signature = None
         self._pose_keys = []                 # per model: (bytes of the pose, bytes of the normal matrix or None) the library holds, or None
+        self._skin_keys = {}                 # model index -> [serial of the skin, its bone count, bytes of the bones or None] the library holds
         self._sky_key = None
         self._last_stats = {}
         self._frame = None
@@ -320,18 +327,25 @@ class DeviceRenderer:
     def sync_scene(self, scene):
         """The library's scene in step with the Python one: everything again when a model, texture or material changed
         (``_scene_signature``), and the models' poses, which are no part of that signature, beside it."""
+        for model in scene.models:
+            active_skin(model)                   # (a skin that no longer fits its vertices: ValueError before any device work)
         sig = self._scene_signature(scene)
         if sig != self._signature:
             self._upload_scene(scene)
             self._signature = sig
             self._pose_keys = [None] * len(scene.models)        # (mr_scene_clear dropped the poses)
+            self._skin_keys = {}                                 # (... and the skins)
         self.sync_poses(scene)
 
     def sync_poses(self, scene):
         """``mr_scene_set_model_pose`` for every model whose ``pose`` is not the one the library holds, and
-        ``mr_scene_set_model_pose_normals`` after it where the normal matrix (``Model.pose_normals``) is not."""
+        ``mr_scene_set_model_pose_normals`` after it where the normal matrix (``Model.pose_normals``) is not; then the
+        same for the skins: a model is keyed by (pose bytes, G bytes) and (serial of its skin, bones bytes), and each of
+        ``mr_scene_set_model_skin`` / ``mr_scene_set_model_bones`` is called when its part changed.  A skin goes to the
+        library when its model first has bones: a scene without bones makes no call."""
         keys = self._pose_keys
         for index, model in enumerate(scene.models):
+            self._sync_skin(index, model)
             pose = getattr(model, "pose", None)
             g = None if pose is None else pose_normal_matrix(model)
             key = None if pose is None else (pose.tobytes(), None if g is None else g.tobytes())
@@ -344,6 +358,29 @@ class DeviceRenderer:
                 _check(self.lib.mr_scene_set_model_pose_normals(self.handle, index, None if g is None else g.ctypes.data),
                        "mr_scene_set_model_pose_normals")
             keys[index] = key
+
+    def _sync_skin(self, index, model):
+        keys = self.__dict__.setdefault("_skin_keys", {})
+        held = keys.get(index)                   # [serial of the skin, its bone count, bytes of the bones or None]
+        skin = active_skin(model)
+        if skin is None:
+            if held is not None and held[2] is not None:       # bones = None, or the skin is gone: the rest position
+                _check(self.lib.mr_scene_set_model_bones(self.handle, index, None, 0), "mr_scene_set_model_bones")
+                held[2] = None
+            return
+        if held is None:
+            held = keys[index] = [None, 0, None]
+        bones = model.bones
+        if held[:2] != [model._skin_serial, len(bones)]:       # (another bone count: the library takes the skin again with it)
+            owners = normal_owners(model) if skin.normals and model.normals is not None else None
+            _check(self.lib.mr_scene_set_model_skin(self.handle, index, skin.joints.ctypes.data, skin.weights.ctypes.data,
+                                                    len(bones), None if owners is None else owners.ctypes.data),
+                   "mr_scene_set_model_skin")
+            held[:] = [model._skin_serial, len(bones), None]
+        key = bones.tobytes()
+        if held[2] != key:
+            _check(self.lib.mr_scene_set_model_bones(self.handle, index, bones.ctypes.data, len(bones)), "mr_scene_set_model_bones")
+            held[2] = key
 
     def _upload_scene(self, scene):
         _check(self.lib.mr_scene_clear(self.handle), "mr_scene_clear")
@@ -692,6 +729,22 @@ class DeviceRenderer:
         out = (C.c_int32 * 4)()
         _check(self.lib.mr_debug_pose(self.handle, out), "mr_debug_pose")
         return tuple(int(x) for x in out)
+
+    def skin_counters(self):
+        """``mr_debug_skin``: (models that have bones, bone matrices the last pose pass uploaded, vertices and normals it
+        skinned)."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.mr_debug_skin(self.handle, out), "mr_debug_skin")
+        return tuple(int(x) for x in out)
+
+    SKIN_TIME_NAMES = ("skin_vertices", "skin_normals")
+
+    def skin_times(self):
+        """Device milliseconds of the two skin kernels of the last pose pass that had a skin to apply
+        (``mr_debug_skin_times``)."""
+        buf = (C.c_float * 2)()
+        _check(self.lib.mr_debug_skin_times(self.handle, buf), "mr_debug_skin_times")
+        return dict(zip(self.SKIN_TIME_NAMES, (float(v) for v in buf)))
 
     POSE_TIME_NAMES = ("pose_vertices", "face_normals", "edge_normals", "face_static", "clusters")
 

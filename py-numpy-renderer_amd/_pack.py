@@ -165,14 +165,178 @@ def check_pose(value):
     return m
 
 
+def _numbers(value, what, dtype=np.float64):
+    """*value* as an array of numbers, with the ``TypeError`` / ``ValueError`` split of ``check_pose``."""
+    if isinstance(value, (str, bytes)):
+        raise TypeError(f"{what} must be an array of numbers, got {type(value).__name__}")
+    try:
+        return np.array(value, dtype=dtype)
+    except TypeError as exc:
+        raise TypeError(f"{what} must be an array of numbers: {exc}") from None
+    except ValueError as exc:
+        raise ValueError(f"{what} must be an array of numbers: {exc}") from None
+
+
+def check_skin(joints, weights, normals=False):
+    """The parts of a ``Skin``: *joints* ``(n, 4)`` integral and not negative, returned as a read-only ``int32`` copy;
+    *weights* the same shape and finite, as a read-only ``float64`` copy; *normals* as ``check_pose_normals`` takes it.
+    ``TypeError`` for what is no array of numbers, ``ValueError`` for a wrong shape or a wrong value."""
+    j = _numbers(joints, "skin joints")
+    w = _numbers(weights, "skin weights")
+    if j.ndim != 2 or j.shape[1] != 4:
+        raise ValueError(f"skin joints must be (n, 4), got shape {j.shape}")
+    if w.shape != j.shape:
+        raise ValueError(f"skin weights must have the joints' shape {j.shape}, got {w.shape}")
+    if not np.isfinite(w).all():
+        raise ValueError("skin weights must be finite")
+    if not np.isfinite(j).all() or (j != np.floor(j)).any():
+        raise ValueError("skin joints must be integers")
+    if (j < 0).any():
+        raise ValueError("skin joints must not be negative")
+    if j.size and j.max() > np.iinfo(np.int32).max:
+        raise ValueError("skin joints must fit 32 bits")
+    if not isinstance(normals, (bool, np.bool_)) and not (isinstance(normals, (int, np.integer)) and int(normals) in (0, 1)):
+        raise TypeError(f"Skin(normals=...) must be True or False, got {normals!r}")
+    j, w = np.ascontiguousarray(j.astype(np.int32)), np.ascontiguousarray(w)
+    j.setflags(write=False)
+    w.setflags(write=False)
+    return j, w, bool(normals)
+
+
+def check_bones(value):
+    """``Model.bones``: ``None``, or a finite ``(b, 4, 4)`` array with b >= 1, returned as a read-only float64 copy."""
+    if value is None:
+        return None
+    b = _numbers(value, "bones")
+    if b.ndim != 3 or b.shape[1:] != (4, 4) or b.shape[0] < 1:
+        raise ValueError(f"bones must be (b, 4, 4) with b >= 1, got shape {b.shape}")
+    if not np.isfinite(b).all():
+        raise ValueError("bones must be finite")
+    b = np.ascontiguousarray(b)
+    b.setflags(write=False)
+    return b
+
+
+def check_skin_pair(skin, bones):
+    """What only the pair can break: every joint names one of the bones."""
+    if skin is not None and bones is not None and skin.joints.size and int(skin.joints.max()) >= len(bones):
+        raise ValueError(f"skin joints reach bone {int(skin.joints.max())}, bones has {len(bones)}")
+
+
+def active_skin(model):
+    """The model's ``Skin`` when it has ``bones`` too and so moves, else ``None``; ``ValueError`` for a skin whose row
+    count is not the vertices' (``vertices`` was replaced after the skin was set)."""
+    skin, bones = getattr(model, "skin", None), getattr(model, "bones", None)
+    if skin is None or bones is None:
+        return None
+    if len(skin.joints) != len(model.vertices):
+        raise ValueError(f"the model's skin has {len(skin.joints)} rows, its vertices {len(model.vertices)}")
+    return skin
+
+
+def normal_owners(model):
+    """(len(normals),) int32: for every vertex normal the (non-negative) vertex index at the first (face, corner) of
+    ``_faces`` in row-major order whose normal column names it; -1 for a normal no corner references."""
+    faces = np.asarray(model._faces)
+    n_normals, n_verts = len(model.normals), len(model.vertices)
+    vertex = _wrap(faces[..., 0].astype(np.int64), n_verts, "vertex").ravel()
+    normal = _wrap(faces[..., 2].astype(np.int64), n_normals, "normal").ravel()
+    owners = np.full(n_normals, -1, dtype=np.int32)
+    which, first = np.unique(normal, return_index=True)
+    owners[which] = vertex[first]
+    return owners
+
+
+def blend_matrices(skin, bones, rows):
+    """S of the vertices *rows* (pure Python): ``S[i][r][c] = dot_chain(W[i], (B[J[i][k]][r][c] for k in 0..3))``."""
+    from ._fp import dot_chain
+    out = np.empty((len(rows), 4, 4), dtype=np.float64)
+    for n, i in enumerate(rows):
+        picked = bones[skin.joints[i]]
+        for r in range(4):
+            for c in range(4):
+                out[n, r, c] = dot_chain(skin.weights[i], picked[:, r, c])
+    return out
+
+
+_native_skin = None          # (mr_host_skin_chain, mr_host_skin_chain3) of the HIP library, or False
+
+
+def _fast_skin():
+    """The library's host helpers, if the library is built (it loads without a GPU); else the loops below."""
+    global _native_skin
+    if _native_skin is None:
+        try:
+            from ._native import load_library
+            lib = load_library()
+            _native_skin = (lib.mr_host_skin_chain, lib.mr_host_skin_chain3)
+        except Exception:           # not built / not loadable here: the pure-Python chains give the same bits
+            _native_skin = False
+    return _native_skin
+
+
+def skinned_vertices(model, native=None):
+    """The float64 vertices of a model that has ``skin`` and ``bones``: ``V'[i] = matmul_chain(float64(vertices[i]), S_i)``
+    with S_i the vertex's blend matrix (``blend_matrices``); ``None`` for a model without the pair.  *native*: ``False``
+    forces the pure-Python chains, the yardstick of the library's ``mr_host_skin_chain``."""
+    skin = active_skin(model)
+    if skin is None:
+        return None
+    verts = np.ascontiguousarray(np.asarray(model.vertices).astype(np.float64))
+    bones = model.bones
+    check_skin_pair(skin, bones)
+    out = np.empty_like(verts)
+    fast = _fast_skin() if native is None or native else False
+    if fast:
+        fast[0](verts.ctypes.data, skin.joints.ctypes.data, skin.weights.ctypes.data, bones.ctypes.data, len(verts), out.ctypes.data)
+        return out
+    from ._fp import dot_chain
+    blend = blend_matrices(skin, bones, range(len(verts)))
+    for i in range(len(verts)):
+        for c in range(4):
+            out[i, c] = dot_chain(verts[i], blend[i, :, c])
+    return out
+
+
+def skinned_normals(model, native=None):
+    """The float64 normals ``n'`` of a model whose normals follow its skin (``Skin(..., normals=True)``, ``bones`` set,
+    ``normals`` not ``None``): ``n'[q] = matmul_chain(float64(float32(normals[q])), S_owner[:3, :3])`` with the owner of
+    ``normal_owners``, the widened normal itself where nothing owns it.  Not rounded, not re-normalised.  ``None`` for
+    every other model."""
+    skin = active_skin(model)
+    if skin is None or not skin.normals or model.normals is None:
+        return None
+    vectors = np.ascontiguousarray(np.ascontiguousarray(model.normals, dtype=np.float32)[:, :3].astype(np.float64))
+    owners = normal_owners(model)
+    bones = model.bones
+    check_skin_pair(skin, bones)
+    out = vectors.copy()
+    fast = _fast_skin() if native is None or native else False
+    if fast:
+        fast[1](vectors.ctypes.data, owners.ctypes.data, skin.joints.ctypes.data, skin.weights.ctypes.data, bones.ctypes.data,
+                len(vectors), out.ctypes.data)
+        return out
+    from ._fp import dot_chain
+    owned = np.flatnonzero(owners >= 0)
+    blend = blend_matrices(skin, bones, owners[owned])
+    for n, q in enumerate(owned):
+        for c in range(3):
+            out[q, c] = dot_chain(vectors[q], blend[n, :3, c])
+    return out
+
+
 def posed_vertices(model):
-    """The vertices a model renders with: ``model.vertices``, or with a pose the float64 array
-    ``matmul_chain(float64(vertices), pose)`` (``Model.pose``)."""
+    """The vertices a model renders with: ``model.vertices``; with ``skin`` and ``bones`` the float64 array
+    ``skinned_vertices(model)``; with a pose ``matmul_chain`` of either (widened to float64) and the pose -- skin first,
+    then pose (``Model.skin``, ``Model.pose``)."""
     pose = getattr(model, "pose", None)
+    verts = skinned_vertices(model)
+    if verts is None:
+        verts = np.asarray(model.vertices)
     if pose is None:
-        return np.asarray(model.vertices)
+        return verts
     from ._fp import matmul_chain
-    return matmul_chain(np.asarray(model.vertices).astype(np.float64), pose)
+    return matmul_chain(verts.astype(np.float64), pose)
 
 
 def check_pose_normals(value):
@@ -222,9 +386,17 @@ def _chain_f32(vectors, g):
 
 def posed_normals(model):
     """The vertex normals a model renders with: ``model.normals``, or with ``pose_normals`` and a pose the float32 array
-    ``float32(matmul_chain(float64(float32(normals)), G))``, ``G = normal_matrix(pose)``."""
+    ``float32(matmul_chain(float64(float32(normals)), G))``, ``G = normal_matrix(pose)``.  Normals that follow a skin
+    (``skinned_normals``) take the place of the widened normals: ``float32(n')``, or ``float32(matmul_chain(n', G))``."""
     g = pose_normal_matrix(model)
-    if g is None or model.normals is None:
+    if model.normals is None:
+        return model.normals
+    followed = skinned_normals(model)
+    if followed is not None:
+        from ._fp import matmul_chain
+        shape = np.asarray(model.normals).shape
+        return (followed if g is None else matmul_chain(followed, g)).astype(np.float32).reshape(shape)
+    if g is None:
         return model.normals
     return _chain_f32(model.normals, g)
 
@@ -310,10 +482,11 @@ def _posed_map_id(tex, g, model, textures, seen):
 
 
 def pack_model(model, textures, seen, posed=False) -> PackedModel:
-    """*posed*: pack the arrays the model renders with -- ``posed_vertices`` and, with ``pose_normals``, ``posed_normals``
-    and re-baked object-space normal maps -- instead of ``model.vertices`` / ``normals`` / the maps as registered: what
-    the oracle needs; the device gets the arrays as they are and the matrices beside them (``mr_scene_set_model_pose``,
-    ``mr_scene_set_model_pose_normals``)."""
+    """*posed*: pack the arrays the model renders with -- ``posed_vertices`` (skin, then pose) and, with ``pose_normals`` or
+    a skin the normals follow, ``posed_normals``, and with ``pose_normals`` re-baked object-space normal maps -- instead of
+    ``model.vertices`` / ``normals`` / the maps as registered: what the oracle needs; the device gets the arrays as they
+    are and the matrices and tables beside them (``mr_scene_set_model_pose``, ``mr_scene_set_model_pose_normals``,
+    ``mr_scene_set_model_skin``, ``mr_scene_set_model_bones``)."""
     verts = posed_vertices(model) if posed else np.asarray(model.vertices)
     nmat = pose_normal_matrix(model) if posed else None
     if verts.ndim != 2 or verts.shape[1] != 4:
@@ -324,7 +497,7 @@ def pack_model(model, textures, seen, posed=False) -> PackedModel:
                          f"(got {faces.shape})")
     uv = None if model.uv is None else np.ascontiguousarray(model.uv, dtype=np.float32)
     normals = None if model.normals is None else np.ascontiguousarray(model.normals, dtype=np.float32)
-    if nmat is not None and normals is not None:
+    if posed and normals is not None and (nmat is not None or (active_skin(model) is not None and model.skin.normals)):
         normals = np.ascontiguousarray(posed_normals(model))
     if uv is not None and (uv.ndim != 2 or uv.shape[1] < 2):
         raise ValueError(f"Model.uv must be (T, 3), got {uv.shape}")

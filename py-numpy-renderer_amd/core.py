@@ -6,6 +6,7 @@ ingest rules.  What differs is where the work happens: ``Scene.render`` packs th
 flat arrays (``_pack.py``) and hands it to the HIP library through the C ABI declared in
 ``include/mi355rast.h``; nothing is rasterised or shaded on the host.
 """
+import itertools
 import os
 from functools import cached_property
 from typing import Iterable, List
@@ -61,6 +62,32 @@ class TextureMaps:
             return np.asarray(img.convert("RGB")) / 255
 
 
+_skin_serial = itertools.count(1)      # every assignment of Model.skin gets its own number (the renderer's key)
+
+
+class Skin:
+    """What ``Model.skin`` holds: the static part of linear-blend skinning.  ``joints`` ``(len(vertices), 4)`` integers
+    (kept as read-only ``int32``) and ``weights`` of the same shape (read-only ``float64``): vertex i follows the bones
+    ``joints[i]`` by ``weights[i]``.  ``normals=True`` makes the vertex normals follow as well.  A ``Skin`` is never
+    modified: assign a new one to change it.  ``TypeError`` for what is no array of numbers, ``ValueError`` for a wrong
+    shape, weights that are not finite, joints that are not integral or negative."""
+
+    __slots__ = ("joints", "weights", "normals")
+
+    def __init__(self, joints, weights, normals=False):
+        from ._pack import check_skin
+        j, w, n = check_skin(joints, weights, normals)
+        object.__setattr__(self, "joints", j)
+        object.__setattr__(self, "weights", w)
+        object.__setattr__(self, "normals", n)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Skin is read-only: assign a new Skin to Model.skin")
+
+    def __repr__(self):
+        return f"Skin({len(self.joints)} vertices, normals={self.normals})"
+
+
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
     (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
@@ -85,7 +112,29 @@ class Model:
     and ``map_Ks`` are never touched, and a texture array that another model holds too stays what it was for that model.
     A pose that cannot be inverted raises ``ValueError`` at whichever of the two assignments completes the pair, and
     the attribute keeps its value; without ``pose_normals`` such a pose stays legal.  With ``pose_normals = False`` or
-    ``pose = None`` everything is exactly as without this attribute."""
+    ``pose = None`` everything is exactly as without this attribute.
+
+    ``skin`` and ``bones`` (additions; both ``None`` by default) deform the model by linear-blend skinning, again
+    without a re-upload.  ``skin`` is a ``Skin(joints, weights, normals=False)`` -- the static part, handed to the device
+    once -- and ``bones`` a ``(b, 4, 4)`` array in the row-vector convention of ``pose`` (kept as a read-only float64
+    copy), the part that changes per frame.  With both set the model renders as the reference renders it with
+    ``vertices`` replaced by the float64 array ``V'``: for vertex i with ``J = joints[i]``, ``W = weights[i]``,
+    ``S[r][c] = _fp.dot_chain(W, (B[J[0]][r][c], B[J[1]][r][c], B[J[2]][r][c], B[J[3]][r][c]))`` -- ``rn(W0 * x0)``, then
+    ``fma`` steps in ascending k -- and ``V'[i] = _fp.matmul_chain(float64(vertices[i]), S)``.  Weights are used as given:
+    not normalised, and they need not sum to 1.  With ``pose = M`` as well the vertices are ``matmul_chain(V', M)``: skin
+    first, then pose.  ``V'`` is float64, so a skinned float32 model behaves as a float64 one, as a posed one does.
+    ``vertices`` is never modified; ``bones = None`` gives the un-skinned model back, and a scene whose models all have
+    ``bones = None`` is exactly the scene without these attributes, whatever ``skin`` holds.
+    With ``Skin(..., normals=True)`` normal q follows the blend matrix of its owner, the vertex at the first (face,
+    corner) of ``_faces`` in row-major order whose normal column is q (a normal no corner references stays):
+    ``n' = matmul_chain(float64(float32(normals[q])), S[:3, :3])``, and the model renders with ``float32(n')`` -- with
+    ``pose`` and ``pose_normals`` on top with ``float32(matmul_chain(n', G))``.  ``S[:3, :3]`` itself, not its inverse
+    transpose: exact in direction for bones that rotate, translate and scale uniformly; a shearing bone tilts normals.
+    Tangent-space maps follow by themselves; object-space normal maps do not follow the skin (they keep what
+    ``pose_normals`` does to them).  Assignments are checked at once: ``bones`` without a ``skin``, and a joint that
+    reaches past the last bone -- at whichever of the two assignments completes the pair -- raise ``ValueError`` and the
+    attribute keeps its value; ``skin = None`` drops ``bones`` as well.  A skin whose row count no longer equals
+    ``len(vertices)`` raises ``ValueError`` at ``render()``."""
 
     def __init__(self, vertices, uv, normals, faces, shadowing=False, materials=None,
                  material_group=None, clip=True, depth_test=True):
@@ -105,6 +154,9 @@ class Model:
         self._pose = None
         self._pose_normals = False
         self._normal_matrix = None          # normal_matrix(pose) while pose_normals is on and a pose is set
+        self._skin = None
+        self._bones = None
+        self._skin_serial = 0
 
     # -- ingest ---------------------------------------------------------------------------
     @classmethod
@@ -203,6 +255,39 @@ class Model:
         on = check_pose_normals(value)
         g = normal_matrix(self.pose) if on and self.pose is not None else None
         self._pose_normals, self._normal_matrix = on, g
+
+    @property
+    def skin(self):
+        """``None`` or the model's ``Skin`` (joints, weights, whether the normals follow); see the class docstring."""
+        return getattr(self, "_skin", None)
+
+    @skin.setter
+    def skin(self, value):
+        from ._pack import check_skin_pair
+        if value is None:
+            self._skin, self._bones = None, None          # (no skin, no bones)
+            return
+        if not isinstance(value, Skin):
+            raise TypeError(f"skin must be None or a Skin, got {type(value).__name__}")
+        if len(value.joints) != len(self.vertices):
+            raise ValueError(f"skin must have one row per vertex ({len(self.vertices)}), got {len(value.joints)}")
+        check_skin_pair(value, self.bones)                # (refused here, and the last skin stays)
+        self._skin, self._skin_serial = value, next(_skin_serial)
+
+    @property
+    def bones(self):
+        """``None`` (the rest position) or the ``(b, 4, 4)`` float64 bone matrices (read-only: assign a new array to
+        move the model); see the class docstring."""
+        return getattr(self, "_bones", None)
+
+    @bones.setter
+    def bones(self, value):
+        from ._pack import check_bones, check_skin_pair
+        bones = check_bones(value)
+        if bones is not None and self.skin is None:
+            raise ValueError("bones need a skin: assign Model.skin first")
+        check_skin_pair(self.skin, bones)
+        self._bones = bones
 
     def __matmul__(self, other):
         self.vertices = self.vertices @ other

@@ -7,34 +7,44 @@
 // tile histories and list capacities stay; the silhouette cache goes, it belongs to the geometry.
 // A model that also has a normal matrix (mr_scene_set_model_pose_normals) gets its vertex normals and its object-space
 // normal maps transformed in the same pass (apply_pose_normals), in front of the kernels above.
+// A model that has a skin and bones (mr_scene_set_model_skin, mr_scene_set_model_bones) is to the pass what a posed one
+// is: its vertices come from k_skin_vertices instead of k_pose_vertices (the pose, if any, applied after the skin), its
+// normals, where they follow the skin, from k_skin_normals (apply_skin_normals); everything after that is the same code.
 // The pass is synchronous: it waits for the device before it starts (frames in flight on other streams read the static
 // records: the rule of commit() and mr_scene_add_model) and for its own kernels before it returns.
 #pragma once
 
 namespace {
 
-// mr_scene_set_model_pose behind its argument checks: the matrix is kept, and when the model's float32 bit changes the
-// scene is left for commit() to rebuild
+// A model that moves (a pose, or bones on its skin) has float64 vertices -- the products of float64 matrices: when
+// "moves" changes for a model passed as float32, its faces lose FF_VERTS_F32 or get it back, and the scene is left
+// for commit() to rebuild
+void moved_changed(mr_scene *sc, int32_t model, bool was)
+{
+    const mr_scene::ModelPose &mp = sc->poses[model];
+    const bool now = mp.moved();
+    if (was == now || !mp.verts_f32) return;
+    const size_t f0 = (size_t)sc->model_face_off[model];
+    const size_t f1 = (size_t)model + 1 < sc->model_face_off.size() ? (size_t)sc->model_face_off[model + 1] : sc->face_flags.size();
+    for (size_t f = f0; f < f1; ++f)
+        sc->face_flags[f] = (uint8_t)(now ? sc->face_flags[f] & ~mr::FF_VERTS_F32 : sc->face_flags[f] | mr::FF_VERTS_F32);
+    sc->dirty = true;
+}
+
+// mr_scene_set_model_pose behind its argument checks: the matrix is kept
 void set_model_pose(mr_scene *sc, int32_t model, const double *m16)
 {
     mr_scene::ModelPose &mp = sc->poses[model];
     if (!m16 && !mp.posed) return;
     if (m16 && mp.posed && !std::memcmp(mp.m, m16, sizeof mp.m)) return;
-    const bool was = mp.posed;
+    const bool was = mp.moved();
     mp.posed = m16 != nullptr;
     if (m16) std::memcpy(mp.m, m16, sizeof mp.m);
     if (!mp.posed && mp.has_g) {                     // the normal matrix goes with the pose
         mp.has_g = false;
         sc->pose_g_dirty = true;
     }
-    if (was != mp.posed && mp.verts_f32) {
-        // posed vertices are float64 (the product of float64 matrices): the model's faces lose FF_VERTS_F32, or get it back
-        const size_t f0 = (size_t)sc->model_face_off[model];
-        const size_t f1 = (size_t)model + 1 < sc->model_face_off.size() ? (size_t)sc->model_face_off[model + 1] : sc->face_flags.size();
-        for (size_t f = f0; f < f1; ++f)
-            sc->face_flags[f] = (uint8_t)(mp.posed ? sc->face_flags[f] & ~mr::FF_VERTS_F32 : sc->face_flags[f] | mr::FF_VERTS_F32);
-        sc->dirty = true;
-    }
+    moved_changed(sc, model, was);
     sc->pose_dirty = sc->pose_geom_dirty = true;
 }
 
@@ -47,6 +57,43 @@ void set_model_pose_normals(mr_scene *sc, int32_t model, const double *g9)
     mp.has_g = g9 != nullptr;
     if (g9) std::memcpy(mp.g, g9, sizeof mp.g);
     sc->pose_dirty = sc->pose_g_dirty = true;
+}
+
+// mr_scene_set_model_skin behind its argument checks: the tables are copied; a skin alone moves nothing
+void set_model_skin(mr_scene *sc, int32_t model, const int32_t *joints, const double *weights, int32_t n_bones, const int32_t *owners)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    if (!joints && mp.n_bones == 0) return;
+    const bool was = mp.moved(), was_n = mp.skin_normals();
+    const size_t n = (size_t)mp.n_verts * 4;
+    mp.has_bones = false;                            // a new skin starts in the rest position; no skin, no bones
+    mp.bones.clear();
+    mp.joints.assign(joints ? joints : nullptr, joints ? joints + n : nullptr);
+    mp.weights.assign(joints ? weights : nullptr, joints ? weights + n : nullptr);
+    mp.owners.assign(joints && owners ? owners : nullptr, joints && owners ? owners + mp.n_normals : nullptr);
+    mp.n_bones = joints ? n_bones : 0;
+    sc->skin_tables_dirty = true;
+    if (was) sc->pose_dirty = sc->pose_geom_dirty = true;
+    if (was_n) sc->pose_dirty = sc->pose_g_dirty = true;
+    moved_changed(sc, model, was);
+}
+
+// mr_scene_set_model_bones behind its argument checks
+void set_model_bones(mr_scene *sc, int32_t model, const double *bones16)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    const size_t n = (size_t)mp.n_bones * 16;
+    if (!bones16 && !mp.has_bones) return;
+    if (bones16 && mp.has_bones && !std::memcmp(mp.bones.data(), bones16, n * sizeof(double))) return;
+    const bool was = mp.moved(), was_n = mp.skin_normals();
+    mp.has_bones = bones16 != nullptr;
+    mp.bones.assign(bones16 ? bones16 : nullptr, bones16 ? bones16 + n : nullptr);
+    moved_changed(sc, model, was);
+    sc->pose_dirty = sc->pose_geom_dirty = true;
+    // normals that follow the skin: new bones bring k_skin_normals alone, a model that starts or stops following
+    // the whole normals' part (its normals come from another kernel, or from the pristine copy, then)
+    if (was_n != mp.skin_normals()) sc->pose_g_dirty = true;
+    else if (was_n) sc->skin_n_dirty = true;
 }
 
 // a material's object-space normal map, if it has one
@@ -76,7 +123,7 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
         mr::Vec3Row r;
         std::memset(&r, 0, sizeof r);
         std::memcpy(r.g, mp.g, sizeof r.g);
-        if (mp.n_normals > 0) {
+        if (mp.n_normals > 0 && !mp.skin_normals()) {    // (normals that follow a skin: k_skin_normals applies G as well)
             r.first = mp.normal_off; r.count = mp.n_normals; r.block0 = (int32_t)nblocks.size();
             nblocks.insert(nblocks.end(), (size_t)blocks_for(mp.n_normals, mr::POSE_BLOCK), (int32_t)nrows.size());
             nrows.push_back(r);
@@ -122,7 +169,8 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
             mp.normals_on_device = mp.n_normals > 0;
             continue;
         }
-        if (mp.normals_on_device) {                      // a model whose matrix is gone gets its own normals back
+        if (mp.skin_normals()) mp.normals_on_device = true;    // (apply_skin_normals writes them)
+        else if (mp.normals_on_device) {                 // a model whose matrix is gone gets its own normals back
             const size_t off = (size_t)mp.normal_off * 3 * sizeof(float), bytes = (size_t)mp.n_normals * 3 * sizeof(float);
             HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_normals.p) + off, static_cast<const char *>(sc->d_normals0.p) + off, bytes,
                                    hipMemcpyDeviceToDevice, g_stream));
@@ -160,6 +208,87 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
     return MR_OK;
 }
 
+// The skin tables on the device: joints, weights and normal owners of every model that has a skin, one after the
+// other.  Rebuilt when a skin was set or removed, not when bones change.
+int upload_skin_tables(mr_scene *sc)
+{
+    if (!sc->skin_tables_dirty) return MR_OK;
+    std::vector<int32_t> joints, owners;
+    std::vector<double> weights;
+    for (mr_scene::ModelPose &mp : sc->poses) {
+        if (mp.n_bones == 0) continue;
+        mp.table_off = (int32_t)(joints.size() / 4); mp.owner_off = (int32_t)owners.size();
+        joints.insert(joints.end(), mp.joints.begin(), mp.joints.end());
+        weights.insert(weights.end(), mp.weights.begin(), mp.weights.end());
+        owners.insert(owners.end(), mp.owners.begin(), mp.owners.end());
+    }
+    if (int rc = upload(sc->d_skin_joints, joints, g_stream)) return rc;
+    if (int rc = upload(sc->d_skin_weights, weights, g_stream)) return rc;
+    if (int rc = upload(sc->d_skin_owners, owners, g_stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(g_stream));         // (the vectors go out of scope)
+    sc->skin_tables_dirty = false;
+    return MR_OK;
+}
+
+// The bone table of a pass: the bones of every model that has some, back to back, in one asynchronous upload;
+// first[k] is where model k's start.  sc->bone_table lives until the pass has waited for the stream.
+int upload_bones(mr_scene *sc, std::vector<int32_t> &first)
+{
+    sc->bone_table.clear();
+    first.assign(sc->poses.size(), 0);
+    for (size_t k = 0; k < sc->poses.size(); ++k) {
+        const mr_scene::ModelPose &mp = sc->poses[k];
+        if (!mp.has_bones) continue;
+        first[k] = (int32_t)(sc->bone_table.size() / 16);
+        sc->bone_table.insert(sc->bone_table.end(), mp.bones.begin(), mp.bones.end());
+    }
+    sc->skin_bones = (int32_t)(sc->bone_table.size() / 16);
+    return upload(sc->d_bones, sc->bone_table, g_stream);
+}
+
+struct SkinTables {                                      // (the caller keeps them until it has waited for the stream)
+    std::vector<mr::SkinRow> rows;
+    std::vector<mr::SkinNormalRow> nrows;
+    std::vector<int32_t> blocks, nblocks, bone0;
+};
+
+// The normals of the models whose normals follow their skin (k_skin_normals), after apply_pose_normals where that ran:
+// from the pristine d_normals0 into d_normals.  The bone table is on its way (upload_bones).
+int apply_skin_normals(mr_scene *sc, SkinTables &t)
+{
+    int64_t written = 0;
+    for (size_t k = 0; k < sc->poses.size(); ++k) {
+        mr_scene::ModelPose &mp = sc->poses[k];
+        if (!mp.skin_normals()) continue;
+        mr::SkinNormalRow r;
+        std::memset(&r, 0, sizeof r);
+        r.first = mp.normal_off; r.count = mp.n_normals; r.block0 = (int32_t)t.nblocks.size();
+        r.owner_off = mp.owner_off; r.table_off = mp.table_off; r.bone0 = t.bone0[k];
+        r.has_g = mp.has_g ? 1 : 0;
+        if (mp.has_g) std::memcpy(r.g, mp.g, sizeof r.g);
+        t.nblocks.insert(t.nblocks.end(), (size_t)blocks_for(mp.n_normals, mr::POSE_BLOCK), (int32_t)t.nrows.size());
+        t.nrows.push_back(r);
+        mp.normals_on_device = true;
+        written += mp.n_normals;
+    }
+    sc->skin_normals_written = (int32_t)written;
+    if (t.nrows.empty()) return MR_OK;
+    if (!sc->normals0_valid) {
+        if (int rc = upload(sc->d_normals0, sc->normals, g_stream)) return rc;
+        sc->normals0_valid = true;
+    }
+    if (int rc = upload(sc->d_skin_n_rows, t.nrows, g_stream)) return rc;
+    if (int rc = upload(sc->d_skin_n_blocks, t.nblocks, g_stream)) return rc;
+    HIP_TRY(hipEventRecord(sc->skin_ev[2], g_stream));
+    hipLaunchKernelGGL(mr::k_skin_normals, dim3((unsigned)t.nblocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
+                       sc->d_skin_n_rows.as<mr::SkinNormalRow>(), sc->d_skin_n_blocks.as<int32_t>(), sc->d_normals0.as<float>(),
+                       sc->d_skin_owners.as<int32_t>(), sc->d_skin_joints.as<int4>(), sc->d_skin_weights.as<double4>(),
+                       sc->d_bones.as<double4>(), sc->d_normals.as<float>());
+    HIP_TRY(hipEventRecord(sc->skin_ev[3], g_stream));
+    sc->skin_ran[1] = true;
+    return MR_OK;
+}
+
 // Runs where commit() runs, right after it.  What a pass does depends on what changed: a pose brings all of it, a
 // normal matrix alone (the pose as it was) the normals' part and k_face_static -- vertices, face and edge normals, the
 // cluster records and the silhouette cache stay.
@@ -169,12 +298,16 @@ int apply_poses(mr_scene *sc)
     const bool geom = sc->pose_geom_dirty;
     std::vector<mr::PoseRow> rows;
     std::vector<int32_t> block_row;
-    bool restore = false, normals = false;
-    int64_t written = 0;
+    SkinTables skin;
+    bool restore = false, normals = false, skin_normals = false, bones = false;
+    int64_t written = 0, skinned = 0;
     for (const mr_scene::ModelPose &mp : sc->poses) {
         normals = normals || (sc->pose_g_dirty && (mp.has_g || mp.normals_on_device || mp.maps_on_device));
+        skin_normals = skin_normals || ((sc->pose_g_dirty || sc->skin_n_dirty) && mp.skin_normals());
+        bones = bones || mp.has_bones;
         if (!geom) continue;
-        if (!mp.posed) { restore = restore || mp.on_device; continue; }
+        if (!mp.moved()) { restore = restore || mp.on_device; continue; }
+        if (mp.has_bones) { skinned += mp.n_verts; continue; }      // (its row needs the bone table: below)
         mr::PoseRow r;
         std::memset(&r, 0, sizeof r);
         r.first = mp.vert_off; r.count = mp.n_verts; r.block0 = (int32_t)block_row.size();
@@ -183,8 +316,9 @@ int apply_poses(mr_scene *sc)
         rows.push_back(r);
         written += mp.n_verts;
     }
-    if (rows.empty() && !restore && !normals) {      // (a commit has just uploaded the pristine vertices)
-        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
+    written += skinned;
+    if (rows.empty() && !skinned && !restore && !normals && !skin_normals) {      // (a commit has just uploaded the pristine vertices)
+        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
         return MR_OK;
     }
     if (sc->pos32) return fail(MR_E_INVALID, "pose pass on a scene of float32 face records");   // (set_model_pose leaves such a scene dirty)
@@ -192,17 +326,28 @@ int apply_poses(mr_scene *sc)
     NormalTables normal_tables;
     if (normals)
         if (int rc = apply_pose_normals(sc, normal_tables)) return rc;
+    sc->skin_ran[0] = sc->skin_ran[1] = false;
+    sc->skin_written = sc->skin_normals_written = 0;
+    if (bones && (skinned || skin_normals)) {
+        for (hipEvent_t &e : sc->skin_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        sc->skin_marks = true;
+        if (int rc = upload_skin_tables(sc)) return rc;
+        if (int rc = upload_bones(sc, skin.bone0)) return rc;
+    }
+    if (skin_normals)
+        if (int rc = apply_skin_normals(sc, skin)) return rc;
     const int nf = (int)(sc->faces.size() / 12), ne = (int)sc->edges.size();
     auto face_static = [&] {
         hipLaunchKernelGGL(mr::k_face_static<double>, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
                            sc->d_face_flags.as<uint8_t>(), sc->d_verts.as<double>(), sc->d_uv.as<float>(), sc->d_normals.as<float>(),
                            sc->d_face_pos.as<mr::FacePos64>(), sc->d_face_attr.as<mr::FaceAttr>());
     };
-    if (rows.empty() && !restore) {                  // normal matrices alone: the face records take the new normals
+    if (rows.empty() && !skinned && !restore) {      // normal matrices alone: the face records take the new normals
         if (nf > 0) face_static();
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g_stream));     // (the tables go out of scope)
-        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
+        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
         sc->pose_passes += 1;
         sc->pose_written = 0;
         return MR_OK;
@@ -211,9 +356,9 @@ int apply_poses(mr_scene *sc)
         if (int rc = upload(sc->d_verts0, sc->verts, g_stream)) return rc;
         sc->verts0_valid = true;
     }
-    // a model whose pose was removed gets its own vertices back
+    // a model whose pose or bones were removed gets its own vertices back
     for (mr_scene::ModelPose &mp : sc->poses) {
-        if (mp.posed || !mp.on_device) continue;
+        if (mp.moved() || !mp.on_device) continue;
         const size_t off = (size_t)mp.vert_off * 4 * sizeof(double), bytes = (size_t)mp.n_verts * 4 * sizeof(double);
         HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_verts.p) + off, static_cast<const char *>(sc->d_verts0.p) + off, bytes,
                                hipMemcpyDeviceToDevice, g_stream));
@@ -231,8 +376,36 @@ int apply_poses(mr_scene *sc)
         hipLaunchKernelGGL(mr::k_pose_vertices, dim3((unsigned)block_row.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
                            sc->d_pose_rows.as<mr::PoseRow>(), sc->d_pose_blocks.as<int32_t>(), sc->d_verts0.as<double4>(),
                            sc->d_verts.as<double4>());
-        for (mr_scene::ModelPose &mp : sc->poses) mp.on_device = mp.posed;
     }
+    if (skinned) {
+        // the skinned models: one row each (vertex range, joint / weight offset, first bone, the pose that follows)
+        for (size_t k = 0; k < sc->poses.size(); ++k) {
+            const mr_scene::ModelPose &mp = sc->poses[k];
+            if (!mp.has_bones) continue;
+            mr::SkinRow r;
+            std::memset(&r, 0, sizeof r);
+            r.first = mp.vert_off; r.count = mp.n_verts; r.block0 = (int32_t)skin.blocks.size();
+            r.table_off = mp.table_off; r.bone0 = skin.bone0[k]; r.n_bones = mp.n_bones;
+            r.has_pose = mp.posed ? 1 : 0;
+            if (mp.posed) std::memcpy(r.m, mp.m, sizeof r.m);
+            skin.blocks.insert(skin.blocks.end(), (size_t)blocks_for(mp.n_verts, mr::POSE_BLOCK), (int32_t)skin.rows.size());
+            skin.rows.push_back(r);
+        }
+        if (int rc = upload(sc->d_skin_rows, skin.rows, g_stream)) return rc;
+        if (int rc = upload(sc->d_skin_blocks, skin.blocks, g_stream)) return rc;
+        bool staged = true;                          // the bones of every model of the pass fit the kernel's LDS table
+        for (const mr::SkinRow &r : skin.rows) staged = staged && r.n_bones <= mr::SKIN_LDS_BONES;
+        HIP_TRY(hipEventRecord(sc->skin_ev[0], g_stream));
+        hipLaunchKernelGGL(staged ? mr::k_skin_vertices<true> : mr::k_skin_vertices<false>, dim3((unsigned)skin.blocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
+                           sc->d_skin_rows.as<mr::SkinRow>(), sc->d_skin_blocks.as<int32_t>(), sc->d_verts0.as<double4>(),
+                           sc->d_skin_joints.as<int4>(), sc->d_skin_weights.as<double4>(), sc->d_bones.as<double4>(),
+                           sc->d_verts.as<double4>());
+        HIP_TRY(hipEventRecord(sc->skin_ev[1], g_stream));
+        sc->skin_ran[0] = true;
+        sc->skin_written = (int32_t)skinned;
+    }
+    for (mr_scene::ModelPose &mp : sc->poses)
+        if (mp.moved()) mp.on_device = true;
     HIP_TRY(hipEventRecord(sc->pose_ev[mark++], g_stream));
     if (nf > 0) {
         hipLaunchKernelGGL(mr::k_face_normals, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),
@@ -253,7 +426,7 @@ int apply_poses(mr_scene *sc)
     sc->sil.drop();                                  // the silhouette belongs to the geometry
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));         // (the tables go out of scope)
-    sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
+    sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
     sc->pose_passes += 1;
     sc->pose_written = (int32_t)written;
     return MR_OK;

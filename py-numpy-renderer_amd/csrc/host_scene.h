@@ -42,8 +42,21 @@ struct mr_scene {
         bool normals_on_device = false;       // d_normals holds transformed normals in this model's range
         bool maps_on_device = false;          // this model's materials point at re-baked copies of their maps
         double g[9] = {};
+        // the skin (mr_scene_set_model_skin): joints and weights per vertex, the owner of every normal (empty: the
+        // normals stay), kept on the host and uploaded once per skin; and the bones (mr_scene_set_model_bones), which
+        // make the model move: "has bones" is to the pass what "posed" is
+        std::vector<int32_t> joints, owners;
+        std::vector<double> weights, bones;
+        int32_t n_bones = 0;                  // > 0: the model has a skin
+        bool has_bones = false;
+        int32_t table_off = 0, owner_off = 0; // where the model's rows start in d_skin_joints / d_skin_weights, d_skin_owners
+        bool moved() const { return posed || has_bones; }                                  // d_verts differs from d_verts0
+        bool skin_normals() const { return has_bones && !owners.empty() && n_normals > 0; }  // ... d_normals from d_normals0 by the skin
     };
     std::vector<ModelPose> poses;             // one per model
+    bool skin_tables_dirty = false;           // a skin was set or removed: the device tables are rebuilt by the next pass
+    bool skin_n_dirty = false;                // bones of a model whose normals follow its skin changed
+    int32_t skin_bones = 0, skin_written = 0, skin_normals_written = 0;     // mr_debug_skin
     bool pose_dirty = false;                  // a pose or a normal matrix changed: apply_poses() has work
     bool pose_geom_dirty = false;             // ... and a pose among them: vertices and what is built from them
     bool pose_g_dirty = false;                // ... and a normal matrix among them: normals and re-baked maps
@@ -68,6 +81,13 @@ struct mr_scene {
     hipEvent_t pose_n_ev[3] = {};             // marks round the two kernels (mr_debug_pose_normals_times)
     int pose_n_marks = 0;
     bool pose_n_ran[2] = {};                  // which of the two the last such pass launched
+    // the skin: joints (int4), weights (double4) and normal owners of the skinned models, one after the other; the bone
+    // table of the last pass (its host copy lives until the pass has waited for the stream) and the two kernels' tables
+    DevBuf d_skin_joints, d_skin_weights, d_skin_owners, d_bones, d_skin_rows, d_skin_blocks, d_skin_n_rows, d_skin_n_blocks;
+    std::vector<double> bone_table;
+    hipEvent_t skin_ev[4] = {};               // marks round k_skin_vertices and k_skin_normals (mr_debug_skin_times)
+    bool skin_ran[2] = {};                    // which of the two the last pass launched
+    bool skin_marks = false;
     bool pos32 = false;                      // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
     DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
@@ -311,8 +331,8 @@ int commit(mr_scene *sc)
     sc->normals0_valid = false;               // (and the normals and the materials' map headers)
     for (mr_scene::ModelPose &mp : sc->poses) {
         mp.on_device = mp.normals_on_device = mp.maps_on_device = false;
-        if (mp.posed) sc->pose_dirty = sc->pose_geom_dirty = true;
-        if (mp.has_g) sc->pose_g_dirty = true;
+        if (mp.moved()) sc->pose_dirty = sc->pose_geom_dirty = true;
+        if (mp.has_g || mp.skin_normals()) sc->pose_g_dirty = true;
     }
     return MR_OK;
 }

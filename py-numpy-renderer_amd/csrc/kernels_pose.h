@@ -6,6 +6,9 @@
 //                     mr_host_matmul_chain, bit for bit
 //   k_pose_normals    vertex normals of the models that have a normal matrix G: float32(pristine normal @ G), the same chain
 //   k_pose_texels     the same for the texels of those models' object-space normal maps, into copies of the maps
+//   k_skin_vertices   vertices of the models that have a skin and bones: pristine vertex @ (the vertex's blend of four
+//                     bone matrices), then @ pose where the model has one; mr_host_skin_chain, bit for bit
+//   k_skin_normals    vertex normals of the models whose normals follow their skin: the owner's blend matrix, then G
 //   k_clusters        the per-cluster records (rast_types.h, ClusterRec) from the posed vertices: what build_clusters
 //                     (host_scene.h) builds on the host at commit time, one wavefront per cluster
 //
@@ -88,6 +91,125 @@ k_pose_texels(const Vec3Row *__restrict__ rows, const int32_t *__restrict__ bloc
     const int64_t i = (int64_t)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int64_t)threadIdx.x;
     if (i >= r.count) return;
     pose_vec3(r, r.src, r.dst, i);
+}
+
+// One skinned model (mr_scene_set_model_skin / mr_scene_set_model_bones): its vertex range, where its joints and
+// weights start in the scene's skin tables, where its bones start in the pass's bone table, the pose that follows the
+// skin (if the model has one) and the first of the workgroups of k_skin_vertices that cover the range.
+struct alignas(16) SkinRow {
+    int32_t first, count;
+    int32_t block0, table_off;
+    int32_t bone0, n_bones, has_pose, pad;
+    double m[16];
+};
+static_assert(sizeof(SkinRow) == 160, "SkinRow layout");
+
+// Row r of the blend matrix S of one vertex: S[r][c] = rn(w0 * B[j0][r][c]) followed by fma steps over slots 1..3
+// (_fp.dot_chain over the four slots).  A bone is 16 doubles, row-major: row r is one 32-byte load per slot, from a
+// table of a few kilobytes that every lane of the pass reads (the gathers differ per lane; the table stays in cache).
+__device__ __forceinline__ double4 skin_row(const double4 *__restrict__ bones, const int4 j, const double4 w, int r)
+{
+    const double4 b0 = bones[(size_t)j.x * 4 + r], b1 = bones[(size_t)j.y * 4 + r];
+    const double4 b2 = bones[(size_t)j.z * 4 + r], b3 = bones[(size_t)j.w * 4 + r];
+    double4 s;
+    s.x = chain4(w.x, w.y, w.z, w.w, b0.x, b1.x, b2.x, b3.x);
+    s.y = chain4(w.x, w.y, w.z, w.w, b0.y, b1.y, b2.y, b3.y);
+    s.z = chain4(w.x, w.y, w.z, w.w, b0.z, b1.z, b2.z, b3.z);
+    s.w = chain4(w.x, w.y, w.z, w.w, b0.w, b1.w, b2.w, b3.w);
+    return s;
+}
+
+// One vertex per thread of the skinned models, the tables of k_pose_vertices.  v @ S is the ascending chain over the
+// rows of S, so S is formed and used row by row: rn(v0 * S[0][c]), then one fma per further row (mr_host_skin_chain,
+// bit for bit).  The row's pose, if any, follows as in k_pose_vertices.  One 32-byte load and one 32-byte store per lane.
+// STAGED: the workgroup first copies its model's bones into LDS and the lanes gather from there (measured a little
+// faster than gathering from the cached table: DESIGN.md section 6e); the host launches it only when every skinned
+// model of the pass has at most SKIN_LDS_BONES bones, and the plain kernel otherwise.
+constexpr int SKIN_LDS_BONES = 64;                                 // 8 KB of LDS per workgroup
+
+template <bool STAGED>
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_skin_vertices(const SkinRow *__restrict__ rows, const int32_t *__restrict__ block_row, const double4 *__restrict__ verts0,
+                const int4 *__restrict__ joints, const double4 *__restrict__ weights, const double4 *__restrict__ bones,
+                double4 *__restrict__ verts)
+{
+    const SkinRow &r = rows[block_row[blockIdx.x]];
+    const int i = (int)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int)threadIdx.x;
+    __shared__ double4 staged[STAGED ? SKIN_LDS_BONES * 4 : 1];
+    if constexpr (STAGED) {                                        // (before any lane leaves: every lane meets the barrier)
+        for (int k = (int)threadIdx.x; k < min(r.n_bones, SKIN_LDS_BONES) * 4; k += POSE_BLOCK) staged[k] = bones[(size_t)r.bone0 * 4 + k];
+        __syncthreads();
+    }
+    if (i >= r.count) return;
+    const double4 v = verts0[(size_t)r.first + i];
+    const int4 j = joints[(size_t)r.table_off + i];
+    const double4 w = weights[(size_t)r.table_off + i];
+    const double4 *b = STAGED ? staged : bones + (size_t)r.bone0 * 4;
+    double4 s = skin_row(b, j, w, 0);
+    double4 o;
+    o.x = v.x * s.x; o.y = v.x * s.y; o.z = v.x * s.z; o.w = v.x * s.w;
+    s = skin_row(b, j, w, 1);
+    o.x = fma(v.y, s.x, o.x); o.y = fma(v.y, s.y, o.y); o.z = fma(v.y, s.z, o.z); o.w = fma(v.y, s.w, o.w);
+    s = skin_row(b, j, w, 2);
+    o.x = fma(v.z, s.x, o.x); o.y = fma(v.z, s.y, o.y); o.z = fma(v.z, s.z, o.z); o.w = fma(v.z, s.w, o.w);
+    s = skin_row(b, j, w, 3);
+    o.x = fma(v.w, s.x, o.x); o.y = fma(v.w, s.y, o.y); o.z = fma(v.w, s.z, o.z); o.w = fma(v.w, s.w, o.w);
+    if (r.has_pose) {                                              // (uniform over the workgroup)
+        const double4 p = o;
+        o.x = chain4(p.x, p.y, p.z, p.w, r.m[0], r.m[4], r.m[8], r.m[12]);
+        o.y = chain4(p.x, p.y, p.z, p.w, r.m[1], r.m[5], r.m[9], r.m[13]);
+        o.z = chain4(p.x, p.y, p.z, p.w, r.m[2], r.m[6], r.m[10], r.m[14]);
+        o.w = chain4(p.x, p.y, p.z, p.w, r.m[3], r.m[7], r.m[11], r.m[15]);
+    }
+    verts[(size_t)r.first + i] = o;
+}
+
+// One model whose vertex normals follow its skin: its normal range, where its owner table (per normal: the vertex of
+// the model whose blend matrix the normal takes, -1: the normal stays) and its joints and weights start, its bones, the
+// normal matrix G that follows the skin (if the model has one) and the first of its workgroups.
+struct alignas(8) SkinNormalRow {
+    int32_t first, count;
+    int32_t block0, owner_off;
+    int32_t table_off, bone0, has_g, pad;
+    double g[9];
+};
+static_assert(sizeof(SkinNormalRow) == 104, "SkinNormalRow layout");
+
+// One normal per thread: n' = float64(float32 normal) @ S[:3, :3] of the owner (rows 0..2 of S, the chain of
+// k_skin_vertices without its last step), then n' @ G where the row has one, then ONE rounding to float32.
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_skin_normals(const SkinNormalRow *__restrict__ rows, const int32_t *__restrict__ block_row, const float *__restrict__ normals0,
+               const int32_t *__restrict__ owners, const int4 *__restrict__ joints, const double4 *__restrict__ weights,
+               const double4 *__restrict__ bones, float *__restrict__ normals)
+{
+    const SkinNormalRow &r = rows[block_row[blockIdx.x]];
+    const int i = (int)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int)threadIdx.x;
+    if (i >= r.count) return;
+    const size_t at = ((size_t)r.first + i) * 3;
+    const float3 n = *reinterpret_cast<const float3 *>(normals0 + at);
+    double x = (double)n.x, y = (double)n.y, z = (double)n.z;
+    const int owner = owners[(size_t)r.owner_off + i];
+    if (owner >= 0) {
+        const int4 j = joints[(size_t)r.table_off + owner];
+        const double4 w = weights[(size_t)r.table_off + owner];
+        const double4 *b = bones + (size_t)r.bone0 * 4;
+        double4 s = skin_row(b, j, w, 0);
+        double ox = x * s.x, oy = x * s.y, oz = x * s.z;
+        s = skin_row(b, j, w, 1);
+        ox = fma(y, s.x, ox); oy = fma(y, s.y, oy); oz = fma(y, s.z, oz);
+        s = skin_row(b, j, w, 2);
+        ox = fma(z, s.x, ox); oy = fma(z, s.y, oy); oz = fma(z, s.z, oz);
+        x = ox; y = oy; z = oz;
+    }
+    float3 o;
+    if (r.has_g) {
+        o.x = (float)chain3(x, y, z, r.g[0], r.g[3], r.g[6]);
+        o.y = (float)chain3(x, y, z, r.g[1], r.g[4], r.g[7]);
+        o.z = (float)chain3(x, y, z, r.g[2], r.g[5], r.g[8]);
+    } else {
+        o.x = (float)x; o.y = (float)y; o.z = (float)z;
+    }
+    *reinterpret_cast<float3 *>(normals + at) = o;
 }
 
 __device__ __forceinline__ double shfl_xor_d(double v, int mask)

@@ -109,7 +109,8 @@ int mr_scene_clear(mr_scene *sc)
     sc->verts.clear(); sc->uv.clear(); sc->normals.clear(); sc->faces.clear(); sc->face_flags.clear();
     sc->materials.clear(); sc->model_face_off.clear(); sc->edges.clear(); sc->edge_inc.clear();
     sc->edge_ids.clear(); sc->edge_raw.clear();
-    sc->poses.clear(); sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = false;
+    sc->poses.clear(); sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
+    sc->skin_tables_dirty = true;
     sc->dirty = true;
     sc->last = nullptr;
     sc->sil.drop();
@@ -152,13 +153,15 @@ void mr_scene_destroy(mr_scene *sc)
     for (DevBuf *b : { &sc->d_verts, &sc->d_uv, &sc->d_normals, &sc->d_faces, &sc->d_face_flags, &sc->d_materials, &sc->d_textures, &sc->d_edges,
                        &sc->d_edges32, &sc->d_edge_inc, &sc->d_face_n, &sc->d_face_pos, &sc->d_face_attr, &sc->d_clusters, &sc->d_sky, &sc->d_gamma,
                        &sc->d_verts0, &sc->d_pose_rows, &sc->d_pose_blocks, &sc->d_normals0, &sc->d_normal_rows, &sc->d_normal_blocks,
-                       &sc->d_texel_rows, &sc->d_texel_blocks, &sc->d_rebaked })
+                       &sc->d_texel_rows, &sc->d_texel_blocks, &sc->d_rebaked, &sc->d_skin_joints, &sc->d_skin_weights, &sc->d_skin_owners,
+                       &sc->d_bones, &sc->d_skin_rows, &sc->d_skin_blocks, &sc->d_skin_n_rows, &sc->d_skin_n_blocks })
         b->release();
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sc->skin_ev) if (e) (void)hipEventDestroy(e);
     delete sc;
 }
 
@@ -347,6 +350,41 @@ int mr_scene_set_model_pose_normals(mr_scene *sc, int32_t model, const double *g
     return MR_OK;
 }
 
+int mr_scene_set_model_skin(mr_scene *sc, int32_t model, const int32_t *joints, const double *weights, int32_t n_bones,
+                            const int32_t *normal_owner)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    const mr_scene::ModelPose &mp = sc->poses[model];
+    if (joints) {                                    // validated before the kernels trust them
+        if (!weights || n_bones <= 0) return fail(MR_E_INVALID, "a skin needs joints, weights and at least one bone");
+        for (size_t i = 0; i < (size_t)mp.n_verts * 4; ++i) {
+            if (joints[i] < 0 || joints[i] >= n_bones) return fail(MR_E_INVALID, "joint index out of range");
+            if (!std::isfinite(weights[i])) return fail(MR_E_INVALID, "skin weights must be finite");
+        }
+        if (normal_owner)
+            for (int32_t i = 0; i < mp.n_normals; ++i)
+                if (normal_owner[i] < -1 || normal_owner[i] >= mp.n_verts) return fail(MR_E_INVALID, "normal owner out of range");
+    }
+    set_model_skin(sc, model, joints, weights, n_bones, normal_owner);
+    return MR_OK;
+}
+
+int mr_scene_set_model_bones(mr_scene *sc, int32_t model, const double *bones16, int32_t n_bones)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    const mr_scene::ModelPose &mp = sc->poses[model];
+    if (mp.n_bones == 0) return fail(MR_E_INVALID, "bones need a model that has a skin");
+    if (bones16) {
+        if (n_bones != mp.n_bones) return fail(MR_E_INVALID, "the skin was set for another number of bones");
+        for (size_t i = 0; i < (size_t)n_bones * 16; ++i)
+            if (!std::isfinite(bones16[i])) return fail(MR_E_INVALID, "bone matrices must be finite");
+    }
+    set_model_bones(sc, model, bones16);
+    return MR_OK;
+}
+
 int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats *stats)
 {
     if (!sc || !out_rgb) return fail(MR_E_INVALID, "NULL argument");
@@ -464,6 +502,44 @@ void *mr_host_alloc(uint64_t bytes)
 // out[i][j] = a[i][0] * b[0][j], then fma(a[i][k], b[k][j], .) for k = 1 .. K-1: the order NumPy's BLAS uses for
 // the reference's tiny host-side products, spelled out so that it is the same on any host.
 // Host arithmetic for the Python mirror's per-frame constants; no device involved.
+// Row r of a vertex's blend matrix: every entry rn(w0 * B[j0][r][c]) followed by fma steps over slots 1..3
+static void host_skin_row(const double *bones, const int32_t *j, const double *w, int r, double s[4])
+{
+    for (int c = 0; c < 4; ++c) {
+        double acc = w[0] * bones[(size_t)j[0] * 16 + r * 4 + c];
+        for (int k = 1; k < 4; ++k) acc = std::fma(w[k], bones[(size_t)j[k] * 16 + r * 4 + c], acc);
+        s[c] = acc;
+    }
+}
+
+void mr_host_skin_chain(const double *verts, const int32_t *joints, const double *weights, const double *bones, int32_t n, double *out)
+{
+    for (int32_t i = 0; i < n; ++i) {
+        const double *v = verts + (size_t)i * 4;
+        double s[4], o[4];
+        for (int r = 0; r < 4; ++r) {
+            host_skin_row(bones, joints + (size_t)i * 4, weights + (size_t)i * 4, r, s);
+            for (int c = 0; c < 4; ++c) o[c] = r == 0 ? v[0] * s[c] : std::fma(v[r], s[c], o[c]);
+        }
+        for (int c = 0; c < 4; ++c) out[(size_t)i * 4 + c] = o[c];
+    }
+}
+
+void mr_host_skin_chain3(const double *vectors, const int32_t *owner, const int32_t *joints, const double *weights, const double *bones,
+                         int32_t n, double *out)
+{
+    for (int32_t i = 0; i < n; ++i) {
+        const double *v = vectors + (size_t)i * 3;
+        double s[4], o[3] = { v[0], v[1], v[2] };
+        if (owner[i] >= 0)
+            for (int r = 0; r < 3; ++r) {
+                host_skin_row(bones, joints + (size_t)owner[i] * 4, weights + (size_t)owner[i] * 4, r, s);
+                for (int c = 0; c < 3; ++c) o[c] = r == 0 ? v[0] * s[c] : std::fma(v[r], s[c], o[c]);
+            }
+        for (int c = 0; c < 3; ++c) out[(size_t)i * 3 + c] = o[c];
+    }
+}
+
 void mr_host_matmul_chain(const double *a, const double *b, double *out, int32_t m, int32_t k, int32_t p)
 {
     for (int i = 0; i < m; ++i)
@@ -734,6 +810,26 @@ int mr_debug_pose_normals_times(mr_scene *sc, float *out_ms)
     for (int k = 0; k < MR_N_POSE_NORMALS_TIMES; ++k) {
         out_ms[k] = 0.f;                             // (a kernel that was not launched: not the empty span between two marks)
         if (sc->pose_n_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->pose_n_ev[k], sc->pose_n_ev[k + 1]));
+    }
+    return MR_OK;
+}
+
+int mr_debug_skin(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    int32_t skinned = 0;
+    for (const mr_scene::ModelPose &mp : sc->poses) skinned += mp.has_bones ? 1 : 0;
+    out[0] = skinned; out[1] = sc->skin_bones; out[2] = sc->skin_written; out[3] = sc->skin_normals_written;
+    return MR_OK;
+}
+
+int mr_debug_skin_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->skin_marks) return fail(MR_E_INVALID, "no pass over a skin yet");
+    for (int k = 0; k < MR_N_SKIN_TIMES; ++k) {
+        out_ms[k] = 0.f;                             // (a kernel the last pass did not launch)
+        if (sc->skin_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->skin_ev[2 * k], sc->skin_ev[2 * k + 1]));
     }
     return MR_OK;
 }
