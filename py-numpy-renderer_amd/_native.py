@@ -549,6 +549,11 @@ class DeviceRenderer:
             raise ValueError("the per-face status is not available with more than one light")
         if pf.extra_lights and stripe is not None:
             raise ValueError("striped frames are not available with more than one light")
+        # (the library renders such a frame and refuses to hand the status out: mr_read_face_status)
+        partial = (stripe is not None and int(stripe[1]) > 1) or (
+            row_band is not None and (int(row_band[0]) != 0 or int(row_band[1]) * pf.supersample != pf.height))
+        if face_status and partial:
+            raise ValueError("the per-face status needs the whole frame on one device (no row band, no stripes)")
         self.sync_lights(pf)
         if overlay:
             self.sync_overlay(scene)
