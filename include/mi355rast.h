@@ -373,6 +373,14 @@ int mr_debug_read_tile_records(mr_scene *scene, uint32_t *out, int32_t cap_tiles
  * on with the screen and row test only. */
 int mr_debug_clusters_culled(mr_scene *scene);
 
+/* Diagnostic: how the tile kernel walked the last frame's shadow quads (frames with MR_FRAME_COUNTERS and one light; 0
+ * otherwise): out[0] = (quad, row) items of the span walk, out[1] = (quad, strip) pairs walked a pixel per lane, out[2] =
+ * those of out[1] whose polygon has more than four vertices, out[3] = those with a non-finite edge value (the two kinds
+ * the span walk is not defined for).
+ * MR_QUAD_WALK=strips | spans in the environment (read once per process) forces either walk; the frames do not depend on
+ * it. */
+int mr_debug_quad_walks(mr_scene *scene, uint32_t *out);
+
 /* Diagnostics of the silhouette cache: out[0] = the path the edge half of the most recently enqueued frame
  * with shadows took (0 fused: every edge tested against the light; 1 fused, and captured into the cache; 2 read from the
  * cache; -1 no such frame yet), out[1] = the entries that frame read from the cache (0 unless out[0] == 2), out[2] =

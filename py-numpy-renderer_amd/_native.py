@@ -136,6 +136,7 @@ _PROTOTYPES = {
     "mr_host_overlay_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mr_debug_read_tile_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_clusters_culled": (C.c_int, [C.c_void_p]),
+    "mr_debug_quad_walks": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_host_camera_constants": (None, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3),
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -720,6 +721,13 @@ class DeviceRenderer:
     def clusters_culled(self):
         """Clusters of 64 faces the last frame's set-up dropped whole (counted only under MR_CLUSTER_CULL=count)."""
         return int(_check(self.lib.mr_debug_clusters_culled(self.handle), "mr_debug_clusters_culled"))
+
+    def quad_walks(self):
+        """``mr_debug_quad_walks`` of the last (counted, single-light) frame: ((quad, row) span items, (quad, strip)
+        walks, those of the strip walks with a polygon of more than four vertices, those with a non-finite edge value)."""
+        out = (C.c_uint32 * 4)()
+        _check(self.lib.mr_debug_quad_walks(self.handle, out), "mr_debug_quad_walks")
+        return tuple(int(x) for x in out)
 
     def sil_cache(self):
         """Silhouette cache: (path of the last frame with shadows: 0 fused / 1 captured / 2 cached / -1 none, entries it

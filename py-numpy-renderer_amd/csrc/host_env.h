@@ -9,8 +9,11 @@
 //                               (two edges per lane), 0 .. 4 forced
 //   MR_TILE_ORDER     (auto)    rowmajor | heaviest: the order k_tile takes the tiles in (auto: see launch_tile)
 //   MR_TILE_SPLIT     -1        0 | 1: sharing a heavy tile's quads out over HEAVY_SPLIT workgroups off / on for every grid
-//   MR_SPLIT_COST     400       a whole frame's tile is shared out from this estimated cost ...
+//   MR_SPLIT_COST     400       a whole frame's tile (MR_TILE_SPLIT=1: by default only small grids split) is shared out from this estimated cost ...
 //   MR_SPLIT_QUADS    48        ... and this many shadow quads
+//   MR_QUAD_WALK      (auto)    strips | spans: how k_tile's single-light instantiations walk a tile's shadow quads -- one quad
+//                               at a time over the wavefront's strip, or sixteen (quad, row) spans to a round wherever
+//                               that walk is defined (auto: by the quad and the strip, see k_tile phase 3)
 //   MR_CLUSTER_CULL   (auto)    0 | 1 | box | count: cluster culling off / on / boxes only / on and counted (auto: see
 //                               cluster_cull_mode)
 //   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
@@ -24,6 +27,7 @@ namespace {
 struct Env {
     bool vertex_mfma, resolve_separate, sil_cache;
     int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
+    int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
     unsigned split_cost, split_quads;
     const char *cluster_cull;                     // as set, or NULL
 };
@@ -38,6 +42,7 @@ Env read_env()
         e.resolve_separate = is("MR_RESOLVE_PATH", "separate");
         e.edge_spread = number("MR_EDGE_SPREAD", -2);
         e.tile_order = is("MR_TILE_ORDER", "rowmajor") ? 1 : is("MR_TILE_ORDER", "heaviest") ? 2 : 0;
+        e.quad_walk = is("MR_QUAD_WALK", "strips") ? 1 : is("MR_QUAD_WALK", "spans") ? 2 : 0;
         e.tile_split = number("MR_TILE_SPLIT", -1);
         e.split_cost = (unsigned)number("MR_SPLIT_COST", 400);
         e.split_quads = (unsigned)number("MR_SPLIT_QUADS", 48);

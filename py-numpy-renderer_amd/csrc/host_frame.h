@@ -385,12 +385,17 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     p.ordered = p.env.tile_order == 2 || (p.env.tile_order == 0 && alone);
     // which tiles are shared out over HEAVY_SPLIT workgroups next frame: on a device whose tiles are all resident
     // at once (a rank of a multi-GPU split; there the launch lasts as long as the slowest tile, see HEAVY_SPLIT) every
-    // tile with a quad walk worth sharing; on a whole frame only the handful that outlast everything else (the launch
-    // then ends with them).  MR_TILE_SPLIT=0 | 1 forces it off / on for every grid.
+    // tile with a quad walk worth sharing; on a whole frame the handful that outlast everything else -- which still lead
+    // the order (k_tile<true> and its class rule), but are shared out only with MR_TILE_SPLIT=1 (split_max = 0 otherwise,
+    // see below).  MR_TILE_SPLIT=0 | 1 forces the split off / on for every grid.
     const bool small_grid = p.n_tiles <= 2048;
     p.split_cost = small_grid ? 350u : p.env.split_cost;
     p.split_quads = small_grid ? 32u : p.env.split_quads;
-    p.split_max = small_grid ? (unsigned)HEAVY0_MAX : std::min<unsigned>(SPLIT_MAX_BIG, (unsigned)HEAVY0_MAX);
+    // (Whole frames were shared out too while the strip walk took a heavy tile's quads one after the other, 46 us for the
+    // 111 of c4's heaviest.  With the span walk a lone c4 frame's k_tile lasts 62.9 us with its heavy tiles shared out
+    // and 60.6 us with none (split_max = 0), c3's 73.2 and 70.1, and a rank of eight still gains: 55.8 us against 57.4 for the
+    // slowest rank's rows -- profiles/quad_spans_ab.txt.)
+    p.split_max = small_grid ? (unsigned)HEAVY0_MAX : p.env.tile_split > 0 ? std::min<unsigned>(SPLIT_MAX_BIG, (unsigned)HEAVY0_MAX) : 0u;
     p.split = !p.ml && (p.env.tile_split < 0 ? (small_grid || p.ordered) : p.env.tile_split != 0);
     // small meshes: one edge per 2 / 4 lanes, so that a wavefront rarely finds more silhouette edges than one round
     // of its quad set-up takes (kernels_geometry.h, edge_block)
@@ -537,6 +542,7 @@ int launch_tile(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fra
     ta.tile_class = reinterpret_cast<uint8_t *>(fs->d_hist.p) + p.order_bytes;
     ta.split_arrive = fs->d_split.as<uint32_t>(); ta.split_sten = fs->d_split.as<int32_t>() + HEAVY0_MAX;
     ta.split_cost = p.split_cost; ta.split_quads = p.split_quads; ta.split_max = p.split_max;
+    ta.quad_walk = (uint32_t)p.env.quad_walk;
     ShadeArgs &sh = tka.sh;
     sh.tris = fs->d_tris.as<TriRec>(); sh.face_pos = sc->d_face_pos.p; sh.face_attr = sc->d_face_attr.as<FaceAttr>();
     sh.materials = sc->d_materials.as<Material>();

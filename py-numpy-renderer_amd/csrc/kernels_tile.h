@@ -17,8 +17,14 @@
 //      the keys the first left in LDS) an LDS atomicMax of the face index where its z is the tile's final z.  The reference's sequential rule (a fragment writes when
 //      zbuf >= z, so the last face in order wins ties) is reproduced order-free: smallest z, and
 //      among equal z the largest face index;
-//   3. the tile's shadow quads against the final z, QUAD_BATCH records staged in LDS per round,
-//      one pixel per thread: stencil +-1 in a register (obj/triangular.py:335-368);
+//   3. the tile's shadow quads against the final z, QUAD_BATCH records staged in LDS per round; lane j of every
+//      wavefront classifies quad j against the wavefront's 16x4 strip.  A survivor is then walked in one of two ways
+//      (obj/triangular.py:335-368): the STRIP walk, one quad at a time, every lane its own pixel, stencil +-1 in the
+//      lane's register; or -- single light, where enough of the strip's quads are crossed by an edge -- the SPAN walk:
+//      (quad, row) items dealt to the lanes, sixteen quads to a round, the row's samples found as one interval by
+//      bisection with the strip walk's own rounded edge expression, stencil +-1 as LDS atomics on the pixel's word (the
+//      winner map's, dead by then), read back once behind the last batch.  One depth rule for both (quad_depth_pass).
+//      MR_QUAD_WALK=strips | spans forces either; mr_debug_quad_walks counts them;
 //   4. deferred shading of the winner (kernels_shade.h), finalise, uint8 store.
 //
 // A frame with several lights (k_tile<., ., true>) keeps one stencil count per light in phase 3 and adds the
@@ -232,6 +238,53 @@ struct QuadHead {                     // the first 64 bytes of a QuadRec, as sta
 };
 static_assert(sizeof(QuadHead) == 64, "QuadHead mirrors QuadRec's header");
 
+// How phase 3 of k_tile walks a quad (TileArgs::quad_walk, MR_QUAD_WALK).
+enum : uint32_t { QUAD_WALK_AUTO = 0, QUAD_WALK_STRIPS = 1, QUAD_WALK_SPANS = 2 };
+// auto: a (quad, strip) pair takes the span walk when at least this many of its edges cross the strip (0 would send
+// the fat pairs too, whose every sample is inside: each row is then a loop of sixteen samples in one lane) ...
+#ifndef MR_SPAN_MIN_EDGES
+#define MR_SPAN_MIN_EDGES 1
+#endif
+// ... and the wavefront's strip has at least this many such quads in the batch: a round of spans costs what a few
+// strip walks do, whatever it holds.  Both from the A/B in profiles/quad_spans_ab.txt (c4 / c3, quoted regime, MI355X:
+// edges 1 / quads 6: 0.0782 / 0.0891 ms; 2 / 3: 0.0790 / 0.0924; 3 / 2: 0.0868 / 0.0950; 1 / 12: 0.0790 / 0.0892; the
+// strip walk alone: 0.0905 / --).  A function of the batch's records and the strip, not of timing.
+#ifndef MR_SPAN_MIN_QUADS
+#define MR_SPAN_MIN_QUADS 6
+#endif
+
+// The depth rule of a shadow quad's sample (obj/triangular.py:351-360), the one copy both walks of phase 3 call: does
+// the sample (dpx, dpy) of the quad with plane (q_nx, q_ny, nzq, q_d) pass against the pixel's final z?
+// zq = two_nf / (f_plus_n + (t / nz) * f_minus_n) with t the plane's value at the sample.  The reference's value needs
+// two IEEE divisions; the DECISION needs none: multiplied through by nz, zbest - zq has the sign of E / D with
+// D = f_plus_n * nz + t * f_minus_n and E = zbest * D - two_nf * nz (a0 = f_plus_n * nz and b0 = two_nf * nz come with
+// the staged record).  That settles it unless z-buffer and quad depth agree to nine digits or D is close to its pole
+// (or something is not finite); only then is the exactly rounded expression evaluated.  t itself is computed exactly
+// as the reference does.  Decisions stay bit-exact.  `in`: the lane holds a sample of the quad (the others' verdicts
+// are not used).
+__device__ __forceinline__ bool quad_depth_pass(double q_nx, double q_ny, double nzq, double q_d, double a0, double b0,
+                                                double dpx, double dpy, double zbest, bool rh, bool in,
+                                                double f_plus_n, double f_minus_n, double two_nf)
+{
+    const double t = (q_nx * dpx + q_ny * dpy) + q_d;
+    const double tf = t * f_minus_n;
+    const double den = a0 + tf;
+    const double prod = zbest * den;
+    const double e = prod - b0;
+    // an empty z-buffer entry (+-inf) beats or loses against every finite depth
+    const bool zinf = fabs(zbest) == INFINITY;
+    bool pass = zinf ? (rh ? zbest > 0 : zbest < 0) : (rh ? ((e > 0) == (den > 0)) : ((e < 0) == (den > 0)));
+    const bool clear = zinf || fabs(e) > 1e-9 * (fabs(prod) + fabs(b0));
+    const bool unsure = in && !(clear && fabs(den) > 2e-4 * (fabs(a0) + fabs(tf)));
+    if (__ballot(unsure)) {
+        if (unsure) {
+            const double z = two_nf / (f_plus_n - (-t / nzq) * f_minus_n);     // linearize_z (obj/core.py:226-228)
+            pass = rh ? (zbest >= z) : (zbest <= z);
+        }
+    }
+    return pass;
+}
+
 constexpr int MAT_LDS = 8;            // scenes with up to this many materials keep them in LDS
 static_assert(sizeof(Material) % 8 == 0 && MAT_LDS * sizeof(Material) / 8 <= TILE_PX, "material staging");
 
@@ -277,7 +330,11 @@ constexpr int HEAVY_SPLIT = 4, HEAVY0_MAX = MR_HEAVY0_MAX;
 #ifndef MR_TILE_WAVES
 #define MR_TILE_WAVES 5
 #endif
-constexpr int K_TILE_WAVES = MR_TILE_WAVES;              // wavefronts per SIMD the tile kernel's register budget allows
+constexpr int K_TILE_WAVES = MR_TILE_WAVES;              // wavefronts per SIMD the multi-light tile kernel's register budget allows
+#ifndef MR_TILE_WAVES_1L
+#define MR_TILE_WAVES_1L 6
+#endif
+constexpr int K_TILE_WAVES_1L = MR_TILE_WAVES_1L;        // ... and the single-light instantiations': 80 registers, held by tests/test_kernel_budget.py
 constexpr int SPLIT_FRONT = HEAVY_SPLIT * HEAVY0_MAX;     // extra workgroups of a k_tile<true> launch
 
 // estimated cost of a tile in ~0.1 us from its list lengths: the least-squares fit of the measured tile times of
@@ -305,6 +362,7 @@ struct TileArgs {
     uint8_t *tile_class;          // [n_tiles] what this frame leaves for the next: 1 + the tile's cost class
     uint32_t split_cost, split_quads;   // k_tile<true>: a tile this costly, with this many shadow quads, is shared out next frame ...
     uint32_t split_max;                 // ... if no more than this many are (<= HEAVY0_MAX)
+    uint32_t quad_walk;                 // QUAD_WALK_*: MR_QUAD_WALK (single-light instantiations, phase 3)
 };
 
 // A frame with several lights (k_tile<., ., true>): the lights (all of them, FrameLights) and the stencil taps of
@@ -330,7 +388,7 @@ struct TileKernArgs { FrameConst fc; TileArgs ta; ShadeArgs sh; TileLights ml; }
 // contributions F_k in float32, in the order of the lights: F = min(F_0 + F_1 + ..., 1), every F_k clipped to
 // [0.05, 1] like the reference's one.  Such frames never split tiles.
 template <bool SPLIT, bool SS, bool ML>
-__global__ void __launch_bounds__(TILE_PX, K_TILE_WAVES)
+__global__ void __launch_bounds__(TILE_PX, ML ? K_TILE_WAVES : K_TILE_WAVES_1L)
 k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), phase by phase
 {
     static_assert(!(SPLIT && ML), "frames with several lights do not split their heavy tiles");
@@ -640,7 +698,8 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
     // batch's records (header and first four edges: 192 bytes each) are copied to LDS once, 16 bytes
     // per lane, and every lane then reads the quad it is testing at the same LDS address (a
     // broadcast read).  Adds commute, so the order of the quads never mattered
-    // (obj/triangular.py:365-368); the count stays in this thread's register.
+    // (obj/triangular.py:365-368); the strip walk's count stays in this thread's register, the span walk's in the
+    // pixel's LDS word, and the two are added behind the last batch.
     int sten = 0;
     int sten_x[MAX_LIGHTS - 1] = { 0, 0, 0 };             // ML: lights 1.. (always indexed by constants: registers)
     unsigned int qfrags = 0, qupd = 0;
@@ -652,9 +711,6 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         const uint32_t *__restrict__ quad_items = ta.items[2] + (size_t)tile * ta.cap[2];
         const QuadRec *__restrict__ quads = ta.quads;
         const double f_plus_n = fc.f_plus_n, f_minus_n = fc.f_minus_n, two_nf = fc.two_nf;     // fetched once, see above
-        int px, py;
-        my_pixel(px, py);
-        const double dpx = (double)px, dpy = (double)py;
         // most and least favourable covered z of this wavefront's strip (see the depth verdicts below)
         double zlim = rh ? -INFINITY : INFINITY, zhard = rh ? INFINITY : -INFINITY;
         if (covered) zlim = zhard = zbest;
@@ -663,6 +719,15 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             const double o = __shfl_xor(zlim, off), h = __shfl_xor(zhard, off);
             zlim = rh ? fmax(zlim, o) : fmin(zlim, o);
             zhard = rh ? fmin(zhard, h) : fmax(zhard, h);
+        }
+        // The span walk (single light): the final z in LDS (the keys are there already wherever the tile had small
+        // pairs), and the stencil words it adds to in s_win, dead since `best` was read.  Each thread writes its own
+        // pixel's; the batch's staging barrier stands between these stores and the first span.
+        // (the walk's few arguments are read where they are used, batch by batch: kept in scalar registers from here
+        // on they cost the kernel its sixth wavefront)
+        if (!ML && ta.quad_walk != QUAD_WALK_STRIPS) {
+            if (!n_small) s_key[lp] = z_key(zbest);
+            s_win[lp] = 0;
         }
         const uint32_t q_begin = SPLIT ? (uint32_t)((unsigned long long)part * n_quad / n_parts) : 0u,
                        q_end = SPLIT ? (uint32_t)((unsigned long long)(part + 1) * n_quad / n_parts) : n_quad;    // this part's share
@@ -701,6 +766,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             // Per edge too: an edge whose inner side holds all four corners needs no per-pixel test
             // in this strip (bit i of emask clear); typically one edge of a quad crosses a strip.
             bool q_reject = lane >= n;
+            bool q_finite = true;                           // every term of the corner tests is finite (the span walk needs it)
             int emask = 0;
             if (!q_reject) {
                 const QuadHead &h = *reinterpret_cast<const QuadHead *>(s_quad + lane * QUAD_STAGE_U4);
@@ -717,6 +783,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                         const bool any = c00 > 0 || c10 > 0 || c01 > 0 || c11 > 0;
                         const bool all = c00 > 0 && c10 > 0 && c01 > 0 && c11 > 0;
                         q_reject = q_reject || !any;
+                        if (!ML) q_finite = q_finite && fabs(px0) + fabs(px1) + fabs(py0) + fabs(py1) < INFINITY;
                         if (!all) emask |= 1 << i;
                     }
                 }
@@ -747,9 +814,13 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                                      1e-15 * ((fabs(h.nx) * xb + fabs(h.ny) * yb) + fabs(h.d)) * fabs(inz);
                 const double zs_lo = fmin(za, zb) - slack, zs_hi = fmax(za, zb) + slack;
                 const double den_lo = f_plus_n - zs_hi * f_minus_n, den_hi = f_plus_n - zs_lo * f_minus_n;
-                const bool sane = two_nf > 0 && f_minus_n > 0 && den_lo > 1e-9 * f_plus_n && h.nz != 0 &&
+                // (single light: three products of frame constants, worked out here per batch from copies the compiler
+                // cannot trace -- hoisted out of the batch loop they held six registers through the span walk)
+                double fpn = f_plus_n, tnf = two_nf;
+                if (!ML) asm volatile("" : "+v"(fpn), "+v"(tnf));
+                const bool sane = two_nf > 0 && f_minus_n > 0 && den_lo > 1e-9 * fpn && h.nz != 0 &&
                                   fabs(inz) < 1e300 && den_hi < 1e300;
-                const double lo = two_nf * (1.0 - 1e-12), hi = two_nf * (1.0 + 1e-12);
+                const double lo = tnf * (1.0 - 1e-12), hi = tnf * (1.0 + 1e-12);
                 // rh: a pixel passes when zbuf >= zq; lh: when zbuf <= zq
                 const bool none = rh ? lo > zlim * den_hi : hi < zlim * den_lo;
                 const bool all = rh ? hi <= zhard * den_lo : lo >= zhard * den_hi;
@@ -759,6 +830,104 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             unsigned long long todo = __ballot(!q_reject);
             const unsigned long long allpass = __ballot(q_allpass);
 
+            // ---- the span walk: sliver quads as (quad, row) items, sixteen quads to a round of this wavefront.
+            // For a fixed row y the staged inside test of edge i, rn(rn(rn(x - sx) * ey) - rn(rn(y - sy) * ex)) > 0, has
+            // a constant second term and a first term monotone in x (every step is a monotone function of the one
+            // before, and nothing is NaN: q_finite bounds both products by their finite values at the strip's corners).
+            // So the x that pass form a half-line -- x >= F for ey > 0, x < F for ey < 0, all or none for ey == 0 -- and
+            // F is found by bisection over the row's 16 positions with the very expression the strip walk evaluates
+            // per pixel: no division, no estimate to repair.  The quad's samples in the row are the interval left by its
+            // crossing edges (the others hold on the whole strip: emask) and the clamped box.  Per sample: the depth rule
+            // (quad_depth_pass) against the pixel's final z from LDS, then an LDS atomic add on the pixel's stencil word.
+            // Which quads come here is a function of the batch's records and the strip alone, never of timing.
+            const uint32_t quad_walk = ML ? (uint32_t)QUAD_WALK_STRIPS : kernargs<TileKernArgs>().ta.quad_walk;
+            if (!ML && quad_walk != QUAD_WALK_STRIPS) {
+                const bool span_ok = !q_reject && q_finite && !(emask & 16);
+                unsigned long long smask = __ballot(span_ok && (quad_walk == QUAD_WALK_SPANS || __popc(emask & 15) >= MR_SPAN_MIN_EDGES));
+                if (quad_walk == QUAD_WALK_AUTO && __popcll(smask) < MR_SPAN_MIN_QUADS) smask = 0;
+                todo &= ~smask;
+                if (smask) {
+                    // compaction without LDS: the survivors push their lane to the lanes 0 .. cnt-1 in order, the
+                    // others fill the rest (a permutation), with the strip verdicts beside the lane
+                    const int cnt = __popcll(smask);
+                    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(smask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)smask, 0u));
+                    const int dest = ((smask >> lane) & 1) ? rank : cnt + (lane - rank);
+                    const int list = __builtin_amdgcn_ds_permute(dest << 2, lane | (emask << 8) | ((q_allpass ? 1 : 0) << 16));
+                    const int ly = (tid / WAVE) * (WAVE / TILE_W) + (lane & 3);       // the item's row of the tile
+                    const int y = gy + ly;
+                    const double dy = (double)y;
+                    const FrameConst &fcs = kernargs<TileKernArgs>().fc;
+                    const int f_width = fcs.width, f_band_y0 = fcs.band_y0, f_band_y1 = fcs.band_y1;
+#pragma unroll 1
+                    for (int base = 0; base < cnt; base += WAVE / 4) {
+                        const int k = base + (lane >> 2);
+                        const int it = __builtin_amdgcn_ds_bpermute(k << 2, list);
+                        const int j = it & (WAVE - 1), em = (it >> 8) & 15;
+                        const uint4 *rec = s_quad + j * QUAD_STAGE_U4;
+                        const uint4 hb = rec[2];
+                        const int x0 = (int)(int16_t)(hb.x & 0xffffu), x1 = (int)(int16_t)(hb.x >> 16);
+                        const int y0 = (int)(int16_t)(hb.y & 0xffffu), y1 = (int)(int16_t)(hb.y >> 16);
+                        // positions of the row, 0 .. 16: the box clamped to the tile and the frame
+                        int lo = max(x0 - gx, 0), hi = min(min(x1, f_width) - gx, TILE_W);
+                        const bool item = k < cnt && y >= max(y0, f_band_y0) && y < min(y1, f_band_y1) && lo < hi;
+                        if (counters) {                     // (quad, row) items: mr_debug_quad_walks
+                            const unsigned long long im = __ballot(item);
+                            if (lane == 0 && im) atomicAdd(&kernargs<TileKernArgs>().ta.ctr->pad0[1], (unsigned int)__popcll(im));
+                        }
+                        auto d2 = [](uint32_t l, uint32_t h) { return __hiloint2double((int)h, (int)l); };
+#pragma unroll 1
+                        for (int i = 0; i < 4; ++i) {
+                            if (item && ((em >> i) & 1)) {
+                                const uint4 a = rec[4 + 2 * i], b = rec[5 + 2 * i];
+                                const double sx = d2(a.x, a.y), ex = d2(b.x, b.y), ey = d2(b.z, b.w);
+                                const double cy = (dy - d2(a.z, a.w)) * ex;
+                                const bool down = ey < 0;
+                                // up(p): position p is on the side the half-line extends to on the right
+                                auto up = [&](int p) { return (((double)(gx + p) - sx) * ey - cy > 0) != down; };
+                                int f = up(7) ? 0 : 8;               // first position that is `up`, 0 .. 16
+                                f += up(f + 3) ? 0 : 4;
+                                f += up(f + 1) ? 0 : 2;
+                                f += up(f) ? 0 : 1;
+                                f += up(f) ? 0 : 1;
+                                if (down) hi = min(hi, f); else lo = max(lo, f);
+                            }
+                        }
+                        if (!item) hi = lo;
+                        if (lo < hi) {
+                            const uint4 p0 = rec[0], p1 = rec[1], p3 = rec[3];
+                            const double q_nx = d2(p0.x, p0.y), q_ny = d2(p0.z, p0.w), nzq = d2(p1.x, p1.y), q_d = d2(p1.z, p1.w);
+                            const double a0 = d2(p3.x, p3.y), b0 = d2(p3.z, p3.w);
+                            const bool need_z = !((it >> 16) & 1);
+                            const int delta = hb.w != 0 ? 1 : -1;
+                            unsigned int passed = 0;
+                            for (int x = lo; x < hi; ++x) {
+                                const int p = ly * TILE_W + x;
+                                bool pass = true;
+                                if (need_z)
+                                    pass = quad_depth_pass(q_nx, q_ny, nzq, q_d, a0, b0, (double)(gx + x), dy, z_unkey(s_key[p]), rh, true,
+                                                           f_plus_n, f_minus_n, two_nf);
+                                if (pass) { atomicAdd(&s_win[p], delta); ++passed; }
+                            }
+                            if (counters) {
+                                atomicAdd(&s_cnt[1], (unsigned int)(hi - lo));
+                                if (passed) atomicAdd(&s_cnt[2], passed);
+                            }
+                        }
+                    }
+                }
+            }
+
+            // (single light: the pixel's coordinates are worked out behind the span walk, whose registers they would take)
+            int px, py;
+            my_pixel(px, py);
+            const double dpx = (double)px, dpy = (double)py;
+            if (!ML && counters) {                          // (quad, strip) walks, and those the span walk is not defined for
+                const unsigned long long poly = todo & __ballot((emask & 16) != 0), wild = todo & __ballot(!q_finite);
+                Counters *ctr = kernargs<TileKernArgs>().ta.ctr;
+                if (lane == 0 && todo) atomicAdd(&ctr->pad0[2], (unsigned int)__popcll(todo));
+                if (lane == 0 && poly) atomicAdd(&ctr->pad0[3], (unsigned int)__popcll(poly));
+                if (lane == 0 && wild) atomicAdd(&ctr->pad0[4], (unsigned int)__popcll(wild));
+            }
             while (todo) {
                 const int j = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
@@ -799,34 +968,10 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 qfrags += (unsigned int)__popcll(m);
                 bool pass = true;
                 if (!((allpass >> j) & 1)) {
-                // Depth of the quad at the sample and the test against the z-buffer
-                // (obj/triangular.py:351-360): zq = two_nf / (f_plus_n + (t / nz) * f_minus_n) with
-                // t the plane's value at the sample.  The reference's value needs two IEEE divisions;
-                // the DECISION needs none: multiplied through by nz, zbest - zq has the sign of
-                // E / D with D = f_plus_n * nz + t * f_minus_n and E = zbest * D - two_nf * nz.
-                // That settles it unless z-buffer and quad depth agree to nine digits or D is close
-                // to its pole (or something is not finite); only then is the exactly rounded
-                // expression evaluated.  t itself is computed exactly as the reference does.
-                // Decisions stay bit-exact.
                 const double q_nx = __hiloint2double((int)p0.y, (int)p0.x), q_ny = __hiloint2double((int)p0.w, (int)p0.z);
                 const double nzq = __hiloint2double((int)p1.y, (int)p1.x), q_d = __hiloint2double((int)p1.w, (int)p1.z);
-                const double t = (q_nx * dpx + q_ny * dpy) + q_d;
-                const double a0 = d2(p3.x, p3.y), b0 = d2(p3.z, p3.w);          // f_plus_n * nz, two_nf * nz (staging)
-                const double tf = t * f_minus_n;
-                const double den = a0 + tf;
-                const double prod = zbest * den;
-                const double e = prod - b0;
-                // an empty z-buffer entry (+-inf) beats or loses against every finite depth
-                const bool zinf = fabs(zbest) == INFINITY;
-                pass = zinf ? (rh ? zbest > 0 : zbest < 0) : (rh ? ((e > 0) == (den > 0)) : ((e < 0) == (den > 0)));
-                const bool clear = zinf || fabs(e) > 1e-9 * (fabs(prod) + fabs(b0));
-                const bool unsure = in && !(clear && fabs(den) > 2e-4 * (fabs(a0) + fabs(tf)));
-                if (__ballot(unsure)) {
-                    if (unsure) {
-                        const double z = two_nf / (f_plus_n - (-t / nzq) * f_minus_n);     // linearize_z (obj/core.py:226-228)
-                        pass = rh ? (zbest >= z) : (zbest <= z);
-                    }
-                }
+                pass = quad_depth_pass(q_nx, q_ny, nzq, q_d, d2(p3.x, p3.y), d2(p3.z, p3.w), dpx, dpy, zbest, rh, in,
+                                       f_plus_n, f_minus_n, two_nf);
                 }
                 pass = pass && in;
                 qupd += (unsigned int)__popcll(__ballot(pass));
@@ -840,6 +985,10 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 sten += pass ? (front ? 1 : -1) : 0;
                 }
             }
+        }
+        if (!ML && kernargs<TileKernArgs>().ta.quad_walk != QUAD_WALK_STRIPS) {
+            __syncthreads();                              // every wavefront's spans are in
+            sten += s_win[lp];
         }
     }
 

@@ -778,6 +778,18 @@ int mr_debug_clusters_culled(mr_scene *sc)
     return (int)fs->h_counters->pad0[0];
 }
 
+int mr_debug_quad_walks(mr_scene *sc, uint32_t *out)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (!out) return fail(MR_E_INVALID, "NULL argument");
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = fetch_counters(fs, false)) return rc;
+    HIP_TRY(hipStreamSynchronize(fs->stream));
+    for (int k = 0; k < 4; ++k) out[k] = fs->h_counters->pad0[1 + k];
+    return MR_OK;
+}
+
 int mr_debug_sil_cache(mr_scene *sc, int32_t *out)
 {
     if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
