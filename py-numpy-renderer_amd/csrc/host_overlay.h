@@ -205,4 +205,50 @@ inline void build_overlay_slots(const int32_t *target /* (5, n_points) */, size_
     }
 }
 
+// Distinct values among the n_targets * count targets of one segment (target[k * stride + first .. + count)), counted
+// no further than limit + 1: an open-addressing table of at least twice that many entries, kept between calls.
+struct OverlayCountWork { std::vector<int32_t> keys; };
+inline int32_t count_distinct_targets(const int32_t *target, size_t stride, int n_targets, int32_t first, int32_t count, int32_t limit,
+                                      OverlayCountWork &ws)
+{
+    if (count <= 0 || n_targets <= 0) return 0;
+    if (limit < 0) limit = 0;
+    size_t cap = 16;
+    while (cap < 2 * ((size_t)limit + 1)) cap <<= 1;
+    ws.keys.assign(cap, -1);
+    int32_t distinct = 0;
+    for (int k = 0; k < n_targets; ++k) {
+        const int32_t *t = target + (size_t)k * stride + (size_t)first;
+        for (int32_t i = 0; i < count; ++i) {
+            size_t h = ((uint32_t)t[i] * 2654435761u) & (cap - 1);
+            while (ws.keys[h] != -1 && ws.keys[h] != t[i]) h = (h + 1) & (cap - 1);
+            if (ws.keys[h] == t[i]) continue;
+            ws.keys[h] = t[i];
+            if (++distinct > limit) return distinct;
+        }
+    }
+    return distinct;
+}
+
+// Which segments of the lists k_overlay must replay with its bidding words in global memory because the pixels they
+// touch would overfill its LDS table (kernels_overlay.h): sets `flag` in the count of every segment of `seg` (first,
+// count per segment) that has more than max_targets distinct targets.  Only segments of at most lds_points points are
+// looked at (longer ones take the global path anyway), and of those only the ones with more than max_targets targets
+// in all: a camera-built line (at most three distinct targets per point, host_overlay.h above) up to max_targets / 5
+// points long costs nothing here.  Returns the number of segments marked.
+inline int mark_overlay_segments(const int32_t *target /* (5, n_points) */, size_t n_points, int32_t *seg, size_t n_segments,
+                                 int32_t lds_points, int32_t max_targets, int32_t flag, OverlayCountWork &ws)
+{
+    int marked = 0;
+    for (size_t s = 0; s < n_segments; ++s) {
+        const int32_t first = seg[2 * s], count = seg[2 * s + 1];
+        if (count > lds_points || (long long)5 * count <= max_targets) continue;
+        if (count_distinct_targets(target, n_points, 5, first, count, max_targets, ws) > max_targets) {
+            seg[2 * s + 1] = count | flag;
+            ++marked;
+        }
+    }
+    return marked;
+}
+
 }  // namespace mr_host

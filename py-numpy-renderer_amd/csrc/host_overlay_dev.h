@@ -9,6 +9,9 @@ namespace {
 // and the overlay kernel's scratch.
 struct OverlayCopy {
     DevBuf lists, scratch;
+    DevBuf apply_scratch;                // mr_overlay_apply's compact state and bidding words, per slot of the touched pixels
+    size_t apply_slots = 0;              // the layout `apply_scratch` was last cleared for: number of slots ...
+    uint64_t apply_serial = 0;           // ... of the lists with this ov_serial
     void *staging = nullptr;
     size_t staging_cap = 0;
     size_t off[6] = {};                  // byte offsets of z, targets, segments, tile mask (+ slot ids, touched pixels) in `lists`
@@ -20,7 +23,8 @@ struct OverlayCopy {
     template <class T> const T *list(int i) const { return reinterpret_cast<const T *>(static_cast<const char *>(lists.p) + off[i]); }
     void release()
     {
-        lists.release(); scratch.release();
+        lists.release(); scratch.release(); apply_scratch.release();
+        apply_slots = 0; apply_serial = 0;
         if (staging) (void)hipHostFree(staging);
         if (copied) (void)hipEventDestroy(copied);
         staging = nullptr; staging_cap = 0; serial = 0; copied = nullptr;
@@ -29,6 +33,15 @@ struct OverlayCopy {
 
 // the corners of a frustum's six faces (obj/frustums.py)
 const int32_t FRUSTUM_FACES[24] = { 2, 4, 5, 3,  0, 1, 7, 6,  0, 2, 3, 1,  5, 4, 6, 7,  3, 5, 7, 1,  4, 2, 0, 6 };
+
+// Marks, in the scene's segment list, the segments whose targets would overfill k_overlay's LDS table: the kernel replays
+// them with its bidding words in global memory (kernels_overlay.h, OVERLAY_SEG_GLOBAL).  For every list the scene takes,
+// from the cameras or from mr_scene_set_overlay.
+void mark_global_segments(mr_scene *sc)
+{
+    mr_host::mark_overlay_segments(sc->ov_target.data(), sc->ov_z.size(), sc->ov_seg.data(), sc->ov_seg.size() / 2, mr::OVERLAY_LDS_POINTS,
+                                   mr::OVERLAY_LDS_TARGETS, mr::OVERLAY_SEG_GLOBAL, sc->ov_count_work);
+}
 
 // Builds the overlay's lists from the cameras mr_scene_set_overlay_cameras left (host_overlay.h: clipping, projection,
 // DDA, dashes, index wrapping -- obj/frustums.py:61-103, obj/line.py:6-16), if that has not happened yet.
@@ -50,6 +63,7 @@ void realize_overlay(mr_scene *sc)
     sc->ov_z.assign(lists.z.begin(), lists.z.end());
     sc->ov_seg.resize(2 * lists.seg_first.size());
     for (size_t i = 0; i < lists.seg_first.size(); ++i) { sc->ov_seg[2 * i] = lists.seg_first[i]; sc->ov_seg[2 * i + 1] = lists.seg_count[i]; }
+    mark_global_segments(sc);
     sc->ov_tile_mask.swap(lists.tile_mask);
     sc->ov_height = p.height; sc->ov_width = p.width;
     sc->ov_points = (int32_t)np; sc->ov_segments = (int32_t)lists.seg_first.size();

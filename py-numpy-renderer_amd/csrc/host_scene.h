@@ -102,7 +102,7 @@ struct mr_scene {
     uint64_t ov_serial = 0;                  // bumped whenever the lists change
     std::vector<int32_t> ov_target;          // (5, n_points) pixel row * width + col of every target
     std::vector<double> ov_z;
-    std::vector<int32_t> ov_seg;             // first point, number of points per segment
+    std::vector<int32_t> ov_seg;             // first point, number of points per segment (| OVERLAY_SEG_GLOBAL: mark_global_segments)
     std::vector<uint8_t> ov_tile_mask;       // the 16x16 tiles that hold a target
     // mr_scene_set_overlay_cameras only leaves its arguments here; the lists are built when first needed (realize_overlay)
     // -- for mr_render / mr_render_async AFTER the frame's three kernels have been launched, so that the host walks the
@@ -117,6 +117,7 @@ struct mr_scene {
     std::vector<int32_t> ov_slot_of, ov_touched;
     uint64_t ov_slots_serial = 0;            // the ov_serial the slot lists were built for
     mr_host::OverlaySlotWork ov_slot_work;
+    mr_host::OverlayCountWork ov_count_work;
 
     // ---- lanes of mr_render_async: a stream of the library's own each, and what is in flight on it
     struct Lane { hipStream_t stream = nullptr; bool busy = false; } lanes[MR_ASYNC_LANES];

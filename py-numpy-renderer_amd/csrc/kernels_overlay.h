@@ -19,6 +19,18 @@
 // phases, 206 us at 1080p.  What it must be is exact: the z-buffer it leaves is compared bit for bit with the
 // reference's.  The state arrays are the frame's own buffers (index = pixel) or, when the frame was assembled from
 // several devices, a compact copy of the touched pixels' state (index = slot, pixel_of[slot] the pixel).
+//
+// Where the bids are kept: a segment of at most OVERLAY_LDS_POINTS points whose targets are at most
+// OVERLAY_LDS_TARGETS distinct pixels bids in an LDS hash table of the pixels it touches; every other segment -- longer,
+// or short but spread over more pixels than the table may hold (a list handed to mr_scene_set_overlay need not be a
+// line: five distinct targets per point are valid) -- bids in win / any words in global memory, one per state entry.
+// The host decides (mr_host::mark_overlay_segments counts the distinct targets of the segments that could exceed the
+// limit and sets OVERLAY_SEG_GLOBAL in the device copy of their count), so the table never holds more than three
+// quarters of its entries and cannot fill; both of its probe loops are bounded by the table size all the same, so a
+// miscount would cost a pixel, not the device.  tests/test_overlay_lists_gpu.py holds both halves bit for bit to the
+// statement replay (frustums.OverlayOps.replay) on synthetic lists: every segment length around the block, the LDS
+// limit and the maximum, thousands of bidders on one pixel, the table at, one past and far past its load limit,
+// probes that wrap around its end, a supersampled frame, and a split frame whose lists change between calls.
 #pragma once
 
 #include "kernels_shade.h"
@@ -33,7 +45,7 @@ struct OverlayArgs {
     const double *z;                     // [n_points]
     const int32_t *seg;                  // [2 * n_segments] first point, number of points
     int32_t n_points, n_segments;
-    uint8_t *keep;                       // scratch [n_points] (segments too long for the LDS table)
+    uint8_t *keep;                       // scratch [n_points] (segments too long or too spread out for the LDS table)
     uint32_t *win, *any;                 // scratch [state entries], zero between segments and frames (ditto)
     double *st_z;                        // state: z ...
     float *st_f;                         // ... and float colour (3 per entry)
@@ -58,7 +70,15 @@ constexpr int OVERLAY_MAX_SEGMENT = 32768;      // points of one segment (a fram
 // table of the segment's touched pixels -- at most three per point: a line's neighbours overlap -- in the workgroup's
 // LDS takes the bids instead; longer segments (frames beyond 4K) keep the words in global memory.
 constexpr int OVERLAY_LDS_POINTS = 4096, OVERLAY_TABLE = 16384;
+// The table's load limit: three targets per point of the longest LDS segment, three quarters of the table.  A line
+// stays below it by construction; lists from mr_scene_set_overlay may not (up to five distinct targets per point), so
+// the host counts and sends the segments above it down the global path (OVERLAY_SEG_GLOBAL): the table cannot fill.
+constexpr int OVERLAY_LDS_TARGETS = OVERLAY_TABLE * 3 / 4;
 static_assert(3 * OVERLAY_LDS_POINTS <= OVERLAY_TABLE * 3 / 4 + OVERLAY_LDS_POINTS, "table load");
+static_assert(3 * OVERLAY_LDS_POINTS <= OVERLAY_LDS_TARGETS && OVERLAY_LDS_TARGETS < OVERLAY_TABLE, "table load");
+// bit of a segment's count in the DEVICE copy of the segment list: its bids go through global memory
+constexpr int32_t OVERLAY_SEG_GLOBAL = 1 << 30;
+static_assert(OVERLAY_MAX_SEGMENT < OVERLAY_SEG_GLOBAL, "flag bit clear of the count");
 
 __global__ void __launch_bounds__(OVERLAY_BLOCK)
 k_overlay(const OverlayArgs a, const double sign)
@@ -92,8 +112,8 @@ k_overlay(const OverlayArgs a, const double sign)
     };
     // One POINT per thread and step, its five targets side by side: the loads of a step are independent of each other.
     for (int s = 0; s < a.n_segments; ++s) {
-        const int first = a.seg[2 * s], count = min(a.seg[2 * s + 1], OVERLAY_MAX_SEGMENT);
-        if (count <= OVERLAY_LDS_POINTS) {
+        const int first = a.seg[2 * s], raw = a.seg[2 * s + 1], count = min(raw & ~OVERLAY_SEG_GLOBAL, OVERLAY_MAX_SEGMENT);
+        if (count <= OVERLAY_LDS_POINTS && !(raw & OVERLAY_SEG_GLOBAL)) {
             // A: keep = (z_buffer[row, col] - z) * sign >= 0; B: the kept (k, p) enter their targets in the table and bid
             for (int q = tid; q < count; q += OVERLAY_BLOCK) {
                 const int p = first + q;
@@ -107,11 +127,13 @@ k_overlay(const OverlayArgs a, const double sign)
                     for (int k = 0; k < OVERLAY_TARGETS; ++k) {
                         const uint32_t key = (uint32_t)X[k] + 1u;
                         uint32_t h = hash(key);
-                        for (;;) {
+                        int left = OVERLAY_TABLE;               // (the host keeps the table a quarter empty: never runs out)
+                        for (; left > 0; --left) {
                             const uint32_t seen = atomicCAS(&s_key[h], 0u, key);
                             if (seen == 0u || seen == key) break;
                             h = (h + 1u) & (OVERLAY_TABLE - 1);
                         }
+                        if (left == 0) continue;
                         atomicMax(&s_win[h], ((uint32_t)k << 26 | (uint32_t)q) + 1u);
                         atomicOr(&s_any[h >> 2], (1u << k) << (8 * (h & 3u)));
                     }
@@ -132,9 +154,10 @@ k_overlay(const OverlayArgs a, const double sign)
                     for (int k = 0; k < OVERLAY_TARGETS; ++k) {
                         const uint32_t key = (uint32_t)a.idx[k * np + p] + 1u;
                         uint32_t h = hash(key);
-                        while (s_key[h] != key) h = (h + 1u) & (OVERLAY_TABLE - 1);
+                        int left = OVERLAY_TABLE;
+                        while (left > 0 && s_key[h] != key) { h = (h + 1u) & (OVERLAY_TABLE - 1); --left; }
                         hh[j][k] = (uint16_t)h;
-                        if (s_win[h] == ((uint32_t)k << 26 | (uint32_t)q) + 1u) won[j] |= 1u << k;
+                        if (left > 0 && s_win[h] == ((uint32_t)k << 26 | (uint32_t)q) + 1u) won[j] |= 1u << k;
                     }
                 }
             }
@@ -158,7 +181,8 @@ k_overlay(const OverlayArgs a, const double sign)
             __syncthreads();
             continue;
         }
-        // ---- long segments: the same with the words in global memory (win / any, one per state entry)
+        // ---- long segments, and those the host found to touch more pixels than the table may hold: the same with the
+        // words in global memory (win / any, one per state entry)
         for (int q = tid; q < count; q += OVERLAY_BLOCK) {
             const int p = first + q;
             int X[OVERLAY_TARGETS];

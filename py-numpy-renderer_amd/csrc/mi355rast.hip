@@ -210,7 +210,8 @@ int mr_scene_set_overlay(mr_scene *sc, const mr_overlay_desc *ov)
         return fail(MR_E_INVALID, "overlay description: bad frame size");
     const int np = ov->n_points;
     // validate before the kernel trusts them: segments inside the point range, one after the other; targets pixels
-    // of the frame the description names
+    // of the frame the description names.  (Which pixels a segment's points target is free: a segment that touches more
+    // of them than the kernel's LDS table may hold is valid, and marked for the kernel's global path below.)
     long long expect = 0;
     for (int s = 0; s < ov->n_segments; ++s) {
         const long long first = ov->seg_first[s], count = ov->seg_count[s];
@@ -231,6 +232,7 @@ int mr_scene_set_overlay(mr_scene *sc, const mr_overlay_desc *ov)
     sc->ov_z.assign(ov->z, ov->z + np);
     sc->ov_seg.resize((size_t)2 * ov->n_segments);
     for (int i = 0; i < ov->n_segments; ++i) { sc->ov_seg[2 * i] = ov->seg_first[i]; sc->ov_seg[2 * i + 1] = ov->seg_count[i]; }
+    mark_global_segments(sc);
     const int tiles_x = (ov->width + mr::TILE_W - 1) / mr::TILE_W, tiles_y = (ov->height + mr::TILE_H - 1) / mr::TILE_H;
     sc->ov_tile_mask.assign((size_t)tiles_x * tiles_y, 0);
     for (int32_t t : sc->ov_target) sc->ov_tile_mask[(size_t)(t / ov->width / mr::TILE_H) * tiles_x + (size_t)(t % ov->width / mr::TILE_W)] = 1;
@@ -472,10 +474,15 @@ int mr_overlay_apply(mr_scene *sc, const void *d_parts, int64_t part_stride, int
     if (!fs) return fail(MR_E_DEVICE, "out of frame slots");
     if ((rc = sync_slot_overlay(sc, fs->ov, stream, true))) return rc;
     const int n_slots = (int)sc->ov_touched.size();
-    // the compact state and the bidding words, per slot of the list of touched pixels (the words zero between frames)
-    // (in a buffer this path owns: the matrix-core vertex path does not run on assembled frames)
-    if ((rc = ensure_cleared(fs->d_vclip, (size_t)n_slots * (8 + 12 + 4 + 4) + (size_t)sc->ov_points + 64, stream))) return rc;
-    char *scratch = static_cast<char *>(fs->d_vclip.p);
+    // The compact state and the bidding words, per slot of the list of touched pixels, in a buffer of the slot's overlay
+    // copy that nothing else writes: z | colour | win | any | keep, at offsets that depend on n_slots.  The kernel leaves
+    // win / any zero, so they stay zero from call to call while the layout stays; with other lists (another number of
+    // slots, or another serial) the words may lie where the last call kept colours or z, and the buffer is cleared.
+    OverlayCopy &ov = fs->ov;
+    const bool stale = ov.apply_slots != (size_t)n_slots || ov.apply_serial != sc->ov_serial;
+    if ((rc = ensure_cleared(ov.apply_scratch, (size_t)n_slots * (8 + 12 + 4 + 4) + (size_t)sc->ov_points + 64, stream, 0, stale))) return rc;
+    ov.apply_slots = (size_t)n_slots; ov.apply_serial = sc->ov_serial;
+    char *scratch = static_cast<char *>(ov.apply_scratch.p);
     OverlayArgs oa = overlay_args(sc, fs->ov, true, reinterpret_cast<uint32_t *>(scratch + (size_t)n_slots * 20), (size_t)n_slots);
     oa.st_z = reinterpret_cast<double *>(scratch);
     oa.st_f = reinterpret_cast<float *>(scratch + (size_t)n_slots * 8);

@@ -33,8 +33,9 @@ def test_overlay_on_oracle_buffers_matches_reference(api, oracle_mod, name):
 
 
 def test_statement_lists_are_well_formed(api):
-    """What mr_scene_set_overlay validates: links point forward inside their own segment, targets are pixels
-    of the frame, `touched` is exactly the set of targets."""
+    """The lists as OverlayOps builds them: targets are pixels of the frame (what mr_scene_set_overlay validates, with
+    the segments' layout), `touched` is exactly the set of targets, and the links -- which the device does not take and
+    mr_scene_set_overlay no longer sees -- point forward inside their own segment to a point with the same target."""
     from py_numpy_renderer_amd.frustums import OverlayOps
     scene = scenes.build(api, "diablo_floor_lh_gl")
     ops = OverlayOps(scene.camera, scene.debug_camera, scene.resolution)
