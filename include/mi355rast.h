@@ -479,6 +479,49 @@ int mr_debug_skin(mr_scene *scene, int32_t *out);
 #define MR_N_SKIN_TIMES 2
 int mr_debug_skin_times(mr_scene *scene, float *out_ms);
 
+/* A model's morph targets (blend shapes), CSR by target: target k displaces vertex index[j] by delta[3 j .. 3 j + 2] for
+ * j in [first[k], first[k + 1]); first has n_targets + 1 offsets and starts at 0.  nfirst / nindex / ndelta are the same
+ * for the model's vertex normals (their indices count the normals, not the vertices), or NULL when the normals do not
+ * follow the morph.  first == NULL removes the morph and its weights.  Every index lies inside the model's vertex (normal)
+ * count and is named at most once per target, every delta is finite, n_targets >= 1: checked here, so that the kernels
+ * index without checks.  Everything is copied during the call (as per-vertex lists in ascending target order, padded per
+ * 64 vertices to the longest list among them; the padded totals must fit 32 bits) and nothing is launched; a morph alone
+ * changes no frame.  Setting a morph puts the model in the rest shape (no weights).  MR_E_INVALID otherwise, also for
+ * normal tables on a model without normals. */
+int mr_scene_set_model_morph(mr_scene *scene, int32_t model, int32_t n_targets, const int32_t *first, const int32_t *index,
+                             const double *delta, const int32_t *nfirst, const int32_t *nindex, const double *ndelta);
+
+/* The weights of a model that has a morph: w is (n_targets) float64, used as given (not clamped); NULL is the rest shape
+ * (the model as it was added).  With weights w the model renders as if its vertices were the float64 array
+ *   V_m[i][c] = vertices[i][c], then acc = fma(w[k], delta_k[i][c], acc) for every target k that lists i, k ascending  (c < 3)
+ *   V_m[i][3] = vertices[i][3]
+ * -- a listed target takes its step also with a weight of 0 -- and, with normal tables, its vertex normals the float32
+ * array formed by the same chain from float64(normal), rounded once.  Skin, pose and normal matrix apply to that model:
+ * morph first, then skin, then pose.  V_m is float64: the model behaves as one with vertices_are_f32 == 0, as a posed one
+ * does.  The call copies w and launches nothing; the next frame's pose pass does the work (k_morph_vertices,
+ * k_morph_normals, then the kernels of every pose pass).  MR_E_INVALID for a model index out of range, a model without a
+ * morph, n_targets other than the morph's, or a weight that is not finite. */
+int mr_scene_set_model_morph_weights(mr_scene *scene, int32_t model, const double *w, int32_t n_targets);
+
+/* Host arithmetic, no device needed: V_m of mr_scene_set_model_morph_weights for n vectors -- base and out are (n, width)
+ * float64, width 4 (vertices; the fourth component passes through) or 3 (normals widened to float64; out is not rounded)
+ * -- from the tables as mr_scene_set_model_morph takes them and n_targets weights.  It builds the per-vertex lists the
+ * device path builds and walks them in the kernels' order, bit for bit.  MR_OK, or MR_E_INVALID for tables
+ * mr_scene_set_model_morph would refuse or a width other than 3 and 4. */
+int mr_host_morph_chain(const double *base, int32_t n, int32_t width, int32_t n_targets, const int32_t *first, const int32_t *index,
+                        const double *delta, const double *w, double *out);
+
+/* Diagnostics of the morphs: out[0] = models that have weights now, out[1] = targets (weights) the last pose pass
+ * uploaded, out[2] = vertices and out[3] = normals it morphed, out[4] = entries, padding included, of the lists on the
+ * device.  Does not wait for the device. */
+int mr_debug_morph(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds of the two morph kernels of the last pose pass: [0] k_morph_vertices  [1] k_morph_normals
+ * (0 for one that pass did not launch).  k_morph_vertices runs inside span [0] of mr_debug_pose_times.  MR_E_INVALID
+ * before the first pass over a morph. */
+#define MR_N_MORPH_TIMES 2
+int mr_debug_morph_times(mr_scene *scene, float *out_ms);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

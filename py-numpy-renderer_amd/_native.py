@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_skin, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -152,6 +152,11 @@ _PROTOTYPES = {
     "mr_host_skin_chain3": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "mr_debug_skin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_skin_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_scene_set_model_morph": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "mr_scene_set_model_morph_weights": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "mr_host_morph_chain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
+    "mr_debug_morph": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_morph_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -296,6 +301,7 @@ class DeviceRenderer:
         self._signature = None
         self._pose_keys = []                 # per model: (bytes of the pose, bytes of the normal matrix or None) the library holds, or None
         self._skin_keys = {}                 # model index -> [serial of the skin, its bone count, bytes of the bones or None] the library holds
+        self._morph_keys = {}                # model index -> [serial of the morph, bytes of the weights or None] the library holds
         self._sky_key = None
         self._last_stats = {}
         self._frame = None
@@ -330,12 +336,14 @@ class DeviceRenderer:
         (``_scene_signature``), and the models' poses, which are no part of that signature, beside it."""
         for model in scene.models:
             active_skin(model)                   # (a skin that no longer fits its vertices: ValueError before any device work)
+            active_morph(model)                  # (... or a morph)
         sig = self._scene_signature(scene)
         if sig != self._signature:
             self._upload_scene(scene)
             self._signature = sig
             self._pose_keys = [None] * len(scene.models)        # (mr_scene_clear dropped the poses)
             self._skin_keys = {}                                 # (... and the skins)
+            self._morph_keys = {}                                # (... and the morphs)
         self.sync_poses(scene)
 
     def sync_poses(self, scene):
@@ -343,9 +351,12 @@ class DeviceRenderer:
         ``mr_scene_set_model_pose_normals`` after it where the normal matrix (``Model.pose_normals``) is not; then the
         same for the skins: a model is keyed by (pose bytes, G bytes) and (serial of its skin, bones bytes), and each of
         ``mr_scene_set_model_skin`` / ``mr_scene_set_model_bones`` is called when its part changed.  A skin goes to the
-        library when its model first has bones: a scene without bones makes no call."""
+        library when its model first has bones: a scene without bones makes no call.  The morphs likewise: (serial of the
+        morph, weight bytes), ``mr_scene_set_model_morph`` / ``mr_scene_set_model_morph_weights``, the tables handed over
+        when the model first has weights."""
         keys = self._pose_keys
         for index, model in enumerate(scene.models):
+            self._sync_morph(index, model)
             self._sync_skin(index, model)
             pose = getattr(model, "pose", None)
             g = None if pose is None else pose_normal_matrix(model)
@@ -359,6 +370,31 @@ class DeviceRenderer:
                 _check(self.lib.mr_scene_set_model_pose_normals(self.handle, index, None if g is None else g.ctypes.data),
                        "mr_scene_set_model_pose_normals")
             keys[index] = key
+
+    def _sync_morph(self, index, model):
+        keys = self.__dict__.setdefault("_morph_keys", {})
+        held = keys.get(index)                   # [serial of the morph, bytes of the weights or None]
+        morph = active_morph(model)
+        if morph is None:
+            if held is not None and held[1] is not None:       # morph_weights = None, or the morph is gone: the rest shape
+                _check(self.lib.mr_scene_set_model_morph_weights(self.handle, index, None, 0), "mr_scene_set_model_morph_weights")
+                held[1] = None
+            return
+        if held is None:
+            held = keys[index] = [None, None]
+        if held[0] != model._morph_serial:
+            first, vindex, delta = morph_csr(morph.targets)
+            nfirst, nindex, ndelta = (None, None, None) if morph.normal_targets is None else morph_csr(morph.normal_targets)
+            ptr = lambda a: None if a is None else a.ctypes.data
+            _check(self.lib.mr_scene_set_model_morph(self.handle, index, len(morph.targets), ptr(first), ptr(vindex), ptr(delta),
+                                                     ptr(nfirst), ptr(nindex), ptr(ndelta)), "mr_scene_set_model_morph")
+            held[:] = [model._morph_serial, None]
+        weights = model.morph_weights
+        key = weights.tobytes()
+        if held[1] != key:
+            _check(self.lib.mr_scene_set_model_morph_weights(self.handle, index, weights.ctypes.data, len(weights)),
+                   "mr_scene_set_model_morph_weights")
+            held[1] = key
 
     def _sync_skin(self, index, model):
         keys = self.__dict__.setdefault("_skin_keys", {})
@@ -749,6 +785,21 @@ class DeviceRenderer:
         out = (C.c_int32 * 4)()
         _check(self.lib.mr_debug_skin(self.handle, out), "mr_debug_skin")
         return tuple(int(x) for x in out)
+
+    def morph_counters(self):
+        """``mr_debug_morph``: (models that have morph weights, targets the last pose pass used, vertices and normals it
+        morphed, entries -- padding included -- of the contribution lists on the device)."""
+        out = (C.c_int32 * 5)()
+        _check(self.lib.mr_debug_morph(self.handle, out), "mr_debug_morph")
+        return tuple(int(x) for x in out)
+
+    MORPH_TIME_NAMES = ("morph_vertices", "morph_normals")
+
+    def morph_times(self):
+        """Device milliseconds of the two morph kernels of the last pose pass (``mr_debug_morph_times``)."""
+        buf = (C.c_float * 2)()
+        _check(self.lib.mr_debug_morph_times(self.handle, buf), "mr_debug_morph_times")
+        return dict(zip(self.MORPH_TIME_NAMES, (float(v) for v in buf)))
 
     SKIN_TIME_NAMES = ("skin_vertices", "skin_normals")
 

@@ -234,6 +234,183 @@ def active_skin(model):
     return skin
 
 
+def _morph_entry(entry, what):
+    """One morph target as ``(indices, deltas)``: read-only ``int32`` ``(n_k,)`` and ``float64`` ``(n_k, 3)`` copies.
+    *entry* is a pair of that form or a dense ``(n, 3)`` array, which means ``(arange(n), array)``."""
+    pair = None
+    if isinstance(entry, (tuple, list)) and len(entry) == 2:
+        first, second = _numbers(entry[0], f"{what} indices"), _numbers(entry[1], f"{what} deltas")
+        if first.ndim == 1 and second.ndim == 2:
+            pair = (first, second)
+    if pair is None:
+        dense = _numbers(entry, what)
+        if dense.ndim != 2 or dense.shape[1] != 3:
+            raise ValueError(f"{what} must be (indices, deltas) or a dense (n, 3) array, got shape {dense.shape}")
+        pair = (np.arange(len(dense), dtype=np.float64), dense)
+    i, d = pair
+    if d.shape != (len(i), 3):
+        raise ValueError(f"{what} deltas must be ({len(i)}, 3), got shape {d.shape}")
+    if not np.isfinite(d).all():
+        raise ValueError(f"{what} deltas must be finite")
+    if not np.isfinite(i).all() or (i != np.floor(i)).any():
+        raise ValueError(f"{what} indices must be integers")
+    if (i < 0).any():
+        raise ValueError(f"{what} indices must not be negative")
+    if i.size and i.max() > np.iinfo(np.int32).max:
+        raise ValueError(f"{what} indices must fit 32 bits")
+    i, d = np.ascontiguousarray(i.astype(np.int32)), np.ascontiguousarray(d)
+    if len(np.unique(i)) != len(i):
+        raise ValueError(f"{what} names an index twice")
+    i.setflags(write=False)
+    d.setflags(write=False)
+    return i, d
+
+
+def _morph_entries(value, what):
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__") or not hasattr(value, "__iter__"):
+        raise TypeError(f"{what} must be a sequence of targets, got {type(value).__name__}")
+    return list(value)
+
+
+def check_morph(targets, normal_targets=None):
+    """The parts of a ``Morph``: *targets* a sequence of t >= 1 entries, each a pair ``(indices, deltas)`` -- ``(n_k,)``
+    integral, not negative and without duplicates; ``(n_k, 3)`` finite -- or a dense ``(n, 3)`` array; *normal_targets*
+    ``None`` or t entries of the same forms, ``None`` among them for a target that moves no normal.  Returns two tuples of
+    ``(int32 indices, float64 deltas)`` pairs, read-only copies (the second ``None`` without *normal_targets*).
+    ``TypeError`` for what is no sequence of arrays of numbers, ``ValueError`` for a wrong shape or a wrong value."""
+    entries = _morph_entries(targets, "morph targets")
+    if len(entries) < 1:
+        raise ValueError("a morph needs at least one target")
+    out = tuple(_morph_entry(e, f"morph target {k}") for k, e in enumerate(entries))
+    if normal_targets is None:
+        return out, None
+    entries = _morph_entries(normal_targets, "morph normal_targets")
+    if len(entries) != len(out):
+        raise ValueError(f"normal_targets must have one entry per target ({len(out)}), got {len(entries)}")
+    none = (np.zeros(0, dtype=np.int32), np.zeros((0, 3), dtype=np.float64))
+    for arr in none:
+        arr.setflags(write=False)
+    return out, tuple(none if e is None else _morph_entry(e, f"morph normal target {k}") for k, e in enumerate(entries))
+
+
+def morph_csr(pairs):
+    """The tables of ``check_morph`` as the C ABI takes them, CSR by target: ``(first (t + 1,) int32, index int32,
+    delta (N, 3) float64)``."""
+    first = np.zeros(len(pairs) + 1, dtype=np.int64)
+    first[1:] = np.cumsum([len(i) for i, _ in pairs])
+    if first[-1] > np.iinfo(np.int32).max:
+        raise ValueError("the morph's targets list more than 2^31 - 1 entries")
+    index = np.ascontiguousarray(np.concatenate([i for i, _ in pairs]), dtype=np.int32)
+    delta = np.ascontiguousarray(np.concatenate([d for _, d in pairs]), dtype=np.float64)
+    return np.ascontiguousarray(first, dtype=np.int32), index, delta
+
+
+def check_morph_weights(value):
+    """``Model.morph_weights``: ``None``, or a finite ``(t,)`` array with t >= 1, returned as a read-only float64 copy."""
+    if value is None:
+        return None
+    w = _numbers(value, "morph weights")
+    if w.ndim != 1 or w.shape[0] < 1:
+        raise ValueError(f"morph weights must be (t,) with t >= 1, got shape {w.shape}")
+    if not np.isfinite(w).all():
+        raise ValueError("morph weights must be finite")
+    w = np.ascontiguousarray(w)
+    w.setflags(write=False)
+    return w
+
+
+def check_morph_pair(morph, weights):
+    """What only the pair can break: one weight per target."""
+    if morph is not None and weights is not None and len(weights) != len(morph.targets):
+        raise ValueError(f"the morph has {len(morph.targets)} targets, morph_weights {len(weights)} entries")
+
+
+def check_morph_fits(morph, model):
+    """Every index of *morph* names a vertex (a normal) of *model*; normal targets need a model that has normals."""
+    n = len(model.vertices)
+    reach = max((int(i.max()) for i, _ in morph.targets if i.size), default=-1)
+    if reach >= n:
+        raise ValueError(f"the morph reaches vertex {reach}, the model has {n} vertices")
+    if morph.normal_targets is not None:
+        if model.normals is None:
+            raise ValueError("normal_targets need a model that has normals")
+        reach = max((int(i.max()) for i, _ in morph.normal_targets if i.size), default=-1)
+        if reach >= len(model.normals):
+            raise ValueError(f"the morph reaches normal {reach}, the model has {len(model.normals)} normals")
+
+
+def active_morph(model):
+    """The model's ``Morph`` when it has ``morph_weights`` too and so moves, else ``None``; ``ValueError`` for a morph
+    whose indices no longer fit the model (``vertices`` or ``normals`` was replaced after the morph was set)."""
+    morph, weights = getattr(model, "morph", None), getattr(model, "morph_weights", None)
+    if morph is None or weights is None:
+        return None
+    check_morph_fits(morph, model)
+    check_morph_pair(morph, weights)
+    return morph
+
+
+_native_morph = None         # mr_host_morph_chain of the HIP library, or False
+
+
+def _fast_morph():
+    """The library's host helper, if the library is built (it loads without a GPU); else the loop below."""
+    global _native_morph
+    if _native_morph is None:
+        try:
+            from ._native import load_library
+            _native_morph = load_library().mr_host_morph_chain
+        except Exception:           # not built / not loadable here: the pure-Python chain gives the same bits
+            _native_morph = False
+    return _native_morph
+
+
+def _morph_chain(base, pairs, weights, native):
+    """``acc = base[i][c]``, then ``acc = fma(w[k], d_k[i][c], acc)`` for every target k that lists i, k ascending, for
+    the first three columns of the float64 array *base*; further columns pass through."""
+    base = np.ascontiguousarray(base, dtype=np.float64)
+    out = base.copy()
+    fast = _fast_morph() if native is None or native else False
+    if fast:
+        first, index, delta = morph_csr(pairs)
+        rc = fast(base.ctypes.data, len(base), base.shape[1], len(pairs), first.ctypes.data, index.ctypes.data, delta.ctypes.data,
+                  weights.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise ValueError("mr_host_morph_chain refused the morph's tables")
+        return out
+    from ._fp import fma
+    for k, (index, delta) in enumerate(pairs):
+        w = float(weights[k])
+        for i, d in zip(index.tolist(), delta.tolist()):
+            for c in range(3):
+                out[i, c] = fma(w, d[c], float(out[i, c]))
+    return out
+
+
+def morphed_vertices(model, native=None):
+    """The float64 vertices ``V_m`` of a model that has ``morph`` and ``morph_weights``: vertex i starts from
+    ``float64(vertices[i])`` and takes ``fma(w[k], d_k[i][c], .)`` for every target k that lists it, k ascending, in its
+    first three components; ``None`` for a model without the pair.  *native*: ``False`` forces the pure-Python chain, the
+    yardstick of the library's ``mr_host_morph_chain``."""
+    morph = active_morph(model)
+    if morph is None:
+        return None
+    return _morph_chain(np.asarray(model.vertices).astype(np.float64), morph.targets, model.morph_weights, native)
+
+
+def morphed_normals(model, native=None):
+    """The float32 normals ``N_m`` of a model whose normals follow its morph (``normal_targets``, ``morph_weights`` set,
+    ``normals`` not ``None``): the chain of ``morphed_vertices`` from ``float64(float32(normals))`` over the normal
+    targets, rounded to float32 once, the shape kept.  ``None`` for every other model."""
+    morph = active_morph(model)
+    if morph is None or morph.normal_targets is None or model.normals is None:
+        return None
+    normals = np.ascontiguousarray(model.normals, dtype=np.float32)
+    out = normals.copy()
+    out[:, :3] = _morph_chain(normals[:, :3].astype(np.float64), morph.normal_targets, model.morph_weights, native).astype(np.float32)
+    return out
+
+
 def normal_owners(model):
     """(len(normals),) int32: for every vertex normal the (non-negative) vertex index at the first (face, corner) of
     ``_faces`` in row-major order whose normal column names it; -1 for a normal no corner references."""
@@ -282,7 +459,9 @@ def skinned_vertices(model, native=None):
     skin = active_skin(model)
     if skin is None:
         return None
-    verts = np.ascontiguousarray(np.asarray(model.vertices).astype(np.float64))
+    verts = morphed_vertices(model, native)          # (morph first, then skin)
+    if verts is None:
+        verts = np.ascontiguousarray(np.asarray(model.vertices).astype(np.float64))
     bones = model.bones
     check_skin_pair(skin, bones)
     out = np.empty_like(verts)
@@ -306,7 +485,8 @@ def skinned_normals(model, native=None):
     skin = active_skin(model)
     if skin is None or not skin.normals or model.normals is None:
         return None
-    vectors = np.ascontiguousarray(np.ascontiguousarray(model.normals, dtype=np.float32)[:, :3].astype(np.float64))
+    followed = morphed_normals(model, native)        # (float32: the morph's normals are rounded before the skin takes them)
+    vectors = np.ascontiguousarray(np.ascontiguousarray(model.normals if followed is None else followed, dtype=np.float32)[:, :3].astype(np.float64))
     owners = normal_owners(model)
     bones = model.bones
     check_skin_pair(skin, bones)
@@ -326,11 +506,13 @@ def skinned_normals(model, native=None):
 
 
 def posed_vertices(model):
-    """The vertices a model renders with: ``model.vertices``; with ``skin`` and ``bones`` the float64 array
-    ``skinned_vertices(model)``; with a pose ``matmul_chain`` of either (widened to float64) and the pose -- skin first,
+    """The vertices a model renders with: ``model.vertices``; with ``morph`` and ``morph_weights`` the float64 array
+    ``morphed_vertices(model)``; with ``skin`` and ``bones`` the float64 array ``skinned_vertices(model)`` of that; with a pose ``matmul_chain`` of either (widened to float64) and the pose -- skin first,
     then pose (``Model.skin``, ``Model.pose``)."""
     pose = getattr(model, "pose", None)
     verts = skinned_vertices(model)
+    if verts is None:
+        verts = morphed_vertices(model)
     if verts is None:
         verts = np.asarray(model.vertices)
     if pose is None:
@@ -396,9 +578,11 @@ def posed_normals(model):
         from ._fp import matmul_chain
         shape = np.asarray(model.normals).shape
         return (followed if g is None else matmul_chain(followed, g)).astype(np.float32).reshape(shape)
+    morphed = morphed_normals(model)                 # (the morph's normals take the place of ``normals`` themselves)
+    normals = model.normals if morphed is None else morphed
     if g is None:
-        return model.normals
-    return _chain_f32(model.normals, g)
+        return normals
+    return _chain_f32(normals, g)
 
 
 def posed_normal_map(texels, g):
@@ -482,8 +666,8 @@ def _posed_map_id(tex, g, model, textures, seen):
 
 
 def pack_model(model, textures, seen, posed=False) -> PackedModel:
-    """*posed*: pack the arrays the model renders with -- ``posed_vertices`` (skin, then pose) and, with ``pose_normals`` or
-    a skin the normals follow, ``posed_normals``, and with ``pose_normals`` re-baked object-space normal maps -- instead of
+    """*posed*: pack the arrays the model renders with -- ``posed_vertices`` (morph, then skin, then pose) and, with
+    ``pose_normals``, a skin or a morph the normals follow, ``posed_normals``, and with ``pose_normals`` re-baked object-space normal maps -- instead of
     ``model.vertices`` / ``normals`` / the maps as registered: what the oracle needs; the device gets the arrays as they
     are and the matrices and tables beside them (``mr_scene_set_model_pose``, ``mr_scene_set_model_pose_normals``,
     ``mr_scene_set_model_skin``, ``mr_scene_set_model_bones``)."""
@@ -497,7 +681,9 @@ def pack_model(model, textures, seen, posed=False) -> PackedModel:
                          f"(got {faces.shape})")
     uv = None if model.uv is None else np.ascontiguousarray(model.uv, dtype=np.float32)
     normals = None if model.normals is None else np.ascontiguousarray(model.normals, dtype=np.float32)
-    if posed and normals is not None and (nmat is not None or (active_skin(model) is not None and model.skin.normals)):
+    morph = active_morph(model) if posed else None
+    if posed and normals is not None and (nmat is not None or (active_skin(model) is not None and model.skin.normals)
+                                          or (morph is not None and morph.normal_targets is not None)):
         normals = np.ascontiguousarray(posed_normals(model))
     if uv is not None and (uv.ndim != 2 or uv.shape[1] < 2):
         raise ValueError(f"Model.uv must be (T, 3), got {uv.shape}")

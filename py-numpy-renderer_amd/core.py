@@ -88,6 +88,33 @@ class Skin:
         return f"Skin({len(self.joints)} vertices, normals={self.normals})"
 
 
+_morph_serial = itertools.count(1)     # ... and every assignment of Model.morph
+
+
+class Morph:
+    """What ``Model.morph`` holds: the static part of morph targets (blend shapes).  ``targets`` is a sequence of t >= 1
+    entries, each a pair ``(indices, deltas)`` -- ``(n_k,)`` integers, not negative, no index twice in one target (kept as
+    read-only ``int32``), and ``(n_k, 3)`` finite numbers (read-only ``float64``) -- or a dense ``(n, 3)`` array, which
+    means ``(arange(n), array)``: target k displaces vertex ``indices[j]`` by ``w[k] * deltas[j]``.  ``normal_targets`` is
+    ``None`` or t entries of the same forms (``None`` among them for a target that moves no normal) whose indices count
+    ``model.normals``.  A ``Morph`` is never modified: assign a new one to change it.  ``TypeError`` for what is no
+    sequence of arrays of numbers, ``ValueError`` for a wrong shape or value."""
+
+    __slots__ = ("targets", "normal_targets")
+
+    def __init__(self, targets, normal_targets=None):
+        from ._pack import check_morph
+        t, n = check_morph(targets, normal_targets)
+        object.__setattr__(self, "targets", t)
+        object.__setattr__(self, "normal_targets", n)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Morph is read-only: assign a new Morph to Model.morph")
+
+    def __repr__(self):
+        return f"Morph({len(self.targets)} targets, normal_targets={self.normal_targets is not None})"
+
+
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
     (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
@@ -134,7 +161,24 @@ class Model:
     ``pose_normals`` does to them).  Assignments are checked at once: ``bones`` without a ``skin``, and a joint that
     reaches past the last bone -- at whichever of the two assignments completes the pair -- raise ``ValueError`` and the
     attribute keeps its value; ``skin = None`` drops ``bones`` as well.  A skin whose row count no longer equals
-    ``len(vertices)`` raises ``ValueError`` at ``render()``."""
+    ``len(vertices)`` raises ``ValueError`` at ``render()``.
+
+    ``morph`` and ``morph_weights`` (additions; both ``None`` by default) deform the model by morph targets (blend
+    shapes), again without a re-upload.  ``morph`` is a ``Morph(targets, normal_targets=None)`` -- the static part, handed
+    to the device once -- and ``morph_weights`` a ``(t,)`` array (kept as a read-only float64 copy), the part that changes
+    per frame.  With both set the model renders as the model whose ``vertices`` is the float64 array ``V_m``: for c in
+    0..2 ``acc = float64(vertices[i][c])``, then ``acc = _fp.fma(w[k], d_k[i][c], acc)`` for every target k that lists
+    vertex i, k ascending; ``V_m[i][3] = float64(vertices[i][3])``.  With ``normal_targets`` its ``normals`` is the float32
+    array ``N_m``: the same chain from ``float64(float32(normals[q][c]))`` over the normal targets, rounded to float32
+    once.  Weights are used as given: not clamped, they may be negative or above 1; a target that lists the vertex takes
+    its step even with weight 0, so all-zero weights are not promised to equal ``morph_weights = None`` bit for bit
+    (``-0.0 + 0 * d`` is ``+0.0``) -- ``None`` is the un-morphed model.  Everything else applies to that model: the order is
+    morph, then skin, then pose.  ``V_m`` is float64, so a morphed float32 model behaves as a float64 one.  ``vertices``
+    and ``normals`` are never modified.  Object-space normal maps do not follow a morph; tangent-space maps follow by
+    themselves.  Assignments are checked at once: an index past ``len(vertices)`` (``len(normals)``), ``normal_targets``
+    on a model without normals, ``morph_weights`` without a ``morph``, and a weight count other than t -- at whichever of
+    the two assignments completes the pair -- raise ``ValueError`` and the attribute keeps its value; ``morph = None``
+    drops ``morph_weights`` as well.  A morph whose indices no longer fit the model raises ``ValueError`` at ``render()``."""
 
     def __init__(self, vertices, uv, normals, faces, shadowing=False, materials=None,
                  material_group=None, clip=True, depth_test=True):
@@ -157,6 +201,9 @@ class Model:
         self._skin = None
         self._bones = None
         self._skin_serial = 0
+        self._morph = None
+        self._morph_weights = None
+        self._morph_serial = 0
 
     # -- ingest ---------------------------------------------------------------------------
     @classmethod
@@ -288,6 +335,38 @@ class Model:
             raise ValueError("bones need a skin: assign Model.skin first")
         check_skin_pair(self.skin, bones)
         self._bones = bones
+
+    @property
+    def morph(self):
+        """``None`` or the model's ``Morph`` (targets, normal targets); see the class docstring."""
+        return getattr(self, "_morph", None)
+
+    @morph.setter
+    def morph(self, value):
+        from ._pack import check_morph_fits, check_morph_pair
+        if value is None:
+            self._morph, self._morph_weights = None, None      # (no morph, no weights)
+            return
+        if not isinstance(value, Morph):
+            raise TypeError(f"morph must be None or a Morph, got {type(value).__name__}")
+        check_morph_fits(value, self)
+        check_morph_pair(value, self.morph_weights)        # (refused here, and the last morph stays)
+        self._morph, self._morph_serial = value, next(_morph_serial)
+
+    @property
+    def morph_weights(self):
+        """``None`` (the rest shape) or the ``(t,)`` float64 weights (read-only: assign a new array to move the model);
+        see the class docstring."""
+        return getattr(self, "_morph_weights", None)
+
+    @morph_weights.setter
+    def morph_weights(self, value):
+        from ._pack import check_morph_pair, check_morph_weights
+        weights = check_morph_weights(value)
+        if weights is not None and self.morph is None:
+            raise ValueError("morph_weights need a morph: assign Model.morph first")
+        check_morph_pair(self.morph, weights)
+        self._morph_weights = weights
 
     def __matmul__(self, other):
         self.vertices = self.vertices @ other

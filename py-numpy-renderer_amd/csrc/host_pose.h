@@ -10,6 +10,11 @@
 // A model that has a skin and bones (mr_scene_set_model_skin, mr_scene_set_model_bones) is to the pass what a posed one
 // is: its vertices come from k_skin_vertices instead of k_pose_vertices (the pose, if any, applied after the skin), its
 // normals, where they follow the skin, from k_skin_normals (apply_skin_normals); everything after that is the same code.
+// A model that has a morph and weights (mr_scene_set_model_morph, mr_scene_set_model_morph_weights) comes first in the
+// pass: k_morph_vertices writes its morphed vertices -- straight into d_verts when neither skin nor pose follows, else into
+// d_verts_m, the copy of d_verts0 that k_skin_vertices and k_pose_vertices then take as their pristine source -- and
+// k_morph_normals does the same for its normals with d_normals_m (apply_morph_normals).  The kernels that follow are
+// the same code with another source pointer.
 // The pass is synchronous: it waits for the device before it starts (frames in flight on other streams read the static
 // records: the rule of commit() and mr_scene_add_model) and for its own kernels before it returns.
 #pragma once
@@ -96,6 +101,52 @@ void set_model_bones(mr_scene *sc, int32_t model, const double *bones16)
     else if (was_n) sc->skin_n_dirty = true;
 }
 
+// mr_scene_set_model_morph behind its argument checks (the tables are checked: mr_morph::check_tables): the per-vertex
+// lists are built and kept; a morph alone moves nothing
+int set_model_morph(mr_scene *sc, int32_t model, int32_t n_targets, const int32_t *first, const int32_t *index, const double *delta,
+                    const int32_t *nfirst, const int32_t *nindex, const double *ndelta)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    if (!first && mp.n_targets == 0) return MR_OK;
+    mr_morph::Lists v, n;
+    if (first && !mr_morph::build_lists(mp.n_verts, n_targets, first, index, delta, v))
+        return fail(MR_E_INVALID, "the morph's padded lists do not fit 32-bit offsets");
+    if (first && nfirst && !mr_morph::build_lists(mp.n_normals, n_targets, nfirst, nindex, ndelta, n))
+        return fail(MR_E_INVALID, "the morph's padded lists do not fit 32-bit offsets");
+    const bool was = mp.moved(), was_n = mp.morph_normals();
+    mp.has_weights = false;                          // a new morph starts in the rest shape; no morph, no weights
+    mp.morph_w.clear();
+    mp.morph_v = std::move(v); mp.morph_n = std::move(n);
+    mp.n_targets = first ? n_targets : 0;
+    sc->morph_tables_dirty = true;
+    if (was) sc->pose_dirty = sc->pose_geom_dirty = true;
+    if (was_n) sc->pose_dirty = sc->pose_g_dirty = true;
+    moved_changed(sc, model, was);
+    return MR_OK;
+}
+
+// mr_scene_set_model_morph_weights behind its argument checks
+void set_model_morph_weights(mr_scene *sc, int32_t model, const double *w)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    const size_t n = (size_t)mp.n_targets;
+    if (!w && !mp.has_weights) return;
+    if (w && mp.has_weights && !std::memcmp(mp.morph_w.data(), w, n * sizeof(double))) return;
+    const bool was = mp.moved(), was_n = mp.morph_normals();
+    mp.has_weights = w != nullptr;
+    mp.morph_w.assign(w ? w : nullptr, w ? w + n : nullptr);
+    moved_changed(sc, model, was);
+    sc->pose_dirty = sc->pose_geom_dirty = true;
+    // normals that follow the morph: new weights bring k_morph_normals and whatever takes its result (the skin's
+    // normals, or the normal matrix), a model that starts or stops following the whole normals' part
+    if (was_n != mp.morph_normals()) sc->pose_g_dirty = true;
+    else if (was_n) {
+        sc->morph_n_dirty = true;
+        if (mp.skin_normals()) sc->skin_n_dirty = true;
+        else if (mp.has_g) sc->pose_g_dirty = true;
+    }
+}
+
 // a material's object-space normal map, if it has one
 inline bool object_space_map(const mr_scene *sc, const mr::Material &m)
 {
@@ -169,7 +220,7 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
             mp.normals_on_device = mp.n_normals > 0;
             continue;
         }
-        if (mp.skin_normals()) mp.normals_on_device = true;    // (apply_skin_normals writes them)
+        if (mp.skin_normals() || mp.morph_normals()) mp.normals_on_device = true;    // (apply_skin_normals / apply_morph_normals write them)
         else if (mp.normals_on_device) {                 // a model whose matrix is gone gets its own normals back
             const size_t off = (size_t)mp.normal_off * 3 * sizeof(float), bytes = (size_t)mp.n_normals * 3 * sizeof(float);
             HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_normals.p) + off, static_cast<const char *>(sc->d_normals0.p) + off, bytes,
@@ -192,8 +243,8 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
         if (int rc = upload(sc->d_normal_rows, nrows, g_stream)) return rc;
         if (int rc = upload(sc->d_normal_blocks, nblocks, g_stream)) return rc;
         hipLaunchKernelGGL(mr::k_pose_normals, dim3((unsigned)nblocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
-                           sc->d_normal_rows.as<mr::Vec3Row>(), sc->d_normal_blocks.as<int32_t>(), sc->d_normals0.as<float>(),
-                           sc->d_normals.as<float>());
+                           sc->d_normal_rows.as<mr::Vec3Row>(), sc->d_normal_blocks.as<int32_t>(),
+                           (sc->normals_m_valid ? sc->d_normals_m : sc->d_normals0).as<float>(), sc->d_normals.as<float>());
     }
     HIP_TRY(hipEventRecord(sc->pose_n_ev[1], g_stream));
     if (!trows.empty()) {
@@ -253,7 +304,8 @@ struct SkinTables {                                      // (the caller keeps th
 };
 
 // The normals of the models whose normals follow their skin (k_skin_normals), after apply_pose_normals where that ran:
-// from the pristine d_normals0 into d_normals.  The bone table is on its way (upload_bones).
+// from the pristine d_normals0 (d_normals_m while a morph holds normals there) into d_normals.  The bone table is on its
+// way (upload_bones).
 int apply_skin_normals(mr_scene *sc, SkinTables &t)
 {
     int64_t written = 0;
@@ -281,11 +333,124 @@ int apply_skin_normals(mr_scene *sc, SkinTables &t)
     if (int rc = upload(sc->d_skin_n_blocks, t.nblocks, g_stream)) return rc;
     HIP_TRY(hipEventRecord(sc->skin_ev[2], g_stream));
     hipLaunchKernelGGL(mr::k_skin_normals, dim3((unsigned)t.nblocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
-                       sc->d_skin_n_rows.as<mr::SkinNormalRow>(), sc->d_skin_n_blocks.as<int32_t>(), sc->d_normals0.as<float>(),
+                       sc->d_skin_n_rows.as<mr::SkinNormalRow>(), sc->d_skin_n_blocks.as<int32_t>(),
+                       (sc->normals_m_valid ? sc->d_normals_m : sc->d_normals0).as<float>(),
                        sc->d_skin_owners.as<int32_t>(), sc->d_skin_joints.as<int4>(), sc->d_skin_weights.as<double4>(),
                        sc->d_bones.as<double4>(), sc->d_normals.as<float>());
     HIP_TRY(hipEventRecord(sc->skin_ev[3], g_stream));
     sc->skin_ran[1] = true;
+    return MR_OK;
+}
+
+// The morph lists on the device: the slices of every model that has a morph, its vertices' and then its normals', one
+// after the other in the four planes.  Rebuilt when a morph was set or removed, not when weights change.
+int upload_morph_tables(mr_scene *sc)
+{
+    if (!sc->morph_tables_dirty) return MR_OK;
+    std::vector<int32_t> slices, target;
+    std::vector<double> dx, dy, dz;
+    auto append = [&](const mr_morph::Lists &l, int32_t &slice0) {
+        const int64_t base = (int64_t)target.size();
+        if (base + l.entries() > INT32_MAX) return false;
+        slice0 = (int32_t)slices.size();
+        for (int32_t f : l.slice_first) slices.push_back((int32_t)base + f);
+        target.insert(target.end(), l.target.begin(), l.target.end());
+        dx.insert(dx.end(), l.dx.begin(), l.dx.end());
+        dy.insert(dy.end(), l.dy.begin(), l.dy.end());
+        dz.insert(dz.end(), l.dz.begin(), l.dz.end());
+        return true;
+    };
+    for (mr_scene::ModelPose &mp : sc->poses) {
+        if (mp.n_targets == 0) continue;
+        if (!append(mp.morph_v, mp.slice0_v) || (mp.morph_n.n > 0 && !append(mp.morph_n, mp.slice0_n)))
+            return fail(MR_E_INVALID, "the scene's morph lists do not fit 32-bit offsets");
+    }
+    if (int rc = upload(sc->d_morph_slices, slices, g_stream)) return rc;
+    if (int rc = upload(sc->d_morph_target, target, g_stream)) return rc;
+    if (int rc = upload(sc->d_morph_dx, dx, g_stream)) return rc;
+    if (int rc = upload(sc->d_morph_dy, dy, g_stream)) return rc;
+    if (int rc = upload(sc->d_morph_dz, dz, g_stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(g_stream));         // (the vectors go out of scope)
+    sc->morph_entries = (int32_t)target.size();
+    sc->morph_tables_dirty = false;
+    return MR_OK;
+}
+
+struct MorphTables {                                     // (the caller keeps them until it has waited for the stream)
+    std::vector<mr::MorphRow> rows, nrows;
+    std::vector<int32_t> blocks, nblocks, weight0;
+};
+
+// The weight table of a pass: the weights of every model that has some, back to back, in one asynchronous upload;
+// weight0[k] is where model k's start.  sc->morph_weight_table lives until the pass has waited for the stream.
+int upload_morph_weights(mr_scene *sc, MorphTables &t)
+{
+    sc->morph_weight_table.clear();
+    t.weight0.assign(sc->poses.size(), 0);
+    for (size_t k = 0; k < sc->poses.size(); ++k) {
+        const mr_scene::ModelPose &mp = sc->poses[k];
+        if (!mp.has_weights) continue;
+        t.weight0[k] = (int32_t)sc->morph_weight_table.size();
+        sc->morph_weight_table.insert(sc->morph_weight_table.end(), mp.morph_w.begin(), mp.morph_w.end());
+    }
+    sc->morph_targets = (int32_t)sc->morph_weight_table.size();
+    return upload(sc->d_morph_weights, sc->morph_weight_table, g_stream);
+}
+
+inline mr::MorphRow morph_row(int32_t first, int32_t count, size_t block0, int32_t slice0, int32_t weight0, int32_t n_targets, bool direct)
+{
+    mr::MorphRow r;
+    std::memset(&r, 0, sizeof r);
+    r.first = first; r.count = count; r.block0 = (int32_t)block0; r.slice0 = slice0;
+    r.weight0 = weight0; r.n_targets = n_targets; r.direct = direct ? 1 : 0;
+    return r;
+}
+
+// The normals of the models whose normals follow their morph (k_morph_normals), in front of apply_pose_normals and
+// apply_skin_normals, which take the result: from the pristine d_normals0 into d_normals_m, or straight into d_normals
+// for a model that has neither a normal matrix nor a skin its normals follow.  A model that stopped following gets its
+// range of d_normals_m back.  The weight table is on its way (upload_morph_weights).
+int apply_morph_normals(mr_scene *sc, MorphTables &t)
+{
+    int64_t written = 0;
+    for (size_t k = 0; k < sc->poses.size(); ++k) {
+        mr_scene::ModelPose &mp = sc->poses[k];
+        const size_t off = (size_t)mp.normal_off * 3 * sizeof(float), bytes = (size_t)mp.n_normals * 3 * sizeof(float);
+        if (!mp.morph_normals()) {
+            if (mp.normals_m_morphed && sc->normals_m_valid)
+                HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_normals_m.p) + off, static_cast<const char *>(sc->d_normals0.p) + off, bytes,
+                                       hipMemcpyDeviceToDevice, g_stream));
+            mp.normals_m_morphed = false;
+            continue;
+        }
+        const bool direct = !mp.has_g && !mp.skin_normals();
+        t.nrows.push_back(morph_row(mp.normal_off, mp.n_normals, t.nblocks.size(), mp.slice0_n, t.weight0[k], mp.n_targets, direct));
+        t.nblocks.insert(t.nblocks.end(), (size_t)blocks_for(mp.n_normals, mr::POSE_BLOCK), (int32_t)t.nrows.size() - 1);
+        if (direct) mp.normals_on_device = true;
+        else mp.normals_m_morphed = true;
+        written += mp.n_normals;
+    }
+    sc->morph_normals_written = (int32_t)written;
+    if (t.nrows.empty()) return MR_OK;
+    if (!sc->normals0_valid) {
+        if (int rc = upload(sc->d_normals0, sc->normals, g_stream)) return rc;
+        sc->normals0_valid = true;
+    }
+    if (!sc->normals_m_valid) {
+        const size_t bytes = sc->normals.size() * sizeof(float);
+        HIP_TRY(sc->d_normals_m.ensure(std::max<size_t>(bytes, 16)));
+        HIP_TRY(hipMemcpyAsync(sc->d_normals_m.p, sc->d_normals0.p, bytes, hipMemcpyDeviceToDevice, g_stream));
+        sc->normals_m_valid = true;
+    }
+    if (int rc = upload(sc->d_morph_n_rows, t.nrows, g_stream)) return rc;
+    if (int rc = upload(sc->d_morph_n_blocks, t.nblocks, g_stream)) return rc;
+    HIP_TRY(hipEventRecord(sc->morph_ev[2], g_stream));
+    hipLaunchKernelGGL(mr::k_morph_normals, dim3((unsigned)t.nblocks.size()), dim3(mr::POSE_BLOCK), 0,
+                       g_stream, sc->d_morph_n_rows.as<mr::MorphRow>(), sc->d_morph_n_blocks.as<int32_t>(), sc->d_morph_slices.as<int32_t>(),
+                       sc->d_morph_target.as<int32_t>(), sc->d_morph_dx.as<double>(), sc->d_morph_dy.as<double>(), sc->d_morph_dz.as<double>(),
+                       sc->d_morph_weights.as<double>(), sc->d_normals0.as<float>(), sc->d_normals_m.as<float>(), sc->d_normals.as<float>());
+    HIP_TRY(hipEventRecord(sc->morph_ev[3], g_stream));
+    sc->morph_ran[1] = true;
     return MR_OK;
 }
 
@@ -299,15 +464,20 @@ int apply_poses(mr_scene *sc)
     std::vector<mr::PoseRow> rows;
     std::vector<int32_t> block_row;
     SkinTables skin;
-    bool restore = false, normals = false, skin_normals = false, bones = false;
-    int64_t written = 0, skinned = 0;
+    MorphTables morph;
+    bool restore = false, normals = false, skin_normals = false, bones = false, morph_normals = false, weights = false;
+    int64_t written = 0, skinned = 0, morphed = 0;
     for (const mr_scene::ModelPose &mp : sc->poses) {
         normals = normals || (sc->pose_g_dirty && (mp.has_g || mp.normals_on_device || mp.maps_on_device));
         skin_normals = skin_normals || ((sc->pose_g_dirty || sc->skin_n_dirty) && mp.skin_normals());
+        morph_normals = morph_normals || ((sc->pose_g_dirty || sc->morph_n_dirty) && (mp.morph_normals() || mp.normals_m_morphed));
         bones = bones || mp.has_bones;
+        weights = weights || mp.has_weights;
         if (!geom) continue;
         if (!mp.moved()) { restore = restore || mp.on_device; continue; }
+        if (mp.has_weights) morphed += mp.n_verts;                  // (its row needs the weight table: below)
         if (mp.has_bones) { skinned += mp.n_verts; continue; }      // (its row needs the bone table: below)
+        if (!mp.posed) { written += mp.n_verts; continue; }         // (a morph alone: k_morph_vertices writes d_verts)
         mr::PoseRow r;
         std::memset(&r, 0, sizeof r);
         r.first = mp.vert_off; r.count = mp.n_verts; r.block0 = (int32_t)block_row.size();
@@ -317,12 +487,23 @@ int apply_poses(mr_scene *sc)
         written += mp.n_verts;
     }
     written += skinned;
-    if (rows.empty() && !skinned && !restore && !normals && !skin_normals) {      // (a commit has just uploaded the pristine vertices)
-        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
+    if (rows.empty() && !skinned && !morphed && !restore && !normals && !skin_normals && !morph_normals) {      // (a commit has just uploaded the pristine vertices)
+        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = sc->morph_n_dirty = false;
         return MR_OK;
     }
     if (sc->pos32) return fail(MR_E_INVALID, "pose pass on a scene of float32 face records");   // (set_model_pose leaves such a scene dirty)
     HIP_TRY(hipDeviceSynchronize());                 // no frame may still be reading the records about to be rewritten
+    sc->morph_ran[0] = sc->morph_ran[1] = false;
+    sc->morph_written = sc->morph_normals_written = sc->morph_targets = 0;
+    if (weights && (morphed || morph_normals)) {
+        for (hipEvent_t &e : sc->morph_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        sc->morph_marks = true;
+        if (int rc = upload_morph_tables(sc)) return rc;
+        if (int rc = upload_morph_weights(sc, morph)) return rc;
+    }
+    if (morph_normals)
+        if (int rc = apply_morph_normals(sc, morph)) return rc;
     NormalTables normal_tables;
     if (normals)
         if (int rc = apply_pose_normals(sc, normal_tables)) return rc;
@@ -343,11 +524,11 @@ int apply_poses(mr_scene *sc)
                            sc->d_face_flags.as<uint8_t>(), sc->d_verts.as<double>(), sc->d_uv.as<float>(), sc->d_normals.as<float>(),
                            sc->d_face_pos.as<mr::FacePos64>(), sc->d_face_attr.as<mr::FaceAttr>());
     };
-    if (rows.empty() && !skinned && !restore) {      // normal matrices alone: the face records take the new normals
+    if (rows.empty() && !skinned && !morphed && !restore) {      // normal matrices alone: the face records take the new normals
         if (nf > 0) face_static();
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g_stream));     // (the tables go out of scope)
-        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
+        sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = sc->morph_n_dirty = false;
         sc->pose_passes += 1;
         sc->pose_written = 0;
         return MR_OK;
@@ -370,12 +551,49 @@ int apply_poses(mr_scene *sc)
         if (!e) HIP_TRY(hipEventCreate(&e));
     int mark = 0;
     HIP_TRY(hipEventRecord(sc->pose_ev[mark++], g_stream));
+    // the morphed models first: one row each (vertex range, slices, weights), into d_verts where nothing follows the
+    // morph, else into d_verts_m -- a copy of d_verts0 made once, in which a model whose weights are gone gets its range back
+    for (mr_scene::ModelPose &mp : sc->poses) {
+        if (mp.has_weights || !mp.verts_m_morphed) continue;
+        const size_t off = (size_t)mp.vert_off * 4 * sizeof(double), bytes = (size_t)mp.n_verts * 4 * sizeof(double);
+        if (sc->verts_m_valid)
+            HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_verts_m.p) + off, static_cast<const char *>(sc->d_verts0.p) + off, bytes,
+                                   hipMemcpyDeviceToDevice, g_stream));
+        mp.verts_m_morphed = false;
+    }
+    if (morphed) {
+        if (!sc->verts_m_valid) {
+            const size_t bytes = sc->verts.size() * sizeof(double);
+            HIP_TRY(sc->d_verts_m.ensure(std::max<size_t>(bytes, 16)));
+            HIP_TRY(hipMemcpyAsync(sc->d_verts_m.p, sc->d_verts0.p, bytes, hipMemcpyDeviceToDevice, g_stream));
+            sc->verts_m_valid = true;
+        }
+        for (size_t k = 0; k < sc->poses.size(); ++k) {
+            mr_scene::ModelPose &mp = sc->poses[k];
+            if (!mp.has_weights) continue;
+            const bool direct = !mp.posed && !mp.has_bones;
+            morph.rows.push_back(morph_row(mp.vert_off, mp.n_verts, morph.blocks.size(), mp.slice0_v, morph.weight0[k], mp.n_targets, direct));
+            morph.blocks.insert(morph.blocks.end(), (size_t)blocks_for(mp.n_verts, mr::POSE_BLOCK), (int32_t)morph.rows.size() - 1);
+            if (!direct) mp.verts_m_morphed = true;
+        }
+        if (int rc = upload(sc->d_morph_rows, morph.rows, g_stream)) return rc;
+        if (int rc = upload(sc->d_morph_blocks, morph.blocks, g_stream)) return rc;
+        HIP_TRY(hipEventRecord(sc->morph_ev[0], g_stream));
+        hipLaunchKernelGGL(mr::k_morph_vertices, dim3((unsigned)morph.blocks.size()),
+                           dim3(mr::POSE_BLOCK), 0, g_stream, sc->d_morph_rows.as<mr::MorphRow>(), sc->d_morph_blocks.as<int32_t>(),
+                           sc->d_morph_slices.as<int32_t>(), sc->d_morph_target.as<int32_t>(), sc->d_morph_dx.as<double>(),
+                           sc->d_morph_dy.as<double>(), sc->d_morph_dz.as<double>(), sc->d_morph_weights.as<double>(),
+                           sc->d_verts0.as<double4>(), sc->d_verts_m.as<double4>(), sc->d_verts.as<double4>());
+        HIP_TRY(hipEventRecord(sc->morph_ev[1], g_stream));
+        sc->morph_ran[0] = true;
+        sc->morph_written = (int32_t)morphed;
+    }
+    const double4 *pristine = (sc->verts_m_valid ? sc->d_verts_m : sc->d_verts0).as<double4>();     // what the skin and the pose start from
     if (!rows.empty()) {
         if (int rc = upload(sc->d_pose_rows, rows, g_stream)) return rc;
         if (int rc = upload(sc->d_pose_blocks, block_row, g_stream)) return rc;
         hipLaunchKernelGGL(mr::k_pose_vertices, dim3((unsigned)block_row.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
-                           sc->d_pose_rows.as<mr::PoseRow>(), sc->d_pose_blocks.as<int32_t>(), sc->d_verts0.as<double4>(),
-                           sc->d_verts.as<double4>());
+                           sc->d_pose_rows.as<mr::PoseRow>(), sc->d_pose_blocks.as<int32_t>(), pristine, sc->d_verts.as<double4>());
     }
     if (skinned) {
         // the skinned models: one row each (vertex range, joint / weight offset, first bone, the pose that follows)
@@ -397,7 +615,7 @@ int apply_poses(mr_scene *sc)
         for (const mr::SkinRow &r : skin.rows) staged = staged && r.n_bones <= mr::SKIN_LDS_BONES;
         HIP_TRY(hipEventRecord(sc->skin_ev[0], g_stream));
         hipLaunchKernelGGL(staged ? mr::k_skin_vertices<true> : mr::k_skin_vertices<false>, dim3((unsigned)skin.blocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
-                           sc->d_skin_rows.as<mr::SkinRow>(), sc->d_skin_blocks.as<int32_t>(), sc->d_verts0.as<double4>(),
+                           sc->d_skin_rows.as<mr::SkinRow>(), sc->d_skin_blocks.as<int32_t>(), pristine,
                            sc->d_skin_joints.as<int4>(), sc->d_skin_weights.as<double4>(), sc->d_bones.as<double4>(),
                            sc->d_verts.as<double4>());
         HIP_TRY(hipEventRecord(sc->skin_ev[1], g_stream));
@@ -426,7 +644,7 @@ int apply_poses(mr_scene *sc)
     sc->sil.drop();                                  // the silhouette belongs to the geometry
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));         // (the tables go out of scope)
-    sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
+    sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = sc->morph_n_dirty = false;
     sc->pose_passes += 1;
     sc->pose_written = (int32_t)written;
     return MR_OK;

@@ -50,13 +50,27 @@ struct mr_scene {
         int32_t n_bones = 0;                  // > 0: the model has a skin
         bool has_bones = false;
         int32_t table_off = 0, owner_off = 0; // where the model's rows start in d_skin_joints / d_skin_weights, d_skin_owners
-        bool moved() const { return posed || has_bones; }                                  // d_verts differs from d_verts0
+        // the morph (mr_scene_set_model_morph): the per-vertex contribution lists of its targets (host_morph.h), for the
+        // vertices and, where the caller passed some, for the normals, built on the host once per morph and uploaded with
+        // every other model's; and the weights (mr_scene_set_model_morph_weights), which make the model move
+        mr_morph::Lists morph_v, morph_n;
+        int32_t n_targets = 0;                // > 0: the model has a morph
+        bool has_weights = false;
+        std::vector<double> morph_w;
+        int32_t slice0_v = 0, slice0_n = 0;   // where the model's slices start in d_morph_slices
+        bool verts_m_morphed = false;         // d_verts_m differs from d_verts0 in this model's range
+        bool normals_m_morphed = false;       // ... d_normals_m from d_normals0
+        bool moved() const { return posed || has_bones || has_weights; }                   // d_verts differs from d_verts0
         bool skin_normals() const { return has_bones && !owners.empty() && n_normals > 0; }  // ... d_normals from d_normals0 by the skin
+        bool morph_normals() const { return has_weights && morph_n.n > 0 && n_normals > 0; } // ... or by the morph
     };
     std::vector<ModelPose> poses;             // one per model
     bool skin_tables_dirty = false;           // a skin was set or removed: the device tables are rebuilt by the next pass
     bool skin_n_dirty = false;                // bones of a model whose normals follow its skin changed
     int32_t skin_bones = 0, skin_written = 0, skin_normals_written = 0;     // mr_debug_skin
+    bool morph_tables_dirty = false;          // a morph was set or removed: the device lists are rebuilt by the next pass that needs them
+    bool morph_n_dirty = false;               // weights of a model whose normals follow its morph changed
+    int32_t morph_targets = 0, morph_written = 0, morph_normals_written = 0, morph_entries = 0;   // mr_debug_morph
     bool pose_dirty = false;                  // a pose or a normal matrix changed: apply_poses() has work
     bool pose_geom_dirty = false;             // ... and a pose among them: vertices and what is built from them
     bool pose_g_dirty = false;                // ... and a normal matrix among them: normals and re-baked maps
@@ -88,7 +102,18 @@ struct mr_scene {
     hipEvent_t skin_ev[4] = {};               // marks round k_skin_vertices and k_skin_normals (mr_debug_skin_times)
     bool skin_ran[2] = {};                    // which of the two the last pass launched
     bool skin_marks = false;
-    bool pos32 = false;                      // d_face_pos holds FacePos32 (every model's vertices are float32)
+    // the morphs: the sliced contribution lists of every model that has a morph, one after the other (the slice table,
+    // then four planes: target, delta x / y / z); the weight table of the last pass and the two kernels' tables; and the
+    // copies of d_verts0 / d_normals0 in which the morphed models' ranges hold the morphed arrays: what the skin and pose
+    // kernels take as their pristine source while they exist
+    DevBuf d_morph_slices, d_morph_target, d_morph_dx, d_morph_dy, d_morph_dz, d_morph_weights;
+    DevBuf d_morph_rows, d_morph_blocks, d_morph_n_rows, d_morph_n_blocks, d_verts_m, d_normals_m;
+    bool verts_m_valid = false, normals_m_valid = false;
+    std::vector<double> morph_weight_table;
+    hipEvent_t morph_ev[4] = {};              // marks round k_morph_vertices and k_morph_normals (mr_debug_morph_times)
+    bool morph_ran[2] = {};                   // which of the two the last pass launched
+    bool morph_marks = false;
+    bool pos32 = false;                     // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
     DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
     DevBuf d_gamma;                          // GAMMA_LUT_SIZE float32 thresholds of the finalise step function
@@ -330,10 +355,12 @@ int commit(mr_scene *sc)
     sc->commits += 1;
     sc->verts0_valid = false;
     sc->normals0_valid = false;               // (and the normals and the materials' map headers)
+    sc->verts_m_valid = sc->normals_m_valid = false;
     for (mr_scene::ModelPose &mp : sc->poses) {
         mp.on_device = mp.normals_on_device = mp.maps_on_device = false;
+        mp.verts_m_morphed = mp.normals_m_morphed = false;
         if (mp.moved()) sc->pose_dirty = sc->pose_geom_dirty = true;
-        if (mp.has_g || mp.skin_normals()) sc->pose_g_dirty = true;
+        if (mp.has_g || mp.skin_normals() || mp.morph_normals()) sc->pose_g_dirty = true;
     }
     return MR_OK;
 }

@@ -9,6 +9,10 @@
 //   k_skin_vertices   vertices of the models that have a skin and bones: pristine vertex @ (the vertex's blend of four
 //                     bone matrices), then @ pose where the model has one; mr_host_skin_chain, bit for bit
 //   k_skin_normals    vertex normals of the models whose normals follow their skin: the owner's blend matrix, then G
+//   k_morph_vertices  vertices of the models that have morph targets and weights: pristine vertex plus the weighted
+//                     deltas of the targets that list it, an fma chain in ascending target order over sliced per-vertex
+//                     lists (host_morph.h); mr_host_morph_chain, bit for bit.  Runs first: skin and pose take its result
+//   k_morph_normals   the same over vertex normals, widened and rounded to float32 once
 //   k_clusters        the per-cluster records (rast_types.h, ClusterRec) from the posed vertices: what build_clusters
 //                     (host_scene.h) builds on the host at commit time, one wavefront per cluster
 //
@@ -210,6 +214,87 @@ k_skin_normals(const SkinNormalRow *__restrict__ rows, const int32_t *__restrict
         o.x = (float)x; o.y = (float)y; o.z = (float)z;
     }
     *reinterpret_cast<float3 *>(normals + at) = o;
+}
+
+// One morphed model (mr_scene_set_model_morph / mr_scene_set_model_morph_weights): its vertex (k_morph_vertices) or
+// normal (k_morph_normals) range, where its slices start in the slice table, where its weights start in the pass's
+// weight table, and the first of the workgroups that cover the range.  direct: nothing follows the morph (no skin, no
+// pose / no normal matrix), so the result goes straight into the array every frame kernel reads; otherwise into the
+// array the skin and pose kernels take as their pristine source.
+struct alignas(8) MorphRow {
+    int32_t first, count;
+    int32_t block0, slice0;
+    int32_t weight0, n_targets, direct, pad;
+};
+static_assert(sizeof(MorphRow) == 32, "MorphRow layout");
+static_assert(POSE_BLOCK % WAVE == 0, "a wavefront of the morph kernels walks one slice");
+
+// The morph kernels' body: one vertex (float64 x y z w, w passes through) or one normal (float32 x y z, widened, rounded
+// once at the end) per thread, the tables of k_pose_vertices.  A wavefront holds 64 consecutive vertices of the model:
+// one slice of its contribution lists (host_morph.h).  Entry e of lane l sits at slice_first[s] + e * 64 + l in the
+// four planes, so every load of the walk is one contiguous 256-byte (target) or 512-byte (delta component) access and
+// the trip count is uniform over the wavefront; padding (target -1) is skipped.  Every listed target takes its fma step,
+// in ascending target order (mr_host_morph_chain, bit for bit), also with a weight of 0.  The one gather is w[target],
+// from a table of 8 bytes per target that every workgroup of the model reads: it stays in cache (staging it in LDS was
+// built and timed too and was no faster: DESIGN.md section 6f).
+template <bool NORMALS>
+__device__ __forceinline__ void morph_body(const MorphRow *__restrict__ rows, const int32_t *__restrict__ block_row,
+                                           const int32_t *__restrict__ slice_first, const int32_t *__restrict__ target,
+                                           const double *__restrict__ dx, const double *__restrict__ dy, const double *__restrict__ dz,
+                                           const double *__restrict__ weights, const void *__restrict__ src, void *__restrict__ held,
+                                           void *__restrict__ live)
+{
+    const MorphRow &r = rows[block_row[blockIdx.x]];
+    const int i = (int)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int)threadIdx.x;
+    if (i >= r.count) return;
+    const double *w = weights + (size_t)r.weight0;
+    const size_t at = (size_t)r.first + i;
+    double x, y, z, h = 0.0;
+    if constexpr (NORMALS) {
+        const float3 n = *reinterpret_cast<const float3 *>(static_cast<const float *>(src) + at * 3);
+        x = (double)n.x; y = (double)n.y; z = (double)n.z;
+    } else {
+        const double4 v = static_cast<const double4 *>(src)[at];
+        x = v.x; y = v.y; z = v.z; h = v.w;
+    }
+    const int s = __builtin_amdgcn_readfirstlane(r.slice0 + (i >> 6)), lane = i & (WAVE - 1);     // (i >> 6 is the wavefront's)
+    const int end = slice_first[s + 1];
+    for (int p = slice_first[s]; p < end; p += WAVE) {
+        const int t = target[(size_t)p + lane];
+        if (t < 0) continue;
+        const double wt = w[t];
+        x = fma(wt, dx[(size_t)p + lane], x);
+        y = fma(wt, dy[(size_t)p + lane], y);
+        z = fma(wt, dz[(size_t)p + lane], z);
+    }
+    void *dst = r.direct ? live : held;                            // (uniform over the workgroup)
+    if constexpr (NORMALS) {
+        float3 o;
+        o.x = (float)x; o.y = (float)y; o.z = (float)z;
+        *reinterpret_cast<float3 *>(static_cast<float *>(dst) + at * 3) = o;
+    } else {
+        double4 o;
+        o.x = x; o.y = y; o.z = z; o.w = h;
+        static_cast<double4 *>(dst)[at] = o;
+    }
+}
+
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_morph_vertices(const MorphRow *__restrict__ rows, const int32_t *__restrict__ block_row, const int32_t *__restrict__ slice_first,
+                 const int32_t *__restrict__ target, const double *__restrict__ dx, const double *__restrict__ dy,
+                 const double *__restrict__ dz, const double *__restrict__ weights, const double4 *__restrict__ verts0,
+                 double4 *__restrict__ verts_m, double4 *__restrict__ verts)
+{
+    morph_body<false>(rows, block_row, slice_first, target, dx, dy, dz, weights, verts0, verts_m, verts);
+}
+
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_morph_normals(const MorphRow *__restrict__ rows, const int32_t *__restrict__ block_row, const int32_t *__restrict__ slice_first,
+                const int32_t *__restrict__ target, const double *__restrict__ dx, const double *__restrict__ dy,
+                const double *__restrict__ dz, const double *__restrict__ weights, const float *__restrict__ normals0,
+                float *__restrict__ normals_m, float *__restrict__ normals)
+{
+    morph_body<true>(rows, block_row, slice_first, target, dx, dy, dz, weights, normals0, normals_m, normals);
 }
 
 __device__ __forceinline__ double shfl_xor_d(double v, int mask)

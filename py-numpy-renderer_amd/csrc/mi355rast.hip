@@ -6,7 +6,8 @@
 //   host_silcache.h     the silhouette cache
 //   host_scene.h        the static scene and commit()
 //   host_overlay_dev.h  the debug-frustum overlay's device plumbing (host_overlay.h builds its lists)
-//   host_pose.h         a model's pose, applied on the device in front of the frame
+//   host_morph.h        morph targets: the per-vertex contribution lists (plain C++, no HIP)
+//   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //
 // One process drives one GPU.  A scene keeps its static arrays (vertices, attributes, index arrays, textures, the
@@ -53,6 +54,7 @@
 #include "host_device.h"
 #include "host_env.h"
 #include "host_silcache.h"
+#include "host_morph.h"
 #include "host_scene.h"
 #include "host_pose.h"
 #include "host_overlay_dev.h"
@@ -111,6 +113,7 @@ int mr_scene_clear(mr_scene *sc)
     sc->edge_ids.clear(); sc->edge_raw.clear();
     sc->poses.clear(); sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
     sc->skin_tables_dirty = true;
+    sc->morph_tables_dirty = true; sc->morph_n_dirty = false;
     sc->dirty = true;
     sc->last = nullptr;
     sc->sil.drop();
@@ -154,7 +157,9 @@ void mr_scene_destroy(mr_scene *sc)
                        &sc->d_edges32, &sc->d_edge_inc, &sc->d_face_n, &sc->d_face_pos, &sc->d_face_attr, &sc->d_clusters, &sc->d_sky, &sc->d_gamma,
                        &sc->d_verts0, &sc->d_pose_rows, &sc->d_pose_blocks, &sc->d_normals0, &sc->d_normal_rows, &sc->d_normal_blocks,
                        &sc->d_texel_rows, &sc->d_texel_blocks, &sc->d_rebaked, &sc->d_skin_joints, &sc->d_skin_weights, &sc->d_skin_owners,
-                       &sc->d_bones, &sc->d_skin_rows, &sc->d_skin_blocks, &sc->d_skin_n_rows, &sc->d_skin_n_blocks })
+                       &sc->d_bones, &sc->d_skin_rows, &sc->d_skin_blocks, &sc->d_skin_n_rows, &sc->d_skin_n_blocks, &sc->d_morph_slices,
+                       &sc->d_morph_target, &sc->d_morph_dx, &sc->d_morph_dy, &sc->d_morph_dz, &sc->d_morph_weights, &sc->d_morph_rows,
+                       &sc->d_morph_blocks, &sc->d_morph_n_rows, &sc->d_morph_n_blocks, &sc->d_verts_m, &sc->d_normals_m })
         b->release();
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
@@ -162,6 +167,7 @@ void mr_scene_destroy(mr_scene *sc)
     for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->skin_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sc->morph_ev) if (e) (void)hipEventDestroy(e);
     delete sc;
 }
 
@@ -387,6 +393,37 @@ int mr_scene_set_model_bones(mr_scene *sc, int32_t model, const double *bones16,
     return MR_OK;
 }
 
+int mr_scene_set_model_morph(mr_scene *sc, int32_t model, int32_t n_targets, const int32_t *first, const int32_t *index,
+                             const double *delta, const int32_t *nfirst, const int32_t *nindex, const double *ndelta)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    const mr_scene::ModelPose &mp = sc->poses[model];
+    if (first) {                                     // validated before the kernels trust them
+        if (const char *wrong = mr_morph::check_tables(mp.n_verts, n_targets, first, index, delta)) return fail(MR_E_INVALID, wrong);
+        if (nfirst) {
+            if (mp.n_normals == 0) return fail(MR_E_INVALID, "normal targets on a model without normals");
+            if (const char *wrong = mr_morph::check_tables(mp.n_normals, n_targets, nfirst, nindex, ndelta)) return fail(MR_E_INVALID, wrong);
+        }
+    }
+    return set_model_morph(sc, model, n_targets, first, index, delta, nfirst, nindex, ndelta);
+}
+
+int mr_scene_set_model_morph_weights(mr_scene *sc, int32_t model, const double *w, int32_t n_targets)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    const mr_scene::ModelPose &mp = sc->poses[model];
+    if (mp.n_targets == 0) return fail(MR_E_INVALID, "morph weights need a model that has a morph");
+    if (w) {
+        if (n_targets != mp.n_targets) return fail(MR_E_INVALID, "the morph was set for another number of targets");
+        for (int32_t k = 0; k < n_targets; ++k)
+            if (!std::isfinite(w[k])) return fail(MR_E_INVALID, "morph weights must be finite");
+    }
+    set_model_morph_weights(sc, model, w);
+    return MR_OK;
+}
+
 int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats *stats)
 {
     if (!sc || !out_rgb) return fail(MR_E_INVALID, "NULL argument");
@@ -545,6 +582,18 @@ void mr_host_skin_chain3(const double *vectors, const int32_t *owner, const int3
             }
         for (int c = 0; c < 3; ++c) out[(size_t)i * 3 + c] = o[c];
     }
+}
+
+int mr_host_morph_chain(const double *base, int32_t n, int32_t width, int32_t n_targets, const int32_t *first, const int32_t *index,
+                        const double *delta, const double *w, double *out)
+{
+    if (!base || !w || !out || (width != 3 && width != 4)) return fail(MR_E_INVALID, "mr_host_morph_chain: bad argument");
+    if (const char *wrong = mr_morph::check_tables(n, n_targets, first, index, delta)) return fail(MR_E_INVALID, wrong);
+    mr_morph::Lists lists;                           // the lists the upload path builds, walked in the kernel's order
+    if (!mr_morph::build_lists(n, n_targets, first, index, delta, lists))
+        return fail(MR_E_INVALID, "the morph's padded lists do not fit 32-bit offsets");
+    mr_morph::walk_lists(lists, base, width, w, out);
+    return MR_OK;
 }
 
 void mr_host_matmul_chain(const double *a, const double *b, double *out, int32_t m, int32_t k, int32_t p)
@@ -849,6 +898,27 @@ int mr_debug_skin_times(mr_scene *sc, float *out_ms)
     for (int k = 0; k < MR_N_SKIN_TIMES; ++k) {
         out_ms[k] = 0.f;                             // (a kernel the last pass did not launch)
         if (sc->skin_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->skin_ev[2 * k], sc->skin_ev[2 * k + 1]));
+    }
+    return MR_OK;
+}
+
+int mr_debug_morph(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    int32_t weighted = 0;
+    for (const mr_scene::ModelPose &mp : sc->poses) weighted += mp.has_weights ? 1 : 0;
+    out[0] = weighted; out[1] = sc->morph_targets; out[2] = sc->morph_written; out[3] = sc->morph_normals_written;
+    out[4] = sc->morph_entries;
+    return MR_OK;
+}
+
+int mr_debug_morph_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->morph_marks) return fail(MR_E_INVALID, "no pass over a morph yet");
+    for (int k = 0; k < MR_N_MORPH_TIMES; ++k) {
+        out_ms[k] = 0.f;                             // (a kernel the last pass did not launch)
+        if (sc->morph_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->morph_ev[2 * k], sc->morph_ev[2 * k + 1]));
     }
     return MR_OK;
 }
