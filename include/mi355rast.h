@@ -522,6 +522,41 @@ int mr_debug_morph(mr_scene *scene, int32_t *out);
 #define MR_N_MORPH_TIMES 2
 int mr_debug_morph_times(mr_scene *scene, float *out_ms);
 
+/* on = 1: while the model moves (weights on its morph, bones on its skin, or a pose) and has vertex normals, the pose
+ * pass rebuilds those normals from the moved vertices V -- the float64 array the model renders with -- whenever it
+ * rewrites the model's geometry.  For normal q, L(q) is every face of the model that has at least one corner whose
+ * normal column is q, once, in ascending face order; with a, b, c the vertices of the face's corners 0, 1, 2,
+ *   cr(f) = (b - a) x (c - a)        every operation rounded on its own, no fma
+ *   acc   = cr(L[0]), then acc = acc + cr(L[k]) for k = 1 .. in order, component by component
+ *   l     = sqrt((acc0 * acc0 + acc1 * acc1) + acc2 * acc2);   N[q] = float32(acc / l)
+ * and the normal as it was added stays where L(q) is empty, l is 0, or a component of acc or l is not finite.  For these
+ * normals it takes the place of the morph's normal tables, of the skin's normal owners and of the vector part of the
+ * normal matrix: none of them is applied first (k_morph_normals, k_skin_normals and k_pose_normals leave the model out);
+ * object-space normal maps are re-baked with the normal matrix as ever.  on = 0 (the default) brings those paths back.
+ * The call launches nothing and passes no tables: the per-normal face lists are built from the faces the scene holds
+ * when the flag is first on (sliced per 64 normals, padded to the longest list among them; the padded total must fit
+ * 32 bits).  For a model at rest or without normals the flag changes nothing.  MR_E_INVALID for a model index out of
+ * range or a value other than 0 and 1. */
+int mr_scene_set_model_auto_normals(mr_scene *scene, int32_t model, int32_t on);
+
+/* Host arithmetic, no device needed: N of mr_scene_set_model_auto_normals for one model -- verts (n_verts, 4) float64,
+ * faces12 (n_faces, 12) int32 as the library keeps face rows (corner k at [4 k .. 4 k + 3]: vertex, uv, normal, material;
+ * indices count this model's arrays), normals_in and out (n_normals, 3) float32.  It builds the lists the device path
+ * builds and walks them in the kernel's order, bit for bit.  MR_OK, or MR_E_INVALID for a vertex or normal index out
+ * of range. */
+int mr_host_auto_normals(const double *verts, int32_t n_verts, const int32_t *faces12, int32_t n_faces, const float *normals_in,
+                         int32_t n_normals, float *out);
+
+/* Diagnostics of the rebuilt normals: out[0] = models the last pose pass rebuilt, out[1] = normals it wrote, out[2] =
+ * entries, padding included, of the face lists on the device, out[3] = normals among out[1] that kept the value they
+ * were added with.  Reads a few counters back from the device (the pass has waited for its kernels). */
+int mr_debug_auto_normals(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds of k_auto_normals in the last pose pass (0 if that pass did not launch it); it runs
+ * inside span [0] of mr_debug_pose_times.  MR_E_INVALID before the first pass that rebuilt normals. */
+#define MR_N_AUTO_NORMALS_TIMES 1
+int mr_debug_auto_normals_times(mr_scene *scene, float *out_ms);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

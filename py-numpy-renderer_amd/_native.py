@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, auto_normals_active, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -157,6 +157,10 @@ _PROTOTYPES = {
     "mr_host_morph_chain": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     "mr_debug_morph": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_morph_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_scene_set_model_auto_normals": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "mr_host_auto_normals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_debug_auto_normals": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_auto_normals_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -302,6 +306,7 @@ class DeviceRenderer:
         self._pose_keys = []                 # per model: (bytes of the pose, bytes of the normal matrix or None) the library holds, or None
         self._skin_keys = {}                 # model index -> [serial of the skin, its bone count, bytes of the bones or None] the library holds
         self._morph_keys = {}                # model index -> [serial of the morph, bytes of the weights or None] the library holds
+        self._auto_keys = {}                 # model index -> True where the library holds the auto_normals flag
         self._sky_key = None
         self._last_stats = {}
         self._frame = None
@@ -344,6 +349,7 @@ class DeviceRenderer:
             self._pose_keys = [None] * len(scene.models)        # (mr_scene_clear dropped the poses)
             self._skin_keys = {}                                 # (... and the skins)
             self._morph_keys = {}                                # (... and the morphs)
+            self._auto_keys = {}                                 # (... and the auto_normals flags)
         self.sync_poses(scene)
 
     def sync_poses(self, scene):
@@ -353,9 +359,11 @@ class DeviceRenderer:
         ``mr_scene_set_model_skin`` / ``mr_scene_set_model_bones`` is called when its part changed.  A skin goes to the
         library when its model first has bones: a scene without bones makes no call.  The morphs likewise: (serial of the
         morph, weight bytes), ``mr_scene_set_model_morph`` / ``mr_scene_set_model_morph_weights``, the tables handed over
-        when the model first has weights."""
+        when the model first has weights.  ``Model.auto_normals`` goes over (``mr_scene_set_model_auto_normals``) when
+        it changes for a model it has an effect on -- moved, with normals: a scene without such a model makes no call."""
         keys = self._pose_keys
         for index, model in enumerate(scene.models):
+            self._sync_auto_normals(index, model)
             self._sync_morph(index, model)
             self._sync_skin(index, model)
             pose = getattr(model, "pose", None)
@@ -370,6 +378,13 @@ class DeviceRenderer:
                 _check(self.lib.mr_scene_set_model_pose_normals(self.handle, index, None if g is None else g.ctypes.data),
                        "mr_scene_set_model_pose_normals")
             keys[index] = key
+
+    def _sync_auto_normals(self, index, model):
+        held = self.__dict__.setdefault("_auto_keys", {})
+        on = auto_normals_active(model)
+        if on != held.get(index, False):
+            _check(self.lib.mr_scene_set_model_auto_normals(self.handle, index, int(on)), "mr_scene_set_model_auto_normals")
+            held[index] = on
 
     def _sync_morph(self, index, model):
         keys = self.__dict__.setdefault("_morph_keys", {})
@@ -792,6 +807,21 @@ class DeviceRenderer:
         out = (C.c_int32 * 5)()
         _check(self.lib.mr_debug_morph(self.handle, out), "mr_debug_morph")
         return tuple(int(x) for x in out)
+
+    def auto_normals_counters(self):
+        """``mr_debug_auto_normals``: (models whose normals the last pose pass rebuilt, normals it wrote, entries --
+        padding included -- of the face lists on the device, normals among those written that kept their authored value)."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.mr_debug_auto_normals(self.handle, out), "mr_debug_auto_normals")
+        return tuple(int(x) for x in out)
+
+    AUTO_NORMALS_TIME_NAMES = ("auto_normals",)
+
+    def auto_normals_times(self):
+        """Device milliseconds of ``k_auto_normals`` in the last pose pass (``mr_debug_auto_normals_times``)."""
+        buf = (C.c_float * 1)()
+        _check(self.lib.mr_debug_auto_normals_times(self.handle, buf), "mr_debug_auto_normals_times")
+        return dict(zip(self.AUTO_NORMALS_TIME_NAMES, (float(v) for v in buf)))
 
     MORPH_TIME_NAMES = ("morph_vertices", "morph_normals")
 

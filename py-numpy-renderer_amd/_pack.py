@@ -524,11 +524,15 @@ def posed_vertices(model):
 def check_pose_normals(value):
     """``Model.pose_normals``: ``True`` / ``False`` (``bool``, ``np.bool_``) or the integers 0 / 1, returned as a
     ``bool``; ``TypeError`` for anything else."""
+    return _check_flag(value, "pose_normals")
+
+
+def _check_flag(value, name):
     if isinstance(value, (bool, np.bool_)):
         return bool(value)
     if isinstance(value, (int, np.integer)) and int(value) in (0, 1):
         return bool(value)
-    raise TypeError(f"pose_normals must be True or False, got {value!r}")
+    raise TypeError(f"{name} must be True or False, got {value!r}")
 
 
 def normal_matrix(pose):
@@ -569,10 +573,15 @@ def _chain_f32(vectors, g):
 def posed_normals(model):
     """The vertex normals a model renders with: ``model.normals``, or with ``pose_normals`` and a pose the float32 array
     ``float32(matmul_chain(float64(float32(normals)), G))``, ``G = normal_matrix(pose)``.  Normals that follow a skin
-    (``skinned_normals``) take the place of the widened normals: ``float32(n')``, or ``float32(matmul_chain(n', G))``."""
+    (``skinned_normals``) take the place of the widened normals: ``float32(n')``, or ``float32(matmul_chain(n', G))``.
+    With ``auto_normals`` on a moved model none of this applies: the normals are ``auto_normals(model)``, those of the
+    final geometry."""
     g = pose_normal_matrix(model)
     if model.normals is None:
         return model.normals
+    rebuilt = auto_normals(model)                    # (``Model.auto_normals``: the normals of the final geometry, nothing applied first)
+    if rebuilt is not None:
+        return rebuilt
     followed = skinned_normals(model)
     if followed is not None:
         from ._fp import matmul_chain
@@ -583,6 +592,99 @@ def posed_normals(model):
     if g is None:
         return normals
     return _chain_f32(normals, g)
+
+
+def check_auto_normals(value):
+    """``Model.auto_normals``: ``True`` / ``False`` (``bool``, ``np.bool_``) or the integers 0 / 1, returned as a
+    ``bool``; ``TypeError`` for anything else (the rules of ``check_pose_normals``)."""
+    return _check_flag(value, "auto_normals")
+
+
+def auto_normals_active(model):
+    """Whether ``Model.auto_normals`` has an effect: the flag is on, ``normals`` is not ``None`` and the model is moved
+    (it has ``morph_weights`` on a morph, ``bones`` on a skin, or a ``pose``)."""
+    if not getattr(model, "auto_normals", False) or model.normals is None:
+        return False
+    return getattr(model, "pose", None) is not None or active_skin(model) is not None or active_morph(model) is not None
+
+
+def face_rows(model):
+    """``_faces`` as the library keeps face rows: ``(F, 12)`` int32, corner k at ``[4 k .. 4 k + 3]`` with the vertex and
+    normal columns wrapped as ``normal_owners`` wraps them; the uv and material columns, which no caller of this reads,
+    are 0."""
+    faces = np.asarray(model._faces)
+    rows = np.zeros((len(faces), 3, 4), dtype=np.int32)
+    rows[..., 0] = _wrap(faces[..., 0].astype(np.int64), len(model.vertices), "vertex")
+    rows[..., 2] = _wrap(faces[..., 2].astype(np.int64), len(model.normals), "normal")
+    return np.ascontiguousarray(rows.reshape(len(faces), 12))
+
+
+_native_auto = None          # mr_host_auto_normals of the HIP library, or False
+
+
+def _fast_auto():
+    """The library's host helper, if the library is built (it loads without a GPU); else the loop below."""
+    global _native_auto
+    if _native_auto is None:
+        try:
+            from ._native import load_library
+            _native_auto = load_library().mr_host_auto_normals
+        except Exception:           # not built / not loadable here: the pure-Python chain gives the same bits
+            _native_auto = False
+    return _native_auto
+
+
+def auto_normals(model, native=None):
+    """The float32 normals N of a model whose ``auto_normals`` has an effect (``auto_normals_active``), the shape of
+    ``normals`` kept, else ``None``.  With V = ``posed_vertices(model)`` (float64) and ``L(q)`` the faces that have at
+    least one corner whose normal column is q, each once, ascending: ``acc`` = the cross product ``(V[b] - V[a]) x
+    (V[c] - V[a])`` of ``L(q)[0]`` (a, b, c the vertex columns of corners 0, 1, 2; every operation rounded on its own),
+    plus those of the further faces in order, component by component; ``l = sqrt((acc0 * acc0 + acc1 * acc1) + acc2 *
+    acc2)``; ``N[q] = float32(acc / l)``.  ``float32(normals[q])`` stays where ``L(q)`` is empty, ``l == 0``, or a
+    component of ``acc`` or ``l`` is not finite.  Only columns 0 to 2 change.  *native*: ``False`` forces the pure-Python
+    loop over Python floats, the yardstick of the library's ``mr_host_auto_normals``."""
+    if not auto_normals_active(model):
+        return None
+    verts = np.ascontiguousarray(np.asarray(posed_vertices(model)).astype(np.float64))
+    normals = np.ascontiguousarray(model.normals, dtype=np.float32)
+    rows = face_rows(model)
+    out = normals.copy()
+    fast = _fast_auto() if native is None or native else False
+    if fast:
+        flat = np.ascontiguousarray(normals[:, :3])
+        res = np.empty_like(flat)
+        rc = fast(verts.ctypes.data, len(verts), rows.ctypes.data, len(rows), flat.ctypes.data, len(flat), res.ctypes.data)
+        if rc != 0:
+            raise ValueError("mr_host_auto_normals refused the model's faces")
+        out[:, :3] = res
+        return out
+    import math
+    lists = [[] for _ in range(len(normals))]
+    for f, row in enumerate(rows.tolist()):
+        for k in range(3):
+            q = row[4 * k + 2]
+            if q not in (row[4 * j + 2] for j in range(k)):
+                lists[q].append(f)
+    v = verts[:, :3].tolist()
+    corners = rows[:, [0, 4, 8]].tolist()
+    for q, faces in enumerate(lists):
+        acc = None
+        for f in faces:
+            a, b, c = (v[i] for i in corners[f])
+            e0 = (b[0] - a[0], b[1] - a[1], b[2] - a[2])
+            e1 = (c[0] - a[0], c[1] - a[1], c[2] - a[2])
+            cr = (e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2], e0[0] * e1[1] - e0[1] * e1[0])
+            acc = cr if acc is None else (acc[0] + cr[0], acc[1] + cr[1], acc[2] + cr[2])
+        if acc is None or not all(math.isfinite(x) for x in acc):
+            continue
+        sq = (acc[0] * acc[0] + acc[1] * acc[1]) + acc[2] * acc[2]
+        if not math.isfinite(sq):                  # (the length would be infinite)
+            continue
+        l = math.sqrt(sq)
+        if l == 0:
+            continue
+        out[q, :3] = np.array([acc[0] / l, acc[1] / l, acc[2] / l], dtype=np.float64).astype(np.float32)
+    return out
 
 
 def posed_normal_map(texels, g):
@@ -667,7 +769,7 @@ def _posed_map_id(tex, g, model, textures, seen):
 
 def pack_model(model, textures, seen, posed=False) -> PackedModel:
     """*posed*: pack the arrays the model renders with -- ``posed_vertices`` (morph, then skin, then pose) and, with
-    ``pose_normals``, a skin or a morph the normals follow, ``posed_normals``, and with ``pose_normals`` re-baked object-space normal maps -- instead of
+    ``pose_normals``, a skin or a morph the normals follow, or ``auto_normals``, ``posed_normals``, and with ``pose_normals`` re-baked object-space normal maps -- instead of
     ``model.vertices`` / ``normals`` / the maps as registered: what the oracle needs; the device gets the arrays as they
     are and the matrices and tables beside them (``mr_scene_set_model_pose``, ``mr_scene_set_model_pose_normals``,
     ``mr_scene_set_model_skin``, ``mr_scene_set_model_bones``)."""
@@ -683,7 +785,8 @@ def pack_model(model, textures, seen, posed=False) -> PackedModel:
     normals = None if model.normals is None else np.ascontiguousarray(model.normals, dtype=np.float32)
     morph = active_morph(model) if posed else None
     if posed and normals is not None and (nmat is not None or (active_skin(model) is not None and model.skin.normals)
-                                          or (morph is not None and morph.normal_targets is not None)):
+                                          or (morph is not None and morph.normal_targets is not None)
+                                          or auto_normals_active(model)):
         normals = np.ascontiguousarray(posed_normals(model))
     if uv is not None and (uv.ndim != 2 or uv.shape[1] < 2):
         raise ValueError(f"Model.uv must be (T, 3), got {uv.shape}")

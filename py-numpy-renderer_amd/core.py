@@ -178,7 +178,21 @@ class Model:
     themselves.  Assignments are checked at once: an index past ``len(vertices)`` (``len(normals)``), ``normal_targets``
     on a model without normals, ``morph_weights`` without a ``morph``, and a weight count other than t -- at whichever of
     the two assignments completes the pair -- raise ``ValueError`` and the attribute keeps its value; ``morph = None``
-    drops ``morph_weights`` as well.  A morph whose indices no longer fit the model raises ``ValueError`` at ``render()``."""
+    drops ``morph_weights`` as well.  A morph whose indices no longer fit the model raises ``ValueError`` at ``render()``.
+
+    ``auto_normals`` (an addition; ``False`` by default; ``True`` / ``False`` / 0 / 1, anything else ``TypeError``)
+    rebuilds the vertex normals of a moved model from its deformed triangles, as any deformer does.  It takes effect
+    while the model is moved (it has ``morph_weights``, ``bones`` or a ``pose``) and ``normals`` is not ``None``; a
+    model at rest renders its authored normals -- ``pose = np.eye(4)`` rebuilds the normals of a mesh that is otherwise
+    at rest.  With V the float64 vertices the model renders with (``_pack.posed_vertices``) and ``L(q)`` the faces that
+    have at least one corner whose normal column is q, each once, in ascending order, ``normals[q]`` becomes the float32
+    of the sum over ``L(q)`` of ``(V[b] - V[a]) x (V[c] - V[a])`` (a, b, c the vertex columns of corners 0, 1, 2; plain
+    float64 operations, added in order) divided by its length (``_pack.auto_normals``); the authored ``float32(normals[q])``
+    stays where ``L(q)`` is empty, the length is 0, or the sum or its length is not finite.  The direction is that of
+    the face normals of the light-facing test, so a mirroring pose flips the normals with the faces.  For the vertex
+    normals it supersedes ``normal_targets``, ``Skin(normals=True)`` and the vector part of ``pose_normals``: none of
+    them is applied first.  Object-space normal maps keep their behaviour (re-baked under ``pose`` and ``pose_normals``,
+    else untouched); tangent-space maps follow by themselves.  ``normals`` itself is never modified."""
 
     def __init__(self, vertices, uv, normals, faces, shadowing=False, materials=None,
                  material_group=None, clip=True, depth_test=True):
@@ -204,6 +218,7 @@ class Model:
         self._morph = None
         self._morph_weights = None
         self._morph_serial = 0
+        self._auto_normals = False
 
     # -- ingest ---------------------------------------------------------------------------
     @classmethod
@@ -302,6 +317,17 @@ class Model:
         on = check_pose_normals(value)
         g = normal_matrix(self.pose) if on and self.pose is not None else None
         self._pose_normals, self._normal_matrix = on, g
+
+    @property
+    def auto_normals(self):
+        """``False`` (the default) or ``True``: the vertex normals of the moved model are rebuilt from its deformed
+        triangles; see the class docstring."""
+        return getattr(self, "_auto_normals", False)
+
+    @auto_normals.setter
+    def auto_normals(self, value):
+        from ._pack import check_auto_normals
+        self._auto_normals = check_auto_normals(value)
 
     @property
     def skin(self):

@@ -15,6 +15,9 @@
 // d_verts_m, the copy of d_verts0 that k_skin_vertices and k_pose_vertices then take as their pristine source -- and
 // k_morph_normals does the same for its normals with d_normals_m (apply_morph_normals).  The kernels that follow are
 // the same code with another source pointer.
+// A model whose flag is on (mr_scene_set_model_auto_normals) and that moves gets its vertex normals from k_auto_normals
+// (apply_auto_normals), after the vertex kernels and in front of k_face_static; k_morph_normals, k_skin_normals and
+// k_pose_normals leave it out of their rows (k_pose_texels does not: its object-space maps are re-baked as ever).
 // The pass is synchronous: it waits for the device before it starts (frames in flight on other streams read the static
 // records: the rule of commit() and mr_scene_add_model) and for its own kernels before it returns.
 #pragma once
@@ -28,6 +31,9 @@ void moved_changed(mr_scene *sc, int32_t model, bool was)
 {
     const mr_scene::ModelPose &mp = sc->poses[model];
     const bool now = mp.moved();
+    // a model whose normals are rebuilt from its mesh (mr_scene_set_model_auto_normals) starts or stops doing so with
+    // "moves": the whole normals' part, as for a model that starts or stops following a skin
+    if (was != now && mp.auto_on && mp.n_normals > 0) sc->pose_dirty = sc->pose_g_dirty = true;
     if (was == now || !mp.verts_f32) return;
     const size_t f0 = (size_t)sc->model_face_off[model];
     const size_t f1 = (size_t)model + 1 < sc->model_face_off.size() ? (size_t)sc->model_face_off[model + 1] : sc->face_flags.size();
@@ -147,6 +153,31 @@ void set_model_morph_weights(mr_scene *sc, int32_t model, const double *w)
     }
 }
 
+// the per-normal face lists of one model, from the faces the scene holds
+bool build_auto_lists(mr_scene *sc, size_t model)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    const int32_t f0 = sc->model_face_off[model];
+    const int32_t f1 = model + 1 < sc->model_face_off.size() ? sc->model_face_off[model + 1] : (int32_t)(sc->faces.size() / 12);
+    return mr_autonormals::build_lists(mp.n_normals, mp.normal_off, sc->faces.data(), f0, f1, mp.auto_lists);
+}
+
+// mr_scene_set_model_auto_normals behind its argument checks: the lists are built when the flag is first on; the flag
+// alone launches nothing, and changes nothing for a model that is at rest or has no normals
+int set_model_auto_normals(mr_scene *sc, int32_t model, bool on)
+{
+    mr_scene::ModelPose &mp = sc->poses[model];
+    if (mp.auto_on == on) return MR_OK;
+    if (on && mp.n_normals > 0 && mp.auto_lists.n == 0) {
+        if (!build_auto_lists(sc, (size_t)model)) return fail(MR_E_INVALID, "the model's padded face lists do not fit 32-bit offsets");
+        sc->auto_tables_dirty = true;
+    }
+    mp.auto_on = on;
+    // the other normals' paths (normal targets, the skin, the normal matrix) go or come back: the whole normals' part
+    if (mp.n_normals > 0 && mp.moved()) sc->pose_dirty = sc->pose_g_dirty = true;
+    return MR_OK;
+}
+
 // a material's object-space normal map, if it has one
 inline bool object_space_map(const mr_scene *sc, const mr::Material &m)
 {
@@ -174,7 +205,7 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
         mr::Vec3Row r;
         std::memset(&r, 0, sizeof r);
         std::memcpy(r.g, mp.g, sizeof r.g);
-        if (mp.n_normals > 0 && !mp.skin_normals()) {    // (normals that follow a skin: k_skin_normals applies G as well)
+        if (mp.n_normals > 0 && !mp.skin_normals() && !mp.auto_normals()) {    // (normals that follow a skin: k_skin_normals applies G as well; rebuilt normals: G has no part in them)
             r.first = mp.normal_off; r.count = mp.n_normals; r.block0 = (int32_t)nblocks.size();
             nblocks.insert(nblocks.end(), (size_t)blocks_for(mp.n_normals, mr::POSE_BLOCK), (int32_t)nrows.size());
             nrows.push_back(r);
@@ -220,7 +251,7 @@ int apply_pose_normals(mr_scene *sc, NormalTables &tables)
             mp.normals_on_device = mp.n_normals > 0;
             continue;
         }
-        if (mp.skin_normals() || mp.morph_normals()) mp.normals_on_device = true;    // (apply_skin_normals / apply_morph_normals write them)
+        if (mp.skin_normals() || mp.morph_normals() || mp.auto_normals()) mp.normals_on_device = true;    // (apply_skin_normals / apply_morph_normals / apply_auto_normals write them)
         else if (mp.normals_on_device) {                 // a model whose matrix is gone gets its own normals back
             const size_t off = (size_t)mp.normal_off * 3 * sizeof(float), bytes = (size_t)mp.n_normals * 3 * sizeof(float);
             HIP_TRY(hipMemcpyAsync(static_cast<char *>(sc->d_normals.p) + off, static_cast<const char *>(sc->d_normals0.p) + off, bytes,
@@ -454,6 +485,79 @@ int apply_morph_normals(mr_scene *sc, MorphTables &t)
     return MR_OK;
 }
 
+// The face lists on the device: the slices of every model that holds lists -- its flag is on, or was on since the last
+// commit: a model whose flag comes back finds its slices where it left them -- one after the other.  Rebuilt when a
+// model's lists were built or the scene was committed (which drops the host lists: they are built again here), not per pass.
+int upload_auto_tables(mr_scene *sc)
+{
+    if (!sc->auto_tables_dirty) return MR_OK;
+    std::vector<int32_t> slices, faces;
+    for (size_t k = 0; k < sc->poses.size(); ++k) {
+        mr_scene::ModelPose &mp = sc->poses[k];
+        if (mp.n_normals == 0 || (!mp.auto_on && mp.auto_lists.n == 0)) continue;
+        if (mp.auto_lists.n == 0 && !build_auto_lists(sc, k))
+            return fail(MR_E_INVALID, "the model's padded face lists do not fit 32-bit offsets");
+        const int64_t base = (int64_t)faces.size();
+        if (base + mp.auto_lists.entries() > INT32_MAX) return fail(MR_E_INVALID, "the scene's face lists do not fit 32-bit offsets");
+        mp.auto_slice0 = (int32_t)slices.size();
+        for (int32_t f : mp.auto_lists.slice_first) slices.push_back((int32_t)base + f);
+        faces.insert(faces.end(), mp.auto_lists.face.begin(), mp.auto_lists.face.end());
+    }
+    if (int rc = upload(sc->d_auto_slices, slices, g_stream)) return rc;
+    if (int rc = upload(sc->d_auto_faces, faces, g_stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(g_stream));         // (the vectors go out of scope)
+    sc->auto_entries = (int32_t)faces.size();
+    sc->auto_tables_dirty = false;
+    return MR_OK;
+}
+
+struct AutoTables {                                      // (the caller keeps them until it has waited for the stream)
+    std::vector<mr::AutoRow> rows;
+    std::vector<int32_t> blocks;
+};
+
+// The normals of the models that rebuild them from their mesh (k_auto_normals), after the vertex kernels -- d_verts holds
+// the moved vertices -- and in front of k_face_static: from d_verts, and the pristine d_normals0 for the values that
+// stay, into d_normals.  Every such model is rebuilt whenever the pass rewrites geometry or the normals' part runs.
+int apply_auto_normals(mr_scene *sc, AutoTables &t)
+{
+    if (int rc = upload_auto_tables(sc)) return rc;
+    int64_t written = 0;
+    for (mr_scene::ModelPose &mp : sc->poses) {
+        if (!mp.auto_normals()) continue;
+        mr::AutoRow r;
+        std::memset(&r, 0, sizeof r);
+        r.first = mp.normal_off; r.count = mp.n_normals; r.block0 = (int32_t)t.blocks.size(); r.slice0 = mp.auto_slice0;
+        t.blocks.insert(t.blocks.end(), (size_t)blocks_for(mp.n_normals, mr::POSE_BLOCK), (int32_t)t.rows.size());
+        t.rows.push_back(r);
+        mp.normals_on_device = true;
+        written += mp.n_normals;
+    }
+    if (t.rows.empty()) return MR_OK;
+    if (!sc->normals0_valid) {
+        if (int rc = upload(sc->d_normals0, sc->normals, g_stream)) return rc;
+        sc->normals0_valid = true;
+    }
+    for (hipEvent_t &e : sc->auto_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    const size_t waves = t.blocks.size() * (mr::POSE_BLOCK / mr::WAVE);
+    HIP_TRY(sc->d_auto_kept.ensure(waves * sizeof(int32_t)));
+    HIP_TRY(hipMemsetAsync(sc->d_auto_kept.p, 0, waves * sizeof(int32_t), g_stream));    // (a wavefront past the range's end writes nothing)
+    if (int rc = upload(sc->d_auto_rows, t.rows, g_stream)) return rc;
+    if (int rc = upload(sc->d_auto_blocks, t.blocks, g_stream)) return rc;
+    HIP_TRY(hipEventRecord(sc->auto_ev[0], g_stream));
+    hipLaunchKernelGGL(mr::k_auto_normals, dim3((unsigned)t.blocks.size()), dim3(mr::POSE_BLOCK), 0, g_stream,
+                       sc->d_auto_rows.as<mr::AutoRow>(), sc->d_auto_blocks.as<int32_t>(), sc->d_auto_slices.as<int32_t>(),
+                       sc->d_auto_faces.as<int32_t>(), sc->d_faces.as<int32_t>(), sc->d_verts.as<double4>(),
+                       sc->d_normals0.as<float>(), sc->d_normals.as<float>(), sc->d_auto_kept.as<int32_t>());
+    HIP_TRY(hipEventRecord(sc->auto_ev[1], g_stream));
+    sc->auto_ran = sc->auto_marks = true;
+    sc->auto_models = (int32_t)t.rows.size();
+    sc->auto_written = (int32_t)written;
+    sc->auto_kept_waves = (int32_t)waves;
+    return MR_OK;
+}
+
 // Runs where commit() runs, right after it.  What a pass does depends on what changed: a pose brings all of it, a
 // normal matrix alone (the pose as it was) the normals' part and k_face_static -- vertices, face and edge normals, the
 // cluster records and the silhouette cache stay.
@@ -461,10 +565,14 @@ int apply_poses(mr_scene *sc)
 {
     if (!sc->pose_dirty) return MR_OK;
     const bool geom = sc->pose_geom_dirty;
+    sc->auto_ran = false;                            // (also a pass that finds nothing to launch rebuilt no normals)
+    sc->auto_models = sc->auto_written = sc->auto_kept_waves = 0;
     std::vector<mr::PoseRow> rows;
     std::vector<int32_t> block_row;
     SkinTables skin;
     MorphTables morph;
+    AutoTables auto_tables;
+    bool auto_n = false;
     bool restore = false, normals = false, skin_normals = false, bones = false, morph_normals = false, weights = false;
     int64_t written = 0, skinned = 0, morphed = 0;
     for (const mr_scene::ModelPose &mp : sc->poses) {
@@ -473,6 +581,7 @@ int apply_poses(mr_scene *sc)
         morph_normals = morph_normals || ((sc->pose_g_dirty || sc->morph_n_dirty) && (mp.morph_normals() || mp.normals_m_morphed));
         bones = bones || mp.has_bones;
         weights = weights || mp.has_weights;
+        auto_n = auto_n || ((geom || sc->pose_g_dirty) && mp.auto_normals());
         if (!geom) continue;
         if (!mp.moved()) { restore = restore || mp.on_device; continue; }
         if (mp.has_weights) morphed += mp.n_verts;                  // (its row needs the weight table: below)
@@ -487,7 +596,7 @@ int apply_poses(mr_scene *sc)
         written += mp.n_verts;
     }
     written += skinned;
-    if (rows.empty() && !skinned && !morphed && !restore && !normals && !skin_normals && !morph_normals) {      // (a commit has just uploaded the pristine vertices)
+    if (rows.empty() && !skinned && !morphed && !restore && !normals && !skin_normals && !morph_normals && !auto_n) {      // (a commit has just uploaded the pristine vertices)
         sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = sc->morph_n_dirty = false;
         return MR_OK;
     }
@@ -525,6 +634,8 @@ int apply_poses(mr_scene *sc)
                            sc->d_face_pos.as<mr::FacePos64>(), sc->d_face_attr.as<mr::FaceAttr>());
     };
     if (rows.empty() && !skinned && !morphed && !restore) {      // normal matrices alone: the face records take the new normals
+        if (auto_n)                                  // (a flag that was turned on: d_verts holds the moved vertices already)
+            if (int rc = apply_auto_normals(sc, auto_tables)) return rc;
         if (nf > 0) face_static();
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g_stream));     // (the tables go out of scope)
@@ -624,6 +735,8 @@ int apply_poses(mr_scene *sc)
     }
     for (mr_scene::ModelPose &mp : sc->poses)
         if (mp.moved()) mp.on_device = true;
+    if (auto_n)                                      // the vertices are in place: the normals rebuilt from them
+        if (int rc = apply_auto_normals(sc, auto_tables)) return rc;
     HIP_TRY(hipEventRecord(sc->pose_ev[mark++], g_stream));
     if (nf > 0) {
         hipLaunchKernelGGL(mr::k_face_normals, dim3((nf + 255) / 256), dim3(256), 0, g_stream, nf, sc->d_faces.as<int32_t>(),

@@ -60,9 +60,15 @@ struct mr_scene {
         int32_t slice0_v = 0, slice0_n = 0;   // where the model's slices start in d_morph_slices
         bool verts_m_morphed = false;         // d_verts_m differs from d_verts0 in this model's range
         bool normals_m_morphed = false;       // ... d_normals_m from d_normals0
+        // the flag of mr_scene_set_model_auto_normals and the per-normal face lists (host_autonormals.h), built when the
+        // flag is first on, dropped by commit() and built again by the next pass that needs them
+        bool auto_on = false;
+        mr_autonormals::Lists auto_lists;
+        int32_t auto_slice0 = 0;              // where the model's slices start in d_auto_slices
         bool moved() const { return posed || has_bones || has_weights; }                   // d_verts differs from d_verts0
-        bool skin_normals() const { return has_bones && !owners.empty() && n_normals > 0; }  // ... d_normals from d_normals0 by the skin
-        bool morph_normals() const { return has_weights && morph_n.n > 0 && n_normals > 0; } // ... or by the morph
+        bool auto_normals() const { return auto_on && n_normals > 0 && moved(); }          // d_normals is rebuilt from d_verts: none of the other three writes it
+        bool skin_normals() const { return has_bones && !owners.empty() && n_normals > 0 && !auto_normals(); }  // ... d_normals from d_normals0 by the skin
+        bool morph_normals() const { return has_weights && morph_n.n > 0 && n_normals > 0 && !auto_normals(); } // ... or by the morph
     };
     std::vector<ModelPose> poses;             // one per model
     bool skin_tables_dirty = false;           // a skin was set or removed: the device tables are rebuilt by the next pass
@@ -71,6 +77,8 @@ struct mr_scene {
     bool morph_tables_dirty = false;          // a morph was set or removed: the device lists are rebuilt by the next pass that needs them
     bool morph_n_dirty = false;               // weights of a model whose normals follow its morph changed
     int32_t morph_targets = 0, morph_written = 0, morph_normals_written = 0, morph_entries = 0;   // mr_debug_morph
+    bool auto_tables_dirty = false;           // a model's lists were built, or the scene was committed: the device lists (of every model that holds some) are rebuilt by the next pass that needs them
+    int32_t auto_models = 0, auto_written = 0, auto_entries = 0, auto_kept_waves = 0;   // mr_debug_auto_normals (the kept count is summed from d_auto_kept when asked for)
     bool pose_dirty = false;                  // a pose or a normal matrix changed: apply_poses() has work
     bool pose_geom_dirty = false;             // ... and a pose among them: vertices and what is built from them
     bool pose_g_dirty = false;                // ... and a normal matrix among them: normals and re-baked maps
@@ -113,6 +121,11 @@ struct mr_scene {
     hipEvent_t morph_ev[4] = {};              // marks round k_morph_vertices and k_morph_normals (mr_debug_morph_times)
     bool morph_ran[2] = {};                   // which of the two the last pass launched
     bool morph_marks = false;
+    // rebuilt normals: the sliced face lists of every model whose flag is on, one after the other (the slice table and
+    // one plane of faces), the kernel's two tables and its per-wavefront counts of normals that kept their value
+    DevBuf d_auto_slices, d_auto_faces, d_auto_rows, d_auto_blocks, d_auto_kept;
+    hipEvent_t auto_ev[2] = {};               // marks round k_auto_normals (mr_debug_auto_normals_times)
+    bool auto_ran = false, auto_marks = false;
     bool pos32 = false;                     // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
     DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
@@ -359,6 +372,8 @@ int commit(mr_scene *sc)
     for (mr_scene::ModelPose &mp : sc->poses) {
         mp.on_device = mp.normals_on_device = mp.maps_on_device = false;
         mp.verts_m_morphed = mp.normals_m_morphed = false;
+        mp.auto_lists.clear();                // (the face lists belong to the committed faces)
+        if (mp.auto_on) sc->auto_tables_dirty = true;
         if (mp.moved()) sc->pose_dirty = sc->pose_geom_dirty = true;
         if (mp.has_g || mp.skin_normals() || mp.morph_normals()) sc->pose_g_dirty = true;
     }

@@ -13,6 +13,9 @@
 //                     deltas of the targets that list it, an fma chain in ascending target order over sliced per-vertex
 //                     lists (host_morph.h); mr_host_morph_chain, bit for bit.  Runs first: skin and pose take its result
 //   k_morph_normals   the same over vertex normals, widened and rounded to float32 once
+//   k_auto_normals    vertex normals of the models that asked for them rebuilt from the moved vertices: the sum of the
+//                     incident faces' cross products over sliced per-normal face lists (host_autonormals.h), normalised
+//                     and rounded to float32 once; mr_host_auto_normals, bit for bit.  Runs after the vertex kernels
 //   k_clusters        the per-cluster records (rast_types.h, ClusterRec) from the posed vertices: what build_clusters
 //                     (host_scene.h) builds on the host at commit time, one wavefront per cluster
 //
@@ -295,6 +298,60 @@ k_morph_normals(const MorphRow *__restrict__ rows, const int32_t *__restrict__ b
                 float *__restrict__ normals_m, float *__restrict__ normals)
 {
     morph_body<true>(rows, block_row, slice_first, target, dx, dy, dz, weights, normals0, normals_m, normals);
+}
+
+// One model whose vertex normals are rebuilt from its deformed mesh (mr_scene_set_model_auto_normals): its normal range,
+// where its slices start in the slice table of the face lists, and the first of the workgroups that cover the range.
+struct alignas(8) AutoRow {
+    int32_t first, count;
+    int32_t block0, slice0;
+};
+static_assert(sizeof(AutoRow) == 16, "AutoRow layout");
+
+// One normal per thread, the tables of k_morph_normals: a wavefront holds 64 consecutive normals of the model, one
+// slice of its face lists (host_autonormals.h).  Entry e of lane l sits at slice_first[s] + e * 64 + l, so the list is
+// read as contiguous 256-byte accesses and the trip count is uniform over the wavefront; padding (-1) is skipped.  Per
+// entry: the face, its three vertex columns from the face table, three gathered 32-byte vertices, the cross product
+// of the double branch of face_unit_normal and three adds -- the first product is taken as it is, so that a -0 stays
+// one -- in ascending face order (mr_host_auto_normals, bit for bit: the library is built with -ffp-contract=off).
+// After the walk normalize3's arithmetic, rounded to float32 once; the authored normal (normals0) stays for an empty
+// list, a sum of length 0 and a sum or length that is not finite.  kept[w] counts those of wavefront w of the launch
+// (written by one lane; read by mr_debug_auto_normals).  The indices were validated when the model was added.  (Lists
+// that hold the three vertex columns themselves, 12 bytes an entry, were built and timed too: DESIGN.md section 6g.)
+__global__ void __launch_bounds__(POSE_BLOCK)
+k_auto_normals(const AutoRow *__restrict__ rows, const int32_t *__restrict__ block_row, const int32_t *__restrict__ slice_first,
+               const int32_t *__restrict__ face_list, const int32_t *__restrict__ faces, const double4 *__restrict__ verts,
+               const float *__restrict__ normals0, float *__restrict__ normals, int32_t *__restrict__ kept)
+{
+    const AutoRow &r = rows[block_row[blockIdx.x]];
+    const int i = (int)(blockIdx.x - (uint32_t)r.block0) * POSE_BLOCK + (int)threadIdx.x;
+    if (i >= r.count) return;
+    const size_t at = ((size_t)r.first + i) * 3;
+    const int s = __builtin_amdgcn_readfirstlane(r.slice0 + (i >> 6)), lane = i & (WAVE - 1);     // (i >> 6 is the wavefront's)
+    const int end = slice_first[s + 1];
+    double ax = 0.0, ay = 0.0, az = 0.0;
+    bool any = false;
+    for (int p = slice_first[s]; p < end; p += WAVE) {
+        const int f = face_list[(size_t)p + lane];
+        if (f < 0) continue;
+        const int32_t *fc = faces + (size_t)f * 12;
+        const double4 a = verts[fc[0]], b = verts[fc[4]], c = verts[fc[8]];
+        const double e0x = b.x - a.x, e0y = b.y - a.y, e0z = b.z - a.z;
+        const double e1x = c.x - a.x, e1y = c.y - a.y, e1z = c.z - a.z;
+        const double cx = e0y * e1z - e0z * e1y, cy = e0z * e1x - e0x * e1z, cz = e0x * e1y - e0y * e1x;
+        ax = any ? ax + cx : cx;
+        ay = any ? ay + cy : cy;
+        az = any ? az + cz : cz;
+        any = true;
+    }
+    const double l = sqrt((ax * ax + ay * ay) + az * az);
+    const bool keep = !any || l == 0 || !isfinite(ax) || !isfinite(ay) || !isfinite(az) || !isfinite(l);
+    float3 o;
+    if (keep) o = *reinterpret_cast<const float3 *>(normals0 + at);
+    else { o.x = (float)(ax / l); o.y = (float)(ay / l); o.z = (float)(az / l); }
+    *reinterpret_cast<float3 *>(normals + at) = o;
+    const int n_kept = __popcll(__ballot(keep));                    // (of the lanes that have a normal)
+    if (lane == 0) kept[blockIdx.x * (POSE_BLOCK / WAVE) + threadIdx.x / WAVE] = n_kept;
 }
 
 __device__ __forceinline__ double shfl_xor_d(double v, int mask)

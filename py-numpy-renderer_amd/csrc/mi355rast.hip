@@ -7,6 +7,7 @@
 //   host_scene.h        the static scene and commit()
 //   host_overlay_dev.h  the debug-frustum overlay's device plumbing (host_overlay.h builds its lists)
 //   host_morph.h        morph targets: the per-vertex contribution lists (plain C++, no HIP)
+//   host_autonormals.h  rebuilt vertex normals: the per-normal face lists (plain C++, no HIP)
 //   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //
@@ -55,6 +56,7 @@
 #include "host_env.h"
 #include "host_silcache.h"
 #include "host_morph.h"
+#include "host_autonormals.h"
 #include "host_scene.h"
 #include "host_pose.h"
 #include "host_overlay_dev.h"
@@ -114,6 +116,7 @@ int mr_scene_clear(mr_scene *sc)
     sc->poses.clear(); sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
     sc->skin_tables_dirty = true;
     sc->morph_tables_dirty = true; sc->morph_n_dirty = false;
+    sc->auto_tables_dirty = true;
     sc->dirty = true;
     sc->last = nullptr;
     sc->sil.drop();
@@ -159,7 +162,8 @@ void mr_scene_destroy(mr_scene *sc)
                        &sc->d_texel_rows, &sc->d_texel_blocks, &sc->d_rebaked, &sc->d_skin_joints, &sc->d_skin_weights, &sc->d_skin_owners,
                        &sc->d_bones, &sc->d_skin_rows, &sc->d_skin_blocks, &sc->d_skin_n_rows, &sc->d_skin_n_blocks, &sc->d_morph_slices,
                        &sc->d_morph_target, &sc->d_morph_dx, &sc->d_morph_dy, &sc->d_morph_dz, &sc->d_morph_weights, &sc->d_morph_rows,
-                       &sc->d_morph_blocks, &sc->d_morph_n_rows, &sc->d_morph_n_blocks, &sc->d_verts_m, &sc->d_normals_m })
+                       &sc->d_morph_blocks, &sc->d_morph_n_rows, &sc->d_morph_n_blocks, &sc->d_verts_m, &sc->d_normals_m,
+                       &sc->d_auto_slices, &sc->d_auto_faces, &sc->d_auto_rows, &sc->d_auto_blocks, &sc->d_auto_kept })
         b->release();
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
@@ -168,6 +172,7 @@ void mr_scene_destroy(mr_scene *sc)
     for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->skin_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->morph_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sc->auto_ev) if (e) (void)hipEventDestroy(e);
     delete sc;
 }
 
@@ -424,6 +429,14 @@ int mr_scene_set_model_morph_weights(mr_scene *sc, int32_t model, const double *
     return MR_OK;
 }
 
+int mr_scene_set_model_auto_normals(mr_scene *sc, int32_t model, int32_t on)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (model < 0 || (size_t)model >= sc->poses.size()) return fail(MR_E_INVALID, "model index out of range");
+    if (on != 0 && on != 1) return fail(MR_E_INVALID, "auto_normals is 0 or 1");
+    return set_model_auto_normals(sc, model, on != 0);
+}
+
 int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats *stats)
 {
     if (!sc || !out_rgb) return fail(MR_E_INVALID, "NULL argument");
@@ -582,6 +595,18 @@ void mr_host_skin_chain3(const double *vectors, const int32_t *owner, const int3
             }
         for (int c = 0; c < 3; ++c) out[(size_t)i * 3 + c] = o[c];
     }
+}
+
+int mr_host_auto_normals(const double *verts, int32_t n_verts, const int32_t *faces12, int32_t n_faces, const float *normals_in,
+                         int32_t n_normals, float *out)
+{
+    if (!verts || !normals_in || !out) return fail(MR_E_INVALID, "mr_host_auto_normals: NULL argument");
+    if (const char *wrong = mr_autonormals::check_faces(faces12, n_faces, n_verts, n_normals)) return fail(MR_E_INVALID, wrong);
+    mr_autonormals::Lists lists;                     // the lists the upload path builds, walked in the kernel's order
+    if (!mr_autonormals::build_lists(n_normals, 0, faces12, 0, n_faces, lists))
+        return fail(MR_E_INVALID, "the padded face lists do not fit 32-bit offsets");
+    mr_autonormals::walk_lists(lists, verts, faces12, normals_in, out);
+    return MR_OK;
 }
 
 int mr_host_morph_chain(const double *base, int32_t n, int32_t width, int32_t n_targets, const int32_t *first, const int32_t *index,
@@ -909,6 +934,28 @@ int mr_debug_morph(mr_scene *sc, int32_t *out)
     for (const mr_scene::ModelPose &mp : sc->poses) weighted += mp.has_weights ? 1 : 0;
     out[0] = weighted; out[1] = sc->morph_targets; out[2] = sc->morph_written; out[3] = sc->morph_normals_written;
     out[4] = sc->morph_entries;
+    return MR_OK;
+}
+
+int mr_debug_auto_normals(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    int64_t kept = 0;
+    if (sc->auto_kept_waves > 0) {                   // (the pass has waited for its kernels)
+        std::vector<int32_t> waves((size_t)sc->auto_kept_waves);
+        HIP_TRY(hipMemcpy(waves.data(), sc->d_auto_kept.p, waves.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t k : waves) kept += k;
+    }
+    out[0] = sc->auto_models; out[1] = sc->auto_written; out[2] = sc->auto_entries; out[3] = (int32_t)kept;
+    return MR_OK;
+}
+
+int mr_debug_auto_normals_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->auto_marks) return fail(MR_E_INVALID, "no pass over rebuilt normals yet");
+    out_ms[0] = 0.f;                                 // (the last pass did not launch it)
+    if (sc->auto_ran) HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->auto_ev[0], sc->auto_ev[1]));
     return MR_OK;
 }
 
