@@ -361,6 +361,8 @@ int mr_read_silhouette_light(mr_scene *scene, int32_t light, int32_t *out_triple
  * [5..7] lengths of the tile's lists: small triangle pairs, big triangle pairs, shadow quads;
  * [8],[9] start and end of the tile's workgroup in 10 ns ticks (low 32 bits); [10],[11] the ticks at
  * which its coverage / z phase and its shadow-quad phase ended.
+ * Words [0..4] and [8..11] are the general kernel's (mr_debug_frame_path out[0] == 1; mr_debug_force_full): the frame-only
+ * kernel writes neither: [0..4] and [8..11] read 0 after such a frame.
  * Returns the number of tiles (tiles are 16 x 16 px, row-major over the rendered rows) or a negative error. */
 #define MR_TILE_RECORD_WORDS 12
 int mr_debug_read_tile_records(mr_scene *scene, uint32_t *out, int32_t cap_tiles);
@@ -380,6 +382,18 @@ int mr_debug_clusters_culled(mr_scene *scene);
  * MR_QUAD_WALK=strips | spans in the environment (read once per process) forces either walk; the frames do not depend on
  * it. */
 int mr_debug_quad_walks(mr_scene *scene, uint32_t *out);
+
+/* The set-up and tile kernels exist in two variants of one source: the frame-only ones, which count nothing, and the
+ * general ones.  A frame takes the general kernels when it carries MR_FRAME_COUNTERS or MR_FRAME_FACE_STATUS or the
+ * scene has a model with depth_test == 0; every other frame the frame-only ones.  The frame, z, winner and stencil do
+ * not depend on the variant.  mr_debug_force_full(scene, 1) makes every later frame of the scene take the general
+ * kernels, (scene, 0) returns to the rule.  Launches nothing. */
+int mr_debug_force_full(mr_scene *scene, int32_t on);
+
+/* Which kernels the most recent frame launched: out[0] = 1 the general variants (k_setup_full, k_tile_full), 0 the
+ * frame-only ones; out[1] = 1 the tile kernel that shares heavy tiles out (SPLIT); out[2] = 1 the supersampled one;
+ * out[3] = 1 the multi-light ones; out[4] = 1 the tile kernel followed the heaviest-first order, 0 row-major.  Does not wait for the device. */
+int mr_debug_frame_path(mr_scene *scene, int32_t *out);
 
 /* Diagnostics of the silhouette cache: out[0] = the path the edge half of the most recently enqueued frame
  * with shadows took (0 fused: every edge tested against the light; 1 fused, and captured into the cache; 2 read from the

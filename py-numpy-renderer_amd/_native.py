@@ -140,6 +140,8 @@ _PROTOTYPES = {
     "mr_host_camera_constants": (None, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3),
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_force_full": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mr_debug_frame_path": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_scene_set_model_pose": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mr_scene_set_model_pose_normals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "mr_debug_pose_normals_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
@@ -786,6 +788,19 @@ class DeviceRenderer:
         out = (C.c_int32 * 4)()
         _check(self.lib.mr_debug_sil_cache(self.handle, out), "mr_debug_sil_cache")
         return tuple(int(x) for x in out)
+
+    def force_full(self, on=True):
+        """``mr_debug_force_full``: every later frame of the scene takes the general kernels (k_setup_full, k_tile_full);
+        ``False`` returns to the rule (frame-only kernels unless the frame is counted, asks for the per-face status or
+        the scene has a ``depth_test=False`` model)."""
+        _check(self.lib.mr_debug_force_full(self.handle, 1 if on else 0), "mr_debug_force_full")
+
+    def frame_path(self):
+        """``mr_debug_frame_path`` of the last frame: dict of bools ``full`` (general kernels, else frame-only), ``split``,
+        ``ss``, ``ml`` (the tile kernel's instantiation) and ``ordered`` (heaviest-first order)."""
+        out = (C.c_int32 * 5)()
+        _check(self.lib.mr_debug_frame_path(self.handle, out), "mr_debug_frame_path")
+        return dict(zip(("full", "split", "ss", "ml", "ordered"), (bool(x) for x in out)))
 
     def pose_counters(self):
         """``mr_debug_pose``: (full commits of the scene so far, pose passes so far, posed models, vertices the last

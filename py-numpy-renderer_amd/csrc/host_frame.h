@@ -35,6 +35,7 @@ struct FrameSlot {
     mr_frame_desc last_frame = {};
     int last_n_tiles = 0;
     bool last_ordered = false;               // the last frame's tile kernel followed the order buffer (else row-major)
+    bool last_full = false, last_split = false;   // the kernels the last frame launched (mr_debug_frame_path)
     bool overlay_deferred = false;           // the last enqueue_frame left the overlay to finish_overlay
     int last_ss_mode = 0;                    // FrameConst::ss_mode of the last frame (finish_overlay resolves after the overlay)
     bool have_frame = false, stats_reduced = false;
@@ -316,12 +317,13 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   timing       MR_FRAME_NO_TIMING records no marks; MR_FRAME_LIGHT_TIMING not all_marks: those around the frame and the tile kernel
 //   ml, ss       several lights / supersampled: the instantiations of k_setup and k_tile
 //   ordered      k_tile takes the heaviest tiles first;  split: it shares heavy tiles out, from split_cost / split_quads, at most split_max
+//   full         the general kernels k_setup_full / k_tile_full; else the frame-only ones k_setup / k_tile (tile_body, kernels_tile.h)
 //   serial       the scene's frame serial with this frame
 //   edge_spread  EDGE_DENSE, or lanes per edge as a shift;  face_blocks, count_blocks: workgroups of k_setup's face half, of k_bin_work's counting
 //   order_bytes  d_hist: the tile order in front, the tiles' class bytes behind
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full;
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -397,6 +399,9 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     // slowest rank's rows -- profiles/quad_spans_ab.txt.)
     p.split_max = small_grid ? (unsigned)HEAVY0_MAX : p.env.tile_split > 0 ? std::min<unsigned>(SPLIT_MAX_BIG, (unsigned)HEAVY0_MAX) : 0u;
     p.split = !p.ml && (p.env.tile_split < 0 ? (small_grid || p.ordered) : p.env.tile_split != 0);
+    // The frame-only kernels count nothing and know no face that writes no z: a frame whose counters or per-face status
+    // somebody reads, and every frame of a scene with a depth_test == False model, takes the general ones.
+    p.full = sc->force_full || sc->has_no_depth || (fc.flags & (MR_FRAME_COUNTERS | MR_FRAME_FACE_STATUS)) != 0;
     // small meshes: one edge per 2 / 4 lanes, so that a wavefront rarely finds more silhouette edges than one round
     // of its quad set-up takes (kernels_geometry.h, edge_block)
     const int spread_env = p.env.edge_spread;                                                         // -1: dense
@@ -506,9 +511,11 @@ int launch_setup(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fr
                                : p.edge_spread == EDGE_DENSE ? blocks_for(fc.n_edges, 2 * SETUP_BLOCK) : blocks_for((long long)fc.n_edges << p.edge_spread, SETUP_BLOCK);
     ska.edge_spread = ska.sil.mode == SIL_CACHED ? EDGE_CACHED : p.edge_spread;
     if (p.ml) ska.lights = lights; else ska.lights.n = 1;      // (only the ML instantiations read them)
-    // k_setup<PRE_XFORM, ML>, by [!ML][!PRE_XFORM] (the order the instantiations have always been emitted in)
-    static void (*const kernel[2][2])(const SetupKernArgs) = { { k_setup<true, true>, k_setup<false, true> }, { k_setup<true, false>, k_setup<false, false> } };
-    hipLaunchKernelGGL(kernel[!p.ml][!p.env.vertex_mfma], dim3(1 + p.face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
+    // k_setup<PRE_XFORM, ML> / k_setup_full<PRE_XFORM, ML>, by [full][!ML][!PRE_XFORM]
+    static void (*const kernel[2][2][2])(const SetupKernArgs) = {
+        { { k_setup<true, true>, k_setup<false, true> }, { k_setup<true, false>, k_setup<false, false> } },
+        { { k_setup_full<true, true>, k_setup_full<false, true> }, { k_setup_full<true, false>, k_setup_full<false, false> } } };
+    hipLaunchKernelGGL(kernel[p.full][!p.ml][!p.env.vertex_mfma], dim3(1 + p.face_blocks + edge_blocks), dim3(SETUP_BLOCK), 0, stream, ska);
     return ska.sil.mode == SIL_CAPTURE ? sc->sil.capture_launched(&sa.ctr->n_quads, stream) : MR_OK;
 }
 
@@ -556,13 +563,16 @@ int launch_tile(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fra
         HIP_TRY(hipMemsetAsync(ta.next_ctr, 0, sizeof(Counters), fs->stream));
         return MR_OK;
     }
-    // k_tile<SPLIT, SS, ML> and the workgroups it takes beyond one per tile, by (ML ? 0 : SPLIT ? 2 : 4) + !SS (the order
-    // the instantiations have always been emitted in); a frame with several lights never splits
-    static const struct { void (*kernel)(const TileKernArgs); int front; } choice[6] = {
-        { k_tile<false, true, true>, 0 },            { k_tile<false, false, true>, 0 },
-        { k_tile<true, true, false>, SPLIT_FRONT },  { k_tile<true, false, false>, SPLIT_FRONT },
-        { k_tile<false, true, false>, 0 },           { k_tile<false, false, false>, 0 } };
-    const auto &c = choice[(p.ml ? 0 : p.split ? 2 : 4) + !p.ss];
+    // k_tile<SPLIT, SS, ML> / k_tile_full<SPLIT, SS, ML> and the workgroups it takes beyond one per tile, by [full] and
+    // (ML ? 0 : SPLIT ? 2 : 4) + !SS; a frame with several lights never splits
+    static const struct { void (*kernel)(const TileKernArgs); int front; } choice[2][6] = {
+        { { k_tile<false, true, true>, 0 },            { k_tile<false, false, true>, 0 },
+          { k_tile<true, true, false>, SPLIT_FRONT },  { k_tile<true, false, false>, SPLIT_FRONT },
+          { k_tile<false, true, false>, 0 },           { k_tile<false, false, false>, 0 } },
+        { { k_tile_full<false, true, true>, 0 },           { k_tile_full<false, false, true>, 0 },
+          { k_tile_full<true, true, false>, SPLIT_FRONT }, { k_tile_full<true, false, false>, SPLIT_FRONT },
+          { k_tile_full<false, true, false>, 0 },          { k_tile_full<false, false, false>, 0 } } };
+    const auto &c = choice[p.full][(p.ml ? 0 : p.split ? 2 : 4) + !p.ss];
     hipLaunchKernelGGL(c.kernel, dim3((unsigned)(p.n_tiles + c.front)), dim3(TILE_PX), 0, fs->stream, tka);
     return MR_OK;
 }
@@ -594,6 +604,7 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
 {
     sc->frame_serial = fs->last_serial = p.serial;
     fs->last_ordered = p.ordered;
+    fs->last_full = p.full; fs->last_split = p.split;
     fs->overlay_deferred = p.deferred;
     fs->last_ss_mode = fc.ss_mode;
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
@@ -667,7 +678,7 @@ int fetch_counters(FrameSlot *fs, bool reduce)
     // mr_render without a stats pointer only needs the overflow flags: no reduction launch
     if (reduce && !fs->stats_reduced && fs->last_n_tiles > 0) {
         hipLaunchKernelGGL(k_reduce_tile_stats, dim3(256), dim3(256), 0, fs->stream, fs->d_tile_stats.as<uint32_t>(),
-                           fs->last_n_tiles, ctr);
+                           fs->last_n_tiles, ctr, fs->last_full ? 1 : 0);
         fs->stats_reduced = true;
     }
     HIP_TRY(hipMemcpyAsync(fs->h_counters, ctr, sizeof(Counters), hipMemcpyDeviceToHost, fs->stream));

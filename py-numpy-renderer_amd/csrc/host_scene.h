@@ -128,6 +128,7 @@ struct mr_scene {
     bool auto_ran = false, auto_marks = false;
     bool pos32 = false;                     // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
+    bool force_full = false;                 // mr_debug_force_full: every frame takes the general kernels (FramePlan::full)
     DevBuf d_sky;                            // cubemap texels, uint8 (6, S, S, 3)
     DevBuf d_gamma;                          // GAMMA_LUT_SIZE float32 thresholds of the finalise step function
     int32_t sky_size = 0;

@@ -326,14 +326,14 @@ struct SetupKernArgs { FrameConst fc; SetupArgs sa; BinArgs bins; uint32_t face_
 template <bool ML>
 __device__ __forceinline__ const LightRec &setup_light(const SetupKernArgs &ka, int k) { return ML ? ka.lights.l[k] : ka.fc.light; }
 
-template <bool PRE_XFORM>
+template <bool PRE_XFORM, bool FULL>
 __device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t ff, const CornerOut &A, const CornerOut &B,
                                                 const CornerOut &C, unsigned int &covered, PrimBox &pb, bool &clip);
 
 // One face: status, TriRec / TriAttr / TriClip.  Returns bit 0 = the face goes on to the tile
 // kernel, bit 1 = its survivor count is left to k_bin_work; `covered` receives the fragments of a
-// face settled as CLIPPED right here.
-template <bool PRE_XFORM>
+// face settled as CLIPPED right here (FULL only: the frame-only kernel counts no fragments, see k_setup).
+template <bool PRE_XFORM, bool FULL>
 __device__ __forceinline__ int tri_setup_one(int f, unsigned int &covered, PrimBox &pb, bool &clip)
 {
     SETUP_ARGS();                                                // phase 1: the face's static record, transform, cull
@@ -375,11 +375,11 @@ __device__ __forceinline__ int tri_setup_one(int f, unsigned int &covered, PrimB
         if (cull) { status[f] = FACE_BACK_FACE_CULLING; return 0; }
     }
 
-    return tri_setup_record<PRE_XFORM>(f, material, ff, A, B, C, covered, pb, clip);
+    return tri_setup_record<PRE_XFORM, FULL>(f, material, ff, A, B, C, covered, pb, clip);
 }
 
 // second half of tri_setup_one: the faces that survive the cull (its own view of the arguments: phase 2)
-template <bool PRE_XFORM>
+template <bool PRE_XFORM, bool FULL>
 __device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t ff, const CornerOut &A, const CornerOut &B,
                                                 const CornerOut &C, unsigned int &covered, PrimBox &pb, bool &clip)
 {
@@ -434,7 +434,7 @@ __device__ __forceinline__ int tri_setup_record(int f, int32_t material, uint8_t
         for (int idx = 0; idx < (int)box && found < 2; ++idx) {
             bool cov;
             found += sample_survives(sc, t, dp, nullptr, bx0 + idx % bw, by0 + idx / bw, cov) ? 1 : 0;
-            covered += cov ? 1u : 0u;
+            if (FULL) covered += cov ? 1u : 0u;
         }
         if (found == 0) {
             status[f] = FACE_CLIPPED;              // never reaches the tile kernel: its fragments are counted here
@@ -539,13 +539,15 @@ constexpr int SETUP_BLOCK = 256;
 
 // Face workgroup: one face per lane.  The list of faces whose survivor count needs a wavefront and
 // the frame's count of set-up faces are appended to with ONE atomic per workgroup.
-template <bool PRE_XFORM>
+template <bool PRE_XFORM, bool FULL>
 __device__ __forceinline__ void tri_setup_block(uint32_t block)
 {
     constexpr int NW = SETUP_BLOCK / WAVE;
     __shared__ uint32_t s_valid[NW], s_count[NW], s_covered;
     const int f = block * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    // (zeroed in the frame-only kernel too, which never reads it: without this one LDS store this compiler's register
+    // allocation of k_setup<false, false> spills 24 bytes -- tests/test_kernel_budget.py)
     if (threadIdx.x == 0) s_covered = 0;
     unsigned int covered = 0;
     PrimBox pb = { 0, 0, 0, 0 };
@@ -561,14 +563,14 @@ __device__ __forceinline__ void tri_setup_block(uint32_t block)
             if (lane == 0 && (fc0.cluster_cull & CC_COUNT)) atomicAdd(&kernargs<SetupKernArgs>().sa.ctr->pad0[0], 1u);   // (MR_CLUSTER_CULL=count: mr_debug_clusters_culled)
         }
     }
-    const int r = go ? tri_setup_one<PRE_XFORM>(f, covered, pb, clip) : 0;
+    const int r = go ? tri_setup_one<PRE_XFORM, FULL>(f, covered, pb, clip) : 0;
     SETUP_ARGS();                                                // phase 3: the tile lists, the workgroup's epilogue
     // the face's own tile lists (kernels_bin.h)
     bin_triangles(fc, bins, (r & 1) != 0, (uint32_t)f, pb, clip);
     const unsigned long long bv = __ballot(r & 1), bc = __ballot(r & 2);
     if (lane == 0) { s_valid[wv] = (uint32_t)__popcll(bv); s_count[wv] = (uint32_t)__popcll(bc); }
     __syncthreads();
-    if (covered) atomicAdd(&s_covered, covered);
+    if (FULL && covered) atomicAdd(&s_covered, covered);
     if (threadIdx.x == 0) {
         uint32_t nv = 0, nc = 0;
         for (int w = 0; w < NW; ++w) { nv += s_valid[w]; nc += s_count[w]; }
@@ -583,7 +585,7 @@ __device__ __forceinline__ void tri_setup_block(uint32_t block)
     __syncthreads();
     const unsigned long long below = (1ull << lane) - 1ull;
     if (r & 2) sa.count_list[s_count[wv] + (uint32_t)__popcll(bc & below)] = (uint32_t)f;
-    if (threadIdx.x == 0 && s_covered) atomicAdd(&sa.ctr->frag_tri, (unsigned long long)s_covered);
+    if (FULL && threadIdx.x == 0 && s_covered) atomicAdd(&sa.ctr->frag_tri, (unsigned long long)s_covered);
 }
 
 // Counts, per listed face, the fragments that survive coverage + clip over the WHOLE frame
@@ -1085,9 +1087,12 @@ __device__ __forceinline__ void edge_block(uint32_t block)
 // First launch of the frame: workgroup 0 puts the frame's tiles in order (a serial walk of some microseconds, hidden
 // behind the others), workgroups [1, 1 + face_blocks) set faces up, the rest look at edges.  ML: a frame with several
 // lights -- an instantiation of its own so that the plain frame's kernel is the code it was.
-template <bool PRE_XFORM, bool ML>
-__global__ void __launch_bounds__(SETUP_BLOCK, MR_SETUP_WAVES)
-k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(), phase by phase
+// FULL == false: the frame-only kernel (k_setup; the plan's choice like the tile kernel's, see tile_body in
+// kernels_tile.h): the fragments of the faces settled here are not counted.  The per-face status bytes, n_valid_tris
+// and the MR_CLUSTER_CULL=count tally stay in both: k_bin_work reads the first in every frame, and mr_stats /
+// mr_debug_clusters_culled report the others for frames that were not counted.
+template <bool PRE_XFORM, bool ML, bool FULL>
+__device__ __forceinline__ void setup_body()
 {
     uint32_t face_blocks;
     {
@@ -1096,8 +1101,20 @@ k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(
         face_blocks = ka.face_blocks;
     }
     const uint32_t b = blockIdx.x - 1;
-    if (b < face_blocks) tri_setup_block<PRE_XFORM>(b);
+    if (b < face_blocks) tri_setup_block<PRE_XFORM, FULL>(b);
     else edge_block<ML>(b - face_blocks);
+}
+template <bool PRE_XFORM, bool ML>
+__global__ void __launch_bounds__(SETUP_BLOCK, MR_SETUP_WAVES)
+k_setup(const SetupKernArgs)            // read through kernargs<SetupKernArgs>(), phase by phase
+{
+    setup_body<PRE_XFORM, ML, false>();
+}
+template <bool PRE_XFORM, bool ML>
+__global__ void __launch_bounds__(SETUP_BLOCK, MR_SETUP_WAVES)
+k_setup_full(const SetupKernArgs)
+{
+    setup_body<PRE_XFORM, ML, true>();
 }
 
 // Second launch: the leftover survivor counts (a few workgroups, first so that their

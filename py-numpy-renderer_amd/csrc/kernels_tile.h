@@ -125,7 +125,8 @@ struct TileBounds { int width, band_y0, band_y1; };
 
 // SWEEP 0 with `cache`: fills it.  SWEEP 1 with `first` > 0: skips the lane's first `first` samples (the cache
 // answered for them).
-template <int SWEEP>
+// FULL == false (a frame-only kernel, see tile_body): no fragment count, and no face of a depth_test == False model.
+template <int SWEEP, bool FULL>
 __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t, int gx, int gy, bool rh,
                                            unsigned long long *s_key, int *s_win, int sub, int lanes, unsigned int &frags,
                                            SweepCache *cache = nullptr, int first = 0)
@@ -135,7 +136,7 @@ __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t
     const PairMath<true> pm(t);
     // Model.depth_test == False (obj/triangular.py:117): the face's fragments are tested, never written to z.
     // The pixel then shows the LAST face in order among those that pass against the final z (see k_tile).
-    const bool nodepth = ((t.flags >> 8) & FF_NO_DEPTH) != 0;
+    const bool nodepth = FULL && ((t.flags >> 8) & FF_NO_DEPTH) != 0;
     const int bw = x1 - x0;
     if (cache) { cache->meta = 0; }
     if (bw <= 0) return;
@@ -147,7 +148,7 @@ __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t
             float u, v, w;
             pm.bary(px, py, u, v, w);
             bool ok = u >= 0 && v >= 0 && w >= 0;
-            if (ok && SWEEP == 0) ++frags;
+            if (FULL && ok && SWEEP == 0) ++frags;
             if (ok && (SWEEP == 1 || !nodepth)) {
                 const double z = pm.depth(u, v, w);
                 if (z == z) {                            // a NaN depth never passes the reference's test
@@ -387,14 +388,21 @@ struct TileKernArgs { FrameConst fc; TileArgs ta; ShadeArgs sh; TileLights ml; }
 // quad is walked); phase 4 works out what of a pixel does not depend on the light once and adds the lights'
 // contributions F_k in float32, in the order of the lights: F = min(F_0 + F_1 + ..., 1), every F_k clipped to
 // [0.05, 1] like the reference's one.  Such frames never split tiles.
-template <bool SPLIT, bool SS, bool ML>
-__global__ void __launch_bounds__(TILE_PX, ML ? K_TILE_WAVES : K_TILE_WAVES_1L)
-k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), phase by phase
+// FULL: the one body of the two kernels below.  FULL == true is the general kernel (k_tile_full).  FULL == false is what
+// a frame rendered for the frame's sake needs (k_tile; the plan's choice, FramePlan::full): no MR_FRAME_COUNTERS, no
+// MR_FRAME_FACE_STATUS, no depth_test == False model in the scene.  It carries no fragment accumulators, ballots or
+// per-tile counts (words 0..4 of the tile's record are not written), `counters` is a constant, and the faces that
+// write no z -- the late pass over the big pairs, the nodepth branches of small_pair -- do not exist.  The list lengths
+// (words 5..7), the overflow reports, the cursors and the class byte are the same in both; the time stamps are zero.  The
+// regime bench.py quotes follows the length of the instruction stream: this is that stream without what the
+// frame cannot use.  Same arithmetic on the same values: every byte of the frame, z, winner and stencil is the same.
+template <bool SPLIT, bool SS, bool ML, bool FULL>
+__device__ __forceinline__ void tile_body()
 {
     static_assert(!(SPLIT && ML), "frames with several lights do not split their heavy tiles");
     __shared__ unsigned long long s_key[TILE_PX];
     __shared__ int s_win[TILE_PX];
-    __shared__ unsigned int s_cnt[TILE_STATS];
+    __shared__ unsigned int s_cnt[TILE_STATS];            // (FULL only: never referenced otherwise, and not allocated)
     __shared__ uint4 s_quad[QUAD_BATCH * QUAD_STAGE_U4];
     __shared__ uint32_t s_id[QUAD_BATCH];
     __shared__ float s_gamma[GAMMA_LUT_SIZE];
@@ -402,6 +410,9 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int lp = tid;                                   // pixel of this thread inside the tile
+    // the four time stamps of the tile's record (mr_debug_read_tile_records): the general kernel's only -- in the regime
+    // bench.py quotes they cost the c4 frame 0.8 % (profiles/frame_only_path_ab.txt); the frame-only kernel leaves zeros
+    auto stamp = []() -> unsigned long long { return FULL ? __builtin_amdgcn_s_memrealtime() : 0ull; };
 
     // ---- 0. which tile, and what it lists
     int tile = 0, part = 0, n_parts = 1, entry = 0, n_tiles, ltr, gx, gy;
@@ -415,7 +426,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         const ShadeArgs &sh = ka.sh;
         n_tiles = fc.tiles_x * fc.tiles_y;
         rh = fc.system == 1;
-        counters = (fc.flags & MR_FRAME_COUNTERS) != 0;
+        counters = FULL && (fc.flags & MR_FRAME_COUNTERS) != 0;
 
         if (blockIdx.x == 0) {
             // The next frame's counter block is the previous frame's (double-buffered by parity; that frame is
@@ -464,7 +475,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         gx = (tile % fc.tiles_x) * TILE_W; gy = tile_row_frame(fc, ltr) * TILE_H;
         const int px = gx + (lp & (TILE_W - 1)), py = gy + lp / TILE_W;
         live = px < fc.width && py >= fc.band_y0 && py < fc.band_y1;
-        t_start = __builtin_amdgcn_s_memrealtime();
+        t_start = stamp();
 
         // list lengths (a list that ran over its capacity is truncated; the host grows it and re-renders)
         n_small_raw = ta.bin_count[tile]; n_big_raw = ta.bin_count[n_tiles + tile]; n_quad_raw = ta.bin_count[2 * n_tiles + tile];
@@ -517,13 +528,13 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 for (int k = 0; k < TILE_REC; ++k) rec[k] = 0;
                 rec[7] = n_quad_raw;
                 rec[8] = rec[10] = rec[11] = (uint32_t)t_start;
-                rec[9] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+                rec[9] = (uint32_t)stamp();
                 ta.bin_count[2 * n_tiles + tile] = 0;
                 ta.tile_class[tile] = (uint8_t)ORDER_CLASSES;
             }
             return;
         }
-        if (tid < TILE_STATS) s_cnt[tid] = 0;
+        if (FULL && tid < TILE_STATS) s_cnt[tid] = 0;
         s_gamma[tid] = sh.gamma_lut[tid];
         if (tid == 0) s_gamma[GAMMA_LUT_SIZE - 1] = sh.gamma_lut[GAMMA_LUT_SIZE - 1];
         mat_lds = fc.n_materials <= MAT_LDS;
@@ -554,7 +565,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         const TriClip *__restrict__ clips = ta.clips;
         const uint32_t *__restrict__ small_items = ta.items[0] + (size_t)tile * ta.cap[0];
         const uint32_t *__restrict__ big_items = ta.items[1] + (size_t)tile * ta.cap[1];
-        const bool same_clip = fc.same_clip != 0, has_no_depth = fc.has_no_depth != 0;
+        const bool same_clip = fc.same_clip != 0, has_no_depth = FULL && fc.has_no_depth != 0;
         const TileBounds tb = { fc.width, fc.band_y0, fc.band_y1 };
         int px, py;
         my_pixel(px, py);
@@ -582,7 +593,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 for (int j = 0; j < n; ++j) {
                     const TriRec &t = *reinterpret_cast<const TriRec *>(s_quad + j * TRI_U4);
                     const uint32_t flags = t.flags;
-                    const bool nodepth = ((flags >> 8) & FF_NO_DEPTH) != 0;
+                    const bool nodepth = FULL && ((flags >> 8) & FF_NO_DEPTH) != 0;
                     if (late && !nodepth) continue;
                     // the pair is the same for every lane, so are its flags: the usual face (neither of the two
                     // summation-order flags) takes a copy of the arithmetic without their selects (see PairMath)
@@ -595,7 +606,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                         in = in && u >= 0 && v >= 0 && w >= 0;
                         const unsigned long long m = __ballot(in);
                         if (!m) return;
-                        if (!late) frags += (unsigned int)__popcll(m);
+                        if (FULL && !late) frags += (unsigned int)__popcll(m);
                         if (nodepth && !late) return;
                         if (flags & TF_CLIP) {
                             if (in) {
@@ -622,7 +633,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         big_pairs(false);
         if (n_small) { s_key[lp] = z_key(zbest); s_win[lp] = -1; }     // the small pairs' LDS z-buffer starts from the big pairs' z
         __syncthreads();                                  // s_cnt is zeroed, the LDS tables are loaded
-        if (lane == 0 && frags) atomicAdd(&s_cnt[0], frags);
+        if (FULL && lane == 0 && frags) atomicAdd(&s_cnt[0], frags);
         if (n_small) {
             // ---- 2. small pairs, SMALL_LANES lanes per triangle, z into the LDS z-buffer
             // The second sweep (who owns the final z?) needs every sample's z key again.  For the first
@@ -649,17 +660,17 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 const TriRec t = tris[small_items[i]];
                 if (round < SWEEP_CACHE_ROUNDS) {
                     SweepCache sc;
-                    small_pair<0>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, &sc);
-                    const bool nodepth = ((t.flags >> 8) & FF_NO_DEPTH) != 0;
+                    small_pair<0, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, &sc);
+                    const bool nodepth = FULL && ((t.flags >> 8) & FF_NO_DEPTH) != 0;
 #pragma unroll
                     for (int c = 0; c < SWEEP_CACHE_K; ++c) c_key[round][c][tid] = sc.key[c];
                     c_meta[round][tid] = nodepth ? (sc.meta & 0xfff00000u) : sc.meta;      // nothing cached for a face that writes no z
                     c_face[round][tid] = (uint32_t)t.face | (nodepth ? 0x80000000u : 0u);
                 } else {
-                    small_pair<0>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags);
+                    small_pair<0, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags);
                 }
             }
-            if (sfrags) atomicAdd(&s_cnt[0], sfrags);
+            if (FULL && sfrags) atomicAdd(&s_cnt[0], sfrags);
             __syncthreads();
 
             // winners: a big pair keeps its face where its z survived (an atomic like the small pairs' sweep: the
@@ -672,7 +683,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 if (round < SWEEP_CACHE_ROUNDS) {
                     const uint32_t meta = c_meta[round][tid], cf = c_face[round][tid];
                     const int walked = (int)(meta >> 20);
-                    const bool nodepth = (cf >> 31) != 0;
+                    const bool nodepth = FULL && (cf >> 31) != 0;
 #pragma unroll
                     for (int c = 0; c < SWEEP_CACHE_K; ++c)
                         if ((meta >> (16 + c)) & 1u) {
@@ -683,7 +694,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                     first = nodepth ? 0 : SWEEP_CACHE_K;
                 }
                 const TriRec t = tris[small_items[i]];
-                small_pair<1>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, nullptr, first);
+                small_pair<1, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, nullptr, first);
             }
             __syncthreads();
             best = s_win[lp];
@@ -692,7 +703,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         if (has_no_depth) big_pairs(true);
     }
     const bool covered = live && best >= 0;
-    const unsigned long long t_raster = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long t_raster = stamp();
 
     // ---- 3. shadow quads against the final z: stencil +-1 (obj/triangular.py:335-368).  The
     // batch's records (header and first four edges: 192 bytes each) are copied to LDS once, 16 bytes
@@ -719,6 +730,13 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             const double o = __shfl_xor(zlim, off), h = __shfl_xor(zhard, off);
             zlim = rh ? fmax(zlim, o) : fmin(zlim, o);
             zhard = rh ? fmin(zhard, h) : fmax(zhard, h);
+        }
+        // (frame-only: both are the same in every lane now, and go to scalar registers -- without the counted frame's
+        // code the compiler hoists the batch loop's invariants out of it, and four vector registers fewer keep it from
+        // spilling them; the general kernel is the code it was)
+        if (!FULL) {
+            zlim = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(zlim)), __builtin_amdgcn_readfirstlane(__double2loint(zlim)));
+            zhard = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(zhard)), __builtin_amdgcn_readfirstlane(__double2loint(zhard)));
         }
         // The span walk (single light): the final z in LDS (the keys are there already wherever the tile had small
         // pairs), and the stencil words it adds to in s_win, dead since `best` was read.  Each thread writes its own
@@ -851,7 +869,9 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                     // others fill the rest (a permutation), with the strip verdicts beside the lane
                     const int cnt = __popcll(smask);
                     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(smask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)smask, 0u));
-                    const int dest = ((smask >> lane) & 1) ? rank : cnt + (lane - rank);
+                    int ln = lane;                          // (frame-only: a copy the compiler cannot trace, or 1 << lane is held from outside the batch loop)
+                    if (!FULL) asm volatile("" : "+v"(ln));
+                    const int dest = ((smask >> ln) & 1) ? rank : cnt + (lane - rank);
                     const int list = __builtin_amdgcn_ds_permute(dest << 2, lane | (emask << 8) | ((q_allpass ? 1 : 0) << 16));
                     const int ly = (tid / WAVE) * (WAVE / TILE_W) + (lane & 3);       // the item's row of the tile
                     const int y = gy + ly;
@@ -965,7 +985,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                 }
                 const unsigned long long m = __ballot(in);
                 if (!m) continue;
-                qfrags += (unsigned int)__popcll(m);
+                if (FULL) qfrags += (unsigned int)__popcll(m);
                 bool pass = true;
                 if (!((allpass >> j) & 1)) {
                 const double q_nx = __hiloint2double((int)p0.y, (int)p0.x), q_ny = __hiloint2double((int)p0.w, (int)p0.z);
@@ -974,7 +994,7 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
                                        f_plus_n, f_minus_n, two_nf);
                 }
                 pass = pass && in;
-                qupd += (unsigned int)__popcll(__ballot(pass));
+                if (FULL) qupd += (unsigned int)__popcll(__ballot(pass));
                 if (ML) {
                     const int lt = __builtin_amdgcn_readfirstlane((int)(hb.w >> 1)), d = pass ? (front ? 1 : -1) : 0;
                     if (lt == 0) sten += d;
@@ -1001,7 +1021,9 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         __shared__ uint32_t s_ticket;
         const TileArgs &ta = kernargs<TileKernArgs>().ta;
         int32_t *mine = ta.split_sten + ((size_t)entry * HEAVY_SPLIT + part) * TILE_PX;
-        mine[lp] = sten;
+        int l = lp;                                       // (frame-only: an untraceable copy like my_pixel's, or 4 * lp is held -- and spilled -- from phase 2 to here)
+        if (!FULL) asm volatile("" : "+v"(l));
+        mine[l] = sten;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) {
@@ -1018,9 +1040,9 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
         }
         __syncthreads();
         for (int k = 0; k < n_parts; ++k)
-            if (k != part) sten += ta.split_sten[((size_t)entry * HEAVY_SPLIT + k) * TILE_PX + lp];
+            if (k != part) sten += ta.split_sten[((size_t)entry * HEAVY_SPLIT + k) * TILE_PX + l];
     }
-    const unsigned long long t_quads = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long t_quads = stamp();
 
     // ---- 4. deferred shading + finalise (kernels_shade.h; obj/core.py:640)
     const bool lit = (int16_t)sten == 0;                  // the reference's buffer is int16
@@ -1142,16 +1164,16 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
             if (qupd) atomicAdd(&s_cnt[2], qupd);
         }
     }
-    __syncthreads();
+    if (FULL) __syncthreads();
     // per-tile partial counts, summed by k_reduce_tile_stats (thousands of workgroups adding to
     // one cache line of counters would serialise at the memory side)
     const TileArgs &ta = kernargs<TileKernArgs>().ta;
     uint32_t *rec = ta.tile_stats + (size_t)tile * TILE_REC;
-    if (tid < TILE_STATS) rec[tid] = s_cnt[tid];
+    if (FULL && tid < TILE_STATS) rec[tid] = s_cnt[tid];
     if (tid == 0) {                                       // list lengths; timing for mr_debug_read_tile_records
         rec[5] = n_small_raw; rec[6] = n_big_raw; rec[7] = n_quad_raw;
         rec[8] = (uint32_t)t_start;
-        rec[9] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+        rec[9] = (uint32_t)stamp();
         rec[10] = (uint32_t)t_raster; rec[11] = (uint32_t)t_quads;
         if (n_small_raw > ta.cap[0]) { atomicOr(&ta.ctr->overflow, 1u); atomicMax(&ta.ctr->max_list[0], n_small_raw); }
         if (n_big_raw > ta.cap[1]) { atomicOr(&ta.ctr->overflow, 2u); atomicMax(&ta.ctr->max_list[1], n_big_raw); }
@@ -1166,10 +1188,26 @@ k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), 
     }
 }
 
+// The frame-only kernel (FULL == false, see tile_body) ...
+template <bool SPLIT, bool SS, bool ML>
+__global__ void __launch_bounds__(TILE_PX, ML ? K_TILE_WAVES : K_TILE_WAVES_1L)
+k_tile(const TileKernArgs)            // read through kernargs<TileKernArgs>(), phase by phase
+{
+    tile_body<SPLIT, SS, ML, false>();
+}
+// ... and the general one: counted frames, per-face status, scenes with a depth_test == False model, mr_debug_force_full.
+template <bool SPLIT, bool SS, bool ML>
+__global__ void __launch_bounds__(TILE_PX, ML ? K_TILE_WAVES : K_TILE_WAVES_1L)
+k_tile_full(const TileKernArgs)
+{
+    tile_body<SPLIT, SS, ML, true>();
+}
+
 // Sums the per-tile partial counts and list lengths into the frame counters; grid-stride over
-// tiles, one atomic per workgroup and counter; run only when the statistics are asked for.
+// tiles, one atomic per workgroup and counter; run only when the statistics are asked for.  `counted` == 0: the frame's
+// tile kernel was the frame-only one, which leaves words 0..4 of the records alone: only the list lengths are summed.
 __global__ void __launch_bounds__(256)
-k_reduce_tile_stats(const uint32_t *__restrict__ tile_stats, int n_tiles, Counters *__restrict__ ctr)
+k_reduce_tile_stats(const uint32_t *__restrict__ tile_stats, int n_tiles, Counters *__restrict__ ctr, int counted)
 {
     constexpr int NS = TILE_STATS + 2;                    // + triangle pairs, all pairs
     __shared__ unsigned long long part[NS][256 / WAVE];
@@ -1179,7 +1217,7 @@ k_reduce_tile_stats(const uint32_t *__restrict__ tile_stats, int n_tiles, Counte
     for (size_t t = gid; t < (size_t)n_tiles; t += gsz) {
         const uint32_t *rec = tile_stats + t * TILE_REC;
 #pragma unroll
-        for (int k = 0; k < TILE_STATS; ++k) acc[k] += rec[k];
+        for (int k = 0; k < TILE_STATS; ++k) acc[k] += counted ? rec[k] : 0u;
         acc[TILE_STATS] += (unsigned long long)rec[5] + rec[6];
         acc[TILE_STATS + 1] += (unsigned long long)rec[5] + rec[6] + rec[7];
     }

@@ -846,6 +846,9 @@ int mr_debug_read_tile_records(mr_scene *sc, uint32_t *out, int32_t cap_tiles)
     HIP_TRY(hipDeviceSynchronize());
     static_assert(mr::TILE_REC == MR_TILE_RECORD_WORDS, "tile record size is part of the ABI");
     if (n > 0) HIP_TRY(hipMemcpy(out, fs->d_tile_stats.p, (size_t)n * mr::TILE_REC * 4, hipMemcpyDeviceToHost));
+    if (!fs->last_full)                              // the frame-only tile kernel does not write the counts: they read 0
+        for (int t = 0; t < n; ++t)
+            for (int k = 0; k < mr::TILE_STATS; ++k) out[(size_t)t * mr::TILE_REC + k] = 0u;
     return fs->last_n_tiles;
 }
 
@@ -868,6 +871,23 @@ int mr_debug_quad_walks(mr_scene *sc, uint32_t *out)
     if (int rc = fetch_counters(fs, false)) return rc;
     HIP_TRY(hipStreamSynchronize(fs->stream));
     for (int k = 0; k < 4; ++k) out[k] = fs->h_counters->pad0[1 + k];
+    return MR_OK;
+}
+
+int mr_debug_force_full(mr_scene *sc, int32_t on)
+{
+    if (!sc) return fail(MR_E_INVALID, "NULL argument");
+    sc->force_full = on != 0;
+    return MR_OK;
+}
+
+int mr_debug_frame_path(mr_scene *sc, int32_t *out)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (!out) return fail(MR_E_INVALID, "NULL argument");
+    out[0] = fs->last_full ? 1 : 0; out[1] = fs->last_split ? 1 : 0; out[2] = fs->last_ss_mode ? 1 : 0;
+    out[3] = fs->last_n_lights > 1 ? 1 : 0; out[4] = fs->last_ordered ? 1 : 0;
     return MR_OK;
 }
 

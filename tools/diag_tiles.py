@@ -9,7 +9,8 @@ name = sys.argv[1] if len(sys.argv) > 1 else "c4_torus200k_1080p"
 shadows = (sys.argv[2] != "0") if len(sys.argv) > 2 else True
 sc = scenes.build(api, name)
 be = sc._backend()
-for _ in range(5):
+for i in range(5):
+    be.force_full(i == 4)             # the tile records' time stamps are the general kernel's: the last frame takes it
     be.render(sc, shadows=shadows, counters=False)
 r = be.read_tile_records().astype(np.int64)
 start, end = r[:, 8], r[:, 9]
