@@ -383,6 +383,14 @@ int mr_debug_clusters_culled(mr_scene *scene);
  * it. */
 int mr_debug_quad_walks(mr_scene *scene, uint32_t *out);
 
+/* Diagnostic: where the winners' sweep over the last frame's small (triangle, tile) pairs got its z keys (frames with
+ * MR_FRAME_COUNTERS; 0 otherwise): out[0] = covered samples answered from the lanes' logs, out[1] = samples walked again
+ * by lanes whose log had run over (or that met a face of a depth_test == 0 model).  The general kernel of a frame with
+ * several lights keeps no log: out[0] = 0 there.
+ * MR_PAIR_LOG=0 .. 4 in the environment (read once per process) sets the entries a lane's log may hold, 0 for none: every
+ * sample is then walked again; the frames do not depend on it. */
+int mr_debug_pair_log(mr_scene *scene, uint32_t *out);
+
 /* The set-up and tile kernels exist in two variants of one source: the frame-only ones, which count nothing, and the
  * general ones.  A frame takes the general kernels when it carries MR_FRAME_COUNTERS or MR_FRAME_FACE_STATUS or the
  * scene has a model with depth_test == 0; every other frame the frame-only ones.  The frame, z, winner and stencil do

@@ -137,6 +137,7 @@ _PROTOTYPES = {
     "mr_debug_read_tile_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_clusters_culled": (C.c_int, [C.c_void_p]),
     "mr_debug_quad_walks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_pair_log": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_host_camera_constants": (None, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3),
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -780,6 +781,13 @@ class DeviceRenderer:
         walks, those of the strip walks with a polygon of more than four vertices, those with a non-finite edge value)."""
         out = (C.c_uint32 * 4)()
         _check(self.lib.mr_debug_quad_walks(self.handle, out), "mr_debug_quad_walks")
+        return tuple(int(x) for x in out)
+
+    def pair_log(self):
+        """``mr_debug_pair_log`` of the last (counted) frame: (covered samples of small pairs that the winners' sweep
+        answered from the lanes' logs, samples it walked again)."""
+        out = (C.c_uint32 * 2)()
+        _check(self.lib.mr_debug_pair_log(self.handle, out), "mr_debug_pair_log")
         return tuple(int(x) for x in out)
 
     def sil_cache(self):

@@ -14,6 +14,8 @@
 //   MR_QUAD_WALK      (auto)    strips | spans: how k_tile's single-light instantiations walk a tile's shadow quads -- one quad
 //                               at a time over the wavefront's strip, or sixteen (quad, row) spans to a round wherever
 //                               that walk is defined (auto: by the quad and the strip, see k_tile phase 3)
+//   MR_PAIR_LOG       4         0 .. 4 (mr::PAIR_LOG_K): the covered samples a lane of k_tile's small pairs logs for the winners'
+//                               sweep; past them the lane walks its pairs again (0: every sample is walked again; same bits)
 //   MR_CLUSTER_CULL   (auto)    0 | 1 | box | count: cluster culling off / on / boxes only / on and counted (auto: see
 //                               cluster_cull_mode)
 //   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
@@ -28,6 +30,7 @@ struct Env {
     bool vertex_mfma, resolve_separate, sil_cache;
     int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
     int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
+    int pair_log;                                 // 0 .. mr::PAIR_LOG_K
     unsigned split_cost, split_quads;
     const char *cluster_cull;                     // as set, or NULL
 };
@@ -43,6 +46,7 @@ Env read_env()
         e.edge_spread = number("MR_EDGE_SPREAD", -2);
         e.tile_order = is("MR_TILE_ORDER", "rowmajor") ? 1 : is("MR_TILE_ORDER", "heaviest") ? 2 : 0;
         e.quad_walk = is("MR_QUAD_WALK", "strips") ? 1 : is("MR_QUAD_WALK", "spans") ? 2 : 0;
+        e.pair_log = std::min(std::max(number("MR_PAIR_LOG", mr::PAIR_LOG_K), 0), (int)mr::PAIR_LOG_K);
         e.tile_split = number("MR_TILE_SPLIT", -1);
         e.split_cost = (unsigned)number("MR_SPLIT_COST", 400);
         e.split_quads = (unsigned)number("MR_SPLIT_QUADS", 48);

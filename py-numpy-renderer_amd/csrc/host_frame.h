@@ -550,6 +550,7 @@ int launch_tile(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fra
     ta.split_arrive = fs->d_split.as<uint32_t>(); ta.split_sten = fs->d_split.as<int32_t>() + HEAVY0_MAX;
     ta.split_cost = p.split_cost; ta.split_quads = p.split_quads; ta.split_max = p.split_max;
     ta.quad_walk = (uint32_t)p.env.quad_walk;
+    ta.pair_log = (uint32_t)fc.n_faces <= PAIR_LOG_MAX_FACE ? (uint32_t)p.env.pair_log : 0u;   // (a log entry holds 24 bits of the face)
     ShadeArgs &sh = tka.sh;
     sh.tris = fs->d_tris.as<TriRec>(); sh.face_pos = sc->d_face_pos.p; sh.face_attr = sc->d_face_attr.as<FaceAttr>();
     sh.materials = sc->d_materials.as<Material>();

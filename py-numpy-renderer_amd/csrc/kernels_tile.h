@@ -12,11 +12,14 @@
 //   1. big (triangle, tile) pairs -- a floor triangle -- one PIXEL per thread, the records staged
 //      64 at a time in LDS and read as broadcasts (obj/triangular.py:72-118);
 //   2. small pairs -- a dense mesh's triangles cover a handful of samples -- four lanes per
-//      TRIANGLE (two where the tile lists more than a round of those): they share out the few samples of
-//      the pixel box and do an LDS atomicMin on the order-preserving key of z, then (second sweep, from
-//      the keys the first left in LDS) an LDS atomicMax of the face index where its z is the tile's final z.  The reference's sequential rule (a fragment writes when
-//      zbuf >= z, so the last face in order wins ties) is reproduced order-free: smallest z, and
-//      among equal z the largest face index;
+//      TRIANGLE (two where the tile lists more than a round of those, eight where at most half a round): they share out
+//      the few samples of the pixel box and do an LDS atomicMin on the order-preserving key of z, appending key, pixel
+//      and face of every covered sample to the lane's log in LDS (PairLog); then (second sweep, behind a barrier) an LDS
+//      atomicMax of the face index for the logged keys that equal the tile's final z -- no record, no barycentrics, no
+//      depth; only a lane whose log ran over walks its pairs again, from the sample that did not fit
+//      (MR_PAIR_LOG=0 .. 4 sets the log's capacity, 0 for none; mr_debug_pair_log counts both).  The reference's
+//      sequential rule (a fragment writes when zbuf >= z, so the last face in order wins ties) is reproduced
+//      order-free: smallest z, and among equal z the largest face index;
 //   3. the tile's shadow quads against the final z, QUAD_BATCH records staged in LDS per round; lane j of every
 //      wavefront classifies quad j against the wavefront's 16x4 strip.  A survivor is then walked in one of two ways
 //      (obj/triangular.py:335-368): the STRIP walk, one quad at a time, every lane its own pixel, stencil +-1 in the
@@ -112,24 +115,38 @@ private:
 // index.  Pairs that need the per-fragment clip test never come here (pair_class).
 constexpr int SMALL_LANES = 4;
 
-// What a lane's first sweep leaves for its second (see the winners' sweep in k_tile): the z keys and pixels
-// of its first SWEEP_CACHE_K samples that had a depth, and how many samples it walked in all.
-constexpr int SWEEP_CACHE_K = 2, SWEEP_CACHE_ROUNDS = 2;
-struct SweepCache {
-    unsigned long long key[SWEEP_CACHE_K];
-    uint32_t meta;                    // pixel of sample s in bits 8s..8s+7, "sample s is cached" in bit 16+s, samples walked from bit 20
+// What a lane's first sweep leaves for its second (see the winners' sweep in k_tile): a log of the samples it covered
+// -- z key, pixel and face of every sample that had a depth, in the order it met them, through all its rounds.  A lane
+// covers little more than one sample per pair whatever it walks, so PAIR_LOG_K entries answer for nearly all of them
+// (the bench torus, tools/sim_pair_log.py: all but 0.04 % of the samples walked; three entries would leave 0.7 %, and
+// then most wavefronts still hold a lane that walks again: measured, profiles/pair_log_ab.txt).  Pixel (bits 0..7) and
+// face (bits 8..) share a word, which is what lets four entries fit the staging area: a scene with more than
+// PAIR_LOG_MAX_FACE faces gets capacity 0 from the host.  The first sample that does not fit fixes where the lane
+// walks again from: `resume`, the lane's round in bits 8.. and the walk position inside that pair below (a pair has at
+// most TILE_PX / 2 samples per lane); nothing later of the lane is logged.  Entry e of thread t is at [e][t] of each
+// array: a wavefront's accesses fall on distinct banks whatever entry each lane is at.
+constexpr int PAIR_LOG_K = 4;
+constexpr uint32_t PAIR_LOG_NONE = 0xffffffffu, PAIR_LOG_MAX_FACE = 1u << 24;
+struct PairLog {
+    unsigned long long (*key)[TILE_PX];
+    uint32_t (*word)[TILE_PX];        // pixel | face << 8
+    uint32_t n, cap;                  // entries written; entries the lane may write (TileArgs::pair_log; 0 once it met a face that writes no z)
+    uint32_t resume;                  // PAIR_LOG_NONE: everything so far is in the log
 };
 
 // the frame's limits a tile clamps its pixel boxes to (values, not the frame constants: see kernargs())
 struct TileBounds { int width, band_y0, band_y1; };
 
-// SWEEP 0 with `cache`: fills it.  SWEEP 1 with `first` > 0: skips the lane's first `first` samples (the cache
-// answered for them).
+// SWEEP 0: every sample that has a depth goes to `log` (thread `tid`'s) where the atomic on its key is; returns the walk
+// position of the pair's first sample that did not fit (PAIR_LOG_NONE: all did).  A select, not a branch, and the resume
+// point is put together once per pair by the caller: every level of divergent control flow inside the walk holds a pair
+// of scalar registers, and the multi-light general kernel has none to spare.  SWEEP 1: skips
+// the lane's first `first` samples (the log answered for them), and counts the samples it walks in `frags` (COUNT; SWEEP 0: the fragments).
 // FULL == false (a frame-only kernel, see tile_body): no fragment count, and no face of a depth_test == False model.
-template <int SWEEP, bool FULL>
-__device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t, int gx, int gy, bool rh,
+template <int SWEEP, bool FULL, bool COUNT = FULL>
+__device__ __forceinline__ uint32_t small_pair(const TileBounds &tb, const TriRec &t, int gx, int gy, bool rh,
                                            unsigned long long *s_key, int *s_win, int sub, int lanes, unsigned int &frags,
-                                           SweepCache *cache = nullptr, int first = 0)
+                                           PairLog *log = nullptr, int tid = 0, int first = 0)
 {
     const int x0 = max((int)t.x0, gx), x1 = min((int)t.x1, min(gx + TILE_W, tb.width));
     const int y0 = max(max((int)t.y0, gy), tb.band_y0), y1 = min(min((int)t.y1, gy + TILE_H), tb.band_y1);
@@ -138,8 +155,10 @@ __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t
     // The pixel then shows the LAST face in order among those that pass against the final z (see k_tile).
     const bool nodepth = FULL && ((t.flags >> 8) & FF_NO_DEPTH) != 0;
     const int bw = x1 - x0;
-    if (cache) { cache->meta = 0; }
-    if (bw <= 0) return;
+    uint32_t over = PAIR_LOG_NONE;
+    // a face that writes no z is never logged: the lane walks again from its first such pair at the latest
+    if (SWEEP == 0 && nodepth) { log->cap = 0; over = 0; }
+    if (bw <= 0) return over;
     int px = x0 + sub, py = y0;
     while (px >= x1) { px -= bw; ++py; }
     int walked = 0;
@@ -148,7 +167,7 @@ __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t
             float u, v, w;
             pm.bary(px, py, u, v, w);
             bool ok = u >= 0 && v >= 0 && w >= 0;
-            if (FULL && ok && SWEEP == 0) ++frags;
+            if (COUNT) frags += SWEEP == 0 ? (ok ? 1u : 0u) : 1u;
             if (ok && (SWEEP == 1 || !nodepth)) {
                 const double z = pm.depth(u, v, w);
                 if (z == z) {                            // a NaN depth never passes the reference's test
@@ -156,10 +175,11 @@ __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t
                     const unsigned long long k = z_key(z);
                     if (SWEEP == 0) {
                         if (rh) atomicMin(&s_key[p], k); else atomicMax(&s_key[p], k);
-                        if (cache) {
-#pragma unroll
-                            for (int c = 0; c < SWEEP_CACHE_K; ++c)
-                                if (walked == c) { cache->key[c] = k; cache->meta |= ((uint32_t)p << (8 * c)) | (1u << (16 + c)); }
+                        const bool fits = log->n < log->cap;
+                        over = fits ? over : min(over, (uint32_t)walked);
+                        if (fits) {
+                            log->key[log->n][tid] = k; log->word[log->n][tid] = (uint32_t)p | ((uint32_t)t.face << 8);
+                            ++log->n;
                         }
                     } else if (nodepth ? (rh ? k <= s_key[p] : k >= s_key[p]) : s_key[p] == k) {
                         atomicMax(&s_win[p], t.face);
@@ -171,7 +191,7 @@ __device__ __forceinline__ void small_pair(const TileBounds &tb, const TriRec &t
         px += lanes;
         while (px >= x1) { px -= bw; ++py; }
     }
-    if (cache) cache->meta |= (uint32_t)walked << 20;
+    return over;
 }
 
 // Row of the device's output buffer that screen row py (in local tile row l) lands in.  A band of
@@ -351,6 +371,8 @@ struct TileArgs {
     uint32_t *bin_count;          // cursors = list lengths; zeroed again at the end of the tile
     const uint32_t *items[BIN_CLASSES];
     uint32_t cap[BIN_CLASSES];
+    uint32_t pair_log;            // 0 .. PAIR_LOG_K: MR_PAIR_LOG, the entries a lane's log may hold (phase 2).  (In the hole behind cap[]: the
+                                  // arguments behind it stay where they were, and with them how the kernels' scalar loads group.)
     const uint8_t *tap_mask;      // [tiles of the whole frame] or null: only the tiles marked here write the taps below (the overlay's tiles)
     double *zbuf;                 // optional taps (MR_FRAME_KEEP_BUFFERS): may be null
     int32_t *winner, *stencil;
@@ -534,6 +556,9 @@ __device__ __forceinline__ void tile_body()
             }
             return;
         }
+        // (a tile that goes on stores its first stamp here: carried to the record's other words at the end, it held a
+        // pair of scalar registers through every phase, and the multi-light general kernel spilled it)
+        if (FULL && tid == 0) ta.tile_stats[(size_t)tile * TILE_REC + 8] = (uint32_t)t_start;
         if (FULL && tid < TILE_STATS) s_cnt[tid] = 0;
         s_gamma[tid] = sh.gamma_lut[tid];
         if (tid == 0) s_gamma[GAMMA_LUT_SIZE - 1] = sh.gamma_lut[GAMMA_LUT_SIZE - 1];
@@ -636,19 +661,21 @@ __device__ __forceinline__ void tile_body()
         if (FULL && lane == 0 && frags) atomicAdd(&s_cnt[0], frags);
         if (n_small) {
             // ---- 2. small pairs, SMALL_LANES lanes per triangle, z into the LDS z-buffer
-            // The second sweep (who owns the final z?) needs every sample's z key again.  For the first
-            // SWEEP_CACHE_ROUNDS rounds a lane leaves the keys of its first SWEEP_CACHE_K samples in LDS (the staging
-            // area of the shadow quads, not in use yet: 12 KB, exactly), with the face; the second sweep then
-            // compares those without the record, the barycentrics or the depth -- a mesh triangle of a few pixels is
-            // all cache.  Lanes with more samples, later rounds and faces that do not write z walk again.
-            unsigned long long (*c_key)[SWEEP_CACHE_K][TILE_PX] =
-                reinterpret_cast<unsigned long long (*)[SWEEP_CACHE_K][TILE_PX]>(s_quad);
-            uint32_t (*c_meta)[TILE_PX] = reinterpret_cast<uint32_t (*)[TILE_PX]>(
-                reinterpret_cast<unsigned long long *>(s_quad) + SWEEP_CACHE_ROUNDS * SWEEP_CACHE_K * TILE_PX);
-            uint32_t (*c_face)[TILE_PX] = c_meta + SWEEP_CACHE_ROUNDS;
-            static_assert(SWEEP_CACHE_ROUNDS * TILE_PX * (SWEEP_CACHE_K * 8 + 8) <= (int)sizeof(s_quad), "sweep cache fits the quad area");
+            // The second sweep (who owns the final z?) needs every covered sample's z key again.  The first sweep
+            // leaves them in the lane's log (PairLog; the staging area of the shadow quads, not in use yet: 12 KB,
+            // exactly), and the second compares those without the item, the record, the barycentrics or the depth.
+            // Only a lane whose log ran over -- or that met a face that writes no z -- walks again, from there on.
+            static_assert(PAIR_LOG_K * TILE_PX * (8 + 4) <= (int)sizeof(s_quad), "the pair log fits the quad area");
+            PairLog log;
+            log.key = reinterpret_cast<unsigned long long (*)[TILE_PX]>(s_quad);
+            log.word = reinterpret_cast<uint32_t (*)[TILE_PX]>(log.key + PAIR_LOG_K);
+            log.n = 0;
+            // (the general kernel of a frame with several lights keeps the plain second walk, capacity 0 at compile time:
+            // at 96 registers it spills already, and the log's state cost it 4 to 16 bytes of scratch more, past the
+            // budget tests/test_kernel_layout.py holds it to)
+            log.cap = FULL && ML ? 0u : min(kernargs<TileKernArgs>().ta.pair_log, (uint32_t)PAIR_LOG_K);
+            log.resume = log.cap ? PAIR_LOG_NONE : 0u;        // capacity 0: every sample is walked again
             unsigned int sfrags = 0;
-            int round = 0;
             // SMALL_LANES lanes per pair; two where the list is longer than one round of those (a round is two
             // dependent memory round trips whatever it holds: 65 pairs in two rounds cost twice what 64 do), eight
             // where it is at most half a round (the lanes would idle otherwise; c2's larger triangles: -2 %)
@@ -656,19 +683,11 @@ __device__ __forceinline__ void tile_body()
                           : n_small > (uint32_t)(TILE_PX / (2 * SMALL_LANES)) ? SMALL_LANES : 2 * SMALL_LANES;
             const uint32_t per_round = (uint32_t)(TILE_PX / spl), my_pair = (uint32_t)(tid / spl);
             const int sub = tid % spl;
-            for (uint32_t i = my_pair; i < n_small; i += per_round, ++round) {
+            for (uint32_t i = my_pair; i < n_small; i += per_round) {
                 const TriRec t = tris[small_items[i]];
-                if (round < SWEEP_CACHE_ROUNDS) {
-                    SweepCache sc;
-                    small_pair<0, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, &sc);
-                    const bool nodepth = FULL && ((t.flags >> 8) & FF_NO_DEPTH) != 0;
-#pragma unroll
-                    for (int c = 0; c < SWEEP_CACHE_K; ++c) c_key[round][c][tid] = sc.key[c];
-                    c_meta[round][tid] = nodepth ? (sc.meta & 0xfff00000u) : sc.meta;      // nothing cached for a face that writes no z
-                    c_face[round][tid] = (uint32_t)t.face | (nodepth ? 0x80000000u : 0u);
-                } else {
-                    small_pair<0, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags);
-                }
+                const uint32_t over = small_pair<0, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, &log, tid);
+                // (a lane whose log is full has n == cap from then on: every later covered sample reports `over`, the first counts)
+                log.resume = (log.resume == PAIR_LOG_NONE && over != PAIR_LOG_NONE) ? ((i / per_round) << 8) | over : log.resume;
             }
             if (FULL && sfrags) atomicAdd(&s_cnt[0], sfrags);
             __syncthreads();
@@ -677,24 +696,28 @@ __device__ __forceinline__ void tile_body()
             // largest face index among those at the final z, in any order)
             const unsigned long long kfinal = s_key[lp];
             if (best >= 0 && kfinal == z_key(zbest)) atomicMax(&s_win[lp], best);
-            round = 0;
-            for (uint32_t i = my_pair; i < n_small; i += per_round, ++round) {
-                int first = 0;
-                if (round < SWEEP_CACHE_ROUNDS) {
-                    const uint32_t meta = c_meta[round][tid], cf = c_face[round][tid];
-                    const int walked = (int)(meta >> 20);
-                    const bool nodepth = FULL && (cf >> 31) != 0;
+            const uint32_t n_logged = log.n;
 #pragma unroll
-                    for (int c = 0; c < SWEEP_CACHE_K; ++c)
-                        if ((meta >> (16 + c)) & 1u) {
-                            const int p = (int)((meta >> (8 * c)) & 0xffu);
-                            if (s_key[p] == c_key[round][c][tid]) atomicMax(&s_win[p], (int)(cf & 0x7fffffffu));
-                        }
-                    if (!nodepth && walked <= SWEEP_CACHE_K) continue;     // the cache answered for every sample of this lane
-                    first = nodepth ? 0 : SWEEP_CACHE_K;
+            for (uint32_t e = 0; e < (uint32_t)PAIR_LOG_K; ++e)
+                if (e < n_logged) {
+                    const uint32_t w = log.word[e][tid], p = w & 0xffu;
+                    if (s_key[p] == log.key[e][tid]) atomicMax(&s_win[p], (int)(w >> 8));
                 }
-                const TriRec t = tris[small_items[i]];
-                small_pair<1, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, nullptr, first);
+            sfrags = 0;                                   // (general kernel: the samples walked again)
+            if (log.resume != PAIR_LOG_NONE) {
+                int first = (int)(log.resume & 0xffu);
+                for (uint32_t i = my_pair + (log.resume >> 8) * per_round; i < n_small; i += per_round) {
+                    const TriRec t = tris[small_items[i]];
+                    small_pair<1, FULL, FULL>(tb, t, gx, gy, rh, s_key, s_win, sub, spl, sfrags, nullptr, tid, first);
+                    first = 0;
+                }
+            }
+            if (counters) {                               // mr_debug_pair_log: entries answered from the log, samples walked again
+                unsigned int a = n_logged, b = sfrags;
+#pragma unroll
+                for (int off = WAVE / 2; off; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+                if (lane == 0 && a) atomicAdd(&ta.ctr->pad0[5], a);
+                if (lane == 0 && b) atomicAdd(&ta.ctr->pad0[6], b);
             }
             __syncthreads();
             best = s_win[lp];
@@ -1172,7 +1195,7 @@ __device__ __forceinline__ void tile_body()
     if (FULL && tid < TILE_STATS) rec[tid] = s_cnt[tid];
     if (tid == 0) {                                       // list lengths; timing for mr_debug_read_tile_records
         rec[5] = n_small_raw; rec[6] = n_big_raw; rec[7] = n_quad_raw;
-        rec[8] = (uint32_t)t_start;
+        if (!FULL) rec[8] = 0;                            // (the general kernel stored its first stamp when it took it)
         rec[9] = (uint32_t)stamp();
         rec[10] = (uint32_t)t_raster; rec[11] = (uint32_t)t_quads;
         if (n_small_raw > ta.cap[0]) { atomicOr(&ta.ctr->overflow, 1u); atomicMax(&ta.ctr->max_list[0], n_small_raw); }

@@ -874,6 +874,18 @@ int mr_debug_quad_walks(mr_scene *sc, uint32_t *out)
     return MR_OK;
 }
 
+int mr_debug_pair_log(mr_scene *sc, uint32_t *out)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (!out) return fail(MR_E_INVALID, "NULL argument");
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = fetch_counters(fs, false)) return rc;
+    HIP_TRY(hipStreamSynchronize(fs->stream));
+    for (int k = 0; k < 2; ++k) out[k] = fs->h_counters->pad0[5 + k];
+    return MR_OK;
+}
+
 int mr_debug_force_full(mr_scene *sc, int32_t on)
 {
     if (!sc) return fail(MR_E_INVALID, "NULL argument");

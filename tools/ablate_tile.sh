@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 cp py-numpy-renderer_amd/libmi355rast.so /tmp/lib_orig.so
 for k in ${ABLATE:-0 1 2 3 4 5}; do
   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 -DMR_ABLATE=$k -o py-numpy-renderer_amd/libmi355rast.so tools/_ablate/csrc/mi355rast.hip || exit 1
-  echo "== ablate $k (0 none, 1 shade, 2 quads, 3 small pairs, 4 big pairs, 5 winners sweep)"
+  echo "== ablate $k (0 none, 1 shade, 2 quads, 3 small pairs, 4 big pairs, 5 winners sweep, 6 no second walk of overflowed lanes)"
   bash tools/prof_pmc.sh abl$k ${KERNEL:-k_tile} SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SALU SQ_WAIT_INST_ANY
   KERNEL=${KERNEL:-k_tile} python3 - <<'PY'
 import csv, glob

@@ -1,5 +1,6 @@
 """Copies csrc/ to tools/_ablate/csrc (git-ignored) with MR_ABLATE switches in k_tile: diagnostic builds for
-tools/ablate_tile.sh (1 shading, 2 shadow quads, 3 small pairs, 4 big pairs, 5 the winners' sweep removed).  Never shipped."""
+tools/ablate_tile.sh (1 shading, 2 shadow quads, 3 small pairs, 4 big pairs, 5 the winners' sweep removed,
+6 the winners' sweep answers from the lanes' logs only: overflowed lanes do not walk again).  Never shipped."""
 import os, shutil
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src, dst = os.path.join(ROOT, "py-numpy-renderer_amd", "csrc"), os.path.join(ROOT, "tools", "_ablate", "csrc")
@@ -16,16 +17,16 @@ edits = [
     ("        n_small = min(n_small_raw, ta.cap[0]); n_big = min(n_big_raw, ta.cap[1]); n_quad = min(n_quad_raw, ta.cap[2]);\n",
      "        n_small = min(n_small_raw, ta.cap[0]); n_big = min(n_big_raw, ta.cap[1]); n_quad = min(n_quad_raw, ta.cap[2]);\n"
      "        if (MR_ABLATE == 2) n_quad = 0;\n        if (MR_ABLATE == 3) n_small = 0;\n        if (MR_ABLATE == 4) n_big = 0;\n"),
-    ("            round = 0;\n            for (uint32_t i = my_pair; i < n_small; i += per_round, ++round) {\n                int first = 0;",
-     "            round = 0;\n            for (uint32_t i = my_pair; i < (MR_ABLATE == 5 ? 0u : n_small); i += per_round, ++round) {\n                int first = 0;"),
-    # 6: the winners' sweep answers from the cache only (what would a cache that always answers be worth?)
-    ("                    if (!nodepth && walked <= SWEEP_CACHE_K) continue;     // the cache answered for every sample of this lane",
-     "                    if (MR_ABLATE == 6 || (!nodepth && walked <= SWEEP_CACHE_K)) continue;"),
+    ("            const uint32_t n_logged = log.n;\n",
+     "            const uint32_t n_logged = MR_ABLATE == 5 ? 0u : log.n;\n"),
+    # 6: overflowed lanes do not walk again (what would a log that always answers be worth?)
+    ("            if (log.resume != PAIR_LOG_NONE) {\n",
+     "            if (MR_ABLATE != 5 && MR_ABLATE != 6 && log.resume != PAIR_LOG_NONE) {\n"),
     # 1: no shading arithmetic (the records are still fetched)
     ("            shade_pixel(lc, t, sf, *mp, px, py, lit, rgb);",
      "            if (MR_ABLATE == 1) rgb[0] = (float)sf.world[0][0] + (float)mp->ns + t.d00 + (float)lc.light_pos[0]; else shade_pixel(lc, t, sf, *mp, px, py, lit, rgb);"),
     # 40 / 41: one / two EXTRA dependent scalar loads at the head of every listed tile's chain (what is a round trip worth?)
-    ("        if (tid < TILE_STATS) s_cnt[tid] = 0;\n        s_gamma[tid] = sh.gamma_lut[tid];\n", "        if (MR_ABLATE == 40 || MR_ABLATE == 41) {\n            uint32_t x = ta.bin_count[(uint32_t)(tile * 7 + 1) % (uint32_t)(3 * n_tiles)];\n            if (MR_ABLATE == 41) x = ta.bin_count[(x + (uint32_t)tile * 13u) % (uint32_t)(3 * n_tiles)];\n            if (x == 0xdeadbeefu) return;\n        }\n        if (tid < TILE_STATS) s_cnt[tid] = 0;\n        s_gamma[tid] = sh.gamma_lut[tid];\n"),
+    ("        if (FULL && tid < TILE_STATS) s_cnt[tid] = 0;\n        s_gamma[tid] = sh.gamma_lut[tid];\n", "        if (MR_ABLATE == 40 || MR_ABLATE == 41) {\n            uint32_t x = ta.bin_count[(uint32_t)(tile * 7 + 1) % (uint32_t)(3 * n_tiles)];\n            if (MR_ABLATE == 41) x = ta.bin_count[(x + (uint32_t)tile * 13u) % (uint32_t)(3 * n_tiles)];\n            if (x == 0xdeadbeefu) return;\n        }\n        if (FULL && tid < TILE_STATS) s_cnt[tid] = 0;\n        s_gamma[tid] = sh.gamma_lut[tid];\n"),
     # MR_TILE_PAD_KB: LDS ballast, to hold fewer workgroups on a CU (how does the launch time follow occupancy?)
     ("    __shared__ float s_gamma[GAMMA_LUT_SIZE];\n", "    __shared__ float s_gamma[GAMMA_LUT_SIZE];\n#ifdef MR_TILE_PAD_KB\n    __shared__ uint32_t s_pad[MR_TILE_PAD_KB * 256];\n    if (kernargs<TileKernArgs>().fc.width < 0) { s_pad[threadIdx.x] = 1u; __syncthreads(); if (s_pad[threadIdx.x ^ 1] == 77u) return; }\n#endif\n"),
 ]
@@ -42,7 +43,7 @@ edits = [
     ("    if (count_here) {\n        const int bw = bx1 - bx0;", "    if (count_here && MR_ABLATE != 6) {\n        const int bw = bx1 - bx0;"),
     ("    bin_triangles(fc, bins, (r & 1) != 0, (uint32_t)f, pb, clip);", "    if (MR_ABLATE != 7) bin_triangles(fc, bins, (r & 1) != 0, (uint32_t)f, pb, clip);"),
     ("    sa.tris[f] = t;        // (shading", "    if (MR_ABLATE != 8) sa.tris[f] = t;        // (shading"),
-    ("    if (b < face_blocks) tri_setup_block<PRE_XFORM>(b);", "    if (b < face_blocks) { if (MR_ABLATE != 10 && MR_ABLATE != 17) tri_setup_block<PRE_XFORM>(b); }"),
+    ("    if (b < face_blocks) tri_setup_block<PRE_XFORM, FULL>(b);", "    if (b < face_blocks) { if (MR_ABLATE != 10 && MR_ABLATE != 17) tri_setup_block<PRE_XFORM, FULL>(b); }"),
     ("    else edge_block<ML>(b - face_blocks);", "    else if (MR_ABLATE != 11 && MR_ABLATE != 17) edge_block<ML>(b - face_blocks);"),
     # 60: time stamps along the chain of a wavefront that has silhouette edges (lane 0; sums, maxima and the count in the
     #     counters' padding words, printed by the host when MR_SETUP_TIMES is set): stage k = DBG_T(k)
