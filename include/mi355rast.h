@@ -579,6 +579,55 @@ int mr_debug_auto_normals(mr_scene *scene, int32_t *out);
 #define MR_N_AUTO_NORMALS_TIMES 1
 int mr_debug_auto_normals_times(mr_scene *scene, float *out_ms);
 
+/* The accumulation: a weighted sum of float frames on the device, finalised once (motion blur over poses or bones, an
+ * area light as a point light averaged over positions, a jittered camera, progressive refinement of any of them).  It
+ * lives on the sample grid (Hs, Ws) of its sub-frames -- the frame descriptor's height and width, (s H, s W) with
+ * MR_FRAME_SUPERSAMPLE2/4 -- rows bottom-up like every tap.  With F_k the float32 frame mr_read_frame_f32 would return
+ * after sub-frame k rendered with MR_FRAME_KEEP_FLOAT (after the overlay, after the sum over the lights) and w_k its
+ * weight converted to float32, every operation float32 and rounded on its own (no fma):
+ *   A_0 = w_0 * F_0
+ *   A_k = A_{k-1} + (w_k * F_k)                       k = 1, 2, ...
+ *   M   = the mean of A over each s x s block         (summed row by row from the block's bottom-left sample, times 1 / s^2;
+ *                                                      s = 1: A itself)
+ *   R   = min(M * scale, 1.0f)
+ *   out = uint8(R ** 0.8 * 255), rows flipped         (uint8 (H, W, 3), row 0 = top)
+ * A scene has one accumulation.  Frames rendered in between (mr_render, mr_render_async, mr_render_device) and
+ * mr_scene_clear leave it alone.
+ *
+ * mr_accum_begin empties it (the buffer is kept for reuse).  Launches nothing.
+ * mr_accum_add renders the frame like mr_render does -- on the library's stream, MR_FRAME_KEEP_FLOAT forced on, again
+ * (up to six attempts) after a work list overflowed -- and adds it with k_accum_add once its lists are known to have
+ * held.  It does not wait for that kernel, and no frame bytes are copied to the host.  The first add fixes width, height
+ * and the supersample flags.  MR_E_INVALID for a later add that differs in one of them, for a partial frame (row band,
+ * stripes), for MR_FRAME_FACE_STATUS and for a weight that is not finite and > 0 as float32.
+ * mr_accum_resolve finalises the sum as it stands with `scale` (finite and > 0 as float32) into out_rgb, (H, W, 3)
+ * bytes, and waits.  The sum stays: it may be called again, and adds may follow it.  MR_E_INVALID before the first add.
+ * mr_accum_read_f32 is the tap: A as it stands, float32 (Hs, Ws, 3).  Synchronises the device. */
+int mr_accum_begin(mr_scene *scene);
+int mr_accum_add(mr_scene *scene, const mr_frame_desc *frame, double weight);
+int mr_accum_resolve(mr_scene *scene, double scale, uint8_t *out_rgb);
+int mr_accum_read_f32(mr_scene *scene, float *out_hw3);
+
+/* Diagnostics of the accumulation: out[0] = sub-frames added since mr_accum_begin, out[1] = sub-frames among them that
+ * were rendered again after an overflow (counted per extra attempt), out[2], out[3] = the sample grid's height and
+ * width (0 before the first add).  Does not wait for the device. */
+int mr_debug_accum(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds (HIP events on the library's stream): [0] the last k_accum_add, [1] the last
+ * k_accum_resolve (0 if there was none since mr_accum_begin).  Waits for the last add's kernel.  MR_E_INVALID before
+ * the first add. */
+#define MR_N_ACCUM_TIMES 2
+int mr_debug_accum_times(mr_scene *scene, float *out_ms);
+
+/* Host arithmetic, no device needed: the accumulation's definition for n frames -- frames is (n, height, width, 3)
+ * float32 on the sample grid, weights (n) float64, shift = log2 s (0, 1 or 2) -- bit for bit what the device path
+ * gives for the same F_k.  out_acc receives A, (height, width, 3); out_rgb the bytes, (height >> shift, width >> shift, 3),
+ * each (uint8_t)(powf(R, 0.8f) * 255.0f): the function the device's step table is built from.  Either may be NULL.
+ * MR_E_INVALID for n < 1, a weight or a scale that is not finite and > 0 as float32, a shift outside 0 .. 2, or a
+ * height or width that is no multiple of 1 << shift. */
+int mr_host_accum(const float *frames, const double *weights, int32_t n, int32_t height, int32_t width, int32_t shift,
+                  double scale, float *out_acc, uint8_t *out_rgb);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

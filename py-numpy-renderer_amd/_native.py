@@ -18,6 +18,7 @@ LIB_NAME = "libmi355rast.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 MR_OK = 0
+MR_E_INVALID = -1
 MR_E_OVERFLOW = -4
 FRAME_SHADOWS, FRAME_KEEP_FLOAT, FRAME_FACE_STATUS, FRAME_LIGHT_TIMING, FRAME_SKYBOX, FRAME_COUNTERS = 1, 2, 4, 8, 16, 32
 FRAME_KEEP_BUFFERS = 64
@@ -164,6 +165,13 @@ _PROTOTYPES = {
     "mr_host_auto_normals": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mr_debug_auto_normals": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_auto_normals_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_accum_begin": (C.c_int, [C.c_void_p]),
+    "mr_accum_add": (C.c_int, [C.c_void_p, C.POINTER(FrameDesc), C.c_double]),
+    "mr_accum_resolve": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "mr_accum_read_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_accum": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_accum_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_host_accum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -218,6 +226,33 @@ def _check(rc, what):
         msg = load_library().mr_last_error().decode(errors="replace")
         raise RuntimeError(f"{what} failed ({rc}): {msg}")
     return rc
+
+
+def _check_accum(rc, what):
+    """``_check`` for the accumulation's calls: what the library refuses as an argument (``MR_E_INVALID``) is a
+    ``ValueError`` with its text, everything else a ``RuntimeError``."""
+    if rc == MR_E_INVALID:
+        raise ValueError(f"{what}: " + load_library().mr_last_error().decode(errors="replace"))
+    return _check(rc, what)
+
+
+def host_accum(frames, weights, shift=0, scale=1.0, want_acc=True, want_rgb=True):
+    """``mr_host_accum``: the accumulation's definition on the host, no device.  *frames* is ``(n, Hs, Ws, 3)`` float32
+    (a sequence of ``(Hs, Ws, 3)`` frames will do), *weights* ``(n,)``; returns ``(A, bytes)`` -- float32 ``(Hs, Ws, 3)``
+    and uint8 ``(Hs >> shift, Ws >> shift, 3)``, ``None`` for the one not asked for.  ``ValueError`` with the library's
+    text for what it refuses."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+    if frames.ndim != 4 or frames.shape[3] != 3 or frames.shape[0] != len(weights):
+        raise ValueError(f"frames must be (n, H, W, 3) with one weight each, got {frames.shape} and {len(weights)} weights")
+    n, h, w, _ = frames.shape
+    shift = int(shift)
+    acc = np.empty((h, w, 3), dtype=np.float32) if want_acc else None
+    rgb = np.empty((h >> shift, w >> shift, 3), dtype=np.uint8) if want_rgb and 0 <= shift <= 2 else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check_accum(load_library().mr_host_accum(frames.ctypes.data, weights.ctypes.data, n, h, w, shift, float(scale), ptr(acc),
+                                              ptr(rgb)), "mr_host_accum")
+    return acc, rgb
 
 
 def stripe_out_rows(height, stripe_count):
@@ -597,6 +632,12 @@ class DeviceRenderer:
     def _prepare(self, scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing, overlay):
         """Everything ``render`` / ``render_async`` do before the library call: scene, skybox and overlay in step
         with the Python objects, the frame descriptor, a page-locked output array."""
+        desc, shape = self._prepare_desc(scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe,
+                                         timing, overlay)
+        return desc, self._pinned.array(shape)
+
+    def _prepare_desc(self, scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing, overlay):
+        """``_prepare`` without the output array: the frame descriptor and the shape of the frame's uint8 rows."""
         self.sync_scene(scene)
         self.sync_skybox(scene)
         pf = self.packed_frame(scene, shadows)
@@ -626,7 +667,53 @@ class DeviceRenderer:
         ss = pf.supersample           # (the output of a supersampled frame: s x s samples per pixel)
         rows = (desc.row_end - desc.row_begin) // ss if stripe is None else stripe_out_rows(pf.height, stripe[1])
         self._frame = (pf.height, pf.width)          # the taps' shape: the sample grid
-        return desc, self._pinned.array((rows, pf.width // ss, 3))
+        return desc, (rows, pf.width // ss, 3)
+
+    # -- the accumulation (Scene.accumulate) ------------------------------------------------
+    def accum_begin(self):
+        """``mr_accum_begin``: empties the scene's accumulation."""
+        _check_accum(self.lib.mr_accum_begin(self.handle), "mr_accum_begin")
+        self._accum_shapes = None
+
+    def accum_add(self, scene, weight, shadows=True, overlay=False):
+        """``mr_accum_add``: renders *scene* as it is now -- synchronised exactly as for ``render`` -- and adds its float
+        frame, times *weight*, to the accumulation.  Nothing is copied to the host."""
+        desc, shape = self._prepare_desc(scene, shadows, None, True, False, False, False, None, False, overlay)
+        _check_accum(self.lib.mr_accum_add(self.handle, C.byref(desc), float(weight)), "mr_accum_add")
+        self._last_stats = None
+        if getattr(self, "_accum_shapes", None) is None:
+            self._accum_shapes = ((desc.height, desc.width, 3), shape)      # (the sum's, the result's)
+
+    def accum_resolve(self, scale):
+        """``mr_accum_resolve``: the sum as it stands, finalised with *scale*: uint8 ``(H, W, 3)``, row 0 = top."""
+        if getattr(self, "_accum_shapes", None) is None:
+            raise ValueError("mr_accum_resolve: nothing accumulated yet")
+        out = self._pinned.array(self._accum_shapes[1])
+        _check_accum(self.lib.mr_accum_resolve(self.handle, float(scale), out.ctypes.data), "mr_accum_resolve")
+        return out
+
+    def accum_read(self):
+        """``mr_accum_read_f32``: the sum as it stands, float32 on the sample grid, rows bottom-up."""
+        if getattr(self, "_accum_shapes", None) is None:
+            raise ValueError("mr_accum_read_f32: nothing accumulated yet")
+        out = np.empty(self._accum_shapes[0], dtype=np.float32)
+        _check_accum(self.lib.mr_accum_read_f32(self.handle, out.ctypes.data), "mr_accum_read_f32")
+        return out
+
+    def accum_debug(self):
+        """``mr_debug_accum``: (sub-frames added, sub-frames rendered again after an overflow, the sample grid's height
+        and width)."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.mr_debug_accum(self.handle, out), "mr_debug_accum")
+        return tuple(int(x) for x in out)
+
+    ACCUM_TIME_NAMES = ("accum_add", "accum_resolve")
+
+    def accum_times(self):
+        """Device milliseconds of the last ``k_accum_add`` and the last ``k_accum_resolve`` (``mr_debug_accum_times``)."""
+        buf = (C.c_float * 2)()
+        _check(self.lib.mr_debug_accum_times(self.handle, buf), "mr_debug_accum_times")
+        return dict(zip(self.ACCUM_TIME_NAMES, (float(v) for v in buf)))
 
     ASYNC_LANES = 4
 

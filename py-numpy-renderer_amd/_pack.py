@@ -131,6 +131,23 @@ def check_supersample(value):
     return int(value)
 
 
+def check_accum_factor(value, what):
+    """A sub-frame's weight or the scale of ``Accumulation.result``: a real number that is finite and > 0 once it is a
+    float32 -- what the device multiplies with.  Returned as a Python float (the value as given)."""
+    if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what} must be a real number, got {value!r}")
+    with np.errstate(over="ignore"):
+        as_f32 = np.float32(value)
+    if not np.isfinite(as_f32) or not as_f32 > 0:
+        raise ValueError(f"{what} must be finite and > 0 as float32, got {value!r}")
+    return float(value)
+
+
+def default_accum_scale(weight_sum):
+    """``float32(1 / sum of the weights as given)``, the division in float64."""
+    return float(np.float32(1.0 / float(weight_sum)))
+
+
 def sample_grid(scene):
     """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame."""
     cam = scene.camera

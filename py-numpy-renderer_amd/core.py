@@ -651,6 +651,94 @@ class PendingFrame:
         return self._out
 
 
+class Accumulation:
+    """A weighted sum of the scene's float frames on the device, finalised once (``Scene.accumulate``).
+
+    The sum lives on the sample grid ``(Hs, Ws)`` of its sub-frames -- ``(s*H, s*W)`` for ``Scene.supersample = s`` --
+    rows bottom-up like every tap.  With F_k the float32 frame of sub-frame k (after the overlay, after the sum over
+    the lights) and w_k its weight as a float32, every operation float32 and rounded on its own::
+
+        A_0 = w_0 * F_0
+        A_k = A_{k-1} + (w_k * F_k)
+        M   = mean of A over each s x s block      (row by row from the block's bottom-left sample, times 1 / s^2)
+        R   = min(M * scale, 1)
+        out = uint8(R ** 0.8 * 255), rows flipped  (uint8 (H, W, 3), row 0 = top)
+
+    ``scale`` defaults to ``float32(1 / sum of the weights)``.  Averaging ``render()``'s uint8 frames instead averages
+    after the gamma and after the quantisation: wrong, and banded.  No sub-frame leaves the device; ``result()`` copies
+    the finished bytes.  A scene has one accumulation at a time: ``close()`` it (or leave its ``with`` block) before
+    asking for another.  ``render()`` and ``render_async()`` in between do not disturb it."""
+
+    def __init__(self, scene):
+        self._scene, self._open, self._begun = scene, True, False
+        self._count, self._weight_sum = 0, 0.0
+
+    @property
+    def count(self):
+        """Sub-frames added so far."""
+        return self._count
+
+    @property
+    def weight_sum(self):
+        """Sum of the weights as given (float64)."""
+        return self._weight_sum
+
+    def _check_open(self):
+        if not self._open:
+            raise RuntimeError("this accumulation is closed")
+
+    def add(self, weight=1.0, shadows=True):
+        """Render the scene AS IT IS NOW -- camera, lights, poses, bones, morph weights, ``supersample``,
+        ``draw_debug_frustum`` -- and add the frame times *weight* (finite and > 0 as float32).  The first ``add`` fixes
+        the resolution and ``supersample``: a later one that differs raises ``ValueError``.  Returns ``self``."""
+        from ._pack import check_accum_factor
+        self._check_open()
+        weight = check_accum_factor(weight, "weight")
+        scene = self._scene
+        scene._check_lights()
+        backend = scene._backend()
+        if not self._begun:
+            backend.accum_begin()
+            self._begun = True
+        backend.accum_add(scene, weight, shadows=shadows, overlay=scene.draw_debug_frustum)
+        self._count += 1
+        self._weight_sum += weight
+        return self
+
+    def result(self, scale=None):
+        """The sum as it stands, finalised: ``uint8 (H, W, 3)``, row 0 = top.  The sum stays, so ``add`` may follow
+        (progressive refinement).  ``RuntimeError`` before the first ``add``."""
+        from ._pack import check_accum_factor, default_accum_scale
+        self._check_open()
+        scale = default_accum_scale(self._weight_sum) if scale is None and self._count else scale
+        if scale is not None:
+            scale = check_accum_factor(scale, "scale")
+        if self._count == 0:
+            raise RuntimeError("nothing accumulated yet: add() a sub-frame first")
+        return self._scene._backend().accum_resolve(scale)
+
+    def float_frame(self):
+        """The tap: the sum A as it stands, ``float32 (Hs, Ws, 3)``, rows bottom-up."""
+        self._check_open()
+        if self._count == 0:
+            raise RuntimeError("nothing accumulated yet: add() a sub-frame first")
+        return self._scene._backend().accum_read()
+
+    def close(self):
+        """Gives the scene's accumulation back (the device keeps the buffer for the next one)."""
+        if self._open:
+            self._open = False
+            if self._scene.__dict__.get("_accumulation") is self:
+                self._scene.__dict__["_accumulation"] = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class Scene:
     """``Scene(camera, light, shadows, debug_camera, resolution=(H, W), system, subsystem,
     skymap)`` -- reference ``obj/core.py:558-640``.
@@ -670,6 +758,8 @@ class Scene:
     * ``add_light(light)`` (an addition; up to four lights with ``light``): further shadow-casting lights in the
       same frame -- visibility once, a stencil pass and an additive lighting pass per light; see ``add_light``.
       ``verbose`` and split frames (``multigpu``) refuse more than one light.
+    * ``accumulate()`` / ``render_mean(n, step)`` (an addition): a weighted sum of float frames on the device, finalised
+      once -- see ``Accumulation``.
     """
 
     camera = Bound()
@@ -809,6 +899,28 @@ class Scene:
             for frame in queue:
                 frame.result()
 
+    def accumulate(self):
+        """An ``Accumulation`` of this scene's frames (an addition): ``add(weight)`` renders the scene as it is now and
+        adds its float frame on the device, ``result()`` finalises the weighted sum once -- motion blur over poses or
+        bones, a soft shadow as a light averaged over positions, a jittered camera, progressive refinement.  Usable as
+        a context manager; one per scene at a time (``RuntimeError`` while another is open).  Touches no device before
+        the first ``add``."""
+        if self.__dict__.get("_accumulation") is not None:
+            raise RuntimeError("this scene already has an open accumulation: close() it first")
+        acc = self.__dict__["_accumulation"] = Accumulation(self)
+        return acc
+
+    def render_mean(self, n, step, shadows=True):
+        """The mean of *n* sub-frames: ``step(k)`` is called before sub-frame k (move a light, a pose, the camera),
+        every sub-frame weighs 1 and the scale is the default 1 / n.  Returns ``uint8 (H, W, 3)``."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"render_mean needs n >= 1 sub-frames, got {n!r}")
+        with self.accumulate() as acc:
+            for k in range(int(n)):
+                step(k)
+                acc.add(1.0, shadows=shadows)
+            return acc.result()
+
     def _print_face_report(self, status):
         from .triangular import Errors
         first = 0
@@ -821,6 +933,9 @@ class Scene:
             print('Discarded', histogram)
 
     def close(self):
+        open_acc = self.__dict__.get("_accumulation")
+        if open_acc is not None:                 # (its sum goes with the device's scene)
+            open_acc.close()
         if self._renderer is not None:
             self._renderer.close()
             self._renderer = None

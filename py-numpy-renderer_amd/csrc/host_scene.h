@@ -161,6 +161,16 @@ struct mr_scene {
     // ---- lanes of mr_render_async: a stream of the library's own each, and what is in flight on it
     struct Lane { hipStream_t stream = nullptr; bool busy = false; } lanes[MR_ASYNC_LANES];
 
+    // ---- the accumulation (host_accum.h): the weighted sum of the sub-frames added so far, on their sample grid.  It is
+    // the scene's, not a slot's: frames rendered in between leave it alone, and so does mr_scene_clear
+    struct Accum {
+        DevBuf d_acc;                         // float32 (height, width, 3), rows bottom-up; kept from one accumulation to the next
+        int32_t width = 0, height = 0, ss_flags = 0;      // fixed by the first add
+        int32_t count = 0, rerendered = 0;    // sub-frames added; sub-frames rendered again after an overflow
+        hipEvent_t ev[4] = {};                // marks round the last k_accum_add and the last k_accum_resolve
+        bool ev_ok = false, add_marked = false, resolve_marked = false;
+    } accum;
+
     // ---- frame slots, one per stream that has rendered this scene
     std::vector<std::unique_ptr<FrameSlot>> slots;
     FrameSlot *last = nullptr;               // slot of the most recently enqueued frame

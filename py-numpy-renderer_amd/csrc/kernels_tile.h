@@ -38,6 +38,7 @@
 
 #include "kernels_bin.h"
 #include "kernels_shade.h"
+#include "rast_resolve.h"
 
 namespace mr {
 
@@ -215,20 +216,7 @@ __device__ __forceinline__ uint8_t *ss_out_pixel(uint8_t *out, int width, int ba
 {
     return out + ((size_t)((band_y1 - 1 - py) >> shift) * (width >> shift) + (px >> shift)) * 3;
 }
-// mean of the block whose bottom-left sample is rgb[0]; rows `row` floats apart, samples 3 floats apart
-__device__ __forceinline__ void ss_block_mean(const float *rgb, int row, int shift, float m[3])
-{
-    const int s = 1 << shift;
-    float acc[3] = { 0.f, 0.f, 0.f };
-    for (int j = 0; j < s; ++j)
-        for (int i = 0; i < s; ++i) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] += rgb[j * row + i * 3 + c];
-        }
-    const float inv = 1.0f / (float)(s * s);       // a power of two: exact, and a uniform block keeps its colour
-#pragma unroll
-    for (int c = 0; c < 3; ++c) m[c] = acc[c] * inv;
-}
+// (ss_block_mean, the block's mean: rast_resolve.h)
 // The fused resolve: the tile's 256 sample colours are staged in LDS (s_rgb, 3 floats per sample, row-major from the
 // tile's bottom row); (16 / s)^2 threads each finalise one output pixel.  Call after the barrier behind the staging.
 __device__ __forceinline__ void ss_resolve_tile(const FrameConst &fc, const float *s_rgb, uint8_t *out, int gx, int gy, int tid,

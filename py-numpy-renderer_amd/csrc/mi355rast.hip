@@ -1,4 +1,5 @@
-// mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  This is the one file the library is compiled from;
+// mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file and from
+// accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why);
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -10,6 +11,7 @@
 //   host_autonormals.h  rebuilt vertex normals: the per-normal face lists (plain C++, no HIP)
 //   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
+//   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //
 // One process drives one GPU.  A scene keeps its static arrays (vertices, attributes, index arrays, textures, the
 // unique-edge table with the incident faces' normals, per-face and per-cluster records) resident in HBM; a frame is
@@ -24,7 +26,8 @@
 //                   supersampled frame: resolved to its output pixels in the same kernel)
 //   (k_face_status  MR_FRAME_FACE_STATUS;  k_overlay / k_overlay_export  MR_FRAME_OVERLAY: drawn on a whole frame, the
 //                   touched pixels' state exported from a part of one;  k_resolve_*  what a supersampled frame's
-//                   overlay or MR_RESOLVE_PATH=separate leave to resolve;  D2H of the uint8 rows for mr_render)
+//                   overlay or MR_RESOLVE_PATH=separate leave to resolve;  D2H of the uint8 rows for mr_render;
+//                   k_accum_add behind a sub-frame of mr_accum_add, k_accum_resolve for mr_accum_resolve)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -61,6 +64,7 @@
 #include "host_pose.h"
 #include "host_overlay_dev.h"
 #include "host_frame.h"
+#include "host_accum.h"
 
 // ============================================================================ C ABI
 
@@ -167,6 +171,7 @@ void mr_scene_destroy(mr_scene *sc)
         b->release();
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
+    accum_release(sc->accum);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
@@ -497,6 +502,62 @@ int mr_render_wait(mr_scene *sc, int32_t lane, mr_stats *stats)
     if (stats) *stats = sc->stats;
     if (rc == MR_E_OVERFLOW) return fail(MR_E_OVERFLOW, "the frame overflowed a work list (now grown): render it again");
     return rc;
+}
+
+int mr_accum_begin(mr_scene *sc)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    mr_scene::Accum &a = sc->accum;                  // (the buffer and the events stay for the next accumulation)
+    a.width = a.height = a.ss_flags = 0;
+    a.count = a.rerendered = 0;
+    a.add_marked = a.resolve_marked = false;
+    return MR_OK;
+}
+
+int mr_accum_add(mr_scene *sc, const mr_frame_desc *fr, double weight)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    return accum_add(sc, fr, weight);
+}
+
+int mr_accum_resolve(mr_scene *sc, double scale, uint8_t *out_rgb)
+{
+    if (!sc || !out_rgb) return fail(MR_E_INVALID, "NULL argument");
+    return accum_resolve(sc, scale, out_rgb);
+}
+
+int mr_accum_read_f32(mr_scene *sc, float *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    const mr_scene::Accum &a = sc->accum;
+    if (a.count == 0) return fail(MR_E_INVALID, "nothing accumulated yet");
+    return read_back(a.d_acc, out, (size_t)a.width * a.height * 3, "accumulation");
+}
+
+int mr_debug_accum(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    const mr_scene::Accum &a = sc->accum;
+    out[0] = a.count; out[1] = a.rerendered; out[2] = a.height; out[3] = a.width;
+    return MR_OK;
+}
+
+int mr_debug_accum_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    const mr_scene::Accum &a = sc->accum;
+    if (!a.add_marked) return fail(MR_E_INVALID, "nothing accumulated yet");
+    HIP_TRY(hipEventSynchronize(a.ev[1]));           // (mr_accum_add does not wait for its kernel)
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], a.ev[0], a.ev[1]));
+    out_ms[1] = 0.f;                                 // (no mr_accum_resolve since mr_accum_begin)
+    if (a.resolve_marked) HIP_TRY(hipEventElapsedTime(&out_ms[1], a.ev[2], a.ev[3]));
+    return MR_OK;
+}
+
+int mr_host_accum(const float *frames, const double *weights, int32_t n, int32_t height, int32_t width, int32_t shift, double scale,
+                  float *out_acc, uint8_t *out_rgb)
+{
+    return host_accum(frames, weights, n, height, width, shift, scale, out_acc, out_rgb);
 }
 
 int64_t mr_overlay_state_bytes(mr_scene *sc)
