@@ -171,7 +171,8 @@ int mr_device_available(void);
 int mr_abi_version(void);
 
 /* sizeof() of the ABI structs as this build sees them (0 mr_frame_desc, 1 mr_material,
- * 2 mr_model_desc, 3 mr_stats, 4 mr_overlay_desc, 5 mr_light_desc; -1 otherwise), so a binding can verify its own layout. */
+ * 2 mr_model_desc, 3 mr_stats, 4 mr_overlay_desc, 5 mr_light_desc, 6 mr_ao_desc; -1 otherwise), so a binding can verify
+ * its own layout. */
 int mr_abi_struct_size(int which);
 
 /* Scene() -- obj/core.py:563-582.  Returns NULL on failure. */
@@ -627,6 +628,70 @@ int mr_debug_accum_times(mr_scene *scene, float *out_ms);
  * height or width that is no multiple of 1 << shift. */
 int mr_host_accum(const float *frames, const double *weights, int32_t n, int32_t height, int32_t width, int32_t shift,
                   double scale, float *out_acc, uint8_t *out_rgb);
+
+/* Ambient obscurance from the z-buffer, applied to a frame's float colours before they are finalised: creases and the
+ * space between a model and the floor it stands on get darker than open surfaces.  It lives on the frame's sample grid
+ * (Hs, Ws), rows bottom-up like every tap.  With Z the z-buffer as mr_read_z returns it and F the float frame after the
+ * sum over the lights and BEFORE the overlay:
+ *
+ *   eye depth   e = (float)((m0 * Z + m1) / (m2 * Z + m3)), m = depth_map: the two products, the two sums and the
+ *               quotient float64, each rounded on its own (no fma), the result rounded once to float32.  A sample whose Z
+ *               or whose e is not finite is background.  The z-buffer is no distance (it holds the reference's
+ *               linearize_z of the viewport-transformed z); depth_map is the inverse of the chain from a point z_e on
+ *               the view axis to Z -- projection, division by w, viewport, linearize_z, each a Moebius map, so the chain
+ *               is a product of 2x2 matrices and its inverse the adjugate -- signed so that e > 0 in front of the camera.
+ *               The caller builds it per view; the library only applies it.
+ *   footprint   rp = perspective ? k / e_p : k, then rp = min(max(rp, 1), 32): float32, an IEEE division, in samples.
+ *               k = float32(radius * 0.5 * Hs * |P[1][1]|) makes radius a length in world units.
+ *   taps        eight antipodal pairs i = 0 .. 7 with unit offsets u_i = (cos(i pi / 8), sin(i pi / 8)) * (1 for even i,
+ *               0.5 for odd i), float32 literals (csrc/ao_def.h): dx = (int)rintf(u_i.x * rp), dy likewise, ties to even;
+ *               a = e(x + dx, y + dy), b = e(x - dx, y - dy).
+ *   obscurance  float32, every operation rounded on its own, i ascending:
+ *                 valid_i = both taps inside the frame and not background, fabsf(e_p - a) <= depth_range and
+ *                           fabsf(e_p - b) <= depth_range        (an invalid pair contributes 0: the pair, not one tap)
+ *                 c   = (e_p - a) + (e_p - b)          > 0 in a crease, <= 0 on a plane under perspective and on convex shapes
+ *                 t   = (c - bias) * inv_fall          inv_fall = float32(1 / radius), the quotient in float64
+ *                 occ = t < 0 ? 0 : (t > 1 ? 1 : t);   sum = sum + occ
+ *               ao = 1 - strength * (sum * 0.125f);  ao = ao < 0 ? 0 : ao
+ *   F'[p][ch] = F[p][ch] * ao;  a background sample keeps F.
+ *
+ * Where the frame draws an overlay it goes on F' and Z as ever: its lines are not darkened, and the Z they write is not
+ * seen.  The bytes are the finalise of the result -- block mean, min(., 1), the gamma step, rows flipped: what
+ * mr_host_accum gives for that one frame with weight 1 and scale 1.  mr_read_frame_f32 then returns the final float frame;
+ * mr_read_z is unchanged.  By this definition the whole colour is darkened, not the ambient term alone; with several
+ * lights the obscurance is applied once, after their sum; and a model that writes no z (depth_test = 0) is shaded by what
+ * the buffer holds behind it.
+ *
+ * mr_scene_set_ambient_occlusion copies the description (NULL: off, the default); every frame enqueued afterwards, by
+ * any entry point, uses the copy of its moment, so a caller may set another map per view while frames are in flight.
+ * Such a frame keeps its z-buffer and float frame (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT are implied, every tile
+ * writes its taps) and runs k_ao behind the tile kernel.  A scene without it enqueues what it always did.
+ * MR_E_INVALID for radius, strength, depth_range or k that are not finite and > 0 as float32, strength > 8, a bias that
+ * is not finite and >= 0, an entry of depth_map that is not finite, or perspective other than 0 / 1; and, from the
+ * rendering entry points, for a partial frame (row band, stripes) of such a scene, before any device work: the taps
+ * cross the bands.  MR_E_UNSUPPORTED from a library linked without ao.hip or accum.hip. */
+typedef struct mr_ao_desc {
+    double depth_map[4];       /* m0 .. m3 */
+    double k;                  /* footprint in samples at eye depth 1 (perspective) or everywhere; used as float32 */
+    double radius, strength, depth_range, bias;      /* used as float32 (radius also as 1 / radius) */
+    int32_t perspective;       /* 1: the footprint shrinks with the eye depth; 0: an orthographic camera */
+    int32_t pad;
+} mr_ao_desc;
+int mr_scene_set_ambient_occlusion(mr_scene *scene, const mr_ao_desc *ao);
+
+/* Host arithmetic, no device needed: the definition above for one frame -- z is (height, width) float64, frame and
+ * out_frame (height, width, 3) float32 (they may be the same array) -- bit for bit what k_ao leaves in the float frame.
+ * MR_E_INVALID for what mr_scene_set_ambient_occlusion refuses, a NULL array or a height or width outside 1 .. 32767. */
+int mr_host_ao(const double *z, const float *frame, int32_t height, int32_t width, const mr_ao_desc *ao, float *out_frame);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued k_ao (every enqueue, also one rendered again after an
+ * overflow), out[1], out[2] = the sample rows and columns of the last of them (0 before the first).  Does not wait. */
+int mr_debug_ao(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds of the last k_ao (HIP events on its frame's stream).  Waits for that kernel.
+ * MR_E_INVALID before the first such frame. */
+#define MR_N_AO_TIMES 1
+int mr_debug_ao_times(mr_scene *scene, float *out_ms);
 
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit

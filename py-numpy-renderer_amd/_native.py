@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, auto_normals_active, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -83,6 +83,22 @@ class ModelDesc(C.Structure):
 class OverlayDesc(C.Structure):
     _fields_ = [("n_segments", C.c_int32), ("n_points", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
                 ("seg_first", C.c_void_p), ("seg_count", C.c_void_p), ("target", C.c_void_p), ("z", C.c_void_p)]
+
+
+class AoDesc(C.Structure):
+    _fields_ = [("depth_map", C.c_double * 4), ("k", C.c_double), ("radius", C.c_double), ("strength", C.c_double),
+                ("depth_range", C.c_double), ("bias", C.c_double), ("perspective", C.c_int32), ("pad", C.c_int32)]
+
+
+def fill_ao_desc(ao, depth_map, k, perspective):
+    """``mr_ao_desc`` of an ``AmbientOcclusion`` (or anything with its four attributes) and a view's constants
+    (``_pack.ao_constants``)."""
+    d = AoDesc()
+    for i in range(4):
+        d.depth_map[i] = float(depth_map[i])
+    d.k, d.perspective = float(k), int(perspective)
+    d.radius, d.strength, d.depth_range, d.bias = float(ao.radius), float(ao.strength), float(ao.depth_range), float(ao.bias)
+    return d
 
 
 class Stats(C.Structure):
@@ -172,6 +188,10 @@ _PROTOTYPES = {
     "mr_debug_accum": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_accum_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_host_accum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "mr_scene_set_ambient_occlusion": (C.c_int, [C.c_void_p, C.POINTER(AoDesc)]),
+    "mr_host_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AoDesc), C.c_void_p]),
+    "mr_debug_ao": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_ao_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -213,7 +233,7 @@ def load_library():
             fn.restype, fn.argtypes = res, args
         if lib.mr_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_NAME}: ABI version {lib.mr_abi_version()}, this binding speaks {ABI_VERSION}; rebuild")
-        for which, struct in enumerate((FrameDesc, MaterialDesc, ModelDesc, Stats, OverlayDesc, LightDesc)):
+        for which, struct in enumerate((FrameDesc, MaterialDesc, ModelDesc, Stats, OverlayDesc, LightDesc, AoDesc)):
             if lib.mr_abi_struct_size(which) != C.sizeof(struct):
                 raise RuntimeError(f"{LIB_NAME}: layout of {struct.__name__} differs from the binding "
                                    f"({lib.mr_abi_struct_size(which)} vs {C.sizeof(struct)} bytes); rebuild")
@@ -253,6 +273,20 @@ def host_accum(frames, weights, shift=0, scale=1.0, want_acc=True, want_rgb=True
     _check_accum(load_library().mr_host_accum(frames.ctypes.data, weights.ctypes.data, n, h, w, shift, float(scale), ptr(acc),
                                               ptr(rgb)), "mr_host_accum")
     return acc, rgb
+
+
+def host_ao(z, frame, desc):
+    """``mr_host_ao``: the ambient obscurance's definition on the host, no device.  *z* is ``(Hs, Ws)`` float64, *frame*
+    ``(Hs, Ws, 3)`` float32, *desc* an ``AoDesc``; returns the darkened frame, float32 ``(Hs, Ws, 3)``.  ``ValueError``
+    with the library's text for what it refuses."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if z.ndim != 2 or frame.shape != z.shape + (3,):
+        raise ValueError(f"z must be (H, W) and frame (H, W, 3), got {z.shape} and {frame.shape}")
+    out = np.empty_like(frame)
+    _check_accum(load_library().mr_host_ao(z.ctypes.data, frame.ctypes.data, z.shape[0], z.shape[1], C.byref(desc), out.ctypes.data),
+                 "mr_host_ao")
+    return out
 
 
 def stripe_out_rows(height, stripe_count):
@@ -555,6 +589,33 @@ class DeviceRenderer:
         self._overlay_key = None
         self._overlay_pinned = ops is not None and pin
 
+    @staticmethod
+    def _ao_values(scene):
+        """The scene's ``AmbientOcclusion`` by value (``None`` without one), for ``_frame_key``."""
+        ao = getattr(scene, "ambient_occlusion", None)
+        return None if ao is None else (ao.radius, ao.strength, ao.depth_range, ao.bias)
+
+    def sync_ambient_occlusion(self, scene):
+        """``mr_scene_set_ambient_occlusion`` for the frames enqueued from now on, whenever the description -- the
+        scene's ``AmbientOcclusion`` and the view's depth map and footprint -- is not the one last handed over.  A scene
+        that never had one makes no call."""
+        ao = getattr(scene, "ambient_occlusion", None)
+        if ao is None:
+            if getattr(self, "_ao_key", None) is not None:
+                _check_accum(self.lib.mr_scene_set_ambient_occlusion(self.handle, None), "mr_scene_set_ambient_occlusion")
+                self._ao_key = self._ao_packed = None
+            return
+        # (called behind packed_frame: while its entry lives, camera, resolution and supersample are the same)
+        packed = (getattr(self, "_pack_serial", 0), self._ao_values(scene))
+        if getattr(self, "_ao_packed", None) == packed:
+            return
+        desc = fill_ao_desc(ao, *ao_constants(scene))
+        key = bytes(desc)
+        if getattr(self, "_ao_key", None) != key:
+            _check_accum(self.lib.mr_scene_set_ambient_occlusion(self.handle, C.byref(desc)), "mr_scene_set_ambient_occlusion")
+            self._ao_key = key
+        self._ao_packed = packed
+
     # -- frames ---------------------------------------------------------------------------
     @staticmethod
     def _frame_key(scene, shadows):
@@ -574,7 +635,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -651,6 +712,9 @@ class DeviceRenderer:
         if face_status and partial:
             raise ValueError("the per-face status needs the whole frame on one device (no row band, no stripes)")
         self.sync_lights(pf)
+        if getattr(scene, "ambient_occlusion", None) is not None and partial:
+            raise ValueError("ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands")
+        self.sync_ambient_occlusion(scene)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -715,6 +779,19 @@ class DeviceRenderer:
         _check(self.lib.mr_debug_accum_times(self.handle, buf), "mr_debug_accum_times")
         return dict(zip(self.ACCUM_TIME_NAMES, (float(v) for v in buf)))
 
+    # -- ambient obscurance (Scene.ambient_occlusion) ------------------------------------------
+    def ao_debug(self):
+        """``mr_debug_ao``: (frames that enqueued ``k_ao``, the last one's sample rows, its sample columns)."""
+        out = (C.c_int32 * 3)()
+        _check(self.lib.mr_debug_ao(self.handle, out), "mr_debug_ao")
+        return tuple(int(x) for x in out)
+
+    def ao_time(self):
+        """Device milliseconds of the last ``k_ao`` (``mr_debug_ao_times``)."""
+        buf = (C.c_float * 1)()
+        _check(self.lib.mr_debug_ao_times(self.handle, buf), "mr_debug_ao_times")
+        return float(buf[0])
+
     ASYNC_LANES = 4
 
     def render_async(self, scene, lane, shadows=True, overlay=False):
@@ -757,6 +834,7 @@ class DeviceRenderer:
         if pf.extra_lights and stripe is not None:
             raise ValueError("striped frames are not available with more than one light")
         self.sync_lights(pf)
+        self.sync_ambient_occlusion(scene)
         if overlay:
             self.sync_overlay(scene)
         desc = fill_frame_desc(pf, row_band, False, light_timing, counters=counters, stripe=stripe, no_timing=no_timing,

@@ -148,6 +148,79 @@ def default_accum_scale(weight_sum):
     return float(np.float32(1.0 / float(weight_sum)))
 
 
+def _ao_number(value, what, lowest_allowed):
+    """One parameter of an ``AmbientOcclusion`` as a Python float: a real number that is finite and > 0 (``>= 0`` with
+    *lowest_allowed*) once it is a float32 -- what the device computes with."""
+    if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"ambient occlusion: {what} must be a real number, got {value!r}")
+    with np.errstate(over="ignore"):
+        as_f32 = np.float32(value)
+    if not np.isfinite(as_f32) or as_f32 < 0 or (as_f32 == 0 and not lowest_allowed):
+        raise ValueError(f"ambient occlusion: {what} must be finite and {'>= 0' if lowest_allowed else '> 0'} as float32, got {value!r}")
+    return float(value)
+
+
+def check_ambient_occlusion(radius, strength, depth_range, bias):
+    """The parameters of an ``AmbientOcclusion`` as Python floats ``(radius, strength, depth_range, bias)``, the defaults
+    filled in: ``depth_range = 3 * radius``, ``bias = depth_range / 32``."""
+    radius = _ao_number(radius, "radius", False)
+    strength = _ao_number(strength, "strength", False)
+    if np.float32(strength) > 8:
+        raise ValueError(f"ambient occlusion: strength must be <= 8, got {strength!r}")
+    depth_range = _ao_number(3.0 * radius if depth_range is None else depth_range, "depth_range", False)
+    bias = _ao_number(depth_range / 32.0 if bias is None else bias, "bias", True)
+    if not np.isfinite(np.float32(1.0 / radius)):
+        raise ValueError(f"ambient occlusion: radius must be finite and > 0 as float32, got {radius!r}")
+    return radius, strength, depth_range, bias
+
+
+def depth_map(scene, camera):
+    """``(m0, m1, m2, m3)`` float64 with ``z_e = (m0 * Z + m1) / (m2 * Z + m3)``: the eye depth, > 0 in front of the
+    camera, of a z-buffer value Z of a frame of *scene* seen through *camera*.  The inverse of the chain the reference
+    applies to a point ``z_e`` on the view axis (row vectors, P the projection, V the viewport, n / f near / far)::
+
+        z_c = z_e * P[2,2] + P[3,2]      w_c = z_e * P[2,3] + P[3,3]      ndc = z_c / w_c
+        scr = ndc * V[2,2] + V[3,2]      Z = 2 n f / ((f + n) - scr * (f - n))
+
+    Every step is a Moebius map ``(a x + b) / (c x + d)``, so the chain is the product of three 2x2 matrices and its
+    inverse their adjugate (scaled by its largest entry, which changes no quotient).  The sign: ``z_e`` is negative in
+    front of a right-handed camera and positive in front of a left-handed one; a perspective camera shows the points with
+    ``w_c > 0``, so the depth is ``z_e * sign(P[2,3])``; for an orthographic one (``w_c`` constant) it is the sign under
+    which the middle of [n, f] lands nearer to the middle of the ndc range.  The matrices are *camera*'s own
+    (``projection`` at the scene's aspect ratio, ``viewport``'s z row, which a supersampled grid shares)."""
+    P = np.asarray(camera.projection, dtype=np.float64)
+    V = np.asarray(camera.viewport, dtype=np.float64)
+    n, f = float(camera.near), float(camera.far)
+    project = np.array([[P[2, 2], P[3, 2]], [P[2, 3], P[3, 3]]])
+    to_screen = np.array([[V[2, 2], V[3, 2]], [0.0, 1.0]])
+    linearize = np.array([[0.0, 2 * n * f], [-(f - n), f + n]])
+    (a, b), (c, d) = linearize @ to_screen @ project
+    if P[2, 3] != 0:
+        sign = 1.0 if P[2, 3] > 0 else -1.0
+    else:
+        mid = 0.5 * (n + f)
+        ndc = lambda z: abs((z * P[2, 2] + P[3, 2]) / P[3, 3])
+        sign = 1.0 if ndc(mid) <= ndc(-mid) else -1.0
+    m = np.array([sign * d, -sign * b, -c, a], dtype=np.float64)
+    largest = np.abs(m).max()
+    if not np.isfinite(m).all() or largest == 0:
+        raise ValueError("ambient occlusion: the camera's projection gives no finite depth map")
+    return tuple(float(x) for x in m / largest)
+
+
+def ao_constants(scene, camera=None):
+    """What ``mr_ao_desc`` carries for a frame of *scene* (``ambient_occlusion`` set) through *camera* (default: the
+    scene's): ``(depth_map, k, perspective)`` with ``k = float32(radius * 0.5 * Hs * |P[1,1]|)`` evaluated in float64,
+    Hs the sample grid's height."""
+    camera = scene.camera if camera is None else camera
+    ao = scene.ambient_occlusion
+    P = np.asarray(camera.projection, dtype=np.float64)
+    s = check_supersample(getattr(scene, "supersample", 1))
+    rows = s * int(scene.resolution[0])
+    k = float(np.float32(ao.radius * 0.5 * rows * abs(float(P[1, 1]))))
+    return depth_map(scene, camera), k, int(P[2, 3] != 0)
+
+
 def sample_grid(scene):
     """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame."""
     cam = scene.camera

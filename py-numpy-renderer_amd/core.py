@@ -115,6 +115,31 @@ class Morph:
         return f"Morph({len(self.targets)} targets, normal_targets={self.normal_targets is not None})"
 
 
+class AmbientOcclusion:
+    """What ``Scene.ambient_occlusion`` holds: the parameters of screen-space ambient obscurance from the z-buffer
+    (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6i the reasons).  ``radius`` is a length in world
+    units: a sample at eye depth e looks ``radius * 0.5 * Hs * |P[1][1]| / e`` samples far (between 1 and 32; constant for
+    an orthographic camera), and a crease that deep is fully obscured.  ``strength`` scales the darkening (0 < strength <=
+    8).  ``depth_range`` (default ``3 * radius``) is the largest difference in eye depth a tap may have and still count;
+    ``bias`` (default ``depth_range / 32``) is what a pair of taps must exceed before it darkens.  As float32, ``radius``,
+    ``strength`` and ``depth_range`` must be finite and > 0 and ``bias`` finite and >= 0 (``ValueError``; ``TypeError`` for
+    what is no real number).  An ``AmbientOcclusion`` is never modified: assign a new one to change it."""
+
+    __slots__ = ("radius", "strength", "depth_range", "bias")
+
+    def __init__(self, radius=0.1, strength=1.0, depth_range=None, bias=None):
+        from ._pack import check_ambient_occlusion
+        for name, value in zip(self.__slots__, check_ambient_occlusion(radius, strength, depth_range, bias)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("an AmbientOcclusion is read-only: assign a new one to Scene.ambient_occlusion")
+
+    def __repr__(self):
+        return (f"AmbientOcclusion(radius={self.radius!r}, strength={self.strength!r}, depth_range={self.depth_range!r}, "
+                f"bias={self.bias!r})")
+
+
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
     (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
@@ -760,6 +785,12 @@ class Scene:
       ``verbose`` and split frames (``multigpu``) refuse more than one light.
     * ``accumulate()`` / ``render_mean(n, step)`` (an addition): a weighted sum of float frames on the device, finalised
       once -- see ``Accumulation``.
+    * ``ambient_occlusion`` (an addition; ``None`` by default, or an ``AmbientOcclusion``): screen-space ambient
+      obscurance from the z-buffer, applied on the device to the float frame of every frame of the scene -- ``render``,
+      ``render_async``, ``render_frames``, the sub-frames of an ``Accumulation`` -- after the sum over the lights and before
+      the debug frustum, which is not darkened.  The whole colour is darkened, not the ambient term alone; with several
+      lights it is applied once; a ``depth_test=False`` model is shaded by what the z-buffer holds behind it.  Split
+      frames (``row_band``, ``multigpu``) refuse it.  With ``None`` a scene enqueues exactly what it did without it.
     """
 
     camera = Bound()
@@ -793,6 +824,17 @@ class Scene:
     def supersample(self, value):
         from ._pack import check_supersample
         self._supersample = check_supersample(value)
+
+    @property
+    def ambient_occlusion(self):
+        """``None`` (off, the default) or the scene's ``AmbientOcclusion`` (see the class docstring)."""
+        return self.__dict__.get("_ambient_occlusion")
+
+    @ambient_occlusion.setter
+    def ambient_occlusion(self, value):
+        if value is not None and not isinstance(value, AmbientOcclusion):
+            raise TypeError(f"ambient_occlusion must be None or an AmbientOcclusion, got {type(value).__name__}")
+        self.__dict__["_ambient_occlusion"] = value
 
     @property
     def last_stats(self):

@@ -19,6 +19,7 @@
 //   MR_CLUSTER_CULL   (auto)    0 | 1 | box | count: cluster culling off / on / boxes only / on and counted (auto: see
 //                               cluster_cull_mode)
 //   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
+//   MR_AO_TILE        64x64     32x32 | 64x16: the other workgroup shapes of k_ao (same bits; for the A/B; read in host_ao.h)
 //
 // MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
 // rest are read once per process.

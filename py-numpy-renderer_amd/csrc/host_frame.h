@@ -38,6 +38,7 @@ struct FrameSlot {
     bool last_full = false, last_split = false;   // the kernels the last frame launched (mr_debug_frame_path)
     bool overlay_deferred = false;           // the last enqueue_frame left the overlay to finish_overlay
     int last_ss_mode = 0;                    // FrameConst::ss_mode of the last frame (finish_overlay resolves after the overlay)
+    bool last_ao = false;                    // the last frame ran k_ao: its bytes are the full resolve of the float frame
     bool have_frame = false, stats_reduced = false;
     bool last_copied = false;                // the last frame was followed by a timed device-to-host copy (mr_render, mr_render_async)
 
@@ -156,6 +157,8 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         if (fr->row_begin % s || fr->row_end % s) return fail(MR_E_INVALID, "supersampling: row_begin / row_end must be multiples of s");
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
+    if (sc->ao.on && is_partial(fr))
+        return fail(MR_E_INVALID, "ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands");
     if (sc->n_extra_lights > 0) {
         if (fr->flags & MR_FRAME_FACE_STATUS)
             return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
@@ -321,9 +324,11 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   serial       the scene's frame serial with this frame
 //   edge_spread  EDGE_DENSE, or lanes per edge as a shift;  face_blocks, count_blocks: workgroups of k_setup's face half, of k_bin_work's counting
 //   order_bytes  d_hist: the tile order in front, the tiles' class bytes behind
+//   ao           the scene has ambient obscurance on: k_ao behind the tile kernel, with ao_params, the scene's description now
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao;
+    mr::AoParams ao_params;
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -347,7 +352,7 @@ int plan_overlay(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr:
         return fail(MR_E_INVALID, "overlay on a row band: the bands of the split must be equal");
     if (p.overlay && (sc->ov_width != fc.width || sc->ov_height != fc.height))
         return fail(MR_E_INVALID, "overlay lists were built for a frame of another size");
-    return p.overlay ? sync_slot_overlay(sc, fs->ov, fs->stream, p.partial || fc.ss_mode != 0) : MR_OK;
+    return p.overlay ? sync_slot_overlay(sc, fs->ov, fs->stream, p.partial || (fc.ss_mode != 0 && !p.ao)) : MR_OK;
 }
 
 // Decides what kind of frame this is: fills the plan and the frame's constants.
@@ -360,6 +365,10 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     if (fc.flags & MR_FRAME_FACE_STATUS) fc.flags |= MR_FRAME_KEEP_BUFFERS;
     // (a supersampled frame resolved by k_resolve_full needs every tile's float colour)
     if (fc.ss_mode & SS_SEPARATE) fc.flags |= MR_FRAME_KEEP_FLOAT;
+    // (ambient obscurance reads the whole z-buffer and rewrites the whole float frame: every tile writes its taps, as for
+    // a caller who asked for them)
+    p.ao = sc->ao.on;
+    if (p.ao) { p.ao_params = sc->ao.params; fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT; }
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
     p.taps_asked = (fc.flags & (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT)) != 0;
@@ -578,15 +587,26 @@ int launch_tile(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fra
     return MR_OK;
 }
 
-// ---- 4. behind the tile kernel: the per-face verdicts, the overlay (exported by a device that owns part of the frame,
-// else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638) and a supersampled frame's resolve
-void launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
+// The bytes of a frame that ran k_ao: the tree's finalise of the whole float frame, after the overlay (the accumulation's
+// resolve with scale 1: block mean, min(., 1), the gamma step, rows flipped).
+void launch_ao_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, int ss_mode, uint8_t *d_out)
+{
+    mr_accum::launch_resolve(fs->stream, fs->d_frame.as<float>(), fr.width, fr.height, ss_mode & mr::SS_SHIFT_MASK, 1.0f,
+                             sc->d_gamma.as<float>(), d_out);
+}
+
+// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the overlay (exported by a device that
+// owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638) and the resolve of
+// a supersampled or darkened frame
+int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
 {
     using namespace mr;
     hipStream_t stream = fs->stream;
     if ((fc.flags & MR_FRAME_FACE_STATUS) && fc.n_faces > 0)
         hipLaunchKernelGGL(k_face_status, dim3(blocks_for(fc.n_faces, 256)), dim3(256), 0, stream, fc, fs->d_tris.as<TriRec>(),
                            fs->d_clips.as<TriClip>(), fs->d_z.as<double>(), fs->d_stencil.as<int32_t>(), fs->d_status.as<uint8_t>());
+    if (p.ao && p.n_tiles > 0)
+        if (int rc = launch_ao(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, p.ao_params)) return rc;
     if (p.overlay && p.partial) {
         const int world = fr->stripe_count > 1 ? fr->stripe_count : fr->height / (fr->row_end - fr->row_begin);
         const int rank = fr->stripe_count > 1 ? fr->stripe_index : fr->row_begin / (fr->row_end - fr->row_begin);
@@ -595,9 +615,12 @@ void launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, con
         hipLaunchKernelGGL(k_overlay_export, dim3(blocks_for(n_slots, 256)), dim3(256), 0, stream, fs->ov.list<int32_t>(5), n_slots,
                            fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, world, fr->stripe_count > 1 ? 1 : 0, rank, state);
     } else if (p.overlay) {
-        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.ss_mode ? nullptr : d_out, fc.width, fc.height, fc.system, stream);
+        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.ss_mode || p.ao ? nullptr : d_out, fc.width, fc.height, fc.system, stream);
     }
-    if (!p.deferred) launch_resolve(sc, fs->ov, fs->d_frame.as<float>(), *fr, fc.ss_mode, p.overlay, d_out, stream);   // (deferred: finish_overlay's)
+    if (p.deferred) return MR_OK;                                    // (finish_overlay resolves)
+    if (p.ao) launch_ao_resolve(sc, fs, *fr, fc.ss_mode, d_out);
+    else launch_resolve(sc, fs->ov, fs->d_frame.as<float>(), *fr, fc.ss_mode, p.overlay, d_out, stream);
+    return MR_OK;
 }
 
 // ---- 5. what the slot and the scene remember of the frame
@@ -608,6 +631,7 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
     fs->last_full = p.full; fs->last_split = p.split;
     fs->overlay_deferred = p.deferred;
     fs->last_ss_mode = fc.ss_mode;
+    fs->last_ao = p.ao;
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = p.n_tiles;
     fs->last_n_lights = p.n_lights;
@@ -643,7 +667,7 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     if (p.timing) HIP_TRY(hipEventRecord(fs->ev[3], stream));
     if ((rc = launch_tile(sc, fs, fc, p, lights, d_out))) return rc;
     if (p.timing) HIP_TRY(hipEventRecord(fs->ev[4], stream));
-    launch_after_tile(sc, fs, fr, fc, p, d_out);
+    if ((rc = launch_after_tile(sc, fs, fr, fc, p, d_out))) return rc;
     HIP_TRY(hipGetLastError());
     record_frame(sc, fs, fr, fc, p);
     return MR_OK;
@@ -662,10 +686,11 @@ int finish_overlay(mr_scene *sc, FrameSlot *fs, uint8_t *d_out)
     const bool draw = sc->ov_points != 0;
     if (draw) {
         if (sc->ov_width != fr.width || sc->ov_height != fr.height) return fail(MR_E_INVALID, "overlay lists were built for a frame of another size");
-        if (int rc = sync_slot_overlay(sc, fs->ov, fs->stream, ss_mode != 0)) return rc;
-        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), ss_mode ? nullptr : d_out, fr.width, fr.height, fr.system, fs->stream);
+        if (int rc = sync_slot_overlay(sc, fs->ov, fs->stream, ss_mode != 0 && !fs->last_ao)) return rc;
+        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), ss_mode || fs->last_ao ? nullptr : d_out, fr.width, fr.height, fr.system, fs->stream);
     }
-    launch_resolve(sc, fs->ov, fs->d_frame.as<float>(), fr, ss_mode, draw, d_out, fs->stream);
+    if (fs->last_ao) launch_ao_resolve(sc, fs, fr, ss_mode, d_out);
+    else launch_resolve(sc, fs->ov, fs->d_frame.as<float>(), fr, ss_mode, draw, d_out, fs->stream);
     HIP_TRY(hipGetLastError());
     return MR_OK;
 }

@@ -171,6 +171,15 @@ struct mr_scene {
         bool ev_ok = false, add_marked = false, resolve_marked = false;
     } accum;
 
+    // ---- ambient obscurance (host_ao.h): the description every frame enqueued from now on takes a copy of
+    struct Ao {
+        bool on = false;
+        mr::AoParams params = {};
+        int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued k_ao; the last one's sample grid
+        hipEvent_t ev[2] = {};                // marks round the last k_ao
+        bool ev_ok = false, marked = false;
+    } ao;
+
     // ---- frame slots, one per stream that has rendered this scene
     std::vector<std::unique_ptr<FrameSlot>> slots;
     FrameSlot *last = nullptr;               // slot of the most recently enqueued frame

@@ -1,5 +1,6 @@
-// mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file and from
-// accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why);
+// mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file, from
+// accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), and
+// from ao.hip, which holds the ambient obscurance's kernel in another;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -10,6 +11,7 @@
 //   host_morph.h        morph targets: the per-vertex contribution lists (plain C++, no HIP)
 //   host_autonormals.h  rebuilt vertex normals: the per-normal face lists (plain C++, no HIP)
 //   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
+//   host_ao.h           ambient obscurance from the z-buffer: the description, k_ao's launch, the host mirror
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //
@@ -27,7 +29,8 @@
 //   (k_face_status  MR_FRAME_FACE_STATUS;  k_overlay / k_overlay_export  MR_FRAME_OVERLAY: drawn on a whole frame, the
 //                   touched pixels' state exported from a part of one;  k_resolve_*  what a supersampled frame's
 //                   overlay or MR_RESOLVE_PATH=separate leave to resolve;  D2H of the uint8 rows for mr_render;
-//                   k_accum_add behind a sub-frame of mr_accum_add, k_accum_resolve for mr_accum_resolve)
+//                   k_accum_add behind a sub-frame of mr_accum_add, k_accum_resolve for mr_accum_resolve;
+//                   k_ao behind k_tile in a scene with mr_scene_set_ambient_occlusion, k_accum_resolve for its bytes)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -44,6 +47,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <new>
 #include <string>
@@ -54,6 +58,7 @@
 #include "kernels_tile.h"
 #include "kernels_overlay.h"
 #include "kernels_pose.h"
+#include "ao_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -63,6 +68,7 @@
 #include "host_scene.h"
 #include "host_pose.h"
 #include "host_overlay_dev.h"
+#include "host_ao.h"
 #include "host_frame.h"
 #include "host_accum.h"
 
@@ -77,8 +83,8 @@ int mr_abi_version(void) { return MR_ABI_VERSION; }
 int mr_abi_struct_size(int which)
 {
     static const size_t size[] = { sizeof(mr_frame_desc), sizeof(mr_material), sizeof(mr_model_desc), sizeof(mr_stats),
-                                   sizeof(mr_overlay_desc), sizeof(mr_light_desc) };
-    return which >= 0 && which < 6 ? (int)size[which] : -1;
+                                   sizeof(mr_overlay_desc), sizeof(mr_light_desc), sizeof(mr_ao_desc) };
+    return which >= 0 && which < 7 ? (int)size[which] : -1;
 }
 
 int mr_device_available(void)
@@ -172,6 +178,7 @@ void mr_scene_destroy(mr_scene *sc)
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
     accum_release(sc->accum);
+    ao_release(sc->ao);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
@@ -558,6 +565,39 @@ int mr_host_accum(const float *frames, const double *weights, int32_t n, int32_t
                   float *out_acc, uint8_t *out_rgb)
 {
     return host_accum(frames, weights, n, height, width, shift, scale, out_acc, out_rgb);
+}
+
+int mr_scene_set_ambient_occlusion(mr_scene *sc, const mr_ao_desc *ao)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (!ao) { sc->ao.on = false; return MR_OK; }      // (frames already enqueued took their copy)
+    mr::AoParams p;
+    if (int rc = ao_params(ao, p)) return rc;
+    if (int rc = ao_linked()) return rc;
+    sc->ao.params = p;
+    sc->ao.on = true;
+    return MR_OK;
+}
+
+int mr_host_ao(const double *z, const float *frame, int32_t height, int32_t width, const mr_ao_desc *ao, float *out_frame)
+{
+    return host_ao(z, frame, height, width, ao, out_frame);
+}
+
+int mr_debug_ao(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    out[0] = sc->ao.frames; out[1] = sc->ao.rows; out[2] = sc->ao.cols;
+    return MR_OK;
+}
+
+int mr_debug_ao_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->ao.marked) return fail(MR_E_INVALID, "no frame with ambient occlusion yet");
+    HIP_TRY(hipEventSynchronize(sc->ao.ev[1]));      // (no entry point waits for the kernel itself)
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->ao.ev[0], sc->ao.ev[1]));
+    return MR_OK;
 }
 
 int64_t mr_overlay_state_bytes(mr_scene *sc)

@@ -212,6 +212,9 @@ class BandRenderer:
             raise ValueError("a frame split over devices does not support supersample > 1 (render it on one device)")
         if len(getattr(scene, "lights", ())) > 1:
             raise ValueError("a frame split over devices does not support more than one light (render it on one device)")
+        if getattr(scene, "ambient_occlusion", None) is not None:
+            raise ValueError("a frame split over devices does not support ambient_occlusion: its taps cross the bands "
+                             "(render it on one device)")
         if partition not in ("bands", "stripes", "weighted"):
             raise ValueError(f"unknown partition {partition!r}")
         self.rank, self.world, self.partition = rank, world, partition
