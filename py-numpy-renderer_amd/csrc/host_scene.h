@@ -11,6 +11,37 @@ struct EdgeKey {
     uint32_t inc;      // face * 4 + corner
 };
 
+// What the next pose pass (host_pose.h) has to redo, as bits of mr_scene::pose_dirty: vertices and what is built from
+// them; the whole normals' part; k_skin_normals alone (new bones); k_morph_normals alone (new weights)
+enum PoseDirty : uint8_t { POSE_GEOM = 1, POSE_NORMALS = 2, POSE_SKIN_N = 4, POSE_MORPH_N = 8 };
+
+// Timing marks of one part of the pose pass: events on the library's stream, created when first recorded, round SPANS
+// kernels.  Span k lies between marks k * STRIDE and k * STRIDE + 1: consecutive marks, each the end of one span and the
+// start of the next, with STRIDE 1; a pair of its own per kernel with STRIDE 2.
+template <int SPANS, int STRIDE>
+struct PassMarks {
+    hipEvent_t ev[(SPANS - 1) * STRIDE + 2] = {};
+    bool seen = false;                        // a pass has come this way: until then there is nothing to read
+    bool ran[SPANS] = {};                     // the last pass launched span k's kernel
+    void none_ran() { for (bool &r : ran) r = false; }
+    int mark(int i)
+    {
+        if (!ev[i]) HIP_TRY(hipEventCreate(&ev[i]));
+        HIP_TRY(hipEventRecord(ev[i], g_stream));
+        return MR_OK;
+    }
+    int read(float *out_ms, const char *none_yet) const
+    {
+        if (!seen) return fail(MR_E_INVALID, none_yet);
+        for (int k = 0; k < SPANS; ++k) {
+            out_ms[k] = 0.f;                  // (a kernel the last pass did not launch: not the empty span between two marks)
+            if (ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], ev[k * STRIDE], ev[k * STRIDE + 1]));
+        }
+        return MR_OK;
+    }
+    void release() { for (hipEvent_t &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; } }
+};
+
 }  // namespace
 
 struct mr_scene {
@@ -72,16 +103,12 @@ struct mr_scene {
     };
     std::vector<ModelPose> poses;             // one per model
     bool skin_tables_dirty = false;           // a skin was set or removed: the device tables are rebuilt by the next pass
-    bool skin_n_dirty = false;                // bones of a model whose normals follow its skin changed
     int32_t skin_bones = 0, skin_written = 0, skin_normals_written = 0;     // mr_debug_skin
     bool morph_tables_dirty = false;          // a morph was set or removed: the device lists are rebuilt by the next pass that needs them
-    bool morph_n_dirty = false;               // weights of a model whose normals follow its morph changed
     int32_t morph_targets = 0, morph_written = 0, morph_normals_written = 0, morph_entries = 0;   // mr_debug_morph
     bool auto_tables_dirty = false;           // a model's lists were built, or the scene was committed: the device lists (of every model that holds some) are rebuilt by the next pass that needs them
     int32_t auto_models = 0, auto_written = 0, auto_entries = 0, auto_kept_waves = 0;   // mr_debug_auto_normals (the kept count is summed from d_auto_kept when asked for)
-    bool pose_dirty = false;                  // a pose or a normal matrix changed: apply_poses() has work
-    bool pose_geom_dirty = false;             // ... and a pose among them: vertices and what is built from them
-    bool pose_g_dirty = false;                // ... and a normal matrix among them: normals and re-baked maps
+    uint8_t pose_dirty = 0;                   // PoseDirty bits: what the setters and commit() left for apply_poses()
     int32_t commits = 0, pose_passes = 0, pose_written = 0;      // mr_debug_pose
 
     // ---- device copies of the static scene
@@ -94,22 +121,17 @@ struct mr_scene {
     // the pose pass: the vertices as the caller passed them (d_verts holds what the kernels read) and the pass's two tables
     DevBuf d_verts0, d_pose_rows, d_pose_blocks;
     bool verts0_valid = false;
-    hipEvent_t pose_ev[6] = {};               // marks of the last pass (mr_debug_pose_times)
-    int pose_marks = 0;
+    PassMarks<MR_N_POSE_TIMES, 1> marks_pose;             // six marks round the vertex kernels and the four rebuilds of the last pass over faces
     // the same for normal matrices: the normals as the caller passed them, the tables of k_pose_normals and
     // k_pose_texels, and the re-baked copies of object-space normal maps, one after the other
     DevBuf d_normals0, d_normal_rows, d_normal_blocks, d_texel_rows, d_texel_blocks, d_rebaked;
     bool normals0_valid = false;
-    hipEvent_t pose_n_ev[3] = {};             // marks round the two kernels (mr_debug_pose_normals_times)
-    int pose_n_marks = 0;
-    bool pose_n_ran[2] = {};                  // which of the two the last such pass launched
+    PassMarks<MR_N_POSE_NORMALS_TIMES, 1> marks_normals;  // three marks round the two kernels of the last pass that launched one of them
     // the skin: joints (int4), weights (double4) and normal owners of the skinned models, one after the other; the bone
     // table of the last pass (its host copy lives until the pass has waited for the stream) and the two kernels' tables
     DevBuf d_skin_joints, d_skin_weights, d_skin_owners, d_bones, d_skin_rows, d_skin_blocks, d_skin_n_rows, d_skin_n_blocks;
     std::vector<double> bone_table;
-    hipEvent_t skin_ev[4] = {};               // marks round k_skin_vertices and k_skin_normals (mr_debug_skin_times)
-    bool skin_ran[2] = {};                    // which of the two the last pass launched
-    bool skin_marks = false;
+    PassMarks<MR_N_SKIN_TIMES, 2> marks_skin;             // k_skin_vertices, k_skin_normals
     // the morphs: the sliced contribution lists of every model that has a morph, one after the other (the slice table,
     // then four planes: target, delta x / y / z); the weight table of the last pass and the two kernels' tables; and the
     // copies of d_verts0 / d_normals0 in which the morphed models' ranges hold the morphed arrays: what the skin and pose
@@ -118,14 +140,11 @@ struct mr_scene {
     DevBuf d_morph_rows, d_morph_blocks, d_morph_n_rows, d_morph_n_blocks, d_verts_m, d_normals_m;
     bool verts_m_valid = false, normals_m_valid = false;
     std::vector<double> morph_weight_table;
-    hipEvent_t morph_ev[4] = {};              // marks round k_morph_vertices and k_morph_normals (mr_debug_morph_times)
-    bool morph_ran[2] = {};                   // which of the two the last pass launched
-    bool morph_marks = false;
+    PassMarks<MR_N_MORPH_TIMES, 2> marks_morph;           // k_morph_vertices, k_morph_normals
     // rebuilt normals: the sliced face lists of every model whose flag is on, one after the other (the slice table and
     // one plane of faces), the kernel's two tables and its per-wavefront counts of normals that kept their value
     DevBuf d_auto_slices, d_auto_faces, d_auto_rows, d_auto_blocks, d_auto_kept;
-    hipEvent_t auto_ev[2] = {};               // marks round k_auto_normals (mr_debug_auto_normals_times)
-    bool auto_ran = false, auto_marks = false;
+    PassMarks<1, 2> marks_auto;                           // k_auto_normals
     bool pos32 = false;                     // d_face_pos holds FacePos32 (every model's vertices are float32)
     bool has_no_depth = false;               // some model has depth_test == False (what a frame asks once per scene, not once per frame)
     bool force_full = false;                 // mr_debug_force_full: every frame takes the general kernels (FramePlan::full)
@@ -394,8 +413,8 @@ int commit(mr_scene *sc)
         mp.verts_m_morphed = mp.normals_m_morphed = false;
         mp.auto_lists.clear();                // (the face lists belong to the committed faces)
         if (mp.auto_on) sc->auto_tables_dirty = true;
-        if (mp.moved()) sc->pose_dirty = sc->pose_geom_dirty = true;
-        if (mp.has_g || mp.skin_normals() || mp.morph_normals()) sc->pose_g_dirty = true;
+        if (mp.moved()) sc->pose_dirty |= POSE_GEOM;
+        if (mp.has_g || mp.skin_normals() || mp.morph_normals()) sc->pose_dirty |= POSE_NORMALS;
     }
     return MR_OK;
 }

@@ -123,10 +123,8 @@ int mr_scene_clear(mr_scene *sc)
     sc->verts.clear(); sc->uv.clear(); sc->normals.clear(); sc->faces.clear(); sc->face_flags.clear();
     sc->materials.clear(); sc->model_face_off.clear(); sc->edges.clear(); sc->edge_inc.clear();
     sc->edge_ids.clear(); sc->edge_raw.clear();
-    sc->poses.clear(); sc->pose_dirty = sc->pose_geom_dirty = sc->pose_g_dirty = sc->skin_n_dirty = false;
-    sc->skin_tables_dirty = true;
-    sc->morph_tables_dirty = true; sc->morph_n_dirty = false;
-    sc->auto_tables_dirty = true;
+    sc->poses.clear(); sc->pose_dirty = 0;
+    sc->skin_tables_dirty = sc->morph_tables_dirty = sc->auto_tables_dirty = true;
     sc->dirty = true;
     sc->last = nullptr;
     sc->sil.drop();
@@ -180,11 +178,7 @@ void mr_scene_destroy(mr_scene *sc)
     accum_release(sc->accum);
     ao_release(sc->ao);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
-    for (hipEvent_t e : sc->pose_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : sc->pose_n_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : sc->skin_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : sc->morph_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : sc->auto_ev) if (e) (void)hipEventDestroy(e);
+    sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
 }
 
@@ -1024,20 +1018,13 @@ int mr_debug_pose(mr_scene *sc, int32_t *out)
 int mr_debug_pose_times(mr_scene *sc, float *out_ms)
 {
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (sc->pose_marks != 6) return fail(MR_E_INVALID, "no pose pass over faces yet");
-    for (int k = 0; k < MR_N_POSE_TIMES; ++k) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->pose_ev[k], sc->pose_ev[k + 1]));
-    return MR_OK;
+    return sc->marks_pose.read(out_ms, "no pose pass over faces yet");
 }
 
 int mr_debug_pose_normals_times(mr_scene *sc, float *out_ms)
 {
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (sc->pose_n_marks != 3) return fail(MR_E_INVALID, "no pose pass over normals yet");
-    for (int k = 0; k < MR_N_POSE_NORMALS_TIMES; ++k) {
-        out_ms[k] = 0.f;                             // (a kernel that was not launched: not the empty span between two marks)
-        if (sc->pose_n_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->pose_n_ev[k], sc->pose_n_ev[k + 1]));
-    }
-    return MR_OK;
+    return sc->marks_normals.read(out_ms, "no pose pass over normals yet");
 }
 
 int mr_debug_skin(mr_scene *sc, int32_t *out)
@@ -1052,12 +1039,7 @@ int mr_debug_skin(mr_scene *sc, int32_t *out)
 int mr_debug_skin_times(mr_scene *sc, float *out_ms)
 {
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->skin_marks) return fail(MR_E_INVALID, "no pass over a skin yet");
-    for (int k = 0; k < MR_N_SKIN_TIMES; ++k) {
-        out_ms[k] = 0.f;                             // (a kernel the last pass did not launch)
-        if (sc->skin_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->skin_ev[2 * k], sc->skin_ev[2 * k + 1]));
-    }
-    return MR_OK;
+    return sc->marks_skin.read(out_ms, "no pass over a skin yet");
 }
 
 int mr_debug_morph(mr_scene *sc, int32_t *out)
@@ -1086,21 +1068,13 @@ int mr_debug_auto_normals(mr_scene *sc, int32_t *out)
 int mr_debug_auto_normals_times(mr_scene *sc, float *out_ms)
 {
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->auto_marks) return fail(MR_E_INVALID, "no pass over rebuilt normals yet");
-    out_ms[0] = 0.f;                                 // (the last pass did not launch it)
-    if (sc->auto_ran) HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->auto_ev[0], sc->auto_ev[1]));
-    return MR_OK;
+    return sc->marks_auto.read(out_ms, "no pass over rebuilt normals yet");
 }
 
 int mr_debug_morph_times(mr_scene *sc, float *out_ms)
 {
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->morph_marks) return fail(MR_E_INVALID, "no pass over a morph yet");
-    for (int k = 0; k < MR_N_MORPH_TIMES; ++k) {
-        out_ms[k] = 0.f;                             // (a kernel the last pass did not launch)
-        if (sc->morph_ran[k]) HIP_TRY(hipEventElapsedTime(&out_ms[k], sc->morph_ev[2 * k], sc->morph_ev[2 * k + 1]));
-    }
-    return MR_OK;
+    return sc->marks_morph.read(out_ms, "no pass over a morph yet");
 }
 
 int mr_debug_read_clusters(mr_scene *sc, void *out, int32_t cap_clusters)
