@@ -693,6 +693,66 @@ int mr_debug_ao(mr_scene *scene, int32_t *out);
 #define MR_N_AO_TIMES 1
 int mr_debug_ao_times(mr_scene *scene, float *out_ms);
 
+/* Depth of field from the z-buffer, a thin lens focused at eye depth `focus`, applied to a frame's float colours before
+ * they are finalised: every sample is gathered from the samples whose circle of confusion reaches it.  It lives on the
+ * frame's sample grid (Hs, Ws), rows bottom-up like every tap.  With Z the z-buffer as mr_read_z returns it and F the
+ * float frame after the sum over the lights, after the ambient obscurance where that is on, and BEFORE the overlay:
+ *
+ *   eye depth   e as for the ambient obscurance above (depth_map, the same float64 chain, one rounding to float32); a
+ *               sample whose Z or whose e is not finite is background, e = +inf.
+ *   circle      s = perspective ? kf * (1 - focus / e) : kf * (e - focus): float32 from here on, every operation rounded
+ *               on its own, IEEE divisions.  Signed: > 0 behind the plane in focus.  A background sample has s = kf under
+ *               perspective and +inf under an orthographic camera.  kf = float32(lens_radius * 0.5 * Hs * |P[1][1]| /
+ *               focus), the quotient chain in float64: a point at eye depth e spreads over a disc of lens_radius *
+ *               |e - focus| / focus world units at its own depth, which is |s| samples.
+ *   radius      c = min(|s|, 16);  rr = max(c * c, 0.25f): the squared radius; a sample always covers itself.
+ *   gather      for dy = -16 .. 16 ascending, for dx = -16 .. 16 ascending, q = p + (dx, dy) inside the frame:
+ *                 rr_t = s_q > s_p ? min(rr_q, rr_p) : rr_q      (q behind p: a blurred background does not bleed over a
+ *                                                                 sharper foreground)
+ *                 if (float)(dx * dx + dy * dy) <= rr_t:          (a tap that fails is skipped, not added as a zero)
+ *                     w = 1.0f / rr_t;  W = W + w;  S[ch] = S[ch] + w * F[q][ch]        (the product rounded, then the sum)
+ *   F'[p][ch] = S[ch] / W
+ *
+ * Background samples take part: a sky blurs.  Where c < 0.5 for p and for every q in front of it within 16 samples,
+ * F'[p] == F[p] bit for bit.  One layer only: what a real lens sees round an occluder is not in F; no circle wider than 16
+ * samples; a blurred foreground lets 4 / (4 + pi) of a sharp sample behind it through (that sample's own tap weighs 4, the
+ * foreground's disc over it pi).
+ *
+ * Where the frame draws an overlay it goes on F' and Z as ever: its lines stay sharp.  The bytes are the finalise of the
+ * result, as for the ambient obscurance: what mr_host_accum gives for that one frame with weight 1 and scale 1.
+ * mr_read_frame_f32 then returns the final float frame (the accumulation adds it); mr_read_z is unchanged.
+ *
+ * mr_scene_set_depth_of_field copies the description (NULL: off, the default); every frame enqueued afterwards, by any
+ * entry point, uses the copy of its moment.  Such a frame keeps its z-buffer and float frame (MR_FRAME_KEEP_BUFFERS |
+ * MR_FRAME_KEEP_FLOAT are implied), runs k_dof behind the tile kernel and behind k_ao, and owns a second float frame.  A
+ * scene without it enqueues what it always did.  MR_E_INVALID for focus or kf that are not finite and > 0 as float32, an
+ * entry of depth_map that is not finite, or perspective other than 0 / 1; and, from the rendering entry points, for a
+ * partial frame (row band, stripes) of such a scene, before any device work: the taps cross the bands.
+ * MR_E_UNSUPPORTED from a library linked without dof.hip or accum.hip. */
+typedef struct mr_dof_desc {
+    double depth_map[4];       /* m0 .. m3, as in mr_ao_desc */
+    double kf;                 /* circle of confusion in samples per unit of (1 - focus / e), or per unit of depth: float32 */
+    double focus;              /* eye depth of the plane in focus, in world units; used as float32 */
+    int32_t perspective;       /* 1: a perspective camera; 0: an orthographic one */
+    int32_t pad;
+} mr_dof_desc;
+int mr_scene_set_depth_of_field(mr_scene *scene, const mr_dof_desc *dof);
+
+/* Host arithmetic, no device needed: the definition above for one frame -- z is (height, width) float64, frame and
+ * out_frame (height, width, 3) float32, two different arrays (neighbours' colours are read) -- bit for bit what k_dof
+ * writes.  MR_E_INVALID for what mr_scene_set_depth_of_field refuses, a NULL array, out_frame == frame, or a height or
+ * width outside 1 .. 32767. */
+int mr_host_dof(const double *z, const float *frame, int32_t height, int32_t width, const mr_dof_desc *dof, float *out_frame);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued k_dof (every enqueue, also one rendered again after an
+ * overflow), out[1], out[2] = the sample rows and columns of the last of them (0 before the first).  Does not wait. */
+int mr_debug_dof(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds of the last k_dof (HIP events on its frame's stream).  Waits for that kernel.
+ * MR_E_INVALID before the first such frame. */
+#define MR_N_DOF_TIMES 1
+int mr_debug_dof_times(mr_scene *scene, float *out_ms);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

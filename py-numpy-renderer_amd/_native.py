@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -98,6 +98,20 @@ def fill_ao_desc(ao, depth_map, k, perspective):
         d.depth_map[i] = float(depth_map[i])
     d.k, d.perspective = float(k), int(perspective)
     d.radius, d.strength, d.depth_range, d.bias = float(ao.radius), float(ao.strength), float(ao.depth_range), float(ao.bias)
+    return d
+
+
+class DofDesc(C.Structure):
+    _fields_ = [("depth_map", C.c_double * 4), ("kf", C.c_double), ("focus", C.c_double), ("perspective", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+def fill_dof_desc(depth_map, kf, perspective, focus):
+    """``mr_dof_desc`` of a view's constants (``_pack.dof_constants``)."""
+    d = DofDesc()
+    for i in range(4):
+        d.depth_map[i] = float(depth_map[i])
+    d.kf, d.focus, d.perspective = float(kf), float(focus), int(perspective)
     return d
 
 
@@ -192,6 +206,10 @@ _PROTOTYPES = {
     "mr_host_ao": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(AoDesc), C.c_void_p]),
     "mr_debug_ao": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_ao_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_scene_set_depth_of_field": (C.c_int, [C.c_void_p, C.POINTER(DofDesc)]),
+    "mr_host_dof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DofDesc), C.c_void_p]),
+    "mr_debug_dof": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_dof_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -286,6 +304,20 @@ def host_ao(z, frame, desc):
     out = np.empty_like(frame)
     _check_accum(load_library().mr_host_ao(z.ctypes.data, frame.ctypes.data, z.shape[0], z.shape[1], C.byref(desc), out.ctypes.data),
                  "mr_host_ao")
+    return out
+
+
+def host_dof(z, frame, desc):
+    """``mr_host_dof``: the depth of field's definition on the host, no device.  *z* is ``(Hs, Ws)`` float64, *frame*
+    ``(Hs, Ws, 3)`` float32, *desc* a ``DofDesc``; returns the blurred frame, float32 ``(Hs, Ws, 3)``.  ``ValueError``
+    with the library's text for what it refuses."""
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if z.ndim != 2 or frame.shape != z.shape + (3,):
+        raise ValueError(f"z must be (H, W) and frame (H, W, 3), got {z.shape} and {frame.shape}")
+    out = np.empty_like(frame)
+    _check_accum(load_library().mr_host_dof(z.ctypes.data, frame.ctypes.data, z.shape[0], z.shape[1], C.byref(desc), out.ctypes.data),
+                 "mr_host_dof")
     return out
 
 
@@ -616,6 +648,33 @@ class DeviceRenderer:
             self._ao_key = key
         self._ao_packed = packed
 
+    @staticmethod
+    def _dof_values(scene):
+        """The scene's ``DepthOfField`` by value (``None`` without one), for ``_frame_key``."""
+        dof = getattr(scene, "depth_of_field", None)
+        return None if dof is None else (dof.focus, dof.lens_radius)
+
+    def sync_depth_of_field(self, scene):
+        """``mr_scene_set_depth_of_field`` for the frames enqueued from now on, whenever the description -- the scene's
+        ``DepthOfField`` and the view's depth map, focus and ``kf`` -- is not the one last handed over.  A scene that
+        never had one makes no call."""
+        dof = getattr(scene, "depth_of_field", None)
+        if dof is None:
+            if getattr(self, "_dof_key", None) is not None:
+                _check_accum(self.lib.mr_scene_set_depth_of_field(self.handle, None), "mr_scene_set_depth_of_field")
+                self._dof_key = self._dof_packed = None
+            return
+        # (called behind packed_frame: while its entry lives, camera, resolution and supersample are the same)
+        packed = (getattr(self, "_pack_serial", 0), self._dof_values(scene))
+        if getattr(self, "_dof_packed", None) == packed:
+            return
+        desc = fill_dof_desc(*dof_constants(scene))
+        key = bytes(desc)
+        if getattr(self, "_dof_key", None) != key:
+            _check_accum(self.lib.mr_scene_set_depth_of_field(self.handle, C.byref(desc)), "mr_scene_set_depth_of_field")
+            self._dof_key = key
+        self._dof_packed = packed
+
     # -- frames ---------------------------------------------------------------------------
     @staticmethod
     def _frame_key(scene, shadows):
@@ -635,7 +694,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -715,6 +774,9 @@ class DeviceRenderer:
         if getattr(scene, "ambient_occlusion", None) is not None and partial:
             raise ValueError("ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands")
         self.sync_ambient_occlusion(scene)
+        if getattr(scene, "depth_of_field", None) is not None and partial:
+            raise ValueError("depth of field takes whole frames (no row band, no stripes): its taps cross the bands")
+        self.sync_depth_of_field(scene)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -792,6 +854,19 @@ class DeviceRenderer:
         _check(self.lib.mr_debug_ao_times(self.handle, buf), "mr_debug_ao_times")
         return float(buf[0])
 
+    # -- depth of field (Scene.depth_of_field) ---------------------------------------------------
+    def dof_debug(self):
+        """``mr_debug_dof``: (frames that enqueued ``k_dof``, the last one's sample rows, its sample columns)."""
+        out = (C.c_int32 * 3)()
+        _check(self.lib.mr_debug_dof(self.handle, out), "mr_debug_dof")
+        return tuple(int(x) for x in out)
+
+    def dof_time(self):
+        """Device milliseconds of the last ``k_dof`` (``mr_debug_dof_times``)."""
+        buf = (C.c_float * 1)()
+        _check(self.lib.mr_debug_dof_times(self.handle, buf), "mr_debug_dof_times")
+        return float(buf[0])
+
     ASYNC_LANES = 4
 
     def render_async(self, scene, lane, shadows=True, overlay=False):
@@ -835,6 +910,7 @@ class DeviceRenderer:
             raise ValueError("striped frames are not available with more than one light")
         self.sync_lights(pf)
         self.sync_ambient_occlusion(scene)
+        self.sync_depth_of_field(scene)
         if overlay:
             self.sync_overlay(scene)
         desc = fill_frame_desc(pf, row_band, False, light_timing, counters=counters, stripe=stripe, no_timing=no_timing,

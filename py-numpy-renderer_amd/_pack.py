@@ -221,6 +221,42 @@ def ao_constants(scene, camera=None):
     return depth_map(scene, camera), k, int(P[2, 3] != 0)
 
 
+def check_depth_of_field(focus, lens_radius):
+    """The parameters of a ``DepthOfField`` as ``(focus, lens_radius)``: Python floats that are finite and > 0 as
+    float32; ``focus`` may be ``None`` (the eye depth of the camera's ``center``, per view)."""
+    def number(value, what):
+        if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError(f"depth of field: {what} must be a real number, got {value!r}")
+        with np.errstate(over="ignore"):
+            as_f32 = np.float32(value)
+        if not np.isfinite(as_f32) or as_f32 <= 0:
+            raise ValueError(f"depth of field: {what} must be finite and > 0 as float32, got {value!r}")
+        return float(value)
+    return (None if focus is None else number(focus, "focus")), number(lens_radius, "lens_radius")
+
+
+def dof_constants(scene, camera=None):
+    """What ``mr_dof_desc`` carries for a frame of *scene* (``depth_of_field`` set) through *camera* (default: the
+    scene's): ``(depth_map, kf, perspective, focus)`` with ``focus`` the ``DepthOfField``'s own or, for ``None``, the eye
+    depth of the camera's ``center``, ``|center - position|``, and ``kf = float32(lens_radius * 0.5 * Hs * |P[1,1]| /
+    focus)`` evaluated in float64, Hs the sample grid's height."""
+    camera = scene.camera if camera is None else camera
+    dof = scene.depth_of_field
+    focus = dof.focus
+    if focus is None:
+        focus = float(np.linalg.norm(np.asarray(camera.center, dtype=np.float64).ravel()[:3]
+                                     - np.asarray(camera.position, dtype=np.float64).ravel()[:3]))
+    P = np.asarray(camera.projection, dtype=np.float64)
+    s = check_supersample(getattr(scene, "supersample", 1))
+    rows = s * int(scene.resolution[0])
+    with np.errstate(all="ignore"):
+        kf = float(np.float32(np.float64(dof.lens_radius) * 0.5 * rows * abs(float(P[1, 1])) / np.float64(focus)))
+    if not (np.isfinite(np.float32(focus)) and np.float32(focus) > 0 and np.isfinite(kf) and kf > 0):
+        raise ValueError(f"depth of field: focus {focus!r} and lens_radius {dof.lens_radius!r} give no finite circle of "
+                         f"confusion > 0 for this view (kf = {kf!r})")
+    return depth_map(scene, camera), kf, int(P[2, 3] != 0), float(focus)
+
+
 def sample_grid(scene):
     """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame."""
     cam = scene.camera

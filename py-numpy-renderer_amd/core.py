@@ -140,6 +140,28 @@ class AmbientOcclusion:
                 f"bias={self.bias!r})")
 
 
+class DepthOfField:
+    """What ``Scene.depth_of_field`` holds: a thin lens (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section
+    6j the reasons).  ``focus`` is the eye depth of the plane in focus, in world units; ``None`` (the default) means the eye
+    depth of the camera's ``center``, ``|center - position|``, taken per view.  ``lens_radius`` is the lens' radius in
+    world units: a point at eye depth e spreads over a disc of ``lens_radius * |e - focus| / focus`` world units at its own
+    depth, at most 16 samples on the frame.  As float32 both must be finite and > 0 (``ValueError``; ``TypeError`` for what
+    is no real number).  A ``DepthOfField`` is never modified: assign a new one to change it."""
+
+    __slots__ = ("focus", "lens_radius")
+
+    def __init__(self, focus=None, lens_radius=0.02):
+        from ._pack import check_depth_of_field
+        for name, value in zip(self.__slots__, check_depth_of_field(focus, lens_radius)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a DepthOfField is read-only: assign a new one to Scene.depth_of_field")
+
+    def __repr__(self):
+        return f"DepthOfField(focus={self.focus!r}, lens_radius={self.lens_radius!r})"
+
+
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
     (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
@@ -791,6 +813,11 @@ class Scene:
       the debug frustum, which is not darkened.  The whole colour is darkened, not the ambient term alone; with several
       lights it is applied once; a ``depth_test=False`` model is shaded by what the z-buffer holds behind it.  Split
       frames (``row_band``, ``multigpu``) refuse it.  With ``None`` a scene enqueues exactly what it did without it.
+    * ``depth_of_field`` (an addition; ``None`` by default, or a ``DepthOfField``): a thin lens' blur gathered on the
+      device from the float frame and the z-buffer of every frame of the scene, in one pass -- after the lights' sum and
+      the obscurance, before the debug frustum, whose lines stay sharp.  One layer (what a lens sees round an occluder is
+      not in the frame), no circle wider than 16 samples; the sky blurs too.  Split frames (``row_band``, ``multigpu``)
+      refuse it.  With ``None`` a scene enqueues exactly what it did without it.
     """
 
     camera = Bound()
@@ -835,6 +862,17 @@ class Scene:
         if value is not None and not isinstance(value, AmbientOcclusion):
             raise TypeError(f"ambient_occlusion must be None or an AmbientOcclusion, got {type(value).__name__}")
         self.__dict__["_ambient_occlusion"] = value
+
+    @property
+    def depth_of_field(self):
+        """``None`` (off, the default) or the scene's ``DepthOfField`` (see the class docstring)."""
+        return self.__dict__.get("_depth_of_field")
+
+    @depth_of_field.setter
+    def depth_of_field(self, value):
+        if value is not None and not isinstance(value, DepthOfField):
+            raise TypeError(f"depth_of_field must be None or a DepthOfField, got {type(value).__name__}")
+        self.__dict__["_depth_of_field"] = value
 
     @property
     def last_stats(self):

@@ -15,6 +15,7 @@ struct FrameSlot {
     DevBuf d_vout, d_vclip, d_tris, d_clips, d_status, d_count_list, d_quads, d_sil, d_counters;
     DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_work, d_tile_stats, d_hist, d_split;
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
+    DevBuf d_frame_b;                             // the float frame k_dof writes; then swapped with d_frame, which stays THE float frame
     DevBuf d_stencil_x[mr::MAX_LIGHTS - 1];       // stencil taps of lights 1.. of a frame with several lights
     static_assert(mr::MAX_LIGHTS == MR_MAX_LIGHTS, "the ABI's light count is the kernels'");
     int last_n_lights = 1;                        // lights of the last frame
@@ -38,7 +39,7 @@ struct FrameSlot {
     bool last_full = false, last_split = false;   // the kernels the last frame launched (mr_debug_frame_path)
     bool overlay_deferred = false;           // the last enqueue_frame left the overlay to finish_overlay
     int last_ss_mode = 0;                    // FrameConst::ss_mode of the last frame (finish_overlay resolves after the overlay)
-    bool last_ao = false;                    // the last frame ran k_ao: its bytes are the full resolve of the float frame
+    bool last_post = false;                  // the last frame ran k_ao or k_dof: its bytes are the full resolve of the float frame
     bool have_frame = false, stats_reduced = false;
     bool last_copied = false;                // the last frame was followed by a timed device-to-host copy (mr_render, mr_render_async)
 
@@ -46,7 +47,7 @@ struct FrameSlot {
     void release()
     {
         for (DevBuf *b : { &d_vout, &d_vclip, &d_count_list, &d_tris, &d_clips, &d_status, &d_quads, &d_sil, &d_counters,
-                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_out })
+                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_out })
             b->release();
         for (DevBuf &b : d_items) b.release();
         for (DevBuf &b : d_stencil_x) b.release();
@@ -159,6 +160,8 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
     }
     if (sc->ao.on && is_partial(fr))
         return fail(MR_E_INVALID, "ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands");
+    if (sc->dof.on && is_partial(fr))
+        return fail(MR_E_INVALID, "depth of field takes whole frames (no row band, no stripes): its taps cross the bands");
     if (sc->n_extra_lights > 0) {
         if (fr->flags & MR_FRAME_FACE_STATUS)
             return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
@@ -325,10 +328,14 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   edge_spread  EDGE_DENSE, or lanes per edge as a shift;  face_blocks, count_blocks: workgroups of k_setup's face half, of k_bin_work's counting
 //   order_bytes  d_hist: the tile order in front, the tiles' class bytes behind
 //   ao           the scene has ambient obscurance on: k_ao behind the tile kernel, with ao_params, the scene's description now
+//   dof          the scene has depth of field on: k_dof behind them, with dof_params, likewise
+//   post()       a pass rewrites the float frame behind the tile kernel: the bytes are the full resolve of the result
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof;
     mr::AoParams ao_params;
+    mr::DofParams dof_params;
+    bool post() const { return ao || dof; }
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -352,7 +359,7 @@ int plan_overlay(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr:
         return fail(MR_E_INVALID, "overlay on a row band: the bands of the split must be equal");
     if (p.overlay && (sc->ov_width != fc.width || sc->ov_height != fc.height))
         return fail(MR_E_INVALID, "overlay lists were built for a frame of another size");
-    return p.overlay ? sync_slot_overlay(sc, fs->ov, fs->stream, p.partial || (fc.ss_mode != 0 && !p.ao)) : MR_OK;
+    return p.overlay ? sync_slot_overlay(sc, fs->ov, fs->stream, p.partial || (fc.ss_mode != 0 && !p.post())) : MR_OK;
 }
 
 // Decides what kind of frame this is: fills the plan and the frame's constants.
@@ -369,6 +376,9 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     // a caller who asked for them)
     p.ao = sc->ao.on;
     if (p.ao) { p.ao_params = sc->ao.params; fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT; }
+    // (and so does the depth of field, into a second float frame)
+    p.dof = sc->dof.on;
+    if (p.dof) { p.dof_params = sc->dof.params; fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT; }
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
     p.taps_asked = (fc.flags & (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT)) != 0;
@@ -439,7 +449,8 @@ int grow_slot(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Frame
         { fs->d_status, nF }, { fs->d_quads, (size_t)fs->quad_cap * sizeof(QuadRec) }, { fs->d_sil, (size_t)fs->quad_cap * 2 * sizeof(int32_t) },
         { fs->d_bin_count, (size_t)(BIN_CLASSES * p.n_tiles + 1) * 4 }, { fs->d_work, (size_t)fs->work_cap * sizeof(uint2) },
         { fs->d_tile_stats, nT * TILE_REC * 4 }, { fs->d_z, kept * sizeof(double) }, { fs->d_winner, kept * sizeof(int32_t) },
-        { fs->d_stencil, kept * sizeof(int32_t) }, { fs->d_frame, kept_f * 3 * sizeof(float) } };
+        { fs->d_stencil, kept * sizeof(int32_t) }, { fs->d_frame, kept_f * 3 * sizeof(float) },
+        { fs->d_frame_b, p.dof ? kept_f * 3 * sizeof(float) : 0 } };
     for (const auto &b : sized) HIP_TRY(b.buf.ensure(b.bytes));
     for (int k = 1; k < p.n_lights; ++k) HIP_TRY(fs->d_stencil_x[k - 1].ensure(kept * sizeof(int32_t)));
     if (int rc = ensure_cleared(fs->d_counters, 2 * sizeof(Counters) + sizeof(Sticky), fs->stream)) return rc;
@@ -587,17 +598,17 @@ int launch_tile(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fra
     return MR_OK;
 }
 
-// The bytes of a frame that ran k_ao: the tree's finalise of the whole float frame, after the overlay (the accumulation's
-// resolve with scale 1: block mean, min(., 1), the gamma step, rows flipped).
-void launch_ao_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, int ss_mode, uint8_t *d_out)
+// The bytes of a frame that ran k_ao or k_dof: the tree's finalise of the whole float frame, after the overlay (the
+// accumulation's resolve with scale 1: block mean, min(., 1), the gamma step, rows flipped).
+void launch_post_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, int ss_mode, uint8_t *d_out)
 {
     mr_accum::launch_resolve(fs->stream, fs->d_frame.as<float>(), fr.width, fr.height, ss_mode & mr::SS_SHIFT_MASK, 1.0f,
                              sc->d_gamma.as<float>(), d_out);
 }
 
-// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the overlay (exported by a device that
-// owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638) and the resolve of
-// a supersampled or darkened frame
+// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the depth of field, the overlay (exported
+// by a device that owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638)
+// and the resolve of a supersampled, darkened or blurred frame
 int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
 {
     using namespace mr;
@@ -607,6 +618,13 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
                            fs->d_clips.as<TriClip>(), fs->d_z.as<double>(), fs->d_stencil.as<int32_t>(), fs->d_status.as<uint8_t>());
     if (p.ao && p.n_tiles > 0)
         if (int rc = launch_ao(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, p.ao_params)) return rc;
+    if (p.dof && p.n_tiles > 0) {
+        if (int rc = launch_dof(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fs->d_frame_b.as<float>(), fc.width, fc.height, p.dof_params))
+            return rc;
+        // (the blurred frame is the slot's float frame from here on: the overlay, the resolve, mr_read_frame_f32 and
+        // k_accum_add read d_frame; work enqueued on the stream before this point keeps the pointers it was given)
+        std::swap(fs->d_frame, fs->d_frame_b);
+    }
     if (p.overlay && p.partial) {
         const int world = fr->stripe_count > 1 ? fr->stripe_count : fr->height / (fr->row_end - fr->row_begin);
         const int rank = fr->stripe_count > 1 ? fr->stripe_index : fr->row_begin / (fr->row_end - fr->row_begin);
@@ -615,10 +633,10 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
         hipLaunchKernelGGL(k_overlay_export, dim3(blocks_for(n_slots, 256)), dim3(256), 0, stream, fs->ov.list<int32_t>(5), n_slots,
                            fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, world, fr->stripe_count > 1 ? 1 : 0, rank, state);
     } else if (p.overlay) {
-        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.ss_mode || p.ao ? nullptr : d_out, fc.width, fc.height, fc.system, stream);
+        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.ss_mode || p.post() ? nullptr : d_out, fc.width, fc.height, fc.system, stream);
     }
     if (p.deferred) return MR_OK;                                    // (finish_overlay resolves)
-    if (p.ao) launch_ao_resolve(sc, fs, *fr, fc.ss_mode, d_out);
+    if (p.post()) launch_post_resolve(sc, fs, *fr, fc.ss_mode, d_out);
     else launch_resolve(sc, fs->ov, fs->d_frame.as<float>(), *fr, fc.ss_mode, p.overlay, d_out, stream);
     return MR_OK;
 }
@@ -631,7 +649,7 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
     fs->last_full = p.full; fs->last_split = p.split;
     fs->overlay_deferred = p.deferred;
     fs->last_ss_mode = fc.ss_mode;
-    fs->last_ao = p.ao;
+    fs->last_post = p.post();
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = p.n_tiles;
     fs->last_n_lights = p.n_lights;
@@ -686,10 +704,10 @@ int finish_overlay(mr_scene *sc, FrameSlot *fs, uint8_t *d_out)
     const bool draw = sc->ov_points != 0;
     if (draw) {
         if (sc->ov_width != fr.width || sc->ov_height != fr.height) return fail(MR_E_INVALID, "overlay lists were built for a frame of another size");
-        if (int rc = sync_slot_overlay(sc, fs->ov, fs->stream, ss_mode != 0 && !fs->last_ao)) return rc;
-        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), ss_mode || fs->last_ao ? nullptr : d_out, fr.width, fr.height, fr.system, fs->stream);
+        if (int rc = sync_slot_overlay(sc, fs->ov, fs->stream, ss_mode != 0 && !fs->last_post)) return rc;
+        launch_overlay(sc, fs->ov, fs->d_z.as<double>(), fs->d_frame.as<float>(), ss_mode || fs->last_post ? nullptr : d_out, fr.width, fr.height, fr.system, fs->stream);
     }
-    if (fs->last_ao) launch_ao_resolve(sc, fs, fr, ss_mode, d_out);
+    if (fs->last_post) launch_post_resolve(sc, fs, fr, ss_mode, d_out);
     else launch_resolve(sc, fs->ov, fs->d_frame.as<float>(), fr, ss_mode, draw, d_out, fs->stream);
     HIP_TRY(hipGetLastError());
     return MR_OK;

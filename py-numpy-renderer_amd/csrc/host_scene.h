@@ -199,6 +199,15 @@ struct mr_scene {
         bool ev_ok = false, marked = false;
     } ao;
 
+    // ---- depth of field (host_dof.h): likewise
+    struct Dof {
+        bool on = false;
+        mr::DofParams params = {};
+        int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued k_dof; the last one's sample grid
+        hipEvent_t ev[2] = {};                // marks round the last k_dof
+        bool ev_ok = false, marked = false;
+    } dof;
+
     // ---- frame slots, one per stream that has rendered this scene
     std::vector<std::unique_ptr<FrameSlot>> slots;
     FrameSlot *last = nullptr;               // slot of the most recently enqueued frame

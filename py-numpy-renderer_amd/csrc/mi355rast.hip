@@ -1,6 +1,6 @@
 // mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file, from
-// accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), and
-// from ao.hip, which holds the ambient obscurance's kernel in another;
+// accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), from
+// ao.hip, which holds the ambient obscurance's kernel in another, and from dof.hip, which holds the depth of field's;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -12,6 +12,7 @@
 //   host_autonormals.h  rebuilt vertex normals: the per-normal face lists (plain C++, no HIP)
 //   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
 //   host_ao.h           ambient obscurance from the z-buffer: the description, k_ao's launch, the host mirror
+//   host_dof.h          depth of field from the z-buffer: the description, k_dof's launch, the host mirror
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //
@@ -30,7 +31,8 @@
 //                   touched pixels' state exported from a part of one;  k_resolve_*  what a supersampled frame's
 //                   overlay or MR_RESOLVE_PATH=separate leave to resolve;  D2H of the uint8 rows for mr_render;
 //                   k_accum_add behind a sub-frame of mr_accum_add, k_accum_resolve for mr_accum_resolve;
-//                   k_ao behind k_tile in a scene with mr_scene_set_ambient_occlusion, k_accum_resolve for its bytes)
+//                   k_ao behind k_tile in a scene with mr_scene_set_ambient_occlusion, k_dof behind them in one with
+//                   mr_scene_set_depth_of_field, k_accum_resolve for the bytes of either)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -59,6 +61,7 @@
 #include "kernels_overlay.h"
 #include "kernels_pose.h"
 #include "ao_def.h"
+#include "dof_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -69,6 +72,7 @@
 #include "host_pose.h"
 #include "host_overlay_dev.h"
 #include "host_ao.h"
+#include "host_dof.h"
 #include "host_frame.h"
 #include "host_accum.h"
 
@@ -177,6 +181,7 @@ void mr_scene_destroy(mr_scene *sc)
     sc->sil.release();
     accum_release(sc->accum);
     ao_release(sc->ao);
+    dof_release(sc->dof);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
@@ -591,6 +596,39 @@ int mr_debug_ao_times(mr_scene *sc, float *out_ms)
     if (!sc->ao.marked) return fail(MR_E_INVALID, "no frame with ambient occlusion yet");
     HIP_TRY(hipEventSynchronize(sc->ao.ev[1]));      // (no entry point waits for the kernel itself)
     HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->ao.ev[0], sc->ao.ev[1]));
+    return MR_OK;
+}
+
+int mr_scene_set_depth_of_field(mr_scene *sc, const mr_dof_desc *dof)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (!dof) { sc->dof.on = false; return MR_OK; }      // (frames already enqueued took their copy)
+    mr::DofParams p;
+    if (int rc = dof_params(dof, p)) return rc;
+    if (int rc = dof_linked()) return rc;
+    sc->dof.params = p;
+    sc->dof.on = true;
+    return MR_OK;
+}
+
+int mr_host_dof(const double *z, const float *frame, int32_t height, int32_t width, const mr_dof_desc *dof, float *out_frame)
+{
+    return host_dof(z, frame, height, width, dof, out_frame);
+}
+
+int mr_debug_dof(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    out[0] = sc->dof.frames; out[1] = sc->dof.rows; out[2] = sc->dof.cols;
+    return MR_OK;
+}
+
+int mr_debug_dof_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->dof.marked) return fail(MR_E_INVALID, "no frame with depth of field yet");
+    HIP_TRY(hipEventSynchronize(sc->dof.ev[1]));      // (no entry point waits for the kernel itself)
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->dof.ev[0], sc->dof.ev[1]));
     return MR_OK;
 }
 
