@@ -753,6 +753,25 @@ int mr_debug_dof(mr_scene *scene, int32_t *out);
 #define MR_N_DOF_TIMES 1
 int mr_debug_dof_times(mr_scene *scene, float *out_ms);
 
+/* Diagnostics: the post-frame kernels on buffers the caller supplies -- no frame is rendered.  frames is (n, height,
+ * width, 3) float32 and z (height, width) float64, both on the sample grid, rows bottom-up.  Each frame is uploaded,
+ * darkened in place by k_ao where ao is not NULL (workgroup shape ao_shape: 0 = 64 x 64 samples, 1 = 32 x 32, 2 = 64 x
+ * 16), blurred by k_dof into a second buffer where dof is not NULL (dof_shape: 0 = 32 x 32 samples and 1 024 threads, 1 =
+ * 32 x 32 and 256, 2 = 16 x 16), and, where weights (n) is not NULL, added by k_accum_add into a sum that was filled with
+ * 0xFF bytes first.  out_f32, (height, width, 3), receives the sum, or without weights the one processed frame; out_rgb,
+ * ((height >> shift), (width >> shift), 3) or NULL, k_accum_resolve of it with the shift and the scale.  The shapes come
+ * from the arguments, never from MR_AO_TILE / MR_DOF_TILE.  The scene lends its stream, its step table and the error
+ * text: its frame slots, its last frame and what mr_debug_ao, mr_debug_dof and mr_debug_accum report stay as they were.
+ * The device buffers are the entry's own and released before it returns; it waits for the device.
+ * MR_E_INVALID, before any device call: a NULL scene, frames, z or out_f32; n < 1; height or width outside 1 .. 32767;
+ * n > 1 without weights; a shape outside 0 .. 2 for a description that is given; a shift outside 0 .. 2 or one that does
+ * not divide height and width; a weight or a scale that is not finite and > 0 as float32; whatever
+ * mr_scene_set_ambient_occlusion or mr_scene_set_depth_of_field refuse.  MR_E_UNSUPPORTED from a library linked without
+ * the translation unit of a kernel that is asked for. */
+int mr_debug_post(mr_scene *scene, const float *frames, const double *z, int32_t n, int32_t height, int32_t width,
+                  const mr_ao_desc *ao, int32_t ao_shape, const mr_dof_desc *dof, int32_t dof_shape, const double *weights,
+                  int32_t shift, double scale, float *out_f32, uint8_t *out_rgb);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

@@ -210,6 +210,8 @@ _PROTOTYPES = {
     "mr_host_dof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DofDesc), C.c_void_p]),
     "mr_debug_dof": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_dof_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AoDesc), C.c_int32,
+                                C.POINTER(DofDesc), C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -319,6 +321,34 @@ def host_dof(z, frame, desc):
     _check_accum(load_library().mr_host_dof(z.ctypes.data, frame.ctypes.data, z.shape[0], z.shape[1], C.byref(desc), out.ctypes.data),
                  "mr_host_dof")
     return out
+
+
+def debug_post(handle, frames, z, ao=None, ao_shape=0, dof=None, dof_shape=0, weights=None, shift=0, scale=1.0, want_rgb=True):
+    """``mr_debug_post``: k_ao, k_dof, k_accum_add and k_accum_resolve on the caller's arrays, no frame rendered.  *handle*
+    is a scene handle (``mr_scene_create``, or a ``DeviceRenderer``'s), *frames* ``(n, Hs, Ws, 3)`` float32 (one ``(Hs, Ws,
+    3)`` frame will do), *z* ``(Hs, Ws)`` float64, *ao* an ``AoDesc`` or None, *dof* a ``DofDesc`` or None, the shapes 0 .. 2,
+    *weights* ``(n,)`` or None.  Returns ``(float32 (Hs, Ws, 3), uint8 (Hs >> shift, Ws >> shift, 3) or None)``.
+    ``ValueError`` with the library's text for what it refuses."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    if frames.ndim == 3:
+        frames = frames[None]
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    if frames.ndim != 4 or frames.shape[3] != 3 or z.shape != frames.shape[1:3]:
+        raise ValueError(f"frames must be (n, H, W, 3) and z (H, W), got {frames.shape} and {z.shape}")
+    n, h, w, _ = frames.shape
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        if len(weights) != n:
+            raise ValueError(f"{n} frames and {len(weights)} weights")
+    shift = int(shift)
+    out = np.empty((h, w, 3), dtype=np.float32)
+    rgb = np.empty((h >> shift, w >> shift, 3), dtype=np.uint8) if want_rgb and 0 <= shift <= 2 else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    ref = lambda d: None if d is None else C.byref(d)
+    _check_accum(load_library().mr_debug_post(handle, frames.ctypes.data, z.ctypes.data, n, h, w, ref(ao), int(ao_shape), ref(dof),
+                                              int(dof_shape), ptr(weights), shift, float(scale), out.ctypes.data, ptr(rgb)),
+                 "mr_debug_post")
+    return out, rgb
 
 
 def stripe_out_rows(height, stripe_count):

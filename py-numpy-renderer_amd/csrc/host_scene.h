@@ -348,16 +348,22 @@ std::vector<mr::ClusterRec> build_clusters(const mr_scene *sc)
     return out;
 }
 
+// the thresholds on the device, uploaded once per scene (commit; mr_debug_post on a scene that never committed)
+int ensure_gamma(mr_scene *sc)
+{
+    if (sc->d_gamma.p) return MR_OK;
+    const std::vector<float> lut = gamma_thresholds();
+    HIP_TRY(sc->d_gamma.ensure(lut.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(sc->d_gamma.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+    return MR_OK;
+}
+
 int commit(mr_scene *sc)
 {
     if (!sc->dirty) return MR_OK;
     HIP_TRY(hipDeviceSynchronize());          // no frame may still be reading the old arrays
     sc->sil.drop();                           // the silhouette belongs to the geometry that is about to be replaced
-    if (!sc->d_gamma.p) {
-        const std::vector<float> lut = gamma_thresholds();
-        HIP_TRY(sc->d_gamma.ensure(lut.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(sc->d_gamma.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+    if (int rc = ensure_gamma(sc)) return rc;
     build_edge_table(sc);
     for (mr::Material &m : sc->materials) {
         const mr::Texture none = { nullptr, 0, 0 };

@@ -15,6 +15,7 @@
 //   host_dof.h          depth of field from the z-buffer: the description, k_dof's launch, the host mirror
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
+//   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
 //
 // One process drives one GPU.  A scene keeps its static arrays (vertices, attributes, index arrays, textures, the
 // unique-edge table with the incident faces' normals, per-face and per-cluster records) resident in HBM; a frame is
@@ -75,6 +76,7 @@
 #include "host_dof.h"
 #include "host_frame.h"
 #include "host_accum.h"
+#include "host_post.h"
 
 // ============================================================================ C ABI
 
@@ -630,6 +632,13 @@ int mr_debug_dof_times(mr_scene *sc, float *out_ms)
     HIP_TRY(hipEventSynchronize(sc->dof.ev[1]));      // (no entry point waits for the kernel itself)
     HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->dof.ev[0], sc->dof.ev[1]));
     return MR_OK;
+}
+
+int mr_debug_post(mr_scene *sc, const float *frames, const double *z, int32_t n, int32_t height, int32_t width, const mr_ao_desc *ao,
+                  int32_t ao_shape, const mr_dof_desc *dof, int32_t dof_shape, const double *weights, int32_t shift, double scale,
+                  float *out_f32, uint8_t *out_rgb)
+{
+    return debug_post(sc, frames, z, n, height, width, ao, ao_shape, dof, dof_shape, weights, shift, scale, out_f32, out_rgb);
 }
 
 int64_t mr_overlay_state_bytes(mr_scene *sc)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import ao_ref
+import post_fields
 import scenes
 from conftest import load_golden
 
@@ -142,16 +143,8 @@ def test_mirror_is_the_reference_on_the_captures(native, capture_cases):
 def test_mirror_is_the_reference_on_synthetic_depth_fields(native, shape, seed):
     """Smooth hills with steps and holes, under a perspective and an orthographic footprint; the map is a real Moebius
     map, so the float64 part of the definition is exercised too."""
-    rng = np.random.default_rng(seed)
-    h, w = shape
-    ys, xs = np.mgrid[0:h, 0:w]
-    depth = 2.0 + 0.4 * np.sin(xs / 3.1) * np.cos(ys / 2.3) + 0.3 * (rng.random(shape) < 0.2) + 0.05 * rng.random(shape)
-    m = (-0.05, 0.001, -1.0, -0.0106)
-    z = (m[3] * depth - m[1]) / (m[0] - m[2] * depth)                # the map's inverse: Z of these depths
-    z[rng.random(shape) < 0.1] = np.inf
-    z[rng.random(shape) < 0.02] = -np.inf
-    z[rng.random(shape) < 0.02] = np.nan
-    frame = rng.random(shape + (3,), dtype=np.float32)
+    m = post_fields.MOEBIUS
+    z, frame = post_fields.ao_hills(shape, seed, m)                  # (the field lives in post_fields.py, for the kernel's tests too)
     for k, perspective, kw in ((9.0, 1, {}), (70.0, 1, dict(radius=0.5, strength=3.0)), (5.5, 0, dict(radius=0.2, bias=0.0)),
                                (0.25, 1, dict(strength=8.0, depth_range=10.0))):
         want = ao_ref.apply(z, frame, m, k, perspective, **ao_ref.params(**kw))

@@ -6,6 +6,10 @@ the z-buffer Z and the float frame F the same scene hands out through its taps W
 the scene with obscurance must match it bit for bit, and the frame's bytes must be ``mr_host_accum([F'], [1], scale=1)``
 byte for byte.  Beside it: identities with ``render()``, the overlay, frames in flight, the accumulation, overflow."""
 import ctypes as C
+import hashlib
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +19,8 @@ import scenes
 from multilight_ref import extra_lights
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SQUEEZED = dict(small_pairs=4, big_pairs=2, quads=3, work=16)      # the capacities of test_accumulate_gpu.py's overflow test
 NO_PAIR = 1e30                                                      # a bias no pair passes: t < 0 everywhere, ao == 1
@@ -95,6 +101,42 @@ def test_small_frames(api, resolution, radius):
     assert scene._backend().ao_debug()[1:] == resolution
     assert scene._backend().ao_time() > 0
     scene.close()
+
+
+_CHILD = r"""
+import hashlib, sys
+import numpy as np
+sys.path[:0] = [{root!r}, {tests!r}]
+import scenes
+from py_numpy_renderer_amd import AmbientOcclusion
+api = scenes.product_api()
+scene = scenes.cube_outward(api, resolution=(37, 41))
+scene.ambient_occlusion = AmbientOcclusion(radius=2.0)
+scene.render()
+print("digest", hashlib.sha256(np.ascontiguousarray(scene._backend().read_frame_f32()).tobytes()).hexdigest())
+scene.close()
+"""
+
+
+@pytest.fixture(scope="module")
+def small_digest(api):
+    scene = scenes.cube_outward(api, resolution=(37, 41))
+    scene.ambient_occlusion = _ao(radius=2.0)
+    z, f, got = _hold(scene, "cube_outward at (37, 41), radius 2.0, the default shape")
+    assert _bits(got, f) > 0
+    scene.close()
+    return hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest()
+
+
+@pytest.mark.parametrize("shape", ["32x32", "64x16"])
+def test_every_workgroup_shape_gives_the_same_bits(small_digest, shape):
+    """MR_AO_TILE is read once per process: a fresh child renders with each of the other shapes (ao_shape's parsing;
+    test_post_fields_gpu.py reaches the shapes without it)."""
+    code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"))
+    proc = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MR_AO_TILE=shape), timeout=300, capture_output=True, text=True)
+    assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
+    lines = [ln.split()[1] for ln in proc.stdout.splitlines() if ln.startswith("digest ")]
+    assert lines == [small_digest], f"MR_AO_TILE={shape}: the float frame is not the default shape's"
 
 
 def test_diablo_small_with_the_defaults(api):

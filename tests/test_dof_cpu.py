@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import dof_ref
+import post_fields
 import scenes
 from conftest import load_golden
 
@@ -66,18 +67,8 @@ def test_mirror_is_the_reference_on_the_captures(native, capture_cases):
 def test_mirror_is_the_reference_on_synthetic_depth_fields(native, shape, seed):
     """Hills with steps across the plane in focus, a patch that lies in it, holes of +inf, -inf and NaN; the map is a real
     Moebius map, so the float64 part of the definition is exercised too; kf small, middling and far beyond the clamp."""
-    rng = np.random.default_rng(seed)
-    h, w = shape
-    ys, xs = np.mgrid[0:h, 0:w]
-    focus = 2.2
-    depth = 2.2 + 0.5 * np.sin(xs / 3.1) * np.cos(ys / 2.3) + 0.9 * (rng.random(shape) < 0.2) - 0.8 * (rng.random(shape) < 0.15)
-    depth[h // 3:h // 3 + 5, w // 4:w // 4 + 6] = focus * (1 + 1e-4)
-    m = (-0.05, 0.001, -1.0, -0.0106)
-    z = (m[3] * depth - m[1]) / (m[0] - m[2] * depth)                # the map's inverse: Z of these depths
-    z[rng.random(shape) < 0.1] = np.inf
-    z[rng.random(shape) < 0.03] = -np.inf
-    z[rng.random(shape) < 0.02] = np.nan
-    frame = rng.random(shape + (3,), dtype=np.float32)
+    m, focus = post_fields.MOEBIUS, post_fields.HILLS_FOCUS
+    z, frame = post_fields.dof_hills(shape, seed, m, focus)          # (the field lives in post_fields.py, for the kernel's tests too)
     low, high = [], []
     for kf, perspective in ((0.1, 1), (4.0, 1), (60.0, 1), (1.5, 0), (30.0, 0)):
         s = np.abs(dof_ref.circle(z, m, kf, perspective, focus))
