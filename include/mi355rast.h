@@ -772,6 +772,98 @@ int mr_debug_post(mr_scene *scene, const float *frames, const double *z, int32_t
                   const mr_ao_desc *ao, int32_t ao_shape, const mr_dof_desc *dof, int32_t dof_shape, const double *weights,
                   int32_t shift, double scale, float *out_f32, uint8_t *out_rgb);
 
+/* Motion blur from a per-sample velocity buffer, applied to a frame's float colours before they are finalised: every
+ * sample is gathered from the samples whose motion segment passes over it.  It lives on the frame's sample grid (Hs, Ws),
+ * rows bottom-up like every tap, at integer screen coordinates (x, y).  The library is stateless about time: the caller
+ * hands over the matrices that lead from this frame's samples to where their surface points were on the previous frame's
+ * sample grid (the Python layer keeps the previous camera and poses and builds them, _pack.motion_matrices).  With Z the
+ * z-buffer (mr_read_z), w the winner map (mr_read_winner) and F the float frame after the sum over the lights, after the
+ * ambient obscurance and the depth of field where they are on, and BEFORE the overlay:
+ *
+ *   velocity    class = w < 0 ? 0 : class_of_model[model of face w]     (model: the last m whose first face is <= w)
+ *               T = matrices[class], 4 x 3 row-major;  B = background, 3 x 3 row-major
+ *               finite Z:    u_c = ((x*Z)*T[0][c] + (y*Z)*T[1][c] + Z*T[2][c]) + T[3][c]         c = 0, 1, 2
+ *               background (Z not finite):   u_c = (x*B[0][c] + y*B[1][c]) + B[2][c]
+ *               front = finite Z ? u_2 * Z > 0 : u_2 > 0       (u is Z / w times the previous homogeneous screen position)
+ *               U = front ? ((float)(x - u_0/u_2), (float)(y - u_1/u_2)) : (0, 0), and (0, 0) unless both are finite
+ *               float64, left to right, every operation rounded on its own, IEEE divisions, one rounding to float32.  U is
+ *               the displacement in samples since the previous frame, unclamped: what mr_read_velocity returns.
+ *   segment     v = shutter * U;  L = sqrtf(v.x*v.x + v.y*v.y): float32 from here on, every operation rounded on its own
+ *               0.5f <= L <= FLT_MAX:  h = min(L*0.5f, 16),  d = (v.x / L, v.y / L);   else  h = 0,  d = (1, 0)
+ *   gather      e = the eye depth as for the ambient obscurance (a sample whose Z or e is not finite: e = +inf);
+ *               for dy = -16 .. 16 ascending, for dx = -16 .. 16 ascending, q = p + (dx, dy) inside the frame:
+ *                 o = (-dx, -dy);  along = o.x*d_q.x + o.y*d_q.y;  perp = o.x*d_q.y - o.y*d_q.x
+ *                 h_t = (e_q > e_p && h_p < h_q) ? h_p : h_q       (a moving background does not smear over a stiller
+ *                                                                    foreground)
+ *                 if fabsf(along) <= h_t + 0.5f && fabsf(perp) <= 0.5f:       (a tap that fails is skipped)
+ *                     w = 1.0f / (2.0f*h_t + 1.0f);  W = W + w;  S[ch] = S[ch] + w * F[q][ch]
+ *   F'[p][ch] = S[ch] / W
+ *
+ * Class 0 is "the camera only": the background's class and that of every model whose pose did not change; a model whose
+ * pose changed has a class of its own.  Where h = 0 for p and for every q in front of it within 16 samples, F'[p] == F[p]
+ * bit for bit: a frame in which nothing moves by half a sample is the frame without the pass, byte for byte.  One layer
+ * only: what shows behind a moving object is not in F; no segment longer than 33 samples.  The z-buffer interpolates
+ * linearised depth linearly in screen space, so U is exact at vertices and on faces parallel to the image plane and
+ * inherits that interpolation inside a large slanted triangle.
+ *
+ * Where the frame draws an overlay it goes on F' and Z as ever: its lines stay sharp.  The bytes are the finalise of the
+ * result, as for the ambient obscurance.  mr_read_frame_f32 then returns the final float frame; mr_read_z and
+ * mr_read_winner are unchanged.
+ *
+ * mr_scene_set_motion_blur copies everything during the call (NULL: off, the default); every frame enqueued afterwards, by
+ * any entry point, uses the copy of its moment.  Such a frame keeps its z-buffer, winner map and float frame
+ * (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT are implied), runs k_velocity and k_mblur behind the tile kernel, k_ao and
+ * k_dof, and owns a second float frame and a velocity buffer.  A scene without it enqueues what it always did.
+ * MR_E_INVALID for a shutter outside (0, 1] as float32, an entry of depth_map, of a matrix or of background that is not
+ * finite, n_classes < 1, a class outside 0 .. n_classes - 1, or n_models other than the scene's; and, from the rendering
+ * entry points, for a partial frame (row band, stripes) of such a scene, for a sub-frame of an accumulation, and for a
+ * scene whose number of models changed since the call -- all before any device work.  MR_E_UNSUPPORTED from a library
+ * linked without motion.hip or accum.hip. */
+typedef struct mr_motion_desc {
+    double depth_map[4];           /* m0 .. m3, as in mr_ao_desc */
+    double shutter;                /* the part of the frame interval the shutter is open: (0, 1] as float32 */
+    const double *matrices;        /* n_classes x 12: T of every class, 4 x 3 row-major */
+    double background[9];          /* B, 3 x 3 row-major */
+    const int32_t *class_of_model; /* n_models classes (may be NULL when n_models is 0) */
+    int32_t n_classes, n_models;
+} mr_motion_desc;
+int mr_scene_set_motion_blur(mr_scene *scene, const mr_motion_desc *motion);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what k_velocity and k_mblur write.  z is (height,
+ * width) float64, winner (height, width) int32, face_off the first face of each of motion->n_models models (ascending from
+ * 0), velocity and out_velocity (height, width, 2) float32, frame and out_frame (height, width, 3) float32, two different
+ * arrays.  mr_host_motion_blur reads the description's depth_map and shutter only (its matrices must still be valid).
+ * MR_E_INVALID for what mr_scene_set_motion_blur refuses, a NULL array, out_frame == frame, or a height or width outside
+ * 1 .. 32767. */
+int mr_host_velocity(const double *z, const int32_t *winner, const int32_t *face_off, int32_t height, int32_t width,
+                     const mr_motion_desc *motion, float *out_velocity);
+int mr_host_motion_blur(const double *z, const float *velocity, const float *frame, int32_t height, int32_t width,
+                        const mr_motion_desc *motion, float *out_frame);
+
+/* The last frame's velocity buffer U: float32 (Hs, Ws, 2), rows bottom-up.  MR_E_INVALID when the last frame ran without
+ * motion blur.  Waits for the device. */
+int mr_read_velocity(mr_scene *scene, float *out);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued k_velocity and k_mblur (every enqueue, also one rendered again
+ * after an overflow), out[1], out[2] = the sample rows and columns of the last of them (0 before the first).  Does not wait. */
+int mr_debug_motion(mr_scene *scene, int32_t *out);
+
+/* Device times in milliseconds of the last k_velocity and the last k_mblur (HIP events on their frame's stream).  Waits for
+ * them.  MR_E_INVALID before the first such frame. */
+#define MR_N_MOTION_TIMES 2
+int mr_debug_motion_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: k_velocity and k_mblur on buffers the caller supplies -- no frame is rendered.  z, winner and frame as for
+ * the host mirrors, face_off the first face of each of motion->n_models models; shape is k_mblur's workgroup: 0 = 32 x 32
+ * samples and 1 024 threads, 1 = 32 x 32 and 256, 2 = 16 x 16 (never MR_MBLUR_TILE's).  out_velocity (height, width, 2)
+ * and out_frame (height, width, 3) receive U and F'.  The scene lends its error text only: its frame slots, its last frame
+ * and what mr_debug_motion reports stay as they were.  The device buffers are the entry's own and released before it
+ * returns; it waits for the device.  MR_E_INVALID, before any device call, for a NULL argument, a height or width outside
+ * 1 .. 32767, a shape outside 0 .. 2 and whatever mr_host_velocity refuses. */
+int mr_debug_motion_post(mr_scene *scene, const double *z, const int32_t *winner, const float *frame, const int32_t *face_off,
+                         int32_t height, int32_t width, const mr_motion_desc *motion, int32_t shape, float *out_velocity,
+                         float *out_frame);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, motion_matrices, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -115,6 +115,31 @@ def fill_dof_desc(depth_map, kf, perspective, focus):
     return d
 
 
+class MotionDesc(C.Structure):
+    _fields_ = [("depth_map", C.c_double * 4), ("shutter", C.c_double), ("matrices", C.c_void_p), ("background", C.c_double * 9),
+                ("class_of_model", C.c_void_p), ("n_classes", C.c_int32), ("n_models", C.c_int32)]
+
+
+def fill_motion_desc(depth_map, shutter, matrices, background, class_of_model):
+    """``mr_motion_desc`` of a frame's motion (``_pack.motion_matrices``): *matrices* ``(n_classes, 4, 3)``, *background*
+    ``(3, 3)``, *class_of_model* ``(n_models,)``.  The description points into float64 / int32 copies of the arrays, which it
+    keeps alive (``_arrays``); the library copies everything during the call it is handed to."""
+    matrices = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 4, 3)
+    background = np.ascontiguousarray(background, dtype=np.float64).reshape(3, 3)
+    class_of_model = np.ascontiguousarray(class_of_model, dtype=np.int32).ravel()
+    d = MotionDesc()
+    for i in range(4):
+        d.depth_map[i] = float(depth_map[i])
+    for i in range(9):
+        d.background[i] = float(background.flat[i])
+    d.shutter = float(shutter)
+    d.matrices = matrices.ctypes.data
+    d.class_of_model = class_of_model.ctypes.data if len(class_of_model) else None
+    d.n_classes, d.n_models = len(matrices), len(class_of_model)
+    d._arrays = (matrices, class_of_model)
+    return d
+
+
 class Stats(C.Structure):
     _fields_ = ([(n, C.c_int64) for n in (
         "frag_tri", "frag_quad", "covered_px", "lit_px", "stencil_updates", "n_faces", "n_faces_setup",
@@ -212,6 +237,14 @@ _PROTOTYPES = {
     "mr_debug_dof_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AoDesc), C.c_int32,
                                 C.POINTER(DofDesc), C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
+    "mr_scene_set_motion_blur": (C.c_int, [C.c_void_p, C.POINTER(MotionDesc)]),
+    "mr_host_velocity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MotionDesc), C.c_void_p]),
+    "mr_host_motion_blur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(MotionDesc), C.c_void_p]),
+    "mr_read_velocity": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_motion": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_motion_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_motion_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.POINTER(MotionDesc), C.c_int32, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -349,6 +382,56 @@ def debug_post(handle, frames, z, ao=None, ao_shape=0, dof=None, dof_shape=0, we
                                               int(dof_shape), ptr(weights), shift, float(scale), out.ctypes.data, ptr(rgb)),
                  "mr_debug_post")
     return out, rgb
+
+
+def _motion_arrays(z, winner, frame, face_off, desc):
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    winner = None if winner is None else np.ascontiguousarray(winner, dtype=np.int32)
+    frame = None if frame is None else np.ascontiguousarray(frame, dtype=np.float32)
+    face_off = None if face_off is None else np.ascontiguousarray(face_off, dtype=np.int32).ravel()
+    if z.ndim != 2 or (winner is not None and winner.shape != z.shape) or (frame is not None and frame.shape != z.shape + (3,)):
+        raise ValueError(f"z and winner must be (H, W) and frame (H, W, 3), got {z.shape}, "
+                         f"{None if winner is None else winner.shape} and {None if frame is None else frame.shape}")
+    if face_off is not None and len(face_off) != desc.n_models:
+        raise ValueError(f"{len(face_off)} first faces for {desc.n_models} models")
+    return z, winner, frame, face_off
+
+
+def host_velocity(z, winner, face_off, desc):
+    """``mr_host_velocity``: the velocity's definition on the host, no device.  *z* ``(Hs, Ws)`` float64, *winner* ``(Hs, Ws)``
+    int32, *face_off* the models' first faces, *desc* a ``MotionDesc``; returns U, float32 ``(Hs, Ws, 2)``.  ``ValueError``
+    with the library's text for what it refuses."""
+    z, winner, _, face_off = _motion_arrays(z, winner, None, face_off, desc)
+    out = np.empty(z.shape + (2,), dtype=np.float32)
+    _check_accum(load_library().mr_host_velocity(z.ctypes.data, winner.ctypes.data, face_off.ctypes.data if len(face_off) else None,
+                                                 z.shape[0], z.shape[1], C.byref(desc), out.ctypes.data), "mr_host_velocity")
+    return out
+
+
+def host_motion_blur(z, velocity, frame, desc):
+    """``mr_host_motion_blur``: the blur's definition on the host, no device.  *velocity* ``(Hs, Ws, 2)`` float32, *frame*
+    ``(Hs, Ws, 3)`` float32; returns the blurred frame."""
+    z, _, frame, _ = _motion_arrays(z, None, frame, None, desc)
+    velocity = np.ascontiguousarray(velocity, dtype=np.float32)
+    if velocity.shape != z.shape + (2,):
+        raise ValueError(f"velocity must be (H, W, 2), got {velocity.shape}")
+    out = np.empty_like(frame)
+    _check_accum(load_library().mr_host_motion_blur(z.ctypes.data, velocity.ctypes.data, frame.ctypes.data, z.shape[0], z.shape[1],
+                                                    C.byref(desc), out.ctypes.data), "mr_host_motion_blur")
+    return out
+
+
+def debug_motion_post(handle, z, winner, frame, face_off, desc, shape=0):
+    """``mr_debug_motion_post``: k_velocity and k_mblur on the caller's arrays, no frame rendered; *shape* 0 .. 2 is
+    k_mblur's workgroup.  Returns ``(U float32 (Hs, Ws, 2), blurred frame float32 (Hs, Ws, 3))``."""
+    z, winner, frame, face_off = _motion_arrays(z, winner, frame, face_off, desc)
+    vel = np.empty(z.shape + (2,), dtype=np.float32)
+    out = np.empty_like(frame)
+    _check_accum(load_library().mr_debug_motion_post(handle, z.ctypes.data, winner.ctypes.data, frame.ctypes.data,
+                                                     face_off.ctypes.data if len(face_off) else None, z.shape[0], z.shape[1],
+                                                     C.byref(desc), int(shape), vel.ctypes.data, out.ctypes.data),
+                 "mr_debug_motion_post")
+    return vel, out
 
 
 def stripe_out_rows(height, stripe_count):
@@ -705,6 +788,51 @@ class DeviceRenderer:
             self._dof_key = key
         self._dof_packed = packed
 
+    @staticmethod
+    def _motion_values(scene):
+        """The motion of the frame being issued by value (``None`` without ``motion_blur``), for ``_frame_key``."""
+        return None if getattr(scene, "motion_blur", None) is None else scene.__dict__.get("_motion_frame")
+
+    def issue_motion(self, scene, partial=False, accumulating=False):
+        """A frame of *scene* is being issued: with ``motion_blur`` set, the matrices that lead from it to the previous
+        frame's state (``_pack.motion_matrices``) become the scene's ``_motion_frame`` -- by value, for ``_frame_key`` and
+        ``sync_motion_blur`` -- and its own state becomes the previous one.  A frame rendered again after an overflow
+        (``PendingFrame.result``) takes the matrices of its first attempt and leaves the previous state alone."""
+        mb = getattr(scene, "motion_blur", None)
+        if mb is None:
+            scene.__dict__.pop("_motion_frame", None)
+            return
+        if partial:
+            raise ValueError("motion blur takes whole frames (no row band, no stripes): its taps cross the bands")
+        if accumulating:
+            raise ValueError("motion_blur is not available inside accumulate() / render_mean(): the accumulation is the "
+                             "other way to blur motion, and its sub-frames have no previous frame")
+        replay = scene.__dict__.get("_motion_replay")
+        if replay is not None:
+            scene.__dict__["_motion_frame"] = replay
+            return
+        depth_map, matrices, background, class_of, state = motion_matrices(scene, scene.__dict__.get("_motion_prev"))
+        scene.__dict__["_motion_frame"] = (mb.shutter, tuple(depth_map), matrices.tobytes(), background.tobytes(), class_of.tobytes())
+        scene.__dict__["_motion_prev"] = state
+
+    def sync_motion_blur(self, scene):
+        """``mr_scene_set_motion_blur`` for the frames enqueued from now on, whenever the frame's motion (``issue_motion``)
+        is not the one last handed over.  A scene that never had one makes no call."""
+        frame = self._motion_values(scene)
+        if frame is None:
+            if getattr(self, "_motion_key", None) is not None:
+                _check_accum(self.lib.mr_scene_set_motion_blur(self.handle, None), "mr_scene_set_motion_blur")
+                self._motion_key = None
+            return
+        key = frame
+        if getattr(self, "_motion_key", None) == key:
+            return
+        shutter, depth_map, matrices, background, class_of = frame
+        desc = fill_motion_desc(depth_map, shutter, np.frombuffer(matrices, dtype=np.float64), np.frombuffer(background, dtype=np.float64),
+                                np.frombuffer(class_of, dtype=np.int32))
+        _check_accum(self.lib.mr_scene_set_motion_blur(self.handle, C.byref(desc)), "mr_scene_set_motion_blur")
+        self._motion_key = key
+
     # -- frames ---------------------------------------------------------------------------
     @staticmethod
     def _frame_key(scene, shadows):
@@ -724,7 +852,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -786,8 +914,16 @@ class DeviceRenderer:
                                          timing, overlay)
         return desc, self._pinned.array(shape)
 
-    def _prepare_desc(self, scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing, overlay):
+    @staticmethod
+    def _is_partial(scene, row_band, stripe):
+        """Whether a frame of *scene* with this row band (output rows) and stripe is part of a frame only."""
+        return (stripe is not None and int(stripe[1]) > 1) or (
+            row_band is not None and (int(row_band[0]) != 0 or int(row_band[1]) != int(scene.resolution[0])))
+
+    def _prepare_desc(self, scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing, overlay,
+                      accumulating=False):
         """``_prepare`` without the output array: the frame descriptor and the shape of the frame's uint8 rows."""
+        self.issue_motion(scene, partial=self._is_partial(scene, row_band, stripe), accumulating=accumulating)
         self.sync_scene(scene)
         self.sync_skybox(scene)
         pf = self.packed_frame(scene, shadows)
@@ -807,6 +943,7 @@ class DeviceRenderer:
         if getattr(scene, "depth_of_field", None) is not None and partial:
             raise ValueError("depth of field takes whole frames (no row band, no stripes): its taps cross the bands")
         self.sync_depth_of_field(scene)
+        self.sync_motion_blur(scene)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -834,7 +971,7 @@ class DeviceRenderer:
     def accum_add(self, scene, weight, shadows=True, overlay=False):
         """``mr_accum_add``: renders *scene* as it is now -- synchronised exactly as for ``render`` -- and adds its float
         frame, times *weight*, to the accumulation.  Nothing is copied to the host."""
-        desc, shape = self._prepare_desc(scene, shadows, None, True, False, False, False, None, False, overlay)
+        desc, shape = self._prepare_desc(scene, shadows, None, True, False, False, False, None, False, overlay, accumulating=True)
         _check_accum(self.lib.mr_accum_add(self.handle, C.byref(desc), float(weight)), "mr_accum_add")
         self._last_stats = None
         if getattr(self, "_accum_shapes", None) is None:
@@ -897,6 +1034,26 @@ class DeviceRenderer:
         _check(self.lib.mr_debug_dof_times(self.handle, buf), "mr_debug_dof_times")
         return float(buf[0])
 
+    # -- motion blur (Scene.motion_blur) ---------------------------------------------------------
+    def read_velocity(self):
+        """``mr_read_velocity``: the last frame's velocity buffer U, float32 ``(Hs, Ws, 2)`` on the sample grid, rows
+        bottom-up: the displacement of every sample, in samples, since the previous frame."""
+        return self._tap(self.lib.mr_read_velocity, np.float32, (2,))
+
+    def motion_debug(self):
+        """``mr_debug_motion``: (frames that enqueued ``k_velocity`` and ``k_mblur``, the last one's sample rows, its columns)."""
+        out = (C.c_int32 * 3)()
+        _check(self.lib.mr_debug_motion(self.handle, out), "mr_debug_motion")
+        return tuple(int(x) for x in out)
+
+    MOTION_TIME_NAMES = ("velocity", "mblur")
+
+    def motion_times(self):
+        """Device milliseconds of the last ``k_velocity`` and the last ``k_mblur`` (``mr_debug_motion_times``)."""
+        buf = (C.c_float * 2)()
+        _check(self.lib.mr_debug_motion_times(self.handle, buf), "mr_debug_motion_times")
+        return dict(zip(self.MOTION_TIME_NAMES, (float(v) for v in buf)))
+
     ASYNC_LANES = 4
 
     def render_async(self, scene, lane, shadows=True, overlay=False):
@@ -933,6 +1090,7 @@ class DeviceRenderer:
         """``mr_render_device``: enqueue a frame whose uint8 band lands at device pointer *d_out_ptr*.  With *overlay*
         a device that renders the whole frame draws the debug frustum; one that renders part of it appends the state of
         the touched pixels it owns to its rows (``overlay_state_bytes``, ``overlay_apply``)."""
+        self.issue_motion(scene, partial=self._is_partial(scene, row_band, stripe))
         self.sync_scene(scene)
         self.sync_skybox(scene)
         pf = self.packed_frame(scene, shadows)
@@ -941,6 +1099,7 @@ class DeviceRenderer:
         self.sync_lights(pf)
         self.sync_ambient_occlusion(scene)
         self.sync_depth_of_field(scene)
+        self.sync_motion_blur(scene)
         if overlay:
             self.sync_overlay(scene)
         desc = fill_frame_desc(pf, row_band, False, light_timing, counters=counters, stripe=stripe, no_timing=no_timing,

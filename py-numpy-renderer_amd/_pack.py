@@ -257,6 +257,102 @@ def dof_constants(scene, camera=None):
     return depth_map(scene, camera), kf, int(P[2, 3] != 0), float(focus)
 
 
+def check_motion_blur(shutter):
+    """The parameter of a ``MotionBlur``: a Python float that lies in (0, 1] as float32."""
+    if isinstance(shutter, (bool, str, bytes)) or not isinstance(shutter, (int, float, np.integer, np.floating)):
+        raise TypeError(f"motion blur: shutter must be a real number, got {shutter!r}")
+    with np.errstate(over="ignore"):
+        as_f32 = np.float32(shutter)
+    if not np.isfinite(as_f32) or not (0 < as_f32 <= 1):
+        raise ValueError(f"motion blur: shutter must lie in (0, 1] as float32, got {shutter!r}")
+    return float(shutter)
+
+
+class MotionState:
+    """What a frame leaves for the next one's velocity: ``S = view . projection . viewport`` of its camera on the sample
+    grid (one homogeneous 4x4, world to un-divided screen, float64), the scene's models (the objects themselves: another
+    list is another scene) and a copy of every model's ``pose`` (``None``: the identity)."""
+
+    __slots__ = ("S", "models", "poses")
+
+    def __init__(self, scene):
+        viewport = sample_grid(scene)[3]
+        self.S = np.asarray(scene.camera.MVP, dtype=np.float64) @ np.asarray(viewport, dtype=np.float64)
+        self.models = tuple(scene.models)
+        self.poses = tuple(None if m.pose is None else np.array(m.pose, dtype=np.float64) for m in self.models)
+
+    def same_models(self, other):
+        return len(self.models) == len(other.models) and all(a is b for a, b in zip(self.models, other.models))
+
+
+def motion_matrices(scene, previous):
+    """What ``mr_motion_desc`` carries for a frame of *scene* (``motion_blur`` set) that follows the frame which left
+    *previous* (a ``MotionState``; ``None``, or one of another model list: no previous frame, identity motion):
+    ``(depth_map, T, B, class_of_model, state)`` -- ``T`` float64 ``(n_classes, 4, 3)``, ``B`` float64 ``(3, 3)``,
+    ``class_of_model`` int32 ``(len(scene.models),)`` and ``state``, this frame's own ``MotionState``.
+
+    Row vectors, as upstream.  A sample (x, y) of this frame with z-buffer value Z has the screen row vector ``(x, y,
+    scr_z, 1)``, ``scr_z = ((f + n) - 2 n f / Z) / (f - n)`` (upstream's ``linearize_z`` undone), which is ``1 / Z`` times
+    ``(x Z, y Z, Z, 1) . Lz`` with the constant matrix ``Lz`` below.  With ``S`` as in ``MotionState``, a model moved by
+    ``M`` (its ``pose``) takes that vector to the previous frame's un-divided screen through ``K = inv(S_now) . inv(M_now)
+    . M_prev . S_prev``; class 0 -- the camera only: every model whose pose is the previous frame's -- drops the ``M``
+    factors.  ``T = Lz . K[:, (x, y, w)]``, scaled by its largest entry (a positive factor: the kernel tells front from
+    back by the sign of ``u_2 * Z``).  A model whose current pose is singular, or whose ``T`` is not finite, stays in class
+    0: it moves with the camera alone.  Bones and morph weights contribute nothing.
+
+    ``B`` serves the samples no face covers.  Under a perspective camera they lie at infinity: ``(x, y, s, 1) .
+    inv(S_now)`` has w = 0 for ``s = -(x A[0,3] + y A[1,3] + A[3,3]) / A[2,3]``, ``A = inv(S_now)``, which is linear in
+    ``(x, y, 1)``; under an orthographic one, which sees no point at infinity, they lie on the far plane, ``s = f - n``.
+    ``B = rows(x, y, 1 -> x, y, s, 1) . K_0[:, (x, y, w)]``, scaled likewise."""
+    cam = scene.camera
+    now = MotionState(scene)
+    if previous is None or not now.same_models(previous):
+        previous = now
+    n, f = float(cam.near), float(cam.far)
+    lz = np.array([[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, (f + n) / (f - n), 1.0],
+                   [0.0, 0.0, -2.0 * n * f / (f - n), 0.0]])
+    try:
+        inv_now = np.linalg.inv(now.S)
+    except np.linalg.LinAlgError:
+        raise ValueError("motion blur: the camera's matrices cannot be inverted") from None
+
+    def scaled(m):
+        with np.errstate(all="ignore"):
+            largest = np.abs(m).max()
+            return m / largest if np.isfinite(largest) and largest > 0 else np.full_like(m, np.nan)
+
+    # (a camera that stayed where it was is the identity exactly, not to within the inverse's rounding)
+    k0 = np.eye(4) if previous is now or np.array_equal(previous.S, now.S) else inv_now @ previous.S
+    matrices = [scaled((lz @ k0)[:, (0, 1, 3)])]
+    if not np.isfinite(matrices[0]).all():
+        raise ValueError("motion blur: the camera's matrices give no finite motion")
+    class_of = np.zeros(len(now.models), dtype=np.int32)
+    eye = np.eye(4)
+    for i, (m_now, m_prev) in enumerate(zip(now.poses, previous.poses)):
+        if (m_now is None and m_prev is None) or (m_now is not None and m_prev is not None and np.array_equal(m_now, m_prev)):
+            continue
+        try:
+            inv_m = eye if m_now is None else np.linalg.inv(m_now)
+        except np.linalg.LinAlgError:
+            continue
+        with np.errstate(all="ignore"):
+            t = scaled((lz @ (inv_now @ inv_m @ (eye if m_prev is None else m_prev) @ previous.S))[:, (0, 1, 3)])
+        if not np.isfinite(t).all():
+            continue
+        class_of[i] = len(matrices)
+        matrices.append(t)
+    P = np.asarray(cam.projection, dtype=np.float64)
+    a = inv_now
+    if P[2, 3] != 0 and a[2, 3] != 0:
+        rows = np.array([[1.0, 0.0, -a[0, 3] / a[2, 3], 0.0], [0.0, 1.0, -a[1, 3] / a[2, 3], 0.0], [0.0, 0.0, -a[3, 3] / a[2, 3], 1.0]])
+    else:
+        rows = np.array([[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, f - n, 1.0]])
+    background = scaled((rows @ k0)[:, (0, 1, 3)])
+    if not np.isfinite(background).all():
+        raise ValueError("motion blur: the camera's matrices give no finite motion")
+    return depth_map(scene, cam), np.ascontiguousarray(matrices, dtype=np.float64), np.ascontiguousarray(background), class_of, now
+
+
 def sample_grid(scene):
     """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame."""
     cam = scene.camera

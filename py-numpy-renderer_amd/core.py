@@ -162,6 +162,26 @@ class DepthOfField:
         return f"DepthOfField(focus={self.focus!r}, lens_radius={self.lens_radius!r})"
 
 
+class MotionBlur:
+    """What ``Scene.motion_blur`` holds: the blur of what moved since the previous frame of the scene, gathered in one pass
+    along a per-sample velocity buffer (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6k the reasons).
+    ``shutter`` is the part of the frame interval the shutter is open, in (0, 1] as float32 (``ValueError``; ``TypeError``
+    for what is no real number): a sample that moved by U samples since the previous frame smears over ``shutter * |U|``,
+    at most 33 samples.  A ``MotionBlur`` is never modified: assign a new one to change it."""
+
+    __slots__ = ("shutter",)
+
+    def __init__(self, shutter=0.5):
+        from ._pack import check_motion_blur
+        object.__setattr__(self, "shutter", check_motion_blur(shutter))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a MotionBlur is read-only: assign a new one to Scene.motion_blur")
+
+    def __repr__(self):
+        return f"MotionBlur(shutter={self.shutter!r})"
+
+
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
     (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
@@ -680,6 +700,7 @@ class PendingFrame:
 
     def __init__(self, scene, lane, out, shadows, cameras):
         self._scene, self._lane, self._out, self._shadows, self._cameras = scene, lane, out, shadows, cameras
+        self._motion = scene.__dict__.get("_motion_frame")      # the matrices the frame was issued with (motion_blur)
         self._done = False
 
     def result(self):
@@ -690,10 +711,13 @@ class PendingFrame:
             if not ok:          # a work list overflowed (now grown): render this frame's view again, synchronously
                 now = (scene.camera, scene.debug_camera)
                 scene.camera, scene.debug_camera = self._cameras
+                if scene.motion_blur is not None and self._motion is not None:
+                    scene.__dict__["_motion_replay"] = self._motion      # the same matrices as the first attempt
                 try:
                     self._out = scene.render(shadows=self._shadows)
                 finally:
                     scene.camera, scene.debug_camera = now
+                    scene.__dict__.pop("_motion_replay", None)
             self._done = True
         return self._out
 
@@ -818,6 +842,14 @@ class Scene:
       the obscurance, before the debug frustum, whose lines stay sharp.  One layer (what a lens sees round an occluder is
       not in the frame), no circle wider than 16 samples; the sky blurs too.  Split frames (``row_band``, ``multigpu``)
       refuse it.  With ``None`` a scene enqueues exactly what it did without it.
+    * ``motion_blur`` (an addition; ``None`` by default, or a ``MotionBlur``): every frame is blurred along the screen-space
+      motion of its samples since the PREVIOUS frame of this scene -- the camera and every model's ``pose`` as they were
+      when that frame was issued by ``render()``, ``render_async()`` or a view of ``render_frames()``, in issue order.
+      One pass on the device behind the obscurance and the depth of field, before the debug frustum, whose lines stay
+      sharp; ``scene._backend().read_velocity()`` returns the velocity buffer.  The first frame after ``motion_blur`` is
+      assigned, after ``reset_motion()`` or after the model list changed has no previous frame and is ``render()``'s byte
+      for byte.  Bones and morph weights move nothing here; one layer only.  Split frames (``row_band``, ``multigpu``),
+      ``accumulate()`` and ``render_mean()`` refuse it.  With ``None`` a scene enqueues exactly what it did without it.
     """
 
     camera = Bound()
@@ -873,6 +905,22 @@ class Scene:
         if value is not None and not isinstance(value, DepthOfField):
             raise TypeError(f"depth_of_field must be None or a DepthOfField, got {type(value).__name__}")
         self.__dict__["_depth_of_field"] = value
+
+    @property
+    def motion_blur(self):
+        """``None`` (off, the default) or the scene's ``MotionBlur`` (see the class docstring)."""
+        return self.__dict__.get("_motion_blur")
+
+    @motion_blur.setter
+    def motion_blur(self, value):
+        if value is not None and not isinstance(value, MotionBlur):
+            raise TypeError(f"motion_blur must be None or a MotionBlur, got {type(value).__name__}")
+        self.__dict__["_motion_blur"] = value
+        self.reset_motion()
+
+    def reset_motion(self):
+        """Forgets the previous frame's camera and poses: the next frame has identity motion, its bytes are ``render()``'s."""
+        self.__dict__["_motion_prev"] = None
 
     @property
     def last_stats(self):
@@ -987,6 +1035,9 @@ class Scene:
         the first ``add``."""
         if self.__dict__.get("_accumulation") is not None:
             raise RuntimeError("this scene already has an open accumulation: close() it first")
+        if self.motion_blur is not None:
+            raise ValueError("motion_blur is not available inside accumulate() / render_mean(): the accumulation is the "
+                             "other way to blur motion, and its sub-frames have no previous frame")
         acc = self.__dict__["_accumulation"] = Accumulation(self)
         return acc
 

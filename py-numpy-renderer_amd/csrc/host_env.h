@@ -22,6 +22,8 @@
 //   MR_AO_TILE        64x64     32x32 | 64x16: the other workgroup shapes of k_ao (same bits; for the A/B; read in host_ao.h)
 //   MR_DOF_TILE       32x32     32x32x256 | 16x16: the other workgroup shapes of k_dof -- 32 x 32 samples with 256 threads, not
 //                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B; read in host_dof.h)
+//   MR_MBLUR_TILE     32x32     32x32x256 | 16x16: the other workgroup shapes of k_mblur, as for k_dof (same bits; for the A/B;
+//                               read in host_motion.h)
 //
 // MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
 // rest are read once per process.

@@ -15,7 +15,9 @@ struct FrameSlot {
     DevBuf d_vout, d_vclip, d_tris, d_clips, d_status, d_count_list, d_quads, d_sil, d_counters;
     DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_work, d_tile_stats, d_hist, d_split;
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
-    DevBuf d_frame_b;                             // the float frame k_dof writes; then swapped with d_frame, which stays THE float frame
+    DevBuf d_frame_b;                             // the float frame k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
+    MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur (host_motion.h)
+    bool last_motion = false;                     // the last frame ran k_velocity: mr_read_velocity has something to read
     DevBuf d_stencil_x[mr::MAX_LIGHTS - 1];       // stencil taps of lights 1.. of a frame with several lights
     static_assert(mr::MAX_LIGHTS == MR_MAX_LIGHTS, "the ABI's light count is the kernels'");
     int last_n_lights = 1;                        // lights of the last frame
@@ -51,6 +53,7 @@ struct FrameSlot {
             b->release();
         for (DevBuf &b : d_items) b.release();
         for (DevBuf &b : d_stencil_x) b.release();
+        motion.release();
         ov.release();
         if (events_ok) {
             for (auto &set : ev_ring) for (auto &e : set) (void)hipEventDestroy(e);
@@ -162,6 +165,8 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         return fail(MR_E_INVALID, "ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands");
     if (sc->dof.on && is_partial(fr))
         return fail(MR_E_INVALID, "depth of field takes whole frames (no row band, no stripes): its taps cross the bands");
+    if (sc->motion.on && is_partial(fr))
+        return fail(MR_E_INVALID, "motion blur takes whole frames (no row band, no stripes): its taps cross the bands");
     if (sc->n_extra_lights > 0) {
         if (fr->flags & MR_FRAME_FACE_STATUS)
             return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
@@ -329,13 +334,15 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   order_bytes  d_hist: the tile order in front, the tiles' class bytes behind
 //   ao           the scene has ambient obscurance on: k_ao behind the tile kernel, with ao_params, the scene's description now
 //   dof          the scene has depth of field on: k_dof behind them, with dof_params, likewise
+//   motion       the scene has motion blur on: k_velocity and k_mblur behind them, with motion_params, likewise
 //   post()       a pass rewrites the float frame behind the tile kernel: the bytes are the full resolve of the result
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion;
     mr::AoParams ao_params;
     mr::DofParams dof_params;
-    bool post() const { return ao || dof; }
+    mr::MotionParams motion_params;
+    bool post() const { return ao || dof || motion; }
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -379,6 +386,14 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     // (and so does the depth of field, into a second float frame)
     p.dof = sc->dof.on;
     if (p.dof) { p.dof_params = sc->dof.params; fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT; }
+    // (and the motion blur, which reads the winner map as well)
+    p.motion = sc->motion.on;
+    if (p.motion) {
+        if (sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
+            return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
+        p.motion_params = sc->motion.params;
+        fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
+    }
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
     p.taps_asked = (fc.flags & (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT)) != 0;
@@ -450,7 +465,7 @@ int grow_slot(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Frame
         { fs->d_bin_count, (size_t)(BIN_CLASSES * p.n_tiles + 1) * 4 }, { fs->d_work, (size_t)fs->work_cap * sizeof(uint2) },
         { fs->d_tile_stats, nT * TILE_REC * 4 }, { fs->d_z, kept * sizeof(double) }, { fs->d_winner, kept * sizeof(int32_t) },
         { fs->d_stencil, kept * sizeof(int32_t) }, { fs->d_frame, kept_f * 3 * sizeof(float) },
-        { fs->d_frame_b, p.dof ? kept_f * 3 * sizeof(float) : 0 } };
+        { fs->d_frame_b, p.dof || p.motion ? kept_f * 3 * sizeof(float) : 0 } };
     for (const auto &b : sized) HIP_TRY(b.buf.ensure(b.bytes));
     for (int k = 1; k < p.n_lights; ++k) HIP_TRY(fs->d_stencil_x[k - 1].ensure(kept * sizeof(int32_t)));
     if (int rc = ensure_cleared(fs->d_counters, 2 * sizeof(Counters) + sizeof(Sticky), fs->stream)) return rc;
@@ -606,7 +621,7 @@ void launch_post_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, i
                              sc->d_gamma.as<float>(), d_out);
 }
 
-// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the depth of field, the overlay (exported
+// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the depth of field, the motion blur, the overlay (exported
 // by a device that owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638)
 // and the resolve of a supersampled, darkened or blurred frame
 int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
@@ -624,6 +639,12 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
         // (the blurred frame is the slot's float frame from here on: the overlay, the resolve, mr_read_frame_f32 and
         // k_accum_add read d_frame; work enqueued on the stream before this point keeps the pointers it was given)
         std::swap(fs->d_frame, fs->d_frame_b);
+    }
+    if (p.motion && p.n_tiles > 0) {
+        if (int rc = launch_motion(sc, stream, fs->motion, fs->d_z.as<double>(), fs->d_winner.as<int32_t>(), fs->d_frame.as<float>(),
+                                   fs->d_frame_b.as<float>(), fc.width, fc.height, p.motion_params))
+            return rc;
+        std::swap(fs->d_frame, fs->d_frame_b);          // (the two float frames ping-pong when both passes run)
     }
     if (p.overlay && p.partial) {
         const int world = fr->stripe_count > 1 ? fr->stripe_count : fr->height / (fr->row_end - fr->row_begin);
@@ -650,6 +671,7 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
     fs->overlay_deferred = p.deferred;
     fs->last_ss_mode = fc.ss_mode;
     fs->last_post = p.post();
+    fs->last_motion = p.motion && p.n_tiles > 0;
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = p.n_tiles;
     fs->last_n_lights = p.n_lights;

@@ -208,6 +208,17 @@ struct mr_scene {
         bool ev_ok = false, marked = false;
     } dof;
 
+    // ---- motion blur (host_motion.h): likewise; the tables are the class matrices, the background's, the models' first
+    // faces and their classes as one block (motion_params)
+    struct Motion {
+        bool on = false;
+        mr::MotionParams params = {};
+        std::vector<double> tables;
+        int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued the pass; the last one's sample grid
+        hipEvent_t ev[3] = {};                // marks in front of k_velocity, between the two kernels, behind k_mblur
+        bool ev_ok = false, marked = false;
+    } motion;
+
     // ---- frame slots, one per stream that has rendered this scene
     std::vector<std::unique_ptr<FrameSlot>> slots;
     FrameSlot *last = nullptr;               // slot of the most recently enqueued frame

@@ -1,6 +1,7 @@
 // mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file, from
 // accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), from
-// ao.hip, which holds the ambient obscurance's kernel in another, and from dof.hip, which holds the depth of field's;
+// ao.hip, which holds the ambient obscurance's kernel in another, from dof.hip, which holds the depth of field's, and from
+// motion.hip, which holds the motion blur's two;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -13,6 +14,7 @@
 //   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
 //   host_ao.h           ambient obscurance from the z-buffer: the description, k_ao's launch, the host mirror
 //   host_dof.h          depth of field from the z-buffer: the description, k_dof's launch, the host mirror
+//   host_motion.h       motion blur from a velocity buffer: the description, the two launches, the host mirrors, mr_debug_motion_post
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
@@ -33,7 +35,8 @@
 //                   overlay or MR_RESOLVE_PATH=separate leave to resolve;  D2H of the uint8 rows for mr_render;
 //                   k_accum_add behind a sub-frame of mr_accum_add, k_accum_resolve for mr_accum_resolve;
 //                   k_ao behind k_tile in a scene with mr_scene_set_ambient_occlusion, k_dof behind them in one with
-//                   mr_scene_set_depth_of_field, k_accum_resolve for the bytes of either)
+//                   mr_scene_set_depth_of_field, k_velocity and k_mblur behind those in one with
+//                   mr_scene_set_motion_blur, k_accum_resolve for the bytes of any)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -63,6 +66,7 @@
 #include "kernels_pose.h"
 #include "ao_def.h"
 #include "dof_def.h"
+#include "motion_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -74,6 +78,7 @@
 #include "host_overlay_dev.h"
 #include "host_ao.h"
 #include "host_dof.h"
+#include "host_motion.h"
 #include "host_frame.h"
 #include "host_accum.h"
 #include "host_post.h"
@@ -184,6 +189,7 @@ void mr_scene_destroy(mr_scene *sc)
     accum_release(sc->accum);
     ao_release(sc->ao);
     dof_release(sc->dof);
+    motion_release(sc->motion);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
@@ -639,6 +645,65 @@ int mr_debug_post(mr_scene *sc, const float *frames, const double *z, int32_t n,
                   float *out_f32, uint8_t *out_rgb)
 {
     return debug_post(sc, frames, z, n, height, width, ao, ao_shape, dof, dof_shape, weights, shift, scale, out_f32, out_rgb);
+}
+
+int mr_scene_set_motion_blur(mr_scene *sc, const mr_motion_desc *motion)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (!motion) { sc->motion.on = false; return MR_OK; }      // (frames already enqueued took their copy)
+    if (motion->n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "motion blur: n_models is not the number of the scene's models");
+    mr::MotionParams p;
+    std::vector<double> tables;
+    if (int rc = motion_params(motion, sc->model_face_off.data(), p, tables)) return rc;
+    if (int rc = motion_linked()) return rc;
+    sc->motion.params = p;
+    sc->motion.tables.swap(tables);
+    sc->motion.on = true;
+    return MR_OK;
+}
+
+int mr_host_velocity(const double *z, const int32_t *winner, const int32_t *face_off, int32_t height, int32_t width,
+                     const mr_motion_desc *motion, float *out_velocity)
+{
+    return host_velocity(z, winner, face_off, height, width, motion, out_velocity);
+}
+
+int mr_host_motion_blur(const double *z, const float *velocity, const float *frame, int32_t height, int32_t width,
+                        const mr_motion_desc *motion, float *out_frame)
+{
+    return host_motion_blur(z, velocity, frame, height, width, motion, out_frame);
+}
+
+int mr_read_velocity(mr_scene *sc, float *out)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (!fs->last_motion) return fail(MR_E_INVALID, "the last frame was rendered without motion blur");
+    return read_back(fs->motion.d_vel, out, (size_t)fs->last_frame.width * fs->last_frame.height * 2, "velocity");
+}
+
+int mr_debug_motion(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    out[0] = sc->motion.frames; out[1] = sc->motion.rows; out[2] = sc->motion.cols;
+    return MR_OK;
+}
+
+int mr_debug_motion_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->motion.marked) return fail(MR_E_INVALID, "no frame with motion blur yet");
+    HIP_TRY(hipEventSynchronize(sc->motion.ev[2]));      // (no entry point waits for the kernels themselves)
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->motion.ev[0], sc->motion.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[1], sc->motion.ev[1], sc->motion.ev[2]));
+    return MR_OK;
+}
+
+int mr_debug_motion_post(mr_scene *sc, const double *z, const int32_t *winner, const float *frame, const int32_t *face_off, int32_t height,
+                         int32_t width, const mr_motion_desc *motion, int32_t shape, float *out_velocity, float *out_frame)
+{
+    return debug_motion_post(sc, z, winner, frame, face_off, height, width, motion, shape, out_velocity, out_frame);
 }
 
 int64_t mr_overlay_state_bytes(mr_scene *sc)

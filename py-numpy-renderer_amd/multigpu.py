@@ -218,6 +218,9 @@ class BandRenderer:
         if getattr(scene, "depth_of_field", None) is not None:
             raise ValueError("a frame split over devices does not support depth_of_field: its taps cross the bands "
                              "(render it on one device)")
+        if getattr(scene, "motion_blur", None) is not None:
+            raise ValueError("a frame split over devices does not support motion_blur: its taps cross the bands "
+                             "(render it on one device)")
         if partition not in ("bands", "stripes", "weighted"):
             raise ValueError(f"unknown partition {partition!r}")
         self.rank, self.world, self.partition = rank, world, partition
