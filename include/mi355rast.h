@@ -864,6 +864,75 @@ int mr_debug_motion_post(mr_scene *scene, const double *z, const int32_t *winner
                          int32_t height, int32_t width, const mr_motion_desc *motion, int32_t shape, float *out_velocity,
                          float *out_frame);
 
+/* The velocity of models that bend.  The matrices of mr_motion_desc know the camera and every model's pose; a model whose
+ * bones or morph weights changed moves vertex by vertex.  For the models flagged here, a frame with motion blur computes U
+ * per winner face from the previous frame's deformed vertices instead, without the z-buffer.  With V_k the current world
+ * positions of a face's corners, P_k their positions at the previous frame, Sn = s_now and Sp = s_prev the (x, y, w)
+ * columns of the two frames' view . projection . viewport on the sample grid (4 x 3, row vectors, row-major), in float64,
+ * left to right, every operation rounded on its own:
+ *
+ *   X_k = ((V_k.x*Sn[0][0] + V_k.y*Sn[1][0]) + V_k.z*Sn[2][0]) + Sn[3][0]    likewise Y_k, W_k (columns 1, 2), q_k from P_k, Sp
+ *   A[0] = Y x W,  A[1] = W x X,  A[2] = X x Y          each component  a*b - c*d
+ *   det  = (X_0*A[0][0] + X_1*A[0][1]) + X_2*A[0][2]
+ *   H[r][c] = (A[r][0]*q_0[c] + A[r][1]*q_1[c]) + A[r][2]*q_2[c];   s = max |H[r][c]|
+ *   H = 0 (all nine) unless det and s are finite, det != 0 and s > 0;  else H[r][c] = (det < 0 ? -H[r][c] : H[r][c]) / s
+ *   u_c = (x*H[0][c] + y*H[1][c]) + H[2][c];  front = u_2 > 0;  U as for the background above
+ *
+ * (x, y, 1) . A are the sample's perspective-correct barycentrics on the face's plane, so U is exact there, also inside a
+ * large slanted triangle; a degenerate face or a vertex that is no number has U = (0, 0).  Samples of other models and
+ * uncovered samples keep the U of the matrices.  Frame order: k_velocity, k_face_homography, k_velocity_faces, k_mblur.
+ *
+ * The previous vertices are the library's one piece of state.  While tracking is on (mr_scene_track_vertices; off by
+ * default, and then nothing is copied), every pose pass that is about to rewrite the vertices first copies them all,
+ * device to device.  The vertex serial (mr_scene_vertices_serial) counts the states the device's vertices have held: + 1 for
+ * every commit that uploads them and every pass that rewrites them.  prev_serial is the serial the caller read when the
+ * previous frame was issued: the per-face pass runs only if the copy holds exactly that state.  Otherwise -- a commit or
+ * other passes in between, tracking switched on too late -- the pass is skipped, counted, and the frame's U is the
+ * matrices'.  A frame with no flagged model launches neither kernel.
+ *
+ * mr_scene_set_motion_faces copies everything during the call (NULL: off, the default) and needs
+ * mr_scene_set_motion_blur before it.  MR_E_INVALID for an entry of s_now or s_prev that is not finite, n_models other than
+ * the scene's or a NULL array; the mirrors and the debug entry refuse also a vertex index outside the vertex array, first
+ * faces that do not ascend from 0 and a winner of a flagged model beyond the records -- all before any device work.
+ * MR_E_UNSUPPORTED from a library linked without motion_faces.hip. */
+typedef struct mr_motion_faces_desc {
+    double s_now[12], s_prev[12];  /* Sn, Sp: 4 x 3 row-major */
+    const int32_t *deforming;      /* n_models flags */
+    int32_t n_models;
+    int64_t prev_serial;
+} mr_motion_faces_desc;
+int mr_scene_set_motion_faces(mr_scene *scene, const mr_motion_faces_desc *faces);
+int mr_scene_track_vertices(mr_scene *scene, int32_t on);
+int64_t mr_scene_vertices_serial(mr_scene *scene);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what the two kernels write.  verts_now and verts_prev
+ * are (n_verts, 4) float64, faces n_faces records of 12 int32 with the corners' vertex indices at 0, 4 and 8; out_h receives
+ * 9 doubles a face.  mr_host_velocity_faces overwrites, in velocity_in_out (height, width, 2), U of every sample whose
+ * winner w >= 0 belongs to a model m with hom_off[m] >= 0, from record hom_off[m] + w - face_off[m] of h (n_records x 9);
+ * every other float keeps its bits. */
+int mr_host_face_homographies(const double *verts_now, const double *verts_prev, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                              const double *s_now, const double *s_prev, double *out_h);
+int mr_host_velocity_faces(const int32_t *winner, const int32_t *face_off, const int32_t *hom_off, int32_t n_models, const double *h,
+                           int32_t n_records, int32_t height, int32_t width, float *velocity_in_out);
+
+/* Diagnostics: k_face_homography and k_velocity_faces on arrays the caller supplies -- no frame is rendered.  The flagged
+ * models' faces get records one model after the other; out_h receives them (9 doubles each: room for n_faces), and
+ * velocity_in_out is read, overwritten as above and returned.  On the device both outputs lie between 256 bytes of
+ * sentinel either side; out_guard receives the number of those bytes that changed (0 unless a kernel wrote out of bounds).
+ * The scene lends its error text only.  Waits for the device. */
+int mr_debug_motion_faces_post(mr_scene *scene, const double *verts_now, const double *verts_prev, int32_t n_verts, const int32_t *faces,
+                               int32_t n_faces, const int32_t *face_off, const int32_t *deforming, int32_t n_models, const double *s_now,
+                               const double *s_prev, const int32_t *winner, int32_t height, int32_t width, float *velocity_in_out,
+                               double *out_h, int32_t *out_guard);
+
+/* Diagnostics: the snapshot of the vertices, (n_verts, 4) float64 (MR_E_INVALID before the first); out[0] = frames that ran the
+ * per-face pass, out[1] = frames that had flagged models and skipped it, out[2] = the records of the last pass, out[3] =
+ * snapshots taken; and the device milliseconds of the last k_face_homography and the last k_velocity_faces. */
+int mr_debug_read_prev_vertices(mr_scene *scene, double *out);
+int mr_debug_motion_faces(mr_scene *scene, int32_t *out);
+#define MR_N_MOTION_FACES_TIMES 2
+int mr_debug_motion_faces_times(mr_scene *scene, float *out_ms);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, motion_matrices, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -140,6 +140,27 @@ def fill_motion_desc(depth_map, shutter, matrices, background, class_of_model):
     return d
 
 
+class MotionFacesDesc(C.Structure):
+    _fields_ = [("s_now", C.c_double * 12), ("s_prev", C.c_double * 12), ("deforming", C.c_void_p), ("n_models", C.c_int32),
+                ("prev_serial", C.c_int64)]
+
+
+def fill_motion_faces_desc(s_now, s_prev, deforming, prev_serial):
+    """``mr_motion_faces_desc`` of a frame (``_pack.motion_vertices``): *s_now*, *s_prev* ``(4, 3)``, *deforming*
+    ``(n_models,)``.  The description keeps its int32 copy of the flags alive (``_arrays``); the library copies everything
+    during the call it is handed to."""
+    s_now = np.ascontiguousarray(s_now, dtype=np.float64).reshape(12)
+    s_prev = np.ascontiguousarray(s_prev, dtype=np.float64).reshape(12)
+    deforming = np.ascontiguousarray(deforming, dtype=np.int32).ravel()
+    d = MotionFacesDesc()
+    for i in range(12):
+        d.s_now[i], d.s_prev[i] = float(s_now[i]), float(s_prev[i])
+    d.deforming = deforming.ctypes.data if len(deforming) else None
+    d.n_models, d.prev_serial = len(deforming), int(prev_serial)
+    d._arrays = (deforming,)
+    return d
+
+
 class Stats(C.Structure):
     _fields_ = ([(n, C.c_int64) for n in (
         "frag_tri", "frag_quad", "covered_px", "lit_px", "stencil_updates", "n_faces", "n_faces_setup",
@@ -245,6 +266,18 @@ _PROTOTYPES = {
     "mr_debug_motion_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_motion_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.POINTER(MotionDesc), C.c_int32, C.c_void_p, C.c_void_p]),
+    "mr_scene_set_motion_faces": (C.c_int, [C.c_void_p, C.POINTER(MotionFacesDesc)]),
+    "mr_scene_track_vertices": (C.c_int, [C.c_void_p, C.c_int32]),
+    "mr_scene_vertices_serial": (C.c_int64, [C.c_void_p]),
+    "mr_host_face_homographies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mr_host_velocity_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_void_p]),
+    "mr_debug_motion_faces_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "mr_debug_read_prev_vertices": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_motion_faces": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_motion_faces_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -432,6 +465,91 @@ def debug_motion_post(handle, z, winner, frame, face_off, desc, shape=0):
                                                      C.byref(desc), int(shape), vel.ctypes.data, out.ctypes.data),
                  "mr_debug_motion_post")
     return vel, out
+
+
+def _face_arrays(verts_now, verts_prev, faces, s_now, s_prev):
+    verts_now = np.ascontiguousarray(verts_now, dtype=np.float64)
+    verts_prev = np.ascontiguousarray(verts_prev, dtype=np.float64)
+    faces = np.ascontiguousarray(faces, dtype=np.int32)
+    if verts_now.ndim != 2 or verts_now.shape[1] != 4 or verts_prev.shape != verts_now.shape:
+        raise ValueError(f"the vertices must be two (n, 4) arrays, got {verts_now.shape} and {verts_prev.shape}")
+    if faces.ndim != 2 or faces.shape[1] != 12:
+        raise ValueError(f"faces must be (n, 12) int32 records, got {faces.shape}")
+    s_now = np.ascontiguousarray(s_now, dtype=np.float64)
+    s_prev = np.ascontiguousarray(s_prev, dtype=np.float64)
+    if s_now.shape != (4, 3) or s_prev.shape != (4, 3):
+        raise ValueError(f"s_now and s_prev must be (4, 3), got {s_now.shape} and {s_prev.shape}")
+    return verts_now, verts_prev, faces, s_now, s_prev
+
+
+def face_records(corners):
+    """The 12-int32 face records of ``(n, 3)`` vertex indices: corners at 0, 4 and 8, the rest zero."""
+    corners = np.asarray(corners, dtype=np.int32).reshape(-1, 3)
+    faces = np.zeros((len(corners), 12), dtype=np.int32)
+    faces[:, 0], faces[:, 4], faces[:, 8] = corners[:, 0], corners[:, 1], corners[:, 2]
+    return faces
+
+
+def hom_offsets(face_off, deforming, n_faces):
+    """``(hom_off, n_records)`` as the library lays the flagged models' records out: one model after the other, -1 for a
+    model that is not flagged (or has no face)."""
+    face_off = np.asarray(face_off, dtype=np.int64).ravel()
+    ends = np.append(face_off[1:], int(n_faces))
+    hom_off = np.full(len(face_off), -1, dtype=np.int32)
+    records = 0
+    for m, flagged in enumerate(np.asarray(deforming).ravel()):
+        if flagged and ends[m] > face_off[m]:
+            hom_off[m] = records
+            records += int(ends[m] - face_off[m])
+    return hom_off, records
+
+
+def host_face_homographies(verts_now, verts_prev, faces, s_now, s_prev):
+    """``mr_host_face_homographies``: H of every face on the host, float64 ``(n_faces, 3, 3)``.  ``ValueError`` with the
+    library's text for what it refuses."""
+    verts_now, verts_prev, faces, s_now, s_prev = _face_arrays(verts_now, verts_prev, faces, s_now, s_prev)
+    out = np.empty((len(faces), 3, 3), dtype=np.float64)
+    _check_accum(load_library().mr_host_face_homographies(verts_now.ctypes.data, verts_prev.ctypes.data, len(verts_now), faces.ctypes.data,
+                                                          len(faces), s_now.ctypes.data, s_prev.ctypes.data, out.ctypes.data),
+                 "mr_host_face_homographies")
+    return out
+
+
+def host_velocity_faces(winner, face_off, hom_off, h, velocity):
+    """``mr_host_velocity_faces``: a copy of *velocity* ``(Hs, Ws, 2)`` with U of the flagged models' samples overwritten
+    from the records *h* ``(n_records, 3, 3)``."""
+    winner = np.ascontiguousarray(winner, dtype=np.int32)
+    face_off = np.ascontiguousarray(face_off, dtype=np.int32).ravel()
+    hom_off = np.ascontiguousarray(hom_off, dtype=np.int32).ravel()
+    h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1, 9)
+    out = np.array(velocity, dtype=np.float32, order="C")
+    if winner.ndim != 2 or out.shape != winner.shape + (2,) or len(hom_off) != len(face_off):
+        raise ValueError(f"winner must be (H, W), velocity (H, W, 2) and hom_off as long as face_off, got {winner.shape}, {out.shape}, "
+                         f"{len(hom_off)} and {len(face_off)}")
+    _check_accum(load_library().mr_host_velocity_faces(winner.ctypes.data, face_off.ctypes.data, hom_off.ctypes.data, len(face_off),
+                                                       h.ctypes.data, len(h), winner.shape[0], winner.shape[1], out.ctypes.data),
+                 "mr_host_velocity_faces")
+    return out
+
+
+def debug_motion_faces_post(handle, verts_now, verts_prev, faces, face_off, deforming, s_now, s_prev, winner, velocity):
+    """``mr_debug_motion_faces_post``: k_face_homography and k_velocity_faces on the caller's arrays, no frame rendered.
+    Returns ``(H float64 (n_records, 3, 3), U float32 (Hs, Ws, 2), guard bytes the kernels changed)``."""
+    verts_now, verts_prev, faces, s_now, s_prev = _face_arrays(verts_now, verts_prev, faces, s_now, s_prev)
+    winner = np.ascontiguousarray(winner, dtype=np.int32)
+    face_off = np.ascontiguousarray(face_off, dtype=np.int32).ravel()
+    deforming = np.ascontiguousarray(deforming, dtype=np.int32).ravel()
+    out = np.array(velocity, dtype=np.float32, order="C")
+    if winner.ndim != 2 or out.shape != winner.shape + (2,) or len(deforming) != len(face_off):
+        raise ValueError(f"winner must be (H, W), velocity (H, W, 2) and deforming as long as face_off, got {winner.shape}, {out.shape}, "
+                         f"{len(deforming)} and {len(face_off)}")
+    h = np.full((max(len(faces), 1), 3, 3), np.nan)
+    guard = C.c_int32(-1)
+    _check_accum(load_library().mr_debug_motion_faces_post(
+        handle, verts_now.ctypes.data, verts_prev.ctypes.data, len(verts_now), faces.ctypes.data, len(faces), face_off.ctypes.data,
+        deforming.ctypes.data, len(face_off), s_now.ctypes.data, s_prev.ctypes.data, winner.ctypes.data, winner.shape[0], winner.shape[1],
+        out.ctypes.data, h.ctypes.data, C.byref(guard)), "mr_debug_motion_faces_post")
+    return h[:hom_offsets(face_off, deforming, len(faces))[1]], out, int(guard.value)
 
 
 def stripe_out_rows(height, stripe_count):
@@ -810,10 +928,46 @@ class DeviceRenderer:
         replay = scene.__dict__.get("_motion_replay")
         if replay is not None:
             scene.__dict__["_motion_frame"] = replay
+            scene.__dict__["_motion_faces_frame"] = scene.__dict__.get("_motion_faces_replay")
             return
-        depth_map, matrices, background, class_of, state = motion_matrices(scene, scene.__dict__.get("_motion_prev"))
+        previous = scene.__dict__.get("_motion_prev")
+        depth_map, matrices, background, class_of, state = motion_matrices(scene, previous)
         scene.__dict__["_motion_frame"] = (mb.shutter, tuple(depth_map), matrices.tobytes(), background.tobytes(), class_of.tobytes())
+        scene.__dict__["_motion_faces_frame"] = None
+        if mb.deformation:             # (the per-face velocity of the models that bend: _pack.motion_vertices)
+            s_now, s_prev, deforming, prev_serial = motion_vertices(scene, previous, state)
+            scene.__dict__["_motion_faces_frame"] = (s_now.tobytes(), s_prev.tobytes(), deforming.tobytes(), int(prev_serial))
         scene.__dict__["_motion_prev"] = state
+
+    def sync_motion_faces(self, scene):
+        """``mr_scene_track_vertices`` and ``mr_scene_set_motion_faces`` for the frames enqueued from now on, behind
+        ``sync_motion_blur``: tracking goes on with the first frame of a ``MotionBlur(deformation=True)`` and the frame's
+        description (``issue_motion``) goes over whenever it is not the one last handed over.  A scene that never set the
+        flag makes no call."""
+        frame = None if self._motion_values(scene) is None else scene.__dict__.get("_motion_faces_frame")
+        if frame is None:
+            if getattr(self, "_motion_faces_key", None) is not None:
+                _check_accum(self.lib.mr_scene_set_motion_faces(self.handle, None), "mr_scene_set_motion_faces")
+                _check_accum(self.lib.mr_scene_track_vertices(self.handle, 0), "mr_scene_track_vertices")
+                self._motion_faces_key = None
+            return
+        if getattr(self, "_motion_faces_key", None) is None:
+            _check_accum(self.lib.mr_scene_track_vertices(self.handle, 1), "mr_scene_track_vertices")
+        if getattr(self, "_motion_faces_key", None) == frame:
+            return
+        s_now, s_prev, deforming, prev_serial = frame
+        desc = fill_motion_faces_desc(np.frombuffer(s_now, dtype=np.float64), np.frombuffer(s_prev, dtype=np.float64),
+                                      np.frombuffer(deforming, dtype=np.int32), prev_serial)
+        _check_accum(self.lib.mr_scene_set_motion_faces(self.handle, C.byref(desc)), "mr_scene_set_motion_faces")
+        self._motion_faces_key = frame
+
+    def note_motion_serial(self, scene):
+        """Behind the enqueue of a frame with ``MotionBlur(deformation=True)``: the vertex serial of the state it was
+        rendered from goes into the state it left (``MotionState.serial``), for the next frame's ``prev_serial``."""
+        state = scene.__dict__.get("_motion_prev")
+        if state is not None and state.bones is not None and scene.__dict__.get("_motion_replay") is None \
+                and getattr(scene, "motion_blur", None) is not None:
+            state.serial = int(self.lib.mr_scene_vertices_serial(self.handle))
 
     def sync_motion_blur(self, scene):
         """``mr_scene_set_motion_blur`` for the frames enqueued from now on, whenever the frame's motion (``issue_motion``)
@@ -903,6 +1057,7 @@ class DeviceRenderer:
         stats = Stats()
         _check(self.lib.mr_render(self.handle, C.byref(desc), out.ctypes.data, C.byref(stats) if counters else None),
                "mr_render")
+        self.note_motion_serial(scene)
         # a frame rendered for the frame's sake fetches its statistics only if somebody looks at them
         self._last_stats = stats.as_dict() if counters else None
         return out
@@ -944,6 +1099,7 @@ class DeviceRenderer:
             raise ValueError("depth of field takes whole frames (no row band, no stripes): its taps cross the bands")
         self.sync_depth_of_field(scene)
         self.sync_motion_blur(scene)
+        self.sync_motion_faces(scene)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -1054,6 +1210,31 @@ class DeviceRenderer:
         _check(self.lib.mr_debug_motion_times(self.handle, buf), "mr_debug_motion_times")
         return dict(zip(self.MOTION_TIME_NAMES, (float(v) for v in buf)))
 
+    def read_prev_vertices(self, n_verts):
+        """``mr_debug_read_prev_vertices``: the library's snapshot of the vertices, float64 ``(n_verts, 4)``."""
+        out = np.empty((int(n_verts), 4), dtype=np.float64)
+        _check_accum(self.lib.mr_debug_read_prev_vertices(self.handle, out.ctypes.data), "mr_debug_read_prev_vertices")
+        return out
+
+    def vertices_serial(self):
+        """``mr_scene_vertices_serial``: how many states the device's vertices have held."""
+        return int(self.lib.mr_scene_vertices_serial(self.handle))
+
+    def motion_faces_debug(self):
+        """``mr_debug_motion_faces``: (frames that ran the per-face pass, frames that skipped it, the last pass's records,
+        snapshots of the vertices taken)."""
+        out = (C.c_int32 * 4)()
+        _check(self.lib.mr_debug_motion_faces(self.handle, out), "mr_debug_motion_faces")
+        return tuple(int(x) for x in out)
+
+    MOTION_FACES_TIME_NAMES = ("face_homography", "velocity_faces")
+
+    def motion_faces_times(self):
+        """Device milliseconds of the last ``k_face_homography`` and the last ``k_velocity_faces``."""
+        buf = (C.c_float * 2)()
+        _check(self.lib.mr_debug_motion_faces_times(self.handle, buf), "mr_debug_motion_faces_times")
+        return dict(zip(self.MOTION_FACES_TIME_NAMES, (float(v) for v in buf)))
+
     ASYNC_LANES = 4
 
     def render_async(self, scene, lane, shadows=True, overlay=False):
@@ -1061,6 +1242,7 @@ class DeviceRenderer:
         array the frame will land in.  ``render_wait(lane)`` blocks until it has."""
         desc, out = self._prepare(scene, shadows, None, False, False, False, False, None, False, overlay)
         _check(self.lib.mr_render_async(self.handle, C.byref(desc), out.ctypes.data, int(lane)), "mr_render_async")
+        self.note_motion_serial(scene)
         self._last_stats = None
         return out
 
@@ -1100,12 +1282,14 @@ class DeviceRenderer:
         self.sync_ambient_occlusion(scene)
         self.sync_depth_of_field(scene)
         self.sync_motion_blur(scene)
+        self.sync_motion_faces(scene)
         if overlay:
             self.sync_overlay(scene)
         desc = fill_frame_desc(pf, row_band, False, light_timing, counters=counters, stripe=stripe, no_timing=no_timing,
                                overlay=overlay)
         _check(self.lib.mr_render_device(self.handle, C.byref(desc), C.c_void_p(d_out_ptr),
                                          C.c_void_p(stream_ptr)), "mr_render_device")
+        self.note_motion_serial(scene)
         self._frame = (pf.height, pf.width)
         self._desc = desc
         return desc

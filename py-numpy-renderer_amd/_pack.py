@@ -268,21 +268,62 @@ def check_motion_blur(shutter):
     return float(shutter)
 
 
+def check_motion_deformation(value):
+    """The flag of ``MotionBlur(deformation=...)``: a ``bool``, nothing else."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise TypeError(f"motion blur: deformation must be a bool, got {value!r}")
+    return bool(value)
+
+
 class MotionState:
     """What a frame leaves for the next one's velocity: ``S = view . projection . viewport`` of its camera on the sample
     grid (one homogeneous 4x4, world to un-divided screen, float64), the scene's models (the objects themselves: another
-    list is another scene) and a copy of every model's ``pose`` (``None``: the identity)."""
+    list is another scene) and a copy of every model's ``pose`` (``None``: the identity).  With
+    ``MotionBlur(deformation=True)`` also what bends a model: a copy of every model's ``bones`` and ``morph_weights``, the
+    serials of its ``skin`` and ``morph`` (their identity), and ``serial``, the library's vertex serial once the frame has
+    been enqueued (``None`` until then: ``DeviceRenderer.note_motion_serial``)."""
 
-    __slots__ = ("S", "models", "poses")
+    __slots__ = ("S", "models", "poses", "bones", "weights", "skins", "morphs", "serial")
 
     def __init__(self, scene):
         viewport = sample_grid(scene)[3]
         self.S = np.asarray(scene.camera.MVP, dtype=np.float64) @ np.asarray(viewport, dtype=np.float64)
         self.models = tuple(scene.models)
         self.poses = tuple(None if m.pose is None else np.array(m.pose, dtype=np.float64) for m in self.models)
+        self.bones = self.weights = self.skins = self.morphs = self.serial = None
+        if getattr(getattr(scene, "motion_blur", None), "deformation", False):
+            self.bones = tuple(None if m.bones is None else np.array(m.bones, dtype=np.float64) for m in self.models)
+            self.weights = tuple(None if m.morph_weights is None else np.array(m.morph_weights, dtype=np.float64) for m in self.models)
+            self.skins = tuple((m.skin is not None, m._skin_serial) for m in self.models)
+            self.morphs = tuple((m.morph is not None, m._morph_serial) for m in self.models)
 
     def same_models(self, other):
         return len(self.models) == len(other.models) and all(a is b for a, b in zip(self.models, other.models))
+
+
+def motion_vertices(scene, previous, now=None):
+    """What ``mr_motion_faces_desc`` carries for a frame of *scene* (``MotionBlur(deformation=True)``) that follows the frame
+    which left *previous* (a ``MotionState``; ``None``, one of another model list or one without the deformation's part:
+    no previous frame, nothing flagged): ``(Sn, Sp, deforming, prev_serial)`` -- ``Sn`` and ``Sp`` float64 ``(4, 3)``, the
+    (x, y, w) columns of this frame's and the previous frame's ``S``; ``deforming`` int32 ``(len(scene.models),)``, 1 for a
+    model whose ``bones`` or ``morph_weights`` differ by value, or whose ``skin`` or ``morph`` is another object, than at
+    the previous frame; ``prev_serial`` the vertex serial that frame noted (-1: none).  A flagged model keeps its class
+    in ``motion_matrices``: its samples are overwritten behind ``k_velocity``.  *now* is this frame's own ``MotionState`` where
+    the caller holds it already (``motion_matrices`` returns it): nothing is copied twice."""
+    if now is None:
+        now = MotionState(scene)
+    flags = np.zeros(len(now.models), dtype=np.int32)
+    if previous is None or previous.bones is None or now.bones is None or not now.same_models(previous):
+        return now.S[:, (0, 1, 3)].copy(), now.S[:, (0, 1, 3)].copy(), flags, -1
+
+    def differ(a, b):
+        return (a is None) != (b is None) or (a is not None and not np.array_equal(a, b))
+
+    for i in range(len(flags)):
+        flags[i] = int(differ(now.bones[i], previous.bones[i]) or differ(now.weights[i], previous.weights[i])
+                       or now.skins[i] != previous.skins[i] or now.morphs[i] != previous.morphs[i])
+    serial = -1 if previous.serial is None else int(previous.serial)
+    return (np.ascontiguousarray(now.S[:, (0, 1, 3)]), np.ascontiguousarray(previous.S[:, (0, 1, 3)]), flags, serial)
 
 
 def motion_matrices(scene, previous):

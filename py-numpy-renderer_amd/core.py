@@ -167,19 +167,23 @@ class MotionBlur:
     along a per-sample velocity buffer (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6k the reasons).
     ``shutter`` is the part of the frame interval the shutter is open, in (0, 1] as float32 (``ValueError``; ``TypeError``
     for what is no real number): a sample that moved by U samples since the previous frame smears over ``shutter * |U|``,
-    at most 33 samples.  A ``MotionBlur`` is never modified: assign a new one to change it."""
+    at most 33 samples.  ``deformation`` (a ``bool``, ``TypeError`` else; off by default, and then every frame is what it
+    was without the flag) also gives the samples of a model whose ``bones``, ``morph_weights``, ``skin`` or ``morph`` changed
+    since the previous frame the velocity of their face's deformed vertices, one 3 x 3 matrix per face (section 6l), not the
+    velocity of the model's pose alone.  A ``MotionBlur`` is never modified: assign a new one to change it."""
 
-    __slots__ = ("shutter",)
+    __slots__ = ("shutter", "deformation")
 
-    def __init__(self, shutter=0.5):
-        from ._pack import check_motion_blur
+    def __init__(self, shutter=0.5, deformation=False):
+        from ._pack import check_motion_blur, check_motion_deformation
         object.__setattr__(self, "shutter", check_motion_blur(shutter))
+        object.__setattr__(self, "deformation", check_motion_deformation(deformation))
 
     def __setattr__(self, name, value):
         raise AttributeError("a MotionBlur is read-only: assign a new one to Scene.motion_blur")
 
     def __repr__(self):
-        return f"MotionBlur(shutter={self.shutter!r})"
+        return f"MotionBlur(shutter={self.shutter!r}, deformation={self.deformation!r})"
 
 
 class Model:
@@ -701,6 +705,7 @@ class PendingFrame:
     def __init__(self, scene, lane, out, shadows, cameras):
         self._scene, self._lane, self._out, self._shadows, self._cameras = scene, lane, out, shadows, cameras
         self._motion = scene.__dict__.get("_motion_frame")      # the matrices the frame was issued with (motion_blur)
+        self._motion_faces = scene.__dict__.get("_motion_faces_frame")      # ... and its per-face description (deformation)
         self._done = False
 
     def result(self):
@@ -713,11 +718,13 @@ class PendingFrame:
                 scene.camera, scene.debug_camera = self._cameras
                 if scene.motion_blur is not None and self._motion is not None:
                     scene.__dict__["_motion_replay"] = self._motion      # the same matrices as the first attempt
+                    scene.__dict__["_motion_faces_replay"] = self._motion_faces
                 try:
                     self._out = scene.render(shadows=self._shadows)
                 finally:
                     scene.camera, scene.debug_camera = now
                     scene.__dict__.pop("_motion_replay", None)
+                    scene.__dict__.pop("_motion_faces_replay", None)
             self._done = True
         return self._out
 
@@ -848,8 +855,9 @@ class Scene:
       One pass on the device behind the obscurance and the depth of field, before the debug frustum, whose lines stay
       sharp; ``scene._backend().read_velocity()`` returns the velocity buffer.  The first frame after ``motion_blur`` is
       assigned, after ``reset_motion()`` or after the model list changed has no previous frame and is ``render()``'s byte
-      for byte.  Bones and morph weights move nothing here; one layer only.  Split frames (``row_band``, ``multigpu``),
-      ``accumulate()`` and ``render_mean()`` refuse it.  With ``None`` a scene enqueues exactly what it did without it.
+      for byte.  Bones and morph weights move nothing unless ``MotionBlur(deformation=True)``; one layer only.  Split
+      frames (``row_band``, ``multigpu``), ``accumulate()`` and ``render_mean()`` refuse it.  With ``None`` a scene
+      enqueues exactly what it did without it.
     """
 
     camera = Bound()

@@ -17,6 +17,7 @@ struct FrameSlot {
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
     DevBuf d_frame_b;                             // the float frame k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
     MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur (host_motion.h)
+    MotionFacesSlot motion_faces;                 // the face records and the tables of its per-face pass (host_motion_faces.h)
     bool last_motion = false;                     // the last frame ran k_velocity: mr_read_velocity has something to read
     DevBuf d_stencil_x[mr::MAX_LIGHTS - 1];       // stencil taps of lights 1.. of a frame with several lights
     static_assert(mr::MAX_LIGHTS == MR_MAX_LIGHTS, "the ABI's light count is the kernels'");
@@ -54,6 +55,7 @@ struct FrameSlot {
         for (DevBuf &b : d_items) b.release();
         for (DevBuf &b : d_stencil_x) b.release();
         motion.release();
+        motion_faces.release();
         ov.release();
         if (events_ok) {
             for (auto &set : ev_ring) for (auto &e : set) (void)hipEventDestroy(e);
@@ -391,6 +393,8 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     if (p.motion) {
         if (sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
             return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
+        if (sc->mfaces.on && sc->mfaces.deforming.size() != sc->model_face_off.size())
+            return fail(MR_E_INVALID, "per-face velocity: the scene's models changed since mr_scene_set_motion_faces: hand the flags over again");
         p.motion_params = sc->motion.params;
         fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     }
@@ -641,7 +645,7 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
         std::swap(fs->d_frame, fs->d_frame_b);
     }
     if (p.motion && p.n_tiles > 0) {
-        if (int rc = launch_motion(sc, stream, fs->motion, fs->d_z.as<double>(), fs->d_winner.as<int32_t>(), fs->d_frame.as<float>(),
+        if (int rc = launch_motion(sc, stream, fs->motion, fs->motion_faces, fs->d_z.as<double>(), fs->d_winner.as<int32_t>(), fs->d_frame.as<float>(),
                                    fs->d_frame_b.as<float>(), fc.width, fc.height, p.motion_params))
             return rc;
         std::swap(fs->d_frame, fs->d_frame_b);          // (the two float frames ping-pong when both passes run)

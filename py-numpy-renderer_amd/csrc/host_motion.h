@@ -17,6 +17,10 @@ __attribute__((weak)) void launch_blur(hipStream_t stream, const double *zbuf, c
 
 namespace {
 
+struct MotionFacesSlot;                      // host_motion_faces.h: the per-face velocity of models that bend
+bool motion_faces_due(mr_scene *sc);
+int launch_motion_faces(mr_scene *sc, hipStream_t stream, MotionFacesSlot &ms, const int32_t *winner, float *vel, int width, int height);
+
 inline int motion_linked()
 {
     if (&mr_motion::launch_velocity && &mr_motion::launch_blur && &mr_accum::launch_resolve) return MR_OK;
@@ -93,7 +97,9 @@ struct MotionSlot {
 
 // k_velocity and k_mblur from a frame's own z-buffer, winner map and float frame into the slot's velocity buffer and `out`,
 // on the frame's stream behind its tile kernel, marked for mr_debug_motion_times.  `p` is the copy the frame's plan took.
-int launch_motion(mr_scene *sc, hipStream_t stream, MotionSlot &ms, const double *zbuf, const int32_t *winner, const float *frame, float *out,
+// Between the two, where the scene has flagged models and the snapshot they need (motion_faces_due), k_face_homography and
+// k_velocity_faces overwrite those models' U; k_mblur's span then starts at a mark of its own.
+int launch_motion(mr_scene *sc, hipStream_t stream, MotionSlot &ms, MotionFacesSlot &faces, const double *zbuf, const int32_t *winner, const float *frame, float *out,
                   int width, int height, const mr::MotionParams &p)
 {
     mr_scene::Motion &a = sc->motion;
@@ -122,6 +128,12 @@ int launch_motion(mr_scene *sc, hipStream_t stream, MotionSlot &ms, const double
     HIP_TRY(hipEventRecord(a.ev[0], stream));
     mr_motion::launch_velocity(stream, zbuf, winner, ms.d_tables.as<double>(), ms.d_vel.as<float>(), width, height, p);
     HIP_TRY(hipEventRecord(a.ev[1], stream));
+    a.blur_from = 1;
+    if (motion_faces_due(sc)) {
+        if (int rc = launch_motion_faces(sc, stream, faces, winner, ms.d_vel.as<float>(), width, height)) return rc;
+        HIP_TRY(hipEventRecord(a.ev[3], stream));
+        a.blur_from = 3;
+    }
     mr_motion::launch_blur(stream, zbuf, ms.d_vel.as<float>(), frame, out, width, height, p, mblur_shape());
     HIP_TRY(hipEventRecord(a.ev[2], stream));
     a.marked = true;

@@ -9,8 +9,8 @@
 //
 // apply_poses() runs where commit() runs, right after it: plan_pass() fills a PosePlan, run_pass() is the steps in order,
 // each switched by the plan -- refuse float32 face records; wait for the device (frames in flight read the records about
-// to be rewritten); morph tables and weights; apply_morph_normals; apply_pose_normals; skin tables and bones;
-// apply_skin_normals; move_vertices (restores, mark 0, morph, pose, skin); apply_auto_normals; rebuild_static; wait for
+// to be rewritten); while vertex tracking is on, the snapshot of d_verts (host_motion_faces.h); morph tables and weights;
+// apply_morph_normals; apply_pose_normals; skin tables and bones; apply_skin_normals; move_vertices (restores, mark 0, morph, pose, skin); apply_auto_normals; rebuild_static; wait for
 // the stream (the host side of every table, PassTables, lives until then) -- and the dirty bits are cleared, here alone.
 //
 // The dirty bits (PoseDirty, host_scene.h) and who sets them; mr_scene_clear clears them:
@@ -26,6 +26,8 @@
 #pragma once
 
 namespace {
+
+int snapshot_vertices(mr_scene *sc);                 // host_motion_faces.h
 
 // A model that moves (a pose, or bones on its skin) has float64 vertices -- the products of float64 matrices: when
 // "moves" changes for a model passed as float32, its faces lose FF_VERTS_F32 or get it back, and the scene is left
@@ -728,6 +730,8 @@ int run_pass(mr_scene *sc, const PosePlan &p)
 {
     if (sc->pos32) return fail(MR_E_INVALID, "pose pass on a scene of float32 face records");   // (set_model_pose leaves such a scene dirty)
     HIP_TRY(hipDeviceSynchronize());                 // no frame may still be reading the records about to be rewritten
+    if (p.vertices())                                // (while tracking is on: d_verts as it stands, for the next frame's per-face velocity)
+        if (int rc = snapshot_vertices(sc)) return rc;
     sc->marks_morph.none_ran(); sc->marks_skin.none_ran();
     sc->morph_written = sc->morph_normals_written = sc->morph_targets = sc->skin_written = sc->skin_normals_written = 0;
     PassTables t;
@@ -749,6 +753,7 @@ int run_pass(mr_scene *sc, const PosePlan &p)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));         // (the tables go out of scope)
     sc->pose_passes += 1;
+    if (p.vertices()) sc->vert_serial += 1;          // (another state of d_verts)
     sc->pose_written = (int32_t)p.written;           // (0 where no vertex moved)
     return MR_OK;
 }

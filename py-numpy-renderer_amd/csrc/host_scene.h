@@ -215,9 +215,30 @@ struct mr_scene {
         mr::MotionParams params = {};
         std::vector<double> tables;
         int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued the pass; the last one's sample grid
-        hipEvent_t ev[3] = {};                // marks in front of k_velocity, between the two kernels, behind k_mblur
+        hipEvent_t ev[4] = {};                // marks in front of k_velocity, between the two kernels, behind k_mblur; [3]: behind k_velocity_faces
+        // the mark k_mblur's span starts at: 3 in a frame that ran the per-face pass.  One per scene, like ev[]: every enqueue
+        // records ev[0 .. 2] again and sets this with them, so mr_debug_motion_times always reads the marks and the start
+        // of the LAST frame enqueued, whatever other frames are in flight (diagnostics only)
+        int blur_from = 1;
         bool ev_ok = false, marked = false;
     } motion;
+
+    // ---- the velocity of models that bend (host_motion_faces.h): the description every frame with motion blur reads, the
+    // snapshot of the vertices as the previous pass left them and the serial of the states d_verts has held
+    struct MotionFaces {
+        bool on = false;
+        double s_now[12] = {}, s_prev[12] = {};
+        std::vector<int32_t> deforming;       // per model: its samples take the per-face velocity
+        int64_t prev_serial = -1;             // the vertex serial of the previous frame, as its caller saw it
+        int32_t ran = 0, skipped = 0, records = 0, snapshots = 0;      // mr_debug_motion_faces
+        hipEvent_t ev[3] = {};                // marks in front of k_face_homography, between the two kernels, behind k_velocity_faces
+        bool marked = false;
+    } mfaces;
+    bool track_verts = false;                 // mr_scene_track_vertices
+    int64_t vert_serial = 0;                  // + 1 for every commit that uploads vertices and every pass that rewrites them
+    DevBuf d_verts_prev;                      // d_verts as it was before the last such pass, while tracking is on
+    bool snap_valid = false;
+    int64_t snap_serial = -1, snap_verts = 0; // the serial of the state d_verts_prev holds; its vertices
 
     // ---- frame slots, one per stream that has rendered this scene
     std::vector<std::unique_ptr<FrameSlot>> slots;
@@ -431,6 +452,7 @@ int commit(mr_scene *sc)
     sc->dirty = false;
     // d_verts holds the vertices as they were passed: the poses are applied next (apply_poses)
     sc->commits += 1;
+    sc->vert_serial += 1;                     // (another state of d_verts: host_motion_faces.h)
     sc->verts0_valid = false;
     sc->normals0_valid = false;               // (and the normals and the materials' map headers)
     sc->verts_m_valid = sc->normals_m_valid = false;

@@ -1,7 +1,7 @@
 // mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file, from
 // accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), from
 // ao.hip, which holds the ambient obscurance's kernel in another, from dof.hip, which holds the depth of field's, and from
-// motion.hip, which holds the motion blur's two;
+// motion.hip, which holds the motion blur's two, and from motion_faces.hip, which holds the per-face velocity's two;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -15,6 +15,7 @@
 //   host_ao.h           ambient obscurance from the z-buffer: the description, k_ao's launch, the host mirror
 //   host_dof.h          depth of field from the z-buffer: the description, k_dof's launch, the host mirror
 //   host_motion.h       motion blur from a velocity buffer: the description, the two launches, the host mirrors, mr_debug_motion_post
+//   host_motion_faces.h the velocity of models that bend: the vertex snapshot and its serial, the two launches, the mirrors
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
@@ -67,6 +68,7 @@
 #include "ao_def.h"
 #include "dof_def.h"
 #include "motion_def.h"
+#include "motion_faces_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -79,6 +81,7 @@
 #include "host_ao.h"
 #include "host_dof.h"
 #include "host_motion.h"
+#include "host_motion_faces.h"
 #include "host_frame.h"
 #include "host_accum.h"
 #include "host_post.h"
@@ -190,6 +193,7 @@ void mr_scene_destroy(mr_scene *sc)
     ao_release(sc->ao);
     dof_release(sc->dof);
     motion_release(sc->motion);
+    motion_faces_release(sc);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
@@ -696,7 +700,7 @@ int mr_debug_motion_times(mr_scene *sc, float *out_ms)
     if (!sc->motion.marked) return fail(MR_E_INVALID, "no frame with motion blur yet");
     HIP_TRY(hipEventSynchronize(sc->motion.ev[2]));      // (no entry point waits for the kernels themselves)
     HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->motion.ev[0], sc->motion.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&out_ms[1], sc->motion.ev[1], sc->motion.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[1], sc->motion.ev[sc->motion.blur_from], sc->motion.ev[2]));
     return MR_OK;
 }
 
@@ -704,6 +708,83 @@ int mr_debug_motion_post(mr_scene *sc, const double *z, const int32_t *winner, c
                          int32_t width, const mr_motion_desc *motion, int32_t shape, float *out_velocity, float *out_frame)
 {
     return debug_motion_post(sc, z, winner, frame, face_off, height, width, motion, shape, out_velocity, out_frame);
+}
+
+int mr_scene_set_motion_faces(mr_scene *sc, const mr_motion_faces_desc *d)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (!d) { sc->mfaces.on = false; return MR_OK; }          // (frames already enqueued have run their pass)
+    if (!sc->motion.on) return fail(MR_E_INVALID, "per-face velocity: the scene has no motion blur (mr_scene_set_motion_blur comes first)");
+    if (d->n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "per-face velocity: n_models is not the number of the scene's models");
+    if (d->n_models > 0 && !d->deforming) return fail(MR_E_INVALID, "per-face velocity: deforming is NULL");
+    if (!motion_faces_finite(d->s_now, d->s_prev)) return fail(MR_E_INVALID, "per-face velocity: an entry of s_now or s_prev is not finite");
+    if (int rc = motion_faces_linked()) return rc;
+    mr_scene::MotionFaces &a = sc->mfaces;
+    std::memcpy(a.s_now, d->s_now, sizeof a.s_now); std::memcpy(a.s_prev, d->s_prev, sizeof a.s_prev);
+    a.deforming.assign(d->deforming, d->deforming + d->n_models);
+    a.prev_serial = d->prev_serial;
+    a.on = true;
+    return MR_OK;
+}
+
+int mr_scene_track_vertices(mr_scene *sc, int32_t on)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    sc->track_verts = on != 0;
+    if (!on) sc->snap_valid = false;                           // (what a later pass finds is no previous frame's)
+    return MR_OK;
+}
+
+int64_t mr_scene_vertices_serial(mr_scene *sc)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    return sc->vert_serial;
+}
+
+int mr_host_face_homographies(const double *verts_now, const double *verts_prev, int32_t n_verts, const int32_t *faces, int32_t n_faces,
+                              const double *s_now, const double *s_prev, double *out_h)
+{
+    return host_face_homographies(verts_now, verts_prev, n_verts, faces, n_faces, s_now, s_prev, out_h);
+}
+
+int mr_host_velocity_faces(const int32_t *winner, const int32_t *face_off, const int32_t *hom_off, int32_t n_models, const double *h,
+                           int32_t n_records, int32_t height, int32_t width, float *velocity_in_out)
+{
+    return host_velocity_faces(winner, face_off, hom_off, n_models, h, n_records, height, width, velocity_in_out);
+}
+
+int mr_debug_motion_faces_post(mr_scene *sc, const double *verts_now, const double *verts_prev, int32_t n_verts, const int32_t *faces,
+                               int32_t n_faces, const int32_t *face_off, const int32_t *deforming, int32_t n_models, const double *s_now,
+                               const double *s_prev, const int32_t *winner, int32_t height, int32_t width, float *velocity_in_out,
+                               double *out_h, int32_t *out_guard)
+{
+    return debug_motion_faces_post(sc, verts_now, verts_prev, n_verts, faces, n_faces, face_off, deforming, n_models, s_now, s_prev, winner,
+                                   height, width, velocity_in_out, out_h, out_guard);
+}
+
+int mr_debug_read_prev_vertices(mr_scene *sc, double *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->snap_valid) return fail(MR_E_INVALID, "no snapshot of the vertices yet (mr_scene_track_vertices, then a pose pass)");
+    return read_back(sc->d_verts_prev, out, (size_t)sc->snap_verts * 4, "previous vertices");
+}
+
+int mr_debug_motion_faces(mr_scene *sc, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    out[0] = sc->mfaces.ran; out[1] = sc->mfaces.skipped; out[2] = sc->mfaces.records; out[3] = sc->mfaces.snapshots;
+    return MR_OK;
+}
+
+int mr_debug_motion_faces_times(mr_scene *sc, float *out_ms)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    if (!sc->mfaces.marked) return fail(MR_E_INVALID, "no frame with the per-face velocity yet");
+    HIP_TRY(hipEventSynchronize(sc->mfaces.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->mfaces.ev[0], sc->mfaces.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[1], sc->mfaces.ev[1], sc->mfaces.ev[2]));
+    return MR_OK;
 }
 
 int64_t mr_overlay_state_bytes(mr_scene *sc)

@@ -11,8 +11,14 @@
                   full resolve, the taps every tile now writes and the matrices the host builds.
   (a)  the alternative it replaces: render_mean(--sub, turn) over --sub cameras between the two places of the pan of 8
                   (built outside the clock); ms, minimum / median / maximum of --mean-reps.
+  (d)  deforming  (asked for with --only d) the scene's first model skinned with the `bend` rig of tests/skin_ref.py, its
+                  bones going back and forth between two frames of the rig under a still camera: device us of
+                  k_face_homography and k_velocity_faces (mr_debug_motion_faces_times); Scene.render() of a scene without
+                  the blur whose bones change every frame, vertex tracking off and on, alternated -- the pose pass with
+                  its device-to-device copy; and Scene.render() with MotionBlur(deformation=False) and (deformation=True).
 
     python tools/time_motion.py --out profiles/motion_time.txt [--label WORD] [--only k] [scene ...]
+    python tools/time_motion.py --out profiles/motion_faces_time.txt --only d
 """
 import argparse
 import os
@@ -148,8 +154,68 @@ def measure(api, name):
     scene.close(), plain.close()
 
 
+def measure_deforming(api, name):
+    import skin_ref
+    from py_numpy_renderer_amd import MotionBlur, Skin
+    tag = f"{name:22s}"
+    made = {}
+    for key, blur in (("plain_off", None), ("plain_on", None), ("matrix", MotionBlur(shutter=1.0)), ("faces", MotionBlur(shutter=1.0, deformation=True))):
+        s = made[key] = scenes.build(api, name)
+        s.draw_debug_frustum = False
+        joints, weights, _ = skin_ref.rig(api, s.models[0], "bend")
+        s.models[0].skin = Skin(joints, weights)
+        s.motion_blur = blur
+    bones = [skin_ref.rig(api, made["faces"].models[0], "bend", frame=k)[2] for k in (0, 1)]
+    n_faces, n_verts = len(made["faces"].models[0]._faces), sum(len(m.vertices) for m in made["faces"].models)
+
+    def step(scene, k):
+        scene.models[0].bones = bones[k % 2]
+        scene.render()
+
+    for k in range(4):
+        for s in made.values():
+            step(s, k)
+    tracked = made["plain_on"]._backend()
+    assert tracked.lib.mr_scene_track_vertices(tracked.handle, 1) == 0
+    backend = made["faces"]._backend()
+    us = {"face_homography": [], "velocity_faces": []}
+    for k in range(args.launches):
+        step(made["faces"], k)
+        for key, ms in backend.motion_faces_times().items():
+            us[key].append(ms * 1e3)
+    ran, skipped, records, snapshots = backend.motion_faces_debug()
+    _, hs, ws = backend.motion_debug()
+    a, b = spread(us["face_homography"]), spread(us["velocity_faces"])
+    covered = float((backend.read_winner() < n_faces).mean() - (backend.read_winner() < 0).mean())
+    emit(f"{tag} (d)  k_face_homography {a[0]:.1f} / {a[1]:.1f} / {a[2]:.1f} us ({records} face records, 72 bytes each), k_velocity_faces "
+         f"{b[0]:.1f} / {b[1]:.1f} / {b[2]:.1f} us ({hs} x {ws} samples, {covered:.1%} of them the skinned model's) (minimum / median / maximum of "
+         f"{args.launches} frames; the pass ran in {ran} frames and was skipped in {skipped})")
+    for label, off, on in (("no blur, the bones change every frame: vertex tracking off / on (the pose pass and its copy of "
+                            f"{n_verts} vertices, {n_verts * 32} bytes)", "plain_off", "plain_on"),
+                           ("the bones change every frame: MotionBlur(deformation=False) / (deformation=True)", "matrix", "faces")):
+        per = {off: [], on: []}
+        for rep in range(args.reps):
+            for key in ((off, on) if rep % 2 == 0 else (on, off)):
+                t0 = time.perf_counter()
+                step(made[key], rep)
+                per[key].append((time.perf_counter() - t0) * 1e3)
+        x, y = spread(per[off]), spread(per[on])
+        emit(f"{tag} (d)  Scene.render(), {label}, alternated: {x[0]:.3f} / {x[1]:.3f} ms and {y[0]:.3f} / {y[1]:.3f} ms (minimum / median of "
+             f"{args.reps}): {y[0] - x[0]:+.3f} ms at the minimum, {y[1] - x[1]:+.3f} ms at the median")
+    assert made["plain_on"]._backend().motion_faces_debug()[3] > 0 and made["plain_off"]._backend().motion_faces_debug()[3] == 0
+    for s in made.values():
+        s.close()
+
+
 def main():
     api = scenes.product_api()
+    if "d" in args.only:
+        emit(f"# {args.label + ': ' if args.label else ''}the per-face velocity of a skinned model over {args.launches} frames, Scene.render() over "
+             f"{args.reps} alternated pairs")
+        for name in args.scenes:
+            measure_deforming(api, name)
+        if not set(args.only) & set("kfa"):
+            return
     emit(f"# {args.label + ': ' if args.label else ''}k_velocity and k_mblur over {args.launches} frames, Scene.render() over {args.reps} alternated pairs")
     for name in args.scenes:
         measure(api, name)
