@@ -858,26 +858,36 @@ class DeviceRenderer:
         ao = getattr(scene, "ambient_occlusion", None)
         return None if ao is None else (ao.radius, ao.strength, ao.depth_range, ao.bias)
 
+    def _sync_desc(self, scene, tag, entry, values, fill):
+        """What ``sync_ambient_occlusion`` and ``sync_depth_of_field`` do.  *values* is the scene's object by value, ``None``
+        without one; *fill* builds the description from the scene and the view; *entry* names the library's setter.  The
+        caches are ``_<tag>_key`` (the bytes of the description last handed over) and ``_<tag>_packed`` (what it was built
+        from), read with ``getattr``: they work on a renderer whose ``__init__`` never ran."""
+        key_name, packed_name = "_%s_key" % tag, "_%s_packed" % tag
+        setter = getattr(self.lib, entry)
+        if values(scene) is None:
+            if getattr(self, key_name, None) is not None:
+                _check_accum(setter(self.handle, None), entry)
+                setattr(self, key_name, None)
+                setattr(self, packed_name, None)
+            return
+        # (called behind packed_frame: while its entry lives, camera, resolution and supersample are the same)
+        packed = (getattr(self, "_pack_serial", 0), values(scene))
+        if getattr(self, packed_name, None) == packed:
+            return
+        desc = fill(scene)
+        key = bytes(desc)
+        if getattr(self, key_name, None) != key:
+            _check_accum(setter(self.handle, C.byref(desc)), entry)
+            setattr(self, key_name, key)
+        setattr(self, packed_name, packed)
+
     def sync_ambient_occlusion(self, scene):
         """``mr_scene_set_ambient_occlusion`` for the frames enqueued from now on, whenever the description -- the
         scene's ``AmbientOcclusion`` and the view's depth map and footprint -- is not the one last handed over.  A scene
         that never had one makes no call."""
-        ao = getattr(scene, "ambient_occlusion", None)
-        if ao is None:
-            if getattr(self, "_ao_key", None) is not None:
-                _check_accum(self.lib.mr_scene_set_ambient_occlusion(self.handle, None), "mr_scene_set_ambient_occlusion")
-                self._ao_key = self._ao_packed = None
-            return
-        # (called behind packed_frame: while its entry lives, camera, resolution and supersample are the same)
-        packed = (getattr(self, "_pack_serial", 0), self._ao_values(scene))
-        if getattr(self, "_ao_packed", None) == packed:
-            return
-        desc = fill_ao_desc(ao, *ao_constants(scene))
-        key = bytes(desc)
-        if getattr(self, "_ao_key", None) != key:
-            _check_accum(self.lib.mr_scene_set_ambient_occlusion(self.handle, C.byref(desc)), "mr_scene_set_ambient_occlusion")
-            self._ao_key = key
-        self._ao_packed = packed
+        self._sync_desc(scene, "ao", "mr_scene_set_ambient_occlusion", self._ao_values,
+                        lambda sc: fill_ao_desc(sc.ambient_occlusion, *ao_constants(sc)))
 
     @staticmethod
     def _dof_values(scene):
@@ -889,22 +899,14 @@ class DeviceRenderer:
         """``mr_scene_set_depth_of_field`` for the frames enqueued from now on, whenever the description -- the scene's
         ``DepthOfField`` and the view's depth map, focus and ``kf`` -- is not the one last handed over.  A scene that
         never had one makes no call."""
-        dof = getattr(scene, "depth_of_field", None)
-        if dof is None:
-            if getattr(self, "_dof_key", None) is not None:
-                _check_accum(self.lib.mr_scene_set_depth_of_field(self.handle, None), "mr_scene_set_depth_of_field")
-                self._dof_key = self._dof_packed = None
-            return
-        # (called behind packed_frame: while its entry lives, camera, resolution and supersample are the same)
-        packed = (getattr(self, "_pack_serial", 0), self._dof_values(scene))
-        if getattr(self, "_dof_packed", None) == packed:
-            return
-        desc = fill_dof_desc(*dof_constants(scene))
-        key = bytes(desc)
-        if getattr(self, "_dof_key", None) != key:
-            _check_accum(self.lib.mr_scene_set_depth_of_field(self.handle, C.byref(desc)), "mr_scene_set_depth_of_field")
-            self._dof_key = key
-        self._dof_packed = packed
+        self._sync_desc(scene, "dof", "mr_scene_set_depth_of_field", self._dof_values, lambda sc: fill_dof_desc(*dof_constants(sc)))
+
+    def _sync_post(self, scene):
+        """The post passes of the frame being issued, in the order they run: the four descriptions in step with *scene*."""
+        self.sync_ambient_occlusion(scene)
+        self.sync_depth_of_field(scene)
+        self.sync_motion_blur(scene)
+        self.sync_motion_faces(scene)
 
     @staticmethod
     def _motion_values(scene):
@@ -1094,12 +1096,9 @@ class DeviceRenderer:
         self.sync_lights(pf)
         if getattr(scene, "ambient_occlusion", None) is not None and partial:
             raise ValueError("ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands")
-        self.sync_ambient_occlusion(scene)
         if getattr(scene, "depth_of_field", None) is not None and partial:
             raise ValueError("depth of field takes whole frames (no row band, no stripes): its taps cross the bands")
-        self.sync_depth_of_field(scene)
-        self.sync_motion_blur(scene)
-        self.sync_motion_faces(scene)
+        self._sync_post(scene)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -1117,6 +1116,18 @@ class DeviceRenderer:
         rows = (desc.row_end - desc.row_begin) // ss if stripe is None else stripe_out_rows(pf.height, stripe[1])
         self._frame = (pf.height, pf.width)          # the taps' shape: the sample grid
         return desc, (rows, pf.width // ss, 3)
+
+    def _counts(self, fn, n):
+        """An ``mr_debug_*`` entry that fills *n* int32 counters, as a tuple."""
+        out = (C.c_int32 * n)()
+        _check(fn(self.handle, out), fn.__name__)
+        return tuple(int(x) for x in out)
+
+    def _times(self, fn, names):
+        """An ``mr_debug_*_times`` entry: device milliseconds, one per name."""
+        buf = (C.c_float * len(names))()
+        _check(fn(self.handle, buf), fn.__name__)
+        return dict(zip(names, (float(v) for v in buf)))
 
     # -- the accumulation (Scene.accumulate) ------------------------------------------------
     def accum_begin(self):
@@ -1152,43 +1163,31 @@ class DeviceRenderer:
     def accum_debug(self):
         """``mr_debug_accum``: (sub-frames added, sub-frames rendered again after an overflow, the sample grid's height
         and width)."""
-        out = (C.c_int32 * 4)()
-        _check(self.lib.mr_debug_accum(self.handle, out), "mr_debug_accum")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_accum, 4)
 
     ACCUM_TIME_NAMES = ("accum_add", "accum_resolve")
 
     def accum_times(self):
         """Device milliseconds of the last ``k_accum_add`` and the last ``k_accum_resolve`` (``mr_debug_accum_times``)."""
-        buf = (C.c_float * 2)()
-        _check(self.lib.mr_debug_accum_times(self.handle, buf), "mr_debug_accum_times")
-        return dict(zip(self.ACCUM_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_accum_times, self.ACCUM_TIME_NAMES)
 
     # -- ambient obscurance (Scene.ambient_occlusion) ------------------------------------------
     def ao_debug(self):
         """``mr_debug_ao``: (frames that enqueued ``k_ao``, the last one's sample rows, its sample columns)."""
-        out = (C.c_int32 * 3)()
-        _check(self.lib.mr_debug_ao(self.handle, out), "mr_debug_ao")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_ao, 3)
 
     def ao_time(self):
         """Device milliseconds of the last ``k_ao`` (``mr_debug_ao_times``)."""
-        buf = (C.c_float * 1)()
-        _check(self.lib.mr_debug_ao_times(self.handle, buf), "mr_debug_ao_times")
-        return float(buf[0])
+        return self._times(self.lib.mr_debug_ao_times, ("ao",))["ao"]
 
     # -- depth of field (Scene.depth_of_field) ---------------------------------------------------
     def dof_debug(self):
         """``mr_debug_dof``: (frames that enqueued ``k_dof``, the last one's sample rows, its sample columns)."""
-        out = (C.c_int32 * 3)()
-        _check(self.lib.mr_debug_dof(self.handle, out), "mr_debug_dof")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_dof, 3)
 
     def dof_time(self):
         """Device milliseconds of the last ``k_dof`` (``mr_debug_dof_times``)."""
-        buf = (C.c_float * 1)()
-        _check(self.lib.mr_debug_dof_times(self.handle, buf), "mr_debug_dof_times")
-        return float(buf[0])
+        return self._times(self.lib.mr_debug_dof_times, ("dof",))["dof"]
 
     # -- motion blur (Scene.motion_blur) ---------------------------------------------------------
     def read_velocity(self):
@@ -1198,17 +1197,13 @@ class DeviceRenderer:
 
     def motion_debug(self):
         """``mr_debug_motion``: (frames that enqueued ``k_velocity`` and ``k_mblur``, the last one's sample rows, its columns)."""
-        out = (C.c_int32 * 3)()
-        _check(self.lib.mr_debug_motion(self.handle, out), "mr_debug_motion")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_motion, 3)
 
     MOTION_TIME_NAMES = ("velocity", "mblur")
 
     def motion_times(self):
         """Device milliseconds of the last ``k_velocity`` and the last ``k_mblur`` (``mr_debug_motion_times``)."""
-        buf = (C.c_float * 2)()
-        _check(self.lib.mr_debug_motion_times(self.handle, buf), "mr_debug_motion_times")
-        return dict(zip(self.MOTION_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_motion_times, self.MOTION_TIME_NAMES)
 
     def read_prev_vertices(self, n_verts):
         """``mr_debug_read_prev_vertices``: the library's snapshot of the vertices, float64 ``(n_verts, 4)``."""
@@ -1223,17 +1218,13 @@ class DeviceRenderer:
     def motion_faces_debug(self):
         """``mr_debug_motion_faces``: (frames that ran the per-face pass, frames that skipped it, the last pass's records,
         snapshots of the vertices taken)."""
-        out = (C.c_int32 * 4)()
-        _check(self.lib.mr_debug_motion_faces(self.handle, out), "mr_debug_motion_faces")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_motion_faces, 4)
 
     MOTION_FACES_TIME_NAMES = ("face_homography", "velocity_faces")
 
     def motion_faces_times(self):
         """Device milliseconds of the last ``k_face_homography`` and the last ``k_velocity_faces``."""
-        buf = (C.c_float * 2)()
-        _check(self.lib.mr_debug_motion_faces_times(self.handle, buf), "mr_debug_motion_faces_times")
-        return dict(zip(self.MOTION_FACES_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_motion_faces_times, self.MOTION_FACES_TIME_NAMES)
 
     ASYNC_LANES = 4
 
@@ -1279,10 +1270,7 @@ class DeviceRenderer:
         if pf.extra_lights and stripe is not None:
             raise ValueError("striped frames are not available with more than one light")
         self.sync_lights(pf)
-        self.sync_ambient_occlusion(scene)
-        self.sync_depth_of_field(scene)
-        self.sync_motion_blur(scene)
-        self.sync_motion_faces(scene)
+        self._sync_post(scene)
         if overlay:
             self.sync_overlay(scene)
         desc = fill_frame_desc(pf, row_band, False, light_timing, counters=counters, stripe=stripe, no_timing=no_timing,
@@ -1407,9 +1395,7 @@ class DeviceRenderer:
     def sil_cache(self):
         """Silhouette cache: (path of the last frame with shadows: 0 fused / 1 captured / 2 cached / -1 none, entries it
         read from the cache, captures started so far, usable buffers); see mi355rast.h."""
-        out = (C.c_int32 * 4)()
-        _check(self.lib.mr_debug_sil_cache(self.handle, out), "mr_debug_sil_cache")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_sil_cache, 4)
 
     def force_full(self, on=True):
         """``mr_debug_force_full``: every later frame of the scene takes the general kernels (k_setup_full, k_tile_full);
@@ -1427,72 +1413,54 @@ class DeviceRenderer:
     def pose_counters(self):
         """``mr_debug_pose``: (full commits of the scene so far, pose passes so far, posed models, vertices the last
         pass wrote)."""
-        out = (C.c_int32 * 4)()
-        _check(self.lib.mr_debug_pose(self.handle, out), "mr_debug_pose")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_pose, 4)
 
     def skin_counters(self):
         """``mr_debug_skin``: (models that have bones, bone matrices the last pose pass uploaded, vertices and normals it
         skinned)."""
-        out = (C.c_int32 * 4)()
-        _check(self.lib.mr_debug_skin(self.handle, out), "mr_debug_skin")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_skin, 4)
 
     def morph_counters(self):
         """``mr_debug_morph``: (models that have morph weights, targets the last pose pass used, vertices and normals it
         morphed, entries -- padding included -- of the contribution lists on the device)."""
-        out = (C.c_int32 * 5)()
-        _check(self.lib.mr_debug_morph(self.handle, out), "mr_debug_morph")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_morph, 5)
 
     def auto_normals_counters(self):
         """``mr_debug_auto_normals``: (models whose normals the last pose pass rebuilt, normals it wrote, entries --
         padding included -- of the face lists on the device, normals among those written that kept their authored value)."""
-        out = (C.c_int32 * 4)()
-        _check(self.lib.mr_debug_auto_normals(self.handle, out), "mr_debug_auto_normals")
-        return tuple(int(x) for x in out)
+        return self._counts(self.lib.mr_debug_auto_normals, 4)
 
     AUTO_NORMALS_TIME_NAMES = ("auto_normals",)
 
     def auto_normals_times(self):
         """Device milliseconds of ``k_auto_normals`` in the last pose pass (``mr_debug_auto_normals_times``)."""
-        buf = (C.c_float * 1)()
-        _check(self.lib.mr_debug_auto_normals_times(self.handle, buf), "mr_debug_auto_normals_times")
-        return dict(zip(self.AUTO_NORMALS_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_auto_normals_times, self.AUTO_NORMALS_TIME_NAMES)
 
     MORPH_TIME_NAMES = ("morph_vertices", "morph_normals")
 
     def morph_times(self):
         """Device milliseconds of the two morph kernels of the last pose pass (``mr_debug_morph_times``)."""
-        buf = (C.c_float * 2)()
-        _check(self.lib.mr_debug_morph_times(self.handle, buf), "mr_debug_morph_times")
-        return dict(zip(self.MORPH_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_morph_times, self.MORPH_TIME_NAMES)
 
     SKIN_TIME_NAMES = ("skin_vertices", "skin_normals")
 
     def skin_times(self):
         """Device milliseconds of the two skin kernels of the last pose pass that had a skin to apply
         (``mr_debug_skin_times``)."""
-        buf = (C.c_float * 2)()
-        _check(self.lib.mr_debug_skin_times(self.handle, buf), "mr_debug_skin_times")
-        return dict(zip(self.SKIN_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_skin_times, self.SKIN_TIME_NAMES)
 
     POSE_TIME_NAMES = ("pose_vertices", "face_normals", "edge_normals", "face_static", "clusters")
 
     def pose_times(self):
         """Device milliseconds of the five kernels of the last pose pass (``mr_debug_pose_times``)."""
-        buf = (C.c_float * 5)()
-        _check(self.lib.mr_debug_pose_times(self.handle, buf), "mr_debug_pose_times")
-        return dict(zip(self.POSE_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_pose_times, self.POSE_TIME_NAMES)
 
     POSE_NORMALS_TIME_NAMES = ("pose_normals", "pose_texels")
 
     def pose_normals_times(self):
         """Device milliseconds of the two kernels of the last pose pass that had normal matrices to apply
         (``mr_debug_pose_normals_times``)."""
-        buf = (C.c_float * 2)()
-        _check(self.lib.mr_debug_pose_normals_times(self.handle, buf), "mr_debug_pose_normals_times")
-        return dict(zip(self.POSE_NORMALS_TIME_NAMES, (float(v) for v in buf)))
+        return self._times(self.lib.mr_debug_pose_normals_times, self.POSE_NORMALS_TIME_NAMES)
 
     def read_clusters(self):
         """The per-cluster records of the scene (``mr_debug_read_clusters``): a structured array with ``lo``, ``hi``,

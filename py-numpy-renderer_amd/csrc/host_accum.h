@@ -9,43 +9,18 @@
 // on the sample grid.
 #pragma once
 
-// the two launches of accum.hip, the library's other translation unit; weak, so that a library linked from mi355rast.hip
-// alone (the tools' ablation builds) still loads: it refuses the accumulation instead
-namespace mr_accum {
-__attribute__((weak)) void launch_add(hipStream_t stream, const float *frame, float *acc, size_t n_floats, float w, int first);
-__attribute__((weak)) void launch_resolve(hipStream_t stream, const float *acc, int width, int height, int shift, float scale,
-                                          const float *gamma_lut, uint8_t *out);
-}  // namespace mr_accum
-
 namespace {
 
 inline int accum_linked()
 {
-    if (&mr_accum::launch_add && &mr_accum::launch_resolve) return MR_OK;
-    return fail(MR_E_UNSUPPORTED, "this library was linked without accum.hip: no accumulation kernels (build it with __graft_entry__.build())");
-}
-
-// a weight or a scale as the kernels take it: float32, finite and positive
-inline bool accum_factor(double v, float &out)
-{
-    out = (float)v;
-    return std::isfinite(out) && out > 0.0f;
-}
-
-int accum_events(mr_scene::Accum &a)
-{
-    if (a.ev_ok) return MR_OK;
-    for (hipEvent_t &e : a.ev) HIP_TRY(hipEventCreate(&e));
-    a.ev_ok = true;
-    return MR_OK;
+    return linked("this library was linked without accum.hip: no accumulation kernels (build it with __graft_entry__.build())",
+                  &mr_accum::launch_add, &mr_accum::launch_resolve);
 }
 
 void accum_release(mr_scene::Accum &a)
 {
     a.d_acc.release();
-    if (a.ev_ok)
-        for (hipEvent_t &e : a.ev) (void)hipEventDestroy(e);
-    a = mr_scene::Accum();
+    release_pass(a);
 }
 
 // One sub-frame: rendered on the library's stream and its slot with the float frame kept (no bytes leave the device),
@@ -59,7 +34,7 @@ int accum_add(mr_scene *sc, const mr_frame_desc *fr, double weight)
     if (fr->flags & MR_FRAME_FACE_STATUS) return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available for the sub-frames of an accumulation");
     if (sc->motion.on) return fail(MR_E_INVALID, "motion blur is not available for the sub-frames of an accumulation: the sum is the other way to blur motion");
     float w;
-    if (!accum_factor(weight, w)) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
+    if (!positive_f32(weight, w)) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
     if ((rc = accum_linked())) return rc;
     mr_scene::Accum &a = sc->accum;
     const int32_t ss_flags = fr->flags & (MR_FRAME_SUPERSAMPLE2 | MR_FRAME_SUPERSAMPLE4);
@@ -88,10 +63,10 @@ int accum_add(mr_scene *sc, const mr_frame_desc *fr, double weight)
         HIP_TRY(a.d_acc.ensure(n_floats * sizeof(float)));
         a.width = kept.width; a.height = kept.height; a.ss_flags = ss_flags;
     }
-    if ((rc = accum_events(a))) return rc;
-    HIP_TRY(hipEventRecord(a.ev[0], g_stream));
+    if ((rc = a.marks.create())) return rc;
+    if ((rc = a.marks.record(0, g_stream))) return rc;
     mr_accum::launch_add(g_stream, fs->d_frame.as<float>(), a.d_acc.as<float>(), n_floats, w, a.count == 0 ? 1 : 0);
-    HIP_TRY(hipEventRecord(a.ev[1], g_stream));
+    if ((rc = a.marks.record(1, g_stream))) return rc;
     HIP_TRY(hipGetLastError());
     a.add_marked = true;
     a.count += 1;
@@ -105,16 +80,16 @@ int accum_resolve(mr_scene *sc, double scale, uint8_t *out_rgb)
     mr_scene::Accum &a = sc->accum;
     if (a.count == 0) return fail(MR_E_INVALID, "nothing accumulated yet");
     float s;
-    if (!accum_factor(scale, s)) return fail(MR_E_INVALID, "the scale must be finite and > 0 as float32");
+    if (!positive_f32(scale, s)) return fail(MR_E_INVALID, "the scale must be finite and > 0 as float32");
     if (int rc = accum_linked()) return rc;
     FrameSlot *fs = slot_for(sc, g_stream);
     if (!fs) return fail(MR_E_DEVICE, "out of frame slots");
     const int shift = (a.ss_flags & MR_FRAME_SUPERSAMPLE4) ? 2 : (a.ss_flags & MR_FRAME_SUPERSAMPLE2) ? 1 : 0;
     const long long n_px = (long long)(a.width >> shift) * (a.height >> shift);
     HIP_TRY(fs->d_out.ensure((size_t)n_px * 3));
-    HIP_TRY(hipEventRecord(a.ev[2], g_stream));
+    if (int rc = a.marks.record(2, g_stream)) return rc;
     mr_accum::launch_resolve(g_stream, a.d_acc.as<float>(), a.width, a.height, shift, s, sc->d_gamma.as<float>(), fs->d_out.as<uint8_t>());
-    HIP_TRY(hipEventRecord(a.ev[3], g_stream));
+    if (int rc = a.marks.record(3, g_stream)) return rc;
     HIP_TRY(hipGetLastError());
     a.resolve_marked = true;
     HIP_TRY(hipMemcpyAsync(out_rgb, fs->d_out.p, (size_t)n_px * 3, hipMemcpyDeviceToHost, g_stream));
@@ -143,10 +118,10 @@ int host_accum(const float *frames, const double *weights, int32_t n, int32_t he
     if (shift < 0 || shift > 2) return fail(MR_E_INVALID, "mr_host_accum: shift is 0, 1 or 2");
     if (height % (1 << shift) || width % (1 << shift)) return fail(MR_E_INVALID, "mr_host_accum: height and width must be multiples of 1 << shift");
     float s;
-    if (!accum_factor(scale, s)) return fail(MR_E_INVALID, "the scale must be finite and > 0 as float32");
+    if (!positive_f32(scale, s)) return fail(MR_E_INVALID, "the scale must be finite and > 0 as float32");
     std::vector<float> w((size_t)n);
     for (int32_t k = 0; k < n; ++k)
-        if (!accum_factor(weights[k], w[k])) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
+        if (!positive_f32(weights[k], w[k])) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
     const size_t n_floats = (size_t)height * width * 3;
     std::vector<float> own;
     float *acc = out_acc;

@@ -19,11 +19,10 @@
 //   MR_CLUSTER_CULL   (auto)    0 | 1 | box | count: cluster culling off / on / boxes only / on and counted (auto: see
 //                               cluster_cull_mode)
 //   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
-//   MR_AO_TILE        64x64     32x32 | 64x16: the other workgroup shapes of k_ao (same bits; for the A/B; read in host_ao.h)
+//   MR_AO_TILE        64x64     32x32 | 64x16: the other workgroup shapes of k_ao (same bits; for the A/B)
 //   MR_DOF_TILE       32x32     32x32x256 | 16x16: the other workgroup shapes of k_dof -- 32 x 32 samples with 256 threads, not
-//                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B; read in host_dof.h)
-//   MR_MBLUR_TILE     32x32     32x32x256 | 16x16: the other workgroup shapes of k_mblur, as for k_dof (same bits; for the A/B;
-//                               read in host_motion.h)
+//                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B)
+//   MR_MBLUR_TILE     32x32     32x32x256 | 16x16: the other workgroup shapes of k_mblur, as for k_dof (same bits; for the A/B)
 //
 // MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
 // rest are read once per process.
@@ -36,6 +35,7 @@ struct Env {
     int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
     int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
     int pair_log;                                 // 0 .. mr::PAIR_LOG_K
+    int ao_shape, dof_shape, mblur_shape;         // 0 .. 2: the `shape` of ao.hip's, dof.hip's and motion.hip's launch
     unsigned split_cost, split_quads;
     const char *cluster_cull;                     // as set, or NULL
 };
@@ -45,6 +45,10 @@ Env read_env()
     static const Env once = [] {
         auto is = [](const char *name, const char *value) { const char *e = getenv(name); return e && !strcmp(e, value); };
         auto number = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+        // a workgroup shape by its three spellings; unset or unknown: shape 0
+        auto shape = [&](const char *name, const char *s0, const char *s1, const char *s2) {
+            return is(name, s0) ? 0 : is(name, s1) ? 1 : is(name, s2) ? 2 : 0;
+        };
         Env e = {};
         e.vertex_mfma = is("MR_VERTEX_PATH", "mfma");
         e.resolve_separate = is("MR_RESOLVE_PATH", "separate");
@@ -55,6 +59,9 @@ Env read_env()
         e.tile_split = number("MR_TILE_SPLIT", -1);
         e.split_cost = (unsigned)number("MR_SPLIT_COST", 400);
         e.split_quads = (unsigned)number("MR_SPLIT_QUADS", 48);
+        e.ao_shape = shape("MR_AO_TILE", "64x64", "32x32", "64x16");
+        e.dof_shape = shape("MR_DOF_TILE", "32x32", "32x32x256", "16x16");
+        e.mblur_shape = shape("MR_MBLUR_TILE", "32x32", "32x32x256", "16x16");
         return e;
     }();
     Env e = once;

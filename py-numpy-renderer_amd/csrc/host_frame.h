@@ -141,8 +141,7 @@ inline bool is_partial(const mr_frame_desc *fr) { return fr->row_begin != 0 || f
 int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
 {
     if (!fr) return fail(MR_E_INVALID, "frame descriptor is NULL");
-    if (fr->width <= 0 || fr->height <= 0 || fr->width > 32767 || fr->height > 32767)
-        return fail(MR_E_INVALID, "resolution out of range");
+    if (!frame_size_ok(fr->height, fr->width)) return fail(MR_E_INVALID, "resolution out of range");
     if (fr->system != 1 && fr->system != -1) return fail(MR_E_INVALID, "system must be +1 (RH) or -1 (LH)");
     if (fr->row_begin < 0 || fr->row_end > fr->height || fr->row_begin >= fr->row_end)
         return fail(MR_E_INVALID, "row band must satisfy 0 <= row_begin < row_end <= height");
@@ -163,12 +162,10 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         if (fr->row_begin % s || fr->row_end % s) return fail(MR_E_INVALID, "supersampling: row_begin / row_end must be multiples of s");
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
-    if (sc->ao.on && is_partial(fr))
-        return fail(MR_E_INVALID, "ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands");
-    if (sc->dof.on && is_partial(fr))
-        return fail(MR_E_INVALID, "depth of field takes whole frames (no row band, no stripes): its taps cross the bands");
-    if (sc->motion.on && is_partial(fr))
-        return fail(MR_E_INVALID, "motion blur takes whole frames (no row band, no stripes): its taps cross the bands");
+    const struct { bool on; const char *name; } passes[] = { { sc->ao.on, "ambient occlusion" }, { sc->dof.on, "depth of field" }, { sc->motion.on, "motion blur" } };
+    for (const auto &pass : passes)
+        if (pass.on && is_partial(fr))
+            return fail(MR_E_INVALID, std::string(pass.name) + " takes whole frames (no row band, no stripes): its taps cross the bands");
     if (sc->n_extra_lights > 0) {
         if (fr->flags & MR_FRAME_FACE_STATUS)
             return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
@@ -381,23 +378,15 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     if (fc.flags & MR_FRAME_FACE_STATUS) fc.flags |= MR_FRAME_KEEP_BUFFERS;
     // (a supersampled frame resolved by k_resolve_full needs every tile's float colour)
     if (fc.ss_mode & SS_SEPARATE) fc.flags |= MR_FRAME_KEEP_FLOAT;
-    // (ambient obscurance reads the whole z-buffer and rewrites the whole float frame: every tile writes its taps, as for
-    // a caller who asked for them)
-    p.ao = sc->ao.on;
-    if (p.ao) { p.ao_params = sc->ao.params; fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT; }
-    // (and so does the depth of field, into a second float frame)
-    p.dof = sc->dof.on;
-    if (p.dof) { p.dof_params = sc->dof.params; fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT; }
-    // (and the motion blur, which reads the winner map as well)
-    p.motion = sc->motion.on;
-    if (p.motion) {
-        if (sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
-            return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
-        if (sc->mfaces.on && sc->mfaces.deforming.size() != sc->model_face_off.size())
-            return fail(MR_E_INVALID, "per-face velocity: the scene's models changed since mr_scene_set_motion_faces: hand the flags over again");
-        p.motion_params = sc->motion.params;
-        fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
-    }
+    // (a post pass reads the whole z-buffer -- the motion blur the winner map as well -- and rewrites the whole float frame,
+    // in place or into the second one: every tile writes its taps, as for a caller who asked for them)
+    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on;
+    if (p.motion && sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
+    if (p.motion && sc->mfaces.on && sc->mfaces.deforming.size() != sc->model_face_off.size())
+        return fail(MR_E_INVALID, "per-face velocity: the scene's models changed since mr_scene_set_motion_faces: hand the flags over again");
+    p.ao_params = sc->ao.params; p.dof_params = sc->dof.params; p.motion_params = sc->motion.params;
+    if (p.post()) fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
     p.taps_asked = (fc.flags & (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT)) != 0;
@@ -625,6 +614,11 @@ void launch_post_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, i
                              sc->d_gamma.as<float>(), d_out);
 }
 
+// A pass has written the other float frame: that one is the slot's float frame from here on.  The overlay, the resolve,
+// mr_read_frame_f32 and k_accum_add read d_frame; work enqueued on the stream before this point keeps the pointers it was
+// given; the two ping-pong when k_dof and k_mblur both run.
+inline void swap_float_frames(FrameSlot *fs) { std::swap(fs->d_frame, fs->d_frame_b); }
+
 // ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the depth of field, the motion blur, the overlay (exported
 // by a device that owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638)
 // and the resolve of a supersampled, darkened or blurred frame
@@ -636,19 +630,18 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
         hipLaunchKernelGGL(k_face_status, dim3(blocks_for(fc.n_faces, 256)), dim3(256), 0, stream, fc, fs->d_tris.as<TriRec>(),
                            fs->d_clips.as<TriClip>(), fs->d_z.as<double>(), fs->d_stencil.as<int32_t>(), fs->d_status.as<uint8_t>());
     if (p.ao && p.n_tiles > 0)
-        if (int rc = launch_ao(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, p.ao_params)) return rc;
+        if (int rc = launch_ao(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, p.ao_params, p.env.ao_shape)) return rc;
     if (p.dof && p.n_tiles > 0) {
-        if (int rc = launch_dof(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fs->d_frame_b.as<float>(), fc.width, fc.height, p.dof_params))
+        if (int rc = launch_dof(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fs->d_frame_b.as<float>(), fc.width, fc.height, p.dof_params,
+                                p.env.dof_shape))
             return rc;
-        // (the blurred frame is the slot's float frame from here on: the overlay, the resolve, mr_read_frame_f32 and
-        // k_accum_add read d_frame; work enqueued on the stream before this point keeps the pointers it was given)
-        std::swap(fs->d_frame, fs->d_frame_b);
+        swap_float_frames(fs);
     }
     if (p.motion && p.n_tiles > 0) {
         if (int rc = launch_motion(sc, stream, fs->motion, fs->motion_faces, fs->d_z.as<double>(), fs->d_winner.as<int32_t>(), fs->d_frame.as<float>(),
-                                   fs->d_frame_b.as<float>(), fc.width, fc.height, p.motion_params))
+                                   fs->d_frame_b.as<float>(), fc.width, fc.height, p.motion_params, p.env.mblur_shape))
             return rc;
-        std::swap(fs->d_frame, fs->d_frame_b);          // (the two float frames ping-pong when both passes run)
+        swap_float_frames(fs);
     }
     if (p.overlay && p.partial) {
         const int world = fr->stripe_count > 1 ? fr->stripe_count : fr->height / (fr->row_end - fr->row_begin);

@@ -11,19 +11,12 @@
 // runs only if the snapshot holds exactly that state, else the frame keeps k_velocity's U and the skip is counted.
 #pragma once
 
-namespace mr_motion_faces {
-__attribute__((weak)) void launch_homography(hipStream_t stream, const int32_t *faces, const double *verts, const double *verts_prev,
-                                             const int32_t *tables, double *hom, const mr::MotionFacesParams &p);
-__attribute__((weak)) void launch_velocity_faces(hipStream_t stream, const int32_t *winner, const int32_t *tables, const double *hom, float *vel,
-                                                 int width, int height, int n_models);
-}  // namespace mr_motion_faces
-
 namespace {
 
 inline int motion_faces_linked()
 {
-    if (&mr_motion_faces::launch_homography && &mr_motion_faces::launch_velocity_faces) return MR_OK;
-    return fail(MR_E_UNSUPPORTED, "this library was linked without motion_faces.hip: no per-face velocity (build it with __graft_entry__.build())");
+    return linked("this library was linked without motion_faces.hip: no per-face velocity (build it with __graft_entry__.build())",
+                  &mr_motion_faces::launch_homography, &mr_motion_faces::launch_velocity_faces);
 }
 
 inline bool motion_faces_finite(const double *s_now, const double *s_prev)
@@ -110,7 +103,7 @@ int host_velocity_faces(const int32_t *winner, const int32_t *face_off, const in
                         int32_t n_records, int32_t height, int32_t width, float *velocity)
 {
     if (!winner || !face_off || !hom_off || !h || !velocity) return fail(MR_E_INVALID, "mr_host_velocity_faces: NULL argument");
-    if (!motion_size_ok(height, width)) return fail(MR_E_INVALID, "mr_host_velocity_faces: resolution out of range");
+    if (!frame_size_ok(height, width)) return fail(MR_E_INVALID, "mr_host_velocity_faces: resolution out of range");
     if (n_records < 0) return fail(MR_E_INVALID, "mr_host_velocity_faces: a negative count");
     if (int rc = motion_faces_check_map(winner, face_off, hom_off, n_models, n_records, height, width)) return rc;
     for (int y = 0; y < height; ++y)
@@ -124,29 +117,17 @@ int host_velocity_faces(const int32_t *winner, const int32_t *face_off, const in
     return MR_OK;
 }
 
-// What a frame slot owns for the pass: the records, the tables on the device and a page-locked copy of them that the
-// upload reads, with an event behind the upload (as MotionSlot, host_motion.h).
+// What a frame slot owns for the pass: the staged tables and the records.
 struct MotionFacesSlot {
-    DevBuf d_tables, d_hom;
-    void *h_tables = nullptr;
-    size_t h_cap = 0;
-    hipEvent_t copied = nullptr;
-    bool pending = false;
-    void release()
-    {
-        d_tables.release(); d_hom.release();
-        if (h_tables) (void)hipHostFree(h_tables);
-        if (copied) (void)hipEventDestroy(copied);
-        h_tables = nullptr; h_cap = 0; copied = nullptr; pending = false;
-    }
+    StagedTable tables;
+    DevBuf d_hom;
+    void release() { tables.release(); d_hom.release(); }
 };
 
 void motion_faces_release(mr_scene *sc)
 {
-    mr_scene::MotionFaces &a = sc->mfaces;
-    for (hipEvent_t &e : a.ev) if (e) (void)hipEventDestroy(e);
     sc->d_verts_prev.release();
-    a = mr_scene::MotionFaces();
+    release_pass(sc->mfaces);
 }
 
 // In a pose pass that is about to rewrite d_verts, behind its wait for the device: the snapshot, while tracking is on.
@@ -193,42 +174,20 @@ int launch_motion_faces(mr_scene *sc, hipStream_t stream, MotionFacesSlot &ms, c
     if (!motion_faces_tables(a.deforming.data(), sc->model_face_off.data(), n_models, (int64_t)(sc->faces.size() / 12), tables, p.n_ranges, p.n_records))
         return fail(MR_E_INVALID, "per-face velocity: the models' first faces do not ascend");
     if (p.n_records == 0) return fail(MR_E_INVALID, "per-face velocity: no flagged face (motion_faces_due answers that)");
-    for (hipEvent_t &e : a.ev) if (!e) HIP_TRY(hipEventCreate(&e));
-    const size_t bytes = tables.size() * sizeof(int32_t);
-    if (!ms.copied) HIP_TRY(hipEventCreateWithFlags(&ms.copied, hipEventDisableTiming));
-    if (ms.pending) { HIP_TRY(hipEventSynchronize(ms.copied)); ms.pending = false; }
-    if (bytes > ms.h_cap) {
-        if (ms.h_tables) HIP_TRY(hipHostFree(ms.h_tables));
-        ms.h_tables = nullptr; ms.h_cap = 0;
-        HIP_TRY(hipHostMalloc(&ms.h_tables, bytes * 2, hipHostMallocDefault));
-        ms.h_cap = bytes * 2;
-    }
-    std::memcpy(ms.h_tables, tables.data(), bytes);
-    HIP_TRY(ms.d_tables.ensure(bytes));
+    if (int rc = a.marks.create()) return rc;
     HIP_TRY(ms.d_hom.ensure((size_t)p.n_records * mr::MOTION_H * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(ms.d_tables.p, ms.h_tables, bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(ms.copied, stream));
-    ms.pending = true;
-    HIP_TRY(hipEventRecord(a.ev[0], stream));
-    mr_motion_faces::launch_homography(stream, sc->d_faces.as<int32_t>(), sc->d_verts.as<double>(), sc->d_verts_prev.as<double>(),
-                                       ms.d_tables.as<int32_t>(), ms.d_hom.as<double>(), p);
-    HIP_TRY(hipEventRecord(a.ev[1], stream));
-    mr_motion_faces::launch_velocity_faces(stream, winner, ms.d_tables.as<int32_t>(), ms.d_hom.as<double>(), vel, width, height, n_models);
-    HIP_TRY(hipEventRecord(a.ev[2], stream));
+    if (int rc = ms.tables.stage(tables.data(), tables.size() * sizeof(int32_t), stream)) return rc;
+    const int32_t *d_tables = ms.tables.d_tables.as<int32_t>();
+    if (int rc = a.marks.record(0, stream)) return rc;
+    mr_motion_faces::launch_homography(stream, sc->d_faces.as<int32_t>(), sc->d_verts.as<double>(), sc->d_verts_prev.as<double>(), d_tables,
+                                       ms.d_hom.as<double>(), p);
+    if (int rc = a.marks.record(1, stream)) return rc;
+    mr_motion_faces::launch_velocity_faces(stream, winner, d_tables, ms.d_hom.as<double>(), vel, width, height, n_models);
+    if (int rc = a.marks.record(2, stream)) return rc;
     a.marked = true;
     a.ran += 1; a.records = p.n_records;
     return MR_OK;
 }
-
-// the debug entry's device buffers: released when it returns, by whichever way, once the stream has drained
-struct MotionFacesPostBuffers {
-    DevBuf faces, verts, prev, tables, winner, hom, vel;
-    ~MotionFacesPostBuffers()
-    {
-        if (g_initialised) (void)hipStreamSynchronize(g_stream);
-        for (DevBuf *d : { &faces, &verts, &prev, &tables, &winner, &hom, &vel }) d->release();
-    }
-};
 
 constexpr size_t MOTION_FACES_GUARD = 256;               // bytes of sentinel in front of and behind each output buffer
 constexpr unsigned char MOTION_FACES_SENTINEL = 0xa5;
@@ -243,7 +202,7 @@ int debug_motion_faces_post(mr_scene *sc, const double *verts_now, const double 
 {
     if (!sc || !verts_now || !verts_prev || !faces || !face_off || !deforming || !s_now || !s_prev || !winner || !velocity || !out_h || !out_guard)
         return fail(MR_E_INVALID, "mr_debug_motion_faces_post: NULL argument");
-    if (!motion_size_ok(height, width)) return fail(MR_E_INVALID, "mr_debug_motion_faces_post: resolution out of range");
+    if (!frame_size_ok(height, width)) return fail(MR_E_INVALID, "mr_debug_motion_faces_post: resolution out of range");
     if (n_verts < 0 || n_faces < 0 || n_models < 1) return fail(MR_E_INVALID, "mr_debug_motion_faces_post: a count out of range");
     if (!motion_faces_finite(s_now, s_prev)) return fail(MR_E_INVALID, "per-face velocity: an entry of s_now or s_prev is not finite");
     if (!motion_faces_indices_ok(faces, n_faces, n_verts)) return fail(MR_E_INVALID, "per-face velocity: a vertex index lies outside the vertex array");
@@ -261,7 +220,8 @@ int debug_motion_faces_post(mr_scene *sc, const double *verts_now, const double 
     const std::vector<int32_t> fv(faces, faces + (size_t)n_faces * 12), wv(winner, winner + n);
     const std::vector<double> vn(verts_now, verts_now + (size_t)n_verts * 4), vp(verts_prev, verts_prev + (size_t)n_verts * 4);
     std::vector<unsigned char> guards(4 * G);
-    MotionFacesPostBuffers buf;                          // (behind the vectors: it drains the stream before they go)
+    struct { DevBuf faces, verts, prev, tables, winner, hom, vel; } buf;
+    Drained drained{ &buf.faces, &buf.verts, &buf.prev, &buf.tables, &buf.winner, &buf.hom, &buf.vel };      // (behind the vectors: it drains the stream before they go)
     if (int rc = upload(buf.faces, fv, g_stream)) return rc;
     if (int rc = upload(buf.verts, vn, g_stream)) return rc;
     if (int rc = upload(buf.prev, vp, g_stream)) return rc;

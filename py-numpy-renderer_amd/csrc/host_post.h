@@ -7,16 +7,6 @@
 
 namespace {
 
-// the entry's device buffers: released when it returns, by whichever way, once the stream has drained
-struct PostBuffers {
-    DevBuf z, a, b, sum, rgb;
-    ~PostBuffers()
-    {
-        if (g_initialised) (void)hipStreamSynchronize(g_stream);
-        for (DevBuf *d : { &z, &a, &b, &sum, &rgb }) d->release();
-    }
-};
-
 int debug_post(mr_scene *sc, const float *frames, const double *z, int32_t n, int32_t height, int32_t width, const mr_ao_desc *ao,
                int32_t ao_shape, const mr_dof_desc *dof, int32_t dof_shape, const double *weights, int32_t shift, double scale,
                float *out_f32, uint8_t *out_rgb)
@@ -24,17 +14,17 @@ int debug_post(mr_scene *sc, const float *frames, const double *z, int32_t n, in
     // ---- every refusal, before any device call
     if (!sc || !frames || !z || !out_f32) return fail(MR_E_INVALID, "mr_debug_post: NULL argument");
     if (n < 1) return fail(MR_E_INVALID, "mr_debug_post: n must be at least 1");
-    if (height <= 0 || width <= 0 || height > 32767 || width > 32767) return fail(MR_E_INVALID, "mr_debug_post: resolution out of range");
+    if (!frame_size_ok(height, width)) return fail(MR_E_INVALID, "mr_debug_post: resolution out of range");
     if (n > 1 && !weights) return fail(MR_E_INVALID, "mr_debug_post: several frames need weights (their sum is the result)");
     if (ao && (ao_shape < 0 || ao_shape > 2)) return fail(MR_E_INVALID, "mr_debug_post: the workgroup shape of k_ao is 0, 1 or 2");
     if (dof && (dof_shape < 0 || dof_shape > 2)) return fail(MR_E_INVALID, "mr_debug_post: the workgroup shape of k_dof is 0, 1 or 2");
     if (shift < 0 || shift > 2) return fail(MR_E_INVALID, "mr_debug_post: shift is 0, 1 or 2");
     if (height % (1 << shift) || width % (1 << shift)) return fail(MR_E_INVALID, "mr_debug_post: height and width must be multiples of 1 << shift");
     float s;
-    if (!accum_factor(scale, s)) return fail(MR_E_INVALID, "the scale must be finite and > 0 as float32");
+    if (!positive_f32(scale, s)) return fail(MR_E_INVALID, "the scale must be finite and > 0 as float32");
     std::vector<float> w(weights ? (size_t)n : 0);
     for (size_t k = 0; k < w.size(); ++k)
-        if (!accum_factor(weights[k], w[k])) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
+        if (!positive_f32(weights[k], w[k])) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
     mr::AoParams ap;
     mr::DofParams dp;
     if (ao)
@@ -53,7 +43,8 @@ int debug_post(mr_scene *sc, const float *frames, const double *z, int32_t n, in
     if (out_rgb)
         if (int rc = ensure_gamma(sc)) return rc;
     const size_t n_samples = (size_t)height * width, n_floats = n_samples * 3;
-    PostBuffers buf;
+    struct { DevBuf z, a, b, sum, rgb; } buf;
+    Drained drained{ &buf.z, &buf.a, &buf.b, &buf.sum, &buf.rgb };
     HIP_TRY(buf.z.ensure(n_samples * sizeof(double)));
     HIP_TRY(buf.a.ensure(n_floats * sizeof(float)));
     if (dof) HIP_TRY(buf.b.ensure(n_floats * sizeof(float)));

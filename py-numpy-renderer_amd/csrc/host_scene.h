@@ -186,41 +186,22 @@ struct mr_scene {
         DevBuf d_acc;                         // float32 (height, width, 3), rows bottom-up; kept from one accumulation to the next
         int32_t width = 0, height = 0, ss_flags = 0;      // fixed by the first add
         int32_t count = 0, rerendered = 0;    // sub-frames added; sub-frames rendered again after an overflow
-        hipEvent_t ev[4] = {};                // marks round the last k_accum_add and the last k_accum_resolve
-        bool ev_ok = false, add_marked = false, resolve_marked = false;
+        Marks<4> marks;                       // round the last k_accum_add and the last k_accum_resolve
+        bool add_marked = false, resolve_marked = false;
     } accum;
 
-    // ---- ambient obscurance (host_ao.h): the description every frame enqueued from now on takes a copy of
-    struct Ao {
-        bool on = false;
-        mr::AoParams params = {};
-        int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued k_ao; the last one's sample grid
-        hipEvent_t ev[2] = {};                // marks round the last k_ao
-        bool ev_ok = false, marked = false;
-    } ao;
+    // ---- the passes behind a frame's tile kernel (host_pass.h, PassRecord): ambient obscurance (host_ao.h) and depth of
+    // field (host_dof.h), marked round their one kernel ...
+    struct Ao : PassRecord<2> { mr::AoParams params = {}; } ao;
+    struct Dof : PassRecord<2> { mr::DofParams params = {}; } dof;
 
-    // ---- depth of field (host_dof.h): likewise
-    struct Dof {
-        bool on = false;
-        mr::DofParams params = {};
-        int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued k_dof; the last one's sample grid
-        hipEvent_t ev[2] = {};                // marks round the last k_dof
-        bool ev_ok = false, marked = false;
-    } dof;
-
-    // ---- motion blur (host_motion.h): likewise; the tables are the class matrices, the background's, the models' first
+    // ... and motion blur (host_motion.h), marked in front of k_velocity, behind it, behind k_velocity_faces in a frame that
+    // ran the per-face pass, and behind k_mblur; the tables are the class matrices, the background's, the models' first
     // faces and their classes as one block (motion_params)
-    struct Motion {
-        bool on = false;
+    struct Motion : PassRecord<4> {
         mr::MotionParams params = {};
         std::vector<double> tables;
-        int32_t frames = 0, rows = 0, cols = 0;            // frames that enqueued the pass; the last one's sample grid
-        hipEvent_t ev[4] = {};                // marks in front of k_velocity, between the two kernels, behind k_mblur; [3]: behind k_velocity_faces
-        // the mark k_mblur's span starts at: 3 in a frame that ran the per-face pass.  One per scene, like ev[]: every enqueue
-        // records ev[0 .. 2] again and sets this with them, so mr_debug_motion_times always reads the marks and the start
-        // of the LAST frame enqueued, whatever other frames are in flight (diagnostics only)
-        int blur_from = 1;
-        bool ev_ok = false, marked = false;
+        int blur_from = 1;                    // the mark k_mblur's span starts at: 2 in a frame that ran the per-face pass; set with the marks
     } motion;
 
     // ---- the velocity of models that bend (host_motion_faces.h): the description every frame with motion blur reads, the
@@ -231,7 +212,7 @@ struct mr_scene {
         std::vector<int32_t> deforming;       // per model: its samples take the per-face velocity
         int64_t prev_serial = -1;             // the vertex serial of the previous frame, as its caller saw it
         int32_t ran = 0, skipped = 0, records = 0, snapshots = 0;      // mr_debug_motion_faces
-        hipEvent_t ev[3] = {};                // marks in front of k_face_homography, between the two kernels, behind k_velocity_faces
+        Marks<3> marks;                       // in front of k_face_homography, between the two kernels, behind k_velocity_faces
         bool marked = false;
     } mfaces;
     bool track_verts = false;                 // mr_scene_track_vertices

@@ -12,6 +12,7 @@
 //   host_morph.h        morph targets: the per-vertex contribution lists (plain C++, no HIP)
 //   host_autonormals.h  rebuilt vertex normals: the per-normal face lists (plain C++, no HIP)
 //   host_pose.h         a model's morph, skin and pose, applied on the device in front of the frame
+//   host_pass.h         what the post passes share: weak launches, timing marks, the pass record, the staged table, the checks
 //   host_ao.h           ambient obscurance from the z-buffer: the description, k_ao's launch, the host mirror
 //   host_dof.h          depth of field from the z-buffer: the description, k_dof's launch, the host mirror
 //   host_motion.h       motion blur from a velocity buffer: the description, the two launches, the host mirrors, mr_debug_motion_post
@@ -75,6 +76,7 @@
 #include "host_silcache.h"
 #include "host_morph.h"
 #include "host_autonormals.h"
+#include "host_pass.h"
 #include "host_scene.h"
 #include "host_pose.h"
 #include "host_overlay_dev.h"
@@ -89,6 +91,44 @@
 // ============================================================================ C ABI
 
 static thread_local mr_host::OverlayLists g_overlay_lists;
+
+// mr_scene_set_ambient_occlusion, mr_scene_set_depth_of_field: the description checked and kept for the frames enqueued
+// from now on; NULL switches the pass off
+template <class Pass, class Desc, class Params>
+static int set_pass(mr_scene *sc, Pass mr_scene::*pass, const Desc *d, int (*params)(const Desc *, Params &), int (*pass_linked)())
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    Pass &a = sc->*pass;
+    if (!d) { a.on = false; return MR_OK; }      // (frames already enqueued took their copy)
+    Params p;
+    if (int rc = params(d, p)) return rc;
+    if (int rc = pass_linked()) return rc;
+    a.params = p;
+    a.on = true;
+    return MR_OK;
+}
+
+// mr_debug_ao, mr_debug_dof, mr_debug_motion
+template <class Pass>
+static int pass_counts(mr_scene *sc, Pass mr_scene::*pass, int32_t *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    const Pass &a = sc->*pass;
+    out[0] = a.frames; out[1] = a.rows; out[2] = a.cols;
+    return MR_OK;
+}
+
+// the mr_debug_*_times of the passes: the device time of every span (from mark, to mark) of the last frame that ran the pass
+template <class Pass>
+static int pass_times(mr_scene *sc, Pass mr_scene::*pass, const char *none_yet, float *out_ms, std::initializer_list<std::array<int, 2>> spans)
+{
+    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
+    const Pass &a = sc->*pass;
+    if (!a.marked) return fail(MR_E_INVALID, none_yet);
+    for (const auto &span : spans)
+        if (int rc = a.marks.elapsed(span[0], span[1], out_ms++)) return rc;
+    return MR_OK;
+}
 
 extern "C" {
 
@@ -190,9 +230,7 @@ void mr_scene_destroy(mr_scene *sc)
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
     accum_release(sc->accum);
-    ao_release(sc->ao);
-    dof_release(sc->dof);
-    motion_release(sc->motion);
+    release_pass(sc->ao); release_pass(sc->dof); release_pass(sc->motion);
     motion_faces_release(sc);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
@@ -240,7 +278,7 @@ int mr_scene_set_overlay(mr_scene *sc, const mr_overlay_desc *ov)
     if (!ov || ov->n_points <= 0 || ov->n_segments <= 0) return MR_OK;
     if (!ov->seg_first || !ov->seg_count || !ov->target || !ov->z)
         return fail(MR_E_INVALID, "overlay description has NULL arrays");
-    if (ov->width <= 0 || ov->height <= 0 || ov->width > 32767 || ov->height > 32767)
+    if (!frame_size_ok(ov->height, ov->width))
         return fail(MR_E_INVALID, "overlay description: bad frame size");
     const int np = ov->n_points;
     // validate before the kernel trusts them: segments inside the point range, one after the other; targets pixels
@@ -280,7 +318,7 @@ int mr_scene_set_overlay_cameras(mr_scene *sc, const double *corners, const doub
                                  int32_t height, int32_t width)
 {
     if (!sc) return fail(MR_E_INVALID, "scene is NULL");
-    if (!corners || !planes || !mvp || !viewport || height <= 0 || width <= 0 || height > 32767 || width > 32767)
+    if (!corners || !planes || !mvp || !viewport || !frame_size_ok(height, width))
         return fail(MR_E_INVALID, "mr_scene_set_overlay_cameras: bad argument");
     if (int rc = ensure_init()) return rc;
     mr_scene::OvPending &p = sc->ov_pending;
@@ -565,11 +603,9 @@ int mr_debug_accum_times(mr_scene *sc, float *out_ms)
     if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
     const mr_scene::Accum &a = sc->accum;
     if (!a.add_marked) return fail(MR_E_INVALID, "nothing accumulated yet");
-    HIP_TRY(hipEventSynchronize(a.ev[1]));           // (mr_accum_add does not wait for its kernel)
-    HIP_TRY(hipEventElapsedTime(&out_ms[0], a.ev[0], a.ev[1]));
+    if (int rc = a.marks.elapsed(0, 1, &out_ms[0])) return rc;      // (mr_accum_add does not wait for its kernel)
     out_ms[1] = 0.f;                                 // (no mr_accum_resolve since mr_accum_begin)
-    if (a.resolve_marked) HIP_TRY(hipEventElapsedTime(&out_ms[1], a.ev[2], a.ev[3]));
-    return MR_OK;
+    return a.resolve_marked ? a.marks.elapsed(2, 3, &out_ms[1]) : MR_OK;
 }
 
 int mr_host_accum(const float *frames, const double *weights, int32_t n, int32_t height, int32_t width, int32_t shift, double scale,
@@ -580,14 +616,7 @@ int mr_host_accum(const float *frames, const double *weights, int32_t n, int32_t
 
 int mr_scene_set_ambient_occlusion(mr_scene *sc, const mr_ao_desc *ao)
 {
-    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
-    if (!ao) { sc->ao.on = false; return MR_OK; }      // (frames already enqueued took their copy)
-    mr::AoParams p;
-    if (int rc = ao_params(ao, p)) return rc;
-    if (int rc = ao_linked()) return rc;
-    sc->ao.params = p;
-    sc->ao.on = true;
-    return MR_OK;
+    return set_pass(sc, &mr_scene::ao, ao, ao_params, ao_linked);
 }
 
 int mr_host_ao(const double *z, const float *frame, int32_t height, int32_t width, const mr_ao_desc *ao, float *out_frame)
@@ -597,30 +626,17 @@ int mr_host_ao(const double *z, const float *frame, int32_t height, int32_t widt
 
 int mr_debug_ao(mr_scene *sc, int32_t *out)
 {
-    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
-    out[0] = sc->ao.frames; out[1] = sc->ao.rows; out[2] = sc->ao.cols;
-    return MR_OK;
+    return pass_counts(sc, &mr_scene::ao, out);
 }
 
 int mr_debug_ao_times(mr_scene *sc, float *out_ms)
 {
-    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->ao.marked) return fail(MR_E_INVALID, "no frame with ambient occlusion yet");
-    HIP_TRY(hipEventSynchronize(sc->ao.ev[1]));      // (no entry point waits for the kernel itself)
-    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->ao.ev[0], sc->ao.ev[1]));
-    return MR_OK;
+    return pass_times(sc, &mr_scene::ao, "no frame with ambient occlusion yet", out_ms, { { 0, 1 } });
 }
 
 int mr_scene_set_depth_of_field(mr_scene *sc, const mr_dof_desc *dof)
 {
-    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
-    if (!dof) { sc->dof.on = false; return MR_OK; }      // (frames already enqueued took their copy)
-    mr::DofParams p;
-    if (int rc = dof_params(dof, p)) return rc;
-    if (int rc = dof_linked()) return rc;
-    sc->dof.params = p;
-    sc->dof.on = true;
-    return MR_OK;
+    return set_pass(sc, &mr_scene::dof, dof, dof_params, dof_linked);
 }
 
 int mr_host_dof(const double *z, const float *frame, int32_t height, int32_t width, const mr_dof_desc *dof, float *out_frame)
@@ -630,18 +646,12 @@ int mr_host_dof(const double *z, const float *frame, int32_t height, int32_t wid
 
 int mr_debug_dof(mr_scene *sc, int32_t *out)
 {
-    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
-    out[0] = sc->dof.frames; out[1] = sc->dof.rows; out[2] = sc->dof.cols;
-    return MR_OK;
+    return pass_counts(sc, &mr_scene::dof, out);
 }
 
 int mr_debug_dof_times(mr_scene *sc, float *out_ms)
 {
-    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->dof.marked) return fail(MR_E_INVALID, "no frame with depth of field yet");
-    HIP_TRY(hipEventSynchronize(sc->dof.ev[1]));      // (no entry point waits for the kernel itself)
-    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->dof.ev[0], sc->dof.ev[1]));
-    return MR_OK;
+    return pass_times(sc, &mr_scene::dof, "no frame with depth of field yet", out_ms, { { 0, 1 } });
 }
 
 int mr_debug_post(mr_scene *sc, const float *frames, const double *z, int32_t n, int32_t height, int32_t width, const mr_ao_desc *ao,
@@ -689,19 +699,12 @@ int mr_read_velocity(mr_scene *sc, float *out)
 
 int mr_debug_motion(mr_scene *sc, int32_t *out)
 {
-    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
-    out[0] = sc->motion.frames; out[1] = sc->motion.rows; out[2] = sc->motion.cols;
-    return MR_OK;
+    return pass_counts(sc, &mr_scene::motion, out);
 }
 
 int mr_debug_motion_times(mr_scene *sc, float *out_ms)
 {
-    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->motion.marked) return fail(MR_E_INVALID, "no frame with motion blur yet");
-    HIP_TRY(hipEventSynchronize(sc->motion.ev[2]));      // (no entry point waits for the kernels themselves)
-    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->motion.ev[0], sc->motion.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&out_ms[1], sc->motion.ev[sc->motion.blur_from], sc->motion.ev[2]));
-    return MR_OK;
+    return pass_times(sc, &mr_scene::motion, "no frame with motion blur yet", out_ms, { { 0, 1 }, { sc ? sc->motion.blur_from : 1, 3 } });
 }
 
 int mr_debug_motion_post(mr_scene *sc, const double *z, const int32_t *winner, const float *frame, const int32_t *face_off, int32_t height,
@@ -779,12 +782,7 @@ int mr_debug_motion_faces(mr_scene *sc, int32_t *out)
 
 int mr_debug_motion_faces_times(mr_scene *sc, float *out_ms)
 {
-    if (!sc || !out_ms) return fail(MR_E_INVALID, "NULL argument");
-    if (!sc->mfaces.marked) return fail(MR_E_INVALID, "no frame with the per-face velocity yet");
-    HIP_TRY(hipEventSynchronize(sc->mfaces.ev[2]));
-    HIP_TRY(hipEventElapsedTime(&out_ms[0], sc->mfaces.ev[0], sc->mfaces.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&out_ms[1], sc->mfaces.ev[1], sc->mfaces.ev[2]));
-    return MR_OK;
+    return pass_times(sc, &mr_scene::mfaces, "no frame with the per-face velocity yet", out_ms, { { 0, 1 }, { 1, 2 } });
 }
 
 int64_t mr_overlay_state_bytes(mr_scene *sc)

@@ -452,6 +452,47 @@ def test_without_the_flag_the_frame_is_the_parents(api, native):
     assert Lib.calls[3:] == ["mr_scene_set_motion_faces", "mr_scene_track_vertices"], "off again, tracking too"
 
 
+@pytest.mark.parametrize("attr, sync, entry, make, changed", [
+    ("ambient_occlusion", "sync_ambient_occlusion", "mr_scene_set_ambient_occlusion", lambda pkg: pkg.AmbientOcclusion(radius=0.5),
+     lambda pkg: pkg.AmbientOcclusion(radius=0.25)),
+    ("depth_of_field", "sync_depth_of_field", "mr_scene_set_depth_of_field", lambda pkg: pkg.DepthOfField(lens_radius=0.1),
+     lambda pkg: pkg.DepthOfField(lens_radius=0.2))], ids=["ambient_occlusion", "depth_of_field"])
+def test_a_description_goes_over_when_it_changes_and_only_then(api, native, attr, sync, entry, make, changed):
+    """``DeviceRenderer._sync_desc`` behind its two callers, on a renderer whose ``__init__`` never ran and a library
+    that counts its calls: none without the pass, one with it, none for the same description again, one for a changed
+    one, one -- with a NULL description -- when the pass has gone, and none after that."""
+    import py_numpy_renderer_amd as pkg
+
+    class Lib:                                                      # (counts its calls and keeps whether a description came)
+        def __init__(self):
+            self.calls = []
+
+        def __getattr__(self, name):
+            return lambda handle, desc=None: self.calls.append((name, desc is not None)) or 0
+
+    scene = scenes.cube_small(api)
+    renderer = native.DeviceRenderer.__new__(native.DeviceRenderer)
+    renderer.lib, renderer.handle = Lib(), None
+    go = lambda: getattr(renderer, sync)(scene)
+    go()
+    assert renderer.lib.calls == [], "a scene without the pass makes no call"
+    setattr(scene, attr, make(pkg))
+    go()
+    assert renderer.lib.calls == [(entry, True)]
+    go()
+    setattr(scene, attr, make(pkg))                                 # (an equal object: the description is compared by value)
+    go()
+    assert len(renderer.lib.calls) == 1, "the same description is handed over once"
+    setattr(scene, attr, changed(pkg))
+    go()
+    assert renderer.lib.calls[1:] == [(entry, True)], "a changed description goes over"
+    setattr(scene, attr, None)
+    go()
+    assert renderer.lib.calls[2:] == [(entry, False)], "the pass has gone: one call with a NULL description"
+    go()
+    assert len(renderer.lib.calls) == 3
+
+
 def test_the_python_class(api):
     from py_numpy_renderer_amd import MotionBlur
     mb = MotionBlur()

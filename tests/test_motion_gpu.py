@@ -7,6 +7,10 @@ scene -- the same recipe, camera and poses, without ``motion_blur`` -- hands out
 scene handed to the library.  ``read_velocity()`` and the float frame F' must match bit for bit, the frame's bytes must be
 ``mr_host_accum([F'], [1], scale=1)`` byte for byte, and Z must be unchanged."""
 import ctypes as C
+import hashlib
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +19,8 @@ import motion_ref
 import scenes
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SQUEEZED = dict(small_pairs=4, big_pairs=2, quads=3, work=16)      # the capacities of test_accumulate_gpu.py's overflow test
 SMALL = (136, 152)                                                  # the cube-and-floor captures' size
@@ -325,4 +331,121 @@ def test_refusals_and_switching_off(api):
     with scene.accumulate() as acc:                                     # (and so does an accumulation)
         acc.add(1.0)
         assert acc.result().shape == moved.shape
+    scene.close()
+
+
+# ---------------------------------------------------------------------------- 4. the workgroup shapes of k_mblur
+_PAN = dict(position=(0.8, 3, 4.8), up=(0, 1, 0), fovy=90, near=0.0001, far=400, backface_culling=False, center=(0.2, 0, 0))
+
+_CHILD = r"""
+import hashlib, sys
+import numpy as np
+sys.path[:0] = [{root!r}, {tests!r}]
+import scenes
+from py_numpy_renderer_amd import MotionBlur
+api = scenes.product_api()
+scene = scenes.diablo_floor_lh_gl(api, resolution=(135, 240))
+scene.motion_blur = MotionBlur(shutter=1.0)
+scene.render()
+pan = dict({pan!r})
+scene.camera = api.Camera(pan.pop("position"), up=np.array(pan.pop("up")), **pan)
+scene.render()
+print("digest", hashlib.sha256(np.ascontiguousarray(scene._backend().read_frame_f32()).tobytes()).hexdigest())
+scene.close()
+"""
+
+
+def _panned(api, scene):
+    pan = dict(_PAN)
+    scene.camera = api.Camera(pan.pop("position"), up=np.array(pan.pop("up")), **pan)
+
+
+@pytest.fixture(scope="module")
+def panned_digest(api):
+    """The digest of the float frame of diablo_floor_lh_gl (135, 240) behind a pan of the camera, rendered here with
+    whatever shape this process took (MR_MBLUR_TILE unset: the default's); the frame is not the unblurred one."""
+    scene = scenes.diablo_floor_lh_gl(api, resolution=(135, 240))
+    scene.motion_blur = _blur()
+    scene.render()
+    _panned(api, scene)
+    scene.render()
+    got = scene._backend().read_frame_f32().copy()
+    scene.close()
+    twin = scenes.diablo_floor_lh_gl(api, resolution=(135, 240))
+    _panned(api, twin)
+    _, _, plain = _twin_taps(twin)
+    twin.close()
+    changed = _changed(got, plain)
+    print(f"the pan blurs {changed.mean():.1%} of {changed.size} samples")
+    assert changed.sum() > changed.size // 10, "the second frame is not blurred: equal digests would show nothing"
+    return hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest()
+
+
+@pytest.mark.parametrize("shape", ["32x32", "32x32x256", "16x16", "8x8"])
+def test_every_workgroup_shape_gives_the_same_bits(panned_digest, shape):
+    """MR_MBLUR_TILE is read once per process: a fresh child renders with each shape.  8x8 is a spelling the library does
+    not know: it takes the default shape, so its digest is the default's as well."""
+    assert "MR_MBLUR_TILE" not in os.environ, "this process rendered the reference frame with a shape of its own"
+    code = _CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), pan=_PAN)
+    proc = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MR_MBLUR_TILE=shape), timeout=300, capture_output=True, text=True)
+    assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
+    lines = [ln.split()[1] for ln in proc.stdout.splitlines() if ln.startswith("digest ")]
+    assert lines == [panned_digest], f"MR_MBLUR_TILE={shape}: the float frame is not the default shape's"
+
+
+# ---------------------------------------------------------------------------- 5. the staged tables grow under the slot's frames
+def _own_velocity(scene, label):
+    """``read_velocity()`` of the frame just rendered against ``mr_host_velocity`` on that frame's own z-buffer and
+    winner map; returns (U, winner)."""
+    from py_numpy_renderer_amd import _native
+    backend = scene._backend()
+    u, z, winner = backend.read_velocity().copy(), backend.read_z().copy(), backend.read_winner().copy()
+    want = _native.host_velocity(z, winner, _face_off(scene), _desc(scene))
+    bits = _bits(u, want)
+    print(f"{label}: {bits} of {u.size} velocity floats differ from the mirror, |U| up to {np.hypot(u[..., 0], u[..., 1]).max():.2f}")
+    assert bits == 0, f"{label}: read_velocity() is not mr_host_velocity's on the frame's own taps"
+    return u, winner
+
+
+def test_the_staged_tables_regrow_between_two_frames_of_one_slot(api):
+    """A frame with one motion class, then one whose table block is more than twice as large, on the same slot: the
+    page-locked copy (StagedTable, host_pass.h) is allocated for twice the bytes it was first asked for, so only such a step
+    reaches the branch that frees it and allocates again, behind the wait for the upload that last read it.
+
+    The frames are rendered back to back with ``render()``.  ``render_async`` and ``render_wait`` on one lane would not
+    keep the first upload in flight either: a lane takes one frame at a time, and ``render_wait`` drains its stream
+    before the next frame is staged."""
+    from py_numpy_renderer_amd import _pack, translation
+    pose = lambda *t: np.asarray(translation(t), dtype=np.float64)
+    scene = scenes.cube_outward(api, resolution=(135, 240))
+    for x in (-0.9, 0.9):
+        cube = api.Model.load_model(os.path.join(scenes.ASSETS, "cube", "cube.obj")) @ api.scale(0.3)
+        scene.add_model(cube)
+        cube.pose = pose(x, 0.0, 0.3)
+    scene.motion_blur = _blur()
+    scene.render()
+
+    def table_bytes():                     # (of the frame about to be issued: the block motion_params assembles)
+        _, matrices, background, class_of, _ = _pack.motion_matrices(scene, scene.__dict__["_motion_prev"])
+        return matrices.nbytes + background.nbytes + 2 * class_of.nbytes, int(class_of.max()) + 1
+
+    _look(api, scene, (0.6, 1.0, 1.95))
+    first_bytes, first_classes = table_bytes()
+    scene.render()
+    u, winner = _own_velocity(scene, "the camera moved")
+    assert first_classes == 1 and u[winner >= 0].any()
+
+    scene.models[0].pose = pose(0.1, 0.0, -0.05)
+    scene.models[2].pose = pose(-0.8, 0.05, 0.3)
+    scene.models[3].pose = pose(0.78, 0.05, 0.3)
+    second_bytes, second_classes = table_bytes()
+    print(f"table blocks of {first_bytes} and {second_bytes} bytes, {first_classes} and {second_classes} classes")
+    assert second_classes == 4 and second_bytes > 2 * first_bytes, "the second table fits the first one's staging copy"
+    scene.render()
+    u, winner = _own_velocity(scene, "three models moved, each its own way")
+    faces = np.cumsum([0] + [len(m._faces) for m in scene.models])
+    moved = [np.hypot(*u[(winner >= faces[m]) & (winner < faces[m + 1])].mean(axis=0)) for m in (0, 2, 3)]
+    floor = (winner >= faces[1]) & (winner < faces[2])
+    assert min(moved) > 0.5 and np.abs(u[floor]).max() < 1e-6, f"the three models' mean |U| {moved}; the floor stays"
+    assert scene._backend().motion_debug() == (3, 135, 240)
     scene.close()
