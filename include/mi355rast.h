@@ -849,7 +849,8 @@ int mr_read_velocity(mr_scene *scene, float *out);
 int mr_debug_motion(mr_scene *scene, int32_t *out);
 
 /* Device times in milliseconds of the last k_velocity and the last k_mblur (HIP events on their frame's stream).  Waits for
- * them.  MR_E_INVALID before the first such frame. */
+ * them.  MR_E_INVALID before the first such frame.  A frame of a scene with temporal anti-aliasing took its U from the
+ * k_velocity in front of k_taa and ran none of its own: its velocity span reads 0 (mr_debug_taa_times has that launch). */
 #define MR_N_MOTION_TIMES 2
 int mr_debug_motion_times(mr_scene *scene, float *out_ms);
 
@@ -932,6 +933,81 @@ int mr_debug_read_prev_vertices(mr_scene *scene, double *out);
 int mr_debug_motion_faces(mr_scene *scene, int32_t *out);
 #define MR_N_MOTION_FACES_TIMES 2
 int mr_debug_motion_faces_times(mr_scene *scene, float *out_ms);
+
+/* Temporal anti-aliasing: a frame's float colours blended into the colours the previous frame of the scene left, fetched
+ * where every sample's surface point was.  It lives on the frame's sample grid (Hs, Ws), rows bottom-up, at integer screen
+ * coordinates p = (x, y).  With F the float frame after the sum over the lights and the ambient obscurance -- BEFORE the
+ * depth of field, the motion blur and the overlay -- U the velocity (as for the motion blur: mr_read_velocity), P the
+ * history or none and a = blend, float32 throughout, every operation rounded on its own:
+ *
+ *   C = F[p];   no history: out = C
+ *   rx = (float)x - U.x;  ry = (float)y - U.y;   unless rx in [0, Ws-1] and ry in [0, Hs-1] (or no number): out = C
+ *   x0 = (int)floorf(rx), fx = rx - (float)x0, x1 = min(x0 + 1, Ws-1);   y0, fy, y1 likewise
+ *   t0 = P[y0][x0] + fx*(P[y0][x1] - P[y0][x0]);  t1 likewise on row y1;  H = t0 + fy*(t1 - t0)            per channel
+ *   mn, mx = fminf / fmaxf over F at the 3 x 3 samples round p, coordinates clamped to the frame, rows then columns ascending
+ *   Hk = fminf(fmaxf(H, mn), mx);   out = Hk + a*(C - Hk);   P'[p] = out for every sample
+ *
+ * U == 0 fetches H == P[p] bit for bit, and P == F then gives out == C bit for bit.  The neighbourhood clamp is the only
+ * rejection of stale history.  Frame order: the lights' sum, k_ao, k_velocity (and the per-face pair where due), k_taa,
+ * k_dof, k_mblur, the overlay, the finalise of the result; the history holds the frame as k_taa left it.  With motion blur
+ * on as well, one k_velocity serves both: both descriptions must carry the same matrices, background and classes.
+ *
+ * The scene owns the history: two float frames on the sample grid.  A frame reads the one left by the last frame with the
+ * pass whose mr_render or mr_render_wait returned MR_OK and writes the other, which that return hands over.  A frame that
+ * overflowed a work list hands nothing over: rendered again, it reads the same history.  The history is forgotten by
+ * mr_scene_reset_history, by mr_scene_set_temporal_aa(NULL) and by a frame on a sample grid of another size; the next
+ * frame then has none, and a frame still in flight hands nothing over.
+ *
+ * mr_scene_set_temporal_aa copies everything during the call (NULL: off, the default); every frame enqueued afterwards
+ * by mr_render or mr_render_async uses the copy of its moment, keeps its z-buffer, winner map and float frame
+ * (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT are implied) and owns a second float frame and a velocity buffer.  A scene
+ * without it enqueues what it always did.  MR_E_INVALID for a blend outside (0, 1] as float32 and whatever
+ * mr_scene_set_motion_blur refuses of the matrices; and, from the rendering entry points, for a partial frame (row band,
+ * stripes), a sub-frame of an accumulation, mr_render_device, a scene whose number of models changed since the call,
+ * table blocks that differ from the motion blur's, and a frame enqueued while an earlier one with the pass has not been
+ * waited for (host order is the only ordering between the frames' lanes) -- all before any device work.
+ * MR_E_UNSUPPORTED from a library linked without taa.hip, motion.hip or accum.hip. */
+typedef struct mr_taa_desc {
+    double blend;                  /* the share of the new frame: (0, 1] as float32 */
+    const double *matrices;        /* as in mr_motion_desc: n_classes x 12 */
+    double background[9];
+    const int32_t *class_of_model; /* n_models classes (may be NULL when n_models is 0) */
+    int32_t n_classes, n_models;
+} mr_taa_desc;
+int mr_scene_set_temporal_aa(mr_scene *scene, const mr_taa_desc *taa);
+int mr_scene_reset_history(mr_scene *scene);
+
+/* The history as the scene holds it now: float32 (Hs, Ws, 3), rows bottom-up.  MR_E_INVALID, with a text, when there is
+ * none.  Waits for the device. */
+int mr_read_history(mr_scene *scene, float *out);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what k_taa writes.  frame, history and out_frame
+ * are (height, width, 3) float32, velocity (height, width, 2); history may be NULL (no history).  MR_E_INVALID for a NULL
+ * array, out_frame == frame or == history, a blend outside (0, 1] as float32, or a height or width outside 1 .. 32767. */
+int mr_host_taa(const float *frame, const float *velocity, const float *history, int32_t height, int32_t width, double blend,
+                float *out_frame);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued k_taa (every enqueue, also one rendered again after an
+ * overflow), out[1], out[2] = the sample rows and columns of the last of them (0 before the first), out[3] = k_velocity
+ * launches made in front of k_taa, out[4] = histories handed over, out[5] = 1 while the scene holds a history.  Does not wait. */
+#define MR_N_TAA_COUNTS 6
+int mr_debug_taa(mr_scene *scene, int32_t *out);
+
+/* Device times in milliseconds of the last frame with the pass: its k_velocity (with the per-face pair where that ran) and
+ * its k_taa.  Waits for them.  MR_E_INVALID before the first such frame.  For a frame that ran both this pass and the
+ * motion blur, mr_debug_motion_times reports a velocity span of 0: the one k_velocity is counted here. */
+#define MR_N_TAA_TIMES 2
+int mr_debug_taa_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: k_taa on buffers the caller supplies -- no frame is rendered.  Arrays as for mr_host_taa; shape is the
+ * workgroup: 0 = 32 x 8 samples, 1 = 64 x 4, 2 = 16 x 16, 256 threads each (never MR_TAA_TILE's).  out_frame and
+ * out_history receive the kernel's two outputs; on the device both lie between 256 bytes of sentinel either side, and
+ * out_guard receives the number of those bytes that changed (0 unless the kernel wrote out of bounds).  The scene lends its
+ * error text only: its frame slots, its history and what mr_debug_taa reports stay as they were.  Waits for the device.
+ * MR_E_INVALID, before any device call, for a NULL argument (history may be NULL), a height or width outside 1 .. 32767, a
+ * shape outside 0 .. 2 and a blend outside (0, 1] as float32. */
+int mr_debug_taa_post(mr_scene *scene, const float *frame, const float *velocity, const float *history, int32_t height,
+                      int32_t width, double blend, int32_t shape, float *out_frame, float *out_history, int32_t *out_guard);
 
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit

@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -133,6 +133,29 @@ def fill_motion_desc(depth_map, shutter, matrices, background, class_of_model):
     for i in range(9):
         d.background[i] = float(background.flat[i])
     d.shutter = float(shutter)
+    d.matrices = matrices.ctypes.data
+    d.class_of_model = class_of_model.ctypes.data if len(class_of_model) else None
+    d.n_classes, d.n_models = len(matrices), len(class_of_model)
+    d._arrays = (matrices, class_of_model)
+    return d
+
+
+class TaaDesc(C.Structure):
+    _fields_ = [("blend", C.c_double), ("matrices", C.c_void_p), ("background", C.c_double * 9), ("class_of_model", C.c_void_p),
+                ("n_classes", C.c_int32), ("n_models", C.c_int32)]
+
+
+def fill_taa_desc(blend, matrices, background, class_of_model):
+    """``mr_taa_desc``: *blend* and the velocity's tables as ``fill_motion_desc`` takes them (``_pack.motion_matrices``).  The
+    description keeps its copies of the arrays alive (``_arrays``); the library copies everything during the call it is
+    handed to."""
+    matrices = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 4, 3)
+    background = np.ascontiguousarray(background, dtype=np.float64).reshape(3, 3)
+    class_of_model = np.ascontiguousarray(class_of_model, dtype=np.int32).ravel()
+    d = TaaDesc()
+    d.blend = float(blend)
+    for i in range(9):
+        d.background[i] = float(background.flat[i])
     d.matrices = matrices.ctypes.data
     d.class_of_model = class_of_model.ctypes.data if len(class_of_model) else None
     d.n_classes, d.n_models = len(matrices), len(class_of_model)
@@ -278,6 +301,14 @@ _PROTOTYPES = {
     "mr_debug_read_prev_vertices": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_motion_faces": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_motion_faces_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_scene_set_temporal_aa": (C.c_int, [C.c_void_p, C.POINTER(TaaDesc)]),
+    "mr_scene_reset_history": (C.c_int, [C.c_void_p]),
+    "mr_read_history": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_host_taa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p]),
+    "mr_debug_taa": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_taa_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_taa_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -465,6 +496,40 @@ def debug_motion_post(handle, z, winner, frame, face_off, desc, shape=0):
                                                      C.byref(desc), int(shape), vel.ctypes.data, out.ctypes.data),
                  "mr_debug_motion_post")
     return vel, out
+
+
+def _taa_arrays(frame, velocity, history):
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    velocity = np.ascontiguousarray(velocity, dtype=np.float32)
+    history = None if history is None else np.ascontiguousarray(history, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 3 or velocity.shape != frame.shape[:2] + (2,) or (history is not None and history.shape != frame.shape):
+        raise ValueError(f"frame and history must be (H, W, 3) and velocity (H, W, 2), got {frame.shape}, "
+                         f"{None if history is None else history.shape} and {velocity.shape}")
+    return frame, velocity, history
+
+
+def host_taa(frame, velocity, history, blend):
+    """``mr_host_taa``: the temporal anti-aliasing's definition on the host, no device.  *frame* ``(Hs, Ws, 3)`` float32,
+    *velocity* ``(Hs, Ws, 2)`` float32, *history* like *frame* or ``None`` (no history); returns the blended frame, which is
+    also the new history.  ``ValueError`` with the library's text for what it refuses."""
+    frame, velocity, history = _taa_arrays(frame, velocity, history)
+    out = np.empty_like(frame)
+    _check_accum(load_library().mr_host_taa(frame.ctypes.data, velocity.ctypes.data, None if history is None else history.ctypes.data,
+                                            frame.shape[0], frame.shape[1], float(blend), out.ctypes.data), "mr_host_taa")
+    return out
+
+
+def debug_taa_post(handle, frame, velocity, history, blend, shape=0):
+    """``mr_debug_taa_post``: k_taa on the caller's arrays, no frame rendered; *shape* 0 .. 2 is its workgroup.  Returns
+    ``(the float frame, the new history, guard bytes the kernel changed)``."""
+    frame, velocity, history = _taa_arrays(frame, velocity, history)
+    out, hist = np.empty_like(frame), np.empty_like(frame)
+    guard = C.c_int32(-1)
+    _check_accum(load_library().mr_debug_taa_post(handle, frame.ctypes.data, velocity.ctypes.data,
+                                                  None if history is None else history.ctypes.data, frame.shape[0], frame.shape[1],
+                                                  float(blend), int(shape), out.ctypes.data, hist.ctypes.data, C.byref(guard)),
+                 "mr_debug_taa_post")
+    return out, hist, int(guard.value)
 
 
 def _face_arrays(verts_now, verts_prev, faces, s_now, s_prev):
@@ -902,8 +967,9 @@ class DeviceRenderer:
         self._sync_desc(scene, "dof", "mr_scene_set_depth_of_field", self._dof_values, lambda sc: fill_dof_desc(*dof_constants(sc)))
 
     def _sync_post(self, scene):
-        """The post passes of the frame being issued, in the order they run: the four descriptions in step with *scene*."""
+        """The post passes of the frame being issued, in the order they run: the five descriptions in step with *scene*."""
         self.sync_ambient_occlusion(scene)
+        self.sync_temporal_aa(scene)
         self.sync_depth_of_field(scene)
         self.sync_motion_blur(scene)
         self.sync_motion_faces(scene)
@@ -913,33 +979,93 @@ class DeviceRenderer:
         """The motion of the frame being issued by value (``None`` without ``motion_blur``), for ``_frame_key``."""
         return None if getattr(scene, "motion_blur", None) is None else scene.__dict__.get("_motion_frame")
 
+    @staticmethod
+    def _taa_values(scene):
+        """The temporal anti-aliasing of the frame being issued by value (``None`` without ``temporal_aa``), for ``_frame_key``."""
+        return None if getattr(scene, "temporal_aa", None) is None else scene.__dict__.get("_taa_frame")
+
     def issue_motion(self, scene, partial=False, accumulating=False):
-        """A frame of *scene* is being issued: with ``motion_blur`` set, the matrices that lead from it to the previous
-        frame's state (``_pack.motion_matrices``) become the scene's ``_motion_frame`` -- by value, for ``_frame_key`` and
-        ``sync_motion_blur`` -- and its own state becomes the previous one.  A frame rendered again after an overflow
-        (``PendingFrame.result``) takes the matrices of its first attempt and leaves the previous state alone."""
-        mb = getattr(scene, "motion_blur", None)
+        """A frame of *scene* is being issued: with ``motion_blur`` or ``temporal_aa`` set, the matrices that lead from it to
+        the previous frame's state (``_pack.motion_matrices``) become the scene's ``_motion_frame`` / ``_taa_frame`` -- by
+        value, for ``_frame_key``, ``sync_motion_blur`` and ``sync_temporal_aa``, both from the same tables -- and its own
+        state becomes the previous one.  With ``temporal_aa`` the frame also takes its place k in the jitter's sequence
+        (``_pack.taa_jitter``), which becomes the scene's ``_sample_jitter`` until the frame's descriptor is filled; the
+        history is forgotten -- k = 0, and ``sync_temporal_aa`` calls ``mr_scene_reset_history`` -- after ``reset_motion()`` (which every assignment of
+        ``motion_blur`` or ``temporal_aa`` calls), with another model list and with a sample grid of another size.  A frame
+        rendered again after an overflow (``PendingFrame.result``) takes the matrices and the jitter of its first attempt
+        and leaves the previous state alone."""
+        mb, taa = getattr(scene, "motion_blur", None), getattr(scene, "temporal_aa", None)
         if mb is None:
             scene.__dict__.pop("_motion_frame", None)
+        if taa is None:
+            scene.__dict__.pop("_taa_frame", None)
+        if mb is None and taa is None:
             return
-        if partial:
+        if partial and mb is not None:
             raise ValueError("motion blur takes whole frames (no row band, no stripes): its taps cross the bands")
-        if accumulating:
+        if partial:
+            raise ValueError("temporal AA takes whole frames (no row band, no stripes): its taps cross the bands")
+        if accumulating and mb is not None:
             raise ValueError("motion_blur is not available inside accumulate() / render_mean(): the accumulation is the "
                              "other way to blur motion, and its sub-frames have no previous frame")
-        replay = scene.__dict__.get("_motion_replay")
-        if replay is not None:
-            scene.__dict__["_motion_frame"] = replay
-            scene.__dict__["_motion_faces_frame"] = scene.__dict__.get("_motion_faces_replay")
+        if accumulating:
+            raise ValueError("temporal_aa is not available inside accumulate() / render_mean(): the accumulation is the "
+                             "other way to spread samples over frames, and its sub-frames have no history")
+        if taa is not None and scene.__dict__.get("_pending"):
+            raise ValueError("temporal_aa takes one frame of the scene at a time: another frame is pending, take its "
+                             "result() first (every frame reads the history the frame before it left)")
+        replay, taa_replay = scene.__dict__.get("_motion_replay"), scene.__dict__.get("_taa_replay")
+        if replay is not None or taa_replay is not None:
+            if mb is not None and replay is not None:
+                scene.__dict__["_motion_frame"] = replay
+                scene.__dict__["_motion_faces_frame"] = scene.__dict__.get("_motion_faces_replay")
+            if taa is not None and taa_replay is not None:
+                scene.__dict__["_taa_frame"] = taa_replay
+                scene.__dict__["_sample_jitter"] = taa_replay[4]
             return
         previous = scene.__dict__.get("_motion_prev")
+        if taa is not None:
+            grid = tuple(sample_grid(scene)[1:3])
+            if grid != scene.__dict__.get("_taa_grid"):          # (resolution or supersample: the previous S is another grid's too)
+                previous = None
+            scene.__dict__["_taa_grid"] = grid
         depth_map, matrices, background, class_of, state = motion_matrices(scene, previous)
-        scene.__dict__["_motion_frame"] = (mb.shutter, tuple(depth_map), matrices.tobytes(), background.tobytes(), class_of.tobytes())
-        scene.__dict__["_motion_faces_frame"] = None
-        if mb.deformation:             # (the per-face velocity of the models that bend: _pack.motion_vertices)
-            s_now, s_prev, deforming, prev_serial = motion_vertices(scene, previous, state)
-            scene.__dict__["_motion_faces_frame"] = (s_now.tobytes(), s_prev.tobytes(), deforming.tobytes(), int(prev_serial))
+        if mb is not None:
+            scene.__dict__["_motion_frame"] = (mb.shutter, tuple(depth_map), matrices.tobytes(), background.tobytes(), class_of.tobytes())
+            scene.__dict__["_motion_faces_frame"] = None
+            if mb.deformation:             # (the per-face velocity of the models that bend: _pack.motion_vertices)
+                s_now, s_prev, deforming, prev_serial = motion_vertices(scene, previous, state)
+                scene.__dict__["_motion_faces_frame"] = (s_now.tobytes(), s_prev.tobytes(), deforming.tobytes(), int(prev_serial))
+        if taa is not None:
+            if scene.__dict__.pop("_taa_forget", False) or previous is None or not state.same_models(previous):
+                scene.__dict__["_taa_reset"] = True            # (sync_temporal_aa tells the library)
+                scene.__dict__["_taa_k"] = 0
+            k = scene.__dict__.get("_taa_k", 0)
+            jitter = taa_jitter(k, taa.jitter)
+            scene.__dict__["_taa_k"] = k + 1
+            scene.__dict__["_taa_frame"] = (taa.blend, matrices.tobytes(), background.tobytes(), class_of.tobytes(), jitter)
+            scene.__dict__["_sample_jitter"] = jitter
         scene.__dict__["_motion_prev"] = state
+
+    def sync_temporal_aa(self, scene):
+        """``mr_scene_set_temporal_aa`` for the frames enqueued from now on, whenever the frame's description
+        (``issue_motion``) is not the one last handed over.  A scene that never had one makes no call."""
+        frame = self._taa_values(scene)
+        if scene.__dict__.pop("_taa_reset", False) and getattr(self, "_taa_key", None) is not None:
+            _check_accum(self.lib.mr_scene_reset_history(self.handle), "mr_scene_reset_history")
+        if frame is None:
+            if getattr(self, "_taa_key", None) is not None:
+                _check_accum(self.lib.mr_scene_set_temporal_aa(self.handle, None), "mr_scene_set_temporal_aa")
+                self._taa_key = None
+            return
+        key = frame[:4]
+        if getattr(self, "_taa_key", None) == key:
+            return
+        blend, matrices, background, class_of = key
+        desc = fill_taa_desc(blend, np.frombuffer(matrices, dtype=np.float64), np.frombuffer(background, dtype=np.float64),
+                             np.frombuffer(class_of, dtype=np.int32))
+        _check_accum(self.lib.mr_scene_set_temporal_aa(self.handle, C.byref(desc)), "mr_scene_set_temporal_aa")
+        self._taa_key = key
 
     def sync_motion_faces(self, scene):
         """``mr_scene_track_vertices`` and ``mr_scene_set_motion_faces`` for the frames enqueued from now on, behind
@@ -1008,7 +1134,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -1079,7 +1205,17 @@ class DeviceRenderer:
 
     def _prepare_desc(self, scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing, overlay,
                       accumulating=False):
-        """``_prepare`` without the output array: the frame descriptor and the shape of the frame's uint8 rows."""
+        """``_prepare`` without the output array: the frame descriptor and the shape of the frame's uint8 rows.  The
+        sub-sample offset a ``temporal_aa`` gave the frame (``issue_motion``) lives until the descriptor holds it."""
+        try:
+            return self._prepare_issued(scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing,
+                                        overlay, accumulating)
+        finally:
+            if getattr(scene, "temporal_aa", None) is not None:
+                scene.__dict__.pop("_sample_jitter", None)
+
+    def _prepare_issued(self, scene, shadows, row_band, keep_float, face_status, counters, keep_buffers, stripe, timing, overlay,
+                        accumulating):
         self.issue_motion(scene, partial=self._is_partial(scene, row_band, stripe), accumulating=accumulating)
         self.sync_scene(scene)
         self.sync_skybox(scene)
@@ -1205,6 +1341,27 @@ class DeviceRenderer:
         """Device milliseconds of the last ``k_velocity`` and the last ``k_mblur`` (``mr_debug_motion_times``)."""
         return self._times(self.lib.mr_debug_motion_times, self.MOTION_TIME_NAMES)
 
+    # -- temporal anti-aliasing (Scene.temporal_aa) ----------------------------------------------
+    def read_history(self):
+        """``mr_read_history``: the history as the scene holds it now -- the last complete temporal-AA frame as ``k_taa`` left
+        it -- float32 ``(Hs, Ws, 3)`` on the sample grid, rows bottom-up.  ``ValueError`` with the library's text when
+        there is none."""
+        _, h, w = self.taa_debug()[:3]             # (the grid of the last frame with the pass: the history's, where there is one)
+        out = np.empty((max(h, 1), max(w, 1), 3), dtype=np.float32)
+        _check_accum(self.lib.mr_read_history(self.handle, out.ctypes.data), "mr_read_history")
+        return out
+
+    def taa_debug(self):
+        """``mr_debug_taa``: (frames that enqueued ``k_taa``, the last one's sample rows, its columns, ``k_velocity`` launches
+        made in front of ``k_taa``, histories handed over, 1 while the scene holds a history)."""
+        return self._counts(self.lib.mr_debug_taa, 6)
+
+    TAA_TIME_NAMES = ("velocity", "taa")
+
+    def taa_times(self):
+        """Device milliseconds of the last temporal-AA frame's ``k_velocity`` and ``k_taa`` (``mr_debug_taa_times``)."""
+        return self._times(self.lib.mr_debug_taa_times, self.TAA_TIME_NAMES)
+
     def read_prev_vertices(self, n_verts):
         """``mr_debug_read_prev_vertices``: the library's snapshot of the vertices, float64 ``(n_verts, 4)``."""
         out = np.empty((int(n_verts), 4), dtype=np.float64)
@@ -1263,6 +1420,9 @@ class DeviceRenderer:
         """``mr_render_device``: enqueue a frame whose uint8 band lands at device pointer *d_out_ptr*.  With *overlay*
         a device that renders the whole frame draws the debug frustum; one that renders part of it appends the state of
         the touched pixels it owns to its rows (``overlay_state_bytes``, ``overlay_apply``)."""
+        if getattr(scene, "temporal_aa", None) is not None:
+            raise ValueError("temporal_aa frames are rendered by render() / render_async(): their return hands the history "
+                             "over, and a frame enqueued on a caller's stream has none")
         self.issue_motion(scene, partial=self._is_partial(scene, row_band, stripe))
         self.sync_scene(scene)
         self.sync_skybox(scene)

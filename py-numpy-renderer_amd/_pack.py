@@ -275,6 +275,54 @@ def check_motion_deformation(value):
     return bool(value)
 
 
+def check_temporal_aa(blend, jitter):
+    """The parameters of a ``TemporalAA``: *blend* a Python float that lies in (0, 1] as float32, *jitter* an int in
+    0 .. 64 (the length of the sub-sample sequence; 0: no jitter)."""
+    if isinstance(blend, (bool, str, bytes)) or not isinstance(blend, (int, float, np.integer, np.floating)):
+        raise TypeError(f"temporal AA: blend must be a real number, got {blend!r}")
+    with np.errstate(over="ignore"):
+        as_f32 = np.float32(blend)
+    if not np.isfinite(as_f32) or not (0 < as_f32 <= 1):
+        raise ValueError(f"temporal AA: blend must lie in (0, 1] as float32, got {blend!r}")
+    if isinstance(jitter, (bool, np.bool_)) or not isinstance(jitter, (int, np.integer)):
+        raise TypeError(f"temporal AA: jitter must be an int, got {jitter!r}")
+    if not 0 <= jitter <= 64:
+        raise ValueError(f"temporal AA: jitter must lie in 0 .. 64, got {jitter!r}")
+    return float(blend), int(jitter)
+
+
+def _halton(i, base):
+    """The radical inverse of *i* >= 0 in *base*: Halton's sequence, float64, digit by digit from the lowest."""
+    f, r = 1.0, 0.0
+    while i > 0:
+        f /= base
+        r += f * (i % base)
+        i //= base
+    return r
+
+
+def taa_jitter(k, n):
+    """The sub-sample offset ``(jx, jy)`` of temporal-AA frame *k* (counted since the history was last forgotten) of a
+    sequence of *n*, in sample-grid units, float64: ``(0.0, 0.0)`` for ``k % n == 0`` or ``n == 0``, otherwise
+    ``(halton(k % n, 2) - 0.5, halton(k % n, 3) - 0.5)`` -- in [-0.5, 0.5), period *n*."""
+    k, n = int(k), int(n)
+    if n == 0 or k % n == 0:
+        return 0.0, 0.0
+    return _halton(k % n, 2) - 0.5, _halton(k % n, 3) - 0.5
+
+
+def sample_jitter(scene):
+    """The scene's ``_sample_jitter`` -- the private mechanism that carries a sub-sample offset into ``pack_frame`` -- as a
+    pair of floats, or ``None`` (absent or ``None``: off).  ``TemporalAA`` sets it while it issues a frame."""
+    jitter = getattr(scene, "__dict__", {}).get("_sample_jitter")
+    if jitter is None:
+        return None
+    jx, jy = (float(v) for v in jitter)
+    if not (np.isfinite(jx) and np.isfinite(jy)):
+        raise ValueError(f"_sample_jitter must be two finite numbers, got {jitter!r}")
+    return jx, jy
+
+
 class MotionState:
     """What a frame leaves for the next one's velocity: ``S = view . projection . viewport`` of its camera on the sample
     grid (one homogeneous 4x4, world to un-divided screen, float64), the scene's models (the objects themselves: another
@@ -394,16 +442,26 @@ def motion_matrices(scene, previous):
     return depth_map(scene, cam), np.ascontiguousarray(matrices, dtype=np.float64), np.ascontiguousarray(background), class_of, now
 
 
-def sample_grid(scene):
-    """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame."""
+def sample_grid(scene, jittered=False):
+    """(s, sample-grid height, sample-grid width, sample-grid viewport) of a scene's frame.  With *jittered* -- what
+    ``pack_frame`` hands to the frame, and nothing else -- the scene's ``_sample_jitter`` (``sample_jitter``), in
+    sample-grid units, is added to x and y of the viewport's translation row: the velocity, the overlay's lines and the
+    camera's offsets know nothing of it."""
     cam = scene.camera
     s = check_supersample(getattr(scene, "supersample", 1))
     height, width = (int(v) for v in scene.resolution)
     if s == 1:
-        return 1, height, width, cam.viewport
-    from .transformation import ViewPort
-    return s, s * height, s * width, ViewPort((s * height, s * width), cam.far, cam.near,
-                                              x_offset=cam.x_offset * s, y_offset=cam.y_offset * s)
+        viewport = cam.viewport
+    else:
+        from .transformation import ViewPort
+        height, width = s * height, s * width
+        viewport = ViewPort((height, width), cam.far, cam.near, x_offset=cam.x_offset * s, y_offset=cam.y_offset * s)
+    jitter = sample_jitter(scene) if jittered else None
+    if jitter is not None:
+        viewport = np.array(viewport, dtype=np.float64)
+        viewport[3, 0] += jitter[0]
+        viewport[3, 1] += jitter[1]
+    return s, height, width, viewport
 
 
 def check_pose(value):
@@ -972,7 +1030,7 @@ def pack_light(light) -> PackedLight:
 def pack_frame(scene, shadows=True) -> PackedFrame:
     cam, light = scene.camera, scene.light
     dbg = scene.debug_camera if scene.debug_camera is not None else cam
-    ss, height, width, viewport = sample_grid(scene)
+    ss, height, width, viewport = sample_grid(scene, jittered=True)
     sky = scene.skybox
     sky_tri = sky_rays = None
     if sky is not None and hasattr(sky, "textures"):

@@ -186,6 +186,32 @@ class MotionBlur:
         return f"MotionBlur(shutter={self.shutter!r}, deformation={self.deformation!r})"
 
 
+class TemporalAA:
+    """What ``Scene.temporal_aa`` holds: anti-aliasing spread over consecutive frames.  Every frame is rendered once, with a
+    sub-sample offset of its sample grid, and its float colours are blended into the history -- the previous frame as this
+    pass left it -- fetched where every sample's surface point was (the velocity buffer of ``MotionBlur``).
+
+    ``blend`` (a float32 in (0, 1], default 0.1) is the share of the new frame: ``out = H + blend * (C - H)`` with ``H`` the
+    history, clamped to the colours the 3 x 3 samples round the sample show now -- the one rejection of stale history.
+    ``jitter`` (an int in 0 .. 64, default 8) is the length of the sub-sample sequence, Halton's in bases 2 and 3 minus a
+    half, starting at (0, 0); 0 switches the jitter off.  A ``TemporalAA`` is never modified: assign a new one to change
+    it."""
+
+    __slots__ = ("blend", "jitter")
+
+    def __init__(self, blend=0.1, jitter=8):
+        from ._pack import check_temporal_aa
+        blend, jitter = check_temporal_aa(blend, jitter)
+        object.__setattr__(self, "blend", blend)
+        object.__setattr__(self, "jitter", jitter)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a TemporalAA is read-only: assign a new one to Scene.temporal_aa")
+
+    def __repr__(self):
+        return f"TemporalAA(blend={self.blend!r}, jitter={self.jitter!r})"
+
+
 class Model:
     """Triangle mesh: ``vertices`` (V,4), ``uv`` (T,3), ``normals`` (N,3) and ``_faces``
     (F,3,4) holding per corner ``[vertex, uv, normal, material-group]`` indices.
@@ -706,6 +732,7 @@ class PendingFrame:
         self._scene, self._lane, self._out, self._shadows, self._cameras = scene, lane, out, shadows, cameras
         self._motion = scene.__dict__.get("_motion_frame")      # the matrices the frame was issued with (motion_blur)
         self._motion_faces = scene.__dict__.get("_motion_faces_frame")      # ... and its per-face description (deformation)
+        self._taa = scene.__dict__.get("_taa_frame")            # ... and its blend, matrices and jitter (temporal_aa)
         self._done = False
 
     def result(self):
@@ -719,12 +746,15 @@ class PendingFrame:
                 if scene.motion_blur is not None and self._motion is not None:
                     scene.__dict__["_motion_replay"] = self._motion      # the same matrices as the first attempt
                     scene.__dict__["_motion_faces_replay"] = self._motion_faces
+                if scene.temporal_aa is not None and self._taa is not None:
+                    scene.__dict__["_taa_replay"] = self._taa            # the same jitter and matrices, the same history
                 try:
                     self._out = scene.render(shadows=self._shadows)
                 finally:
                     scene.camera, scene.debug_camera = now
                     scene.__dict__.pop("_motion_replay", None)
                     scene.__dict__.pop("_motion_faces_replay", None)
+                    scene.__dict__.pop("_taa_replay", None)
             self._done = True
         return self._out
 
@@ -858,6 +888,17 @@ class Scene:
       for byte.  Bones and morph weights move nothing unless ``MotionBlur(deformation=True)``; one layer only.  Split
       frames (``row_band``, ``multigpu``), ``accumulate()`` and ``render_mean()`` refuse it.  With ``None`` a scene
       enqueues exactly what it did without it.
+    * ``temporal_aa`` (an addition; ``None`` by default, or a ``TemporalAA``): anti-aliasing spread over consecutive frames.
+      Every frame is rendered once with a sub-sample offset and blended on the device into the history, the previous
+      frame fetched where every sample's surface point was -- behind the lights' sum and the obscurance, in front of the
+      depth of field and the motion blur, which gather from the stabilised frame, and of the debug frustum.  It shares the
+      previous frame's camera and poses with ``motion_blur`` (one velocity pass serves both);
+      ``scene._backend().read_velocity()`` and ``read_history()`` return the velocity and the history.  The history is
+      forgotten when ``temporal_aa`` or ``motion_blur`` is assigned, by ``reset_motion()``, when the model list changed and
+      when the sample grid's size changed (``resolution``, ``supersample``): the next frame is ``render()``'s byte for
+      byte.  One frame of the scene at a time: ``render_async()`` refuses while another frame is pending, and
+      ``render_frames()`` waits for every frame before it issues the next.  Split frames (``row_band``, ``multigpu``),
+      ``accumulate()`` and ``render_mean()`` refuse it.  With ``None`` a scene enqueues exactly what it did without it.
     """
 
     camera = Bound()
@@ -927,8 +968,22 @@ class Scene:
         self.reset_motion()
 
     def reset_motion(self):
-        """Forgets the previous frame's camera and poses: the next frame has identity motion, its bytes are ``render()``'s."""
+        """Forgets the previous frame's camera and poses, and the history of ``temporal_aa``: the next frame has identity
+        motion and no history, its bytes are ``render()``'s."""
         self.__dict__["_motion_prev"] = None
+        self.__dict__["_taa_forget"] = True
+
+    @property
+    def temporal_aa(self):
+        """``None`` (off, the default) or the scene's ``TemporalAA`` (see the class docstring)."""
+        return self.__dict__.get("_temporal_aa")
+
+    @temporal_aa.setter
+    def temporal_aa(self, value):
+        if value is not None and not isinstance(value, TemporalAA):
+            raise TypeError(f"temporal_aa must be None or a TemporalAA, got {type(value).__name__}")
+        self.__dict__["_temporal_aa"] = value
+        self.reset_motion()
 
     @property
     def last_stats(self):
@@ -1009,8 +1064,11 @@ class Scene:
         (longer than the frame's kernels at 1080p) then runs beside the kernels of frame i + 1 and beside the
         host's preparation of frame i + 2.  The reference has no such call: it is an addition for sequences."""
         self._check_lights()
-        backend = self._backend()
         pending = self.__dict__.setdefault("_pending", {})
+        if self.temporal_aa is not None and pending:
+            raise ValueError("temporal_aa takes one frame of the scene at a time: another frame is pending, take its "
+                             "result() first (every frame reads the history the frame before it left)")
+        backend = self._backend()
         lane = next((k for k in range(backend.ASYNC_LANES) if k not in pending), None)
         if lane is None:
             raise RuntimeError("four frames of this scene are already pending: take one's result() first")
@@ -1021,7 +1079,11 @@ class Scene:
 
     def render_frames(self, views, shadows=True, depth=2):
         """Frames of a sequence: for every ``(camera, debug_camera)`` pair of *views* the scene's cameras are set
-        and a frame is rendered; yields the uint8 arrays in order, *depth* frames in flight (``render_async``)."""
+        and a frame is rendered; yields the uint8 arrays in order, *depth* frames in flight (``render_async``).  Under
+        a ``temporal_aa`` every frame reads the history the frame before it left: one frame is issued at a time, and its
+        verdict is waited for before the next is issued, whatever *depth* says."""
+        if self.temporal_aa is not None:
+            depth = 1
         queue = []
         try:
             for camera, debug_camera in views:
@@ -1046,6 +1108,9 @@ class Scene:
         if self.motion_blur is not None:
             raise ValueError("motion_blur is not available inside accumulate() / render_mean(): the accumulation is the "
                              "other way to blur motion, and its sub-frames have no previous frame")
+        if self.temporal_aa is not None:
+            raise ValueError("temporal_aa is not available inside accumulate() / render_mean(): the accumulation is the "
+                             "other way to spread samples over frames, and its sub-frames have no history")
         acc = self.__dict__["_accumulation"] = Accumulation(self)
         return acc
 
@@ -1078,3 +1143,4 @@ class Scene:
         if self._renderer is not None:
             self._renderer.close()
             self._renderer = None
+            self.__dict__["_taa_forget"] = True      # (the history of temporal_aa went with the device's scene)

@@ -33,6 +33,7 @@ int accum_add(mr_scene *sc, const mr_frame_desc *fr, double weight)
     if (is_partial(fr)) return fail(MR_E_INVALID, "an accumulation takes whole frames (no row band, no stripes)");
     if (fr->flags & MR_FRAME_FACE_STATUS) return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available for the sub-frames of an accumulation");
     if (sc->motion.on) return fail(MR_E_INVALID, "motion blur is not available for the sub-frames of an accumulation: the sum is the other way to blur motion");
+    if (sc->taa.on) return fail(MR_E_INVALID, "temporal anti-aliasing is not available for the sub-frames of an accumulation: the sum is the other way to spread samples over frames");
     float w;
     if (!positive_f32(weight, w)) return fail(MR_E_INVALID, "a sub-frame's weight must be finite and > 0 as float32");
     if ((rc = accum_linked())) return rc;

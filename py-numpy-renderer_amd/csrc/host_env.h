@@ -23,6 +23,7 @@
 //   MR_DOF_TILE       32x32     32x32x256 | 16x16: the other workgroup shapes of k_dof -- 32 x 32 samples with 256 threads, not
 //                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B)
 //   MR_MBLUR_TILE     32x32     32x32x256 | 16x16: the other workgroup shapes of k_mblur, as for k_dof (same bits; for the A/B)
+//   MR_TAA_TILE       32x8      64x4 | 16x16: the other workgroup shapes of k_taa, 256 threads each (same bits; for the A/B)
 //
 // MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
 // rest are read once per process.
@@ -35,7 +36,7 @@ struct Env {
     int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
     int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
     int pair_log;                                 // 0 .. mr::PAIR_LOG_K
-    int ao_shape, dof_shape, mblur_shape;         // 0 .. 2: the `shape` of ao.hip's, dof.hip's and motion.hip's launch
+    int ao_shape, dof_shape, mblur_shape, taa_shape;   // 0 .. 2: the `shape` of ao.hip's, dof.hip's, motion.hip's and taa.hip's launch
     unsigned split_cost, split_quads;
     const char *cluster_cull;                     // as set, or NULL
 };
@@ -62,6 +63,7 @@ Env read_env()
         e.ao_shape = shape("MR_AO_TILE", "64x64", "32x32", "64x16");
         e.dof_shape = shape("MR_DOF_TILE", "32x32", "32x32x256", "16x16");
         e.mblur_shape = shape("MR_MBLUR_TILE", "32x32", "32x32x256", "16x16");
+        e.taa_shape = shape("MR_TAA_TILE", "32x8", "64x4", "16x16");
         return e;
     }();
     Env e = once;

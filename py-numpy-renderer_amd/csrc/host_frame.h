@@ -15,8 +15,8 @@ struct FrameSlot {
     DevBuf d_vout, d_vclip, d_tris, d_clips, d_status, d_count_list, d_quads, d_sil, d_counters;
     DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_work, d_tile_stats, d_hist, d_split;
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
-    DevBuf d_frame_b;                             // the float frame k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
-    MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur (host_motion.h)
+    DevBuf d_frame_b;                             // the float frame k_taa, k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
+    MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur or temporal anti-aliasing (host_motion.h)
     MotionFacesSlot motion_faces;                 // the face records and the tables of its per-face pass (host_motion_faces.h)
     bool last_motion = false;                     // the last frame ran k_velocity: mr_read_velocity has something to read
     DevBuf d_stencil_x[mr::MAX_LIGHTS - 1];       // stencil taps of lights 1.. of a frame with several lights
@@ -162,10 +162,14 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         if (fr->row_begin % s || fr->row_end % s) return fail(MR_E_INVALID, "supersampling: row_begin / row_end must be multiples of s");
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
-    const struct { bool on; const char *name; } passes[] = { { sc->ao.on, "ambient occlusion" }, { sc->dof.on, "depth of field" }, { sc->motion.on, "motion blur" } };
+    const struct { bool on; const char *name; } passes[] = { { sc->ao.on, "ambient occlusion" }, { sc->dof.on, "depth of field" }, { sc->motion.on, "motion blur" },
+                                                         { sc->taa.on, "temporal anti-aliasing" } };
     for (const auto &pass : passes)
         if (pass.on && is_partial(fr))
             return fail(MR_E_INVALID, std::string(pass.name) + " takes whole frames (no row band, no stripes): its taps cross the bands");
+    // (host order is the only ordering between the frames that write the history and those that read it)
+    if (sc->taa.on && sc->taa.pending)
+        return fail(MR_E_INVALID, "temporal anti-aliasing: an earlier frame of the scene has not been waited for (mr_render_wait): its history is not there yet");
     if (sc->n_extra_lights > 0) {
         if (fr->flags & MR_FRAME_FACE_STATUS)
             return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
@@ -334,14 +338,17 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   ao           the scene has ambient obscurance on: k_ao behind the tile kernel, with ao_params, the scene's description now
 //   dof          the scene has depth of field on: k_dof behind them, with dof_params, likewise
 //   motion       the scene has motion blur on: k_velocity and k_mblur behind them, with motion_params, likewise
+//   taa          the scene has temporal anti-aliasing on: k_velocity and k_taa behind k_ao, in front of k_dof, with taa_params and
+//                taa_vel (the velocity's scalars), likewise
 //   post()       a pass rewrites the float frame behind the tile kernel: the bytes are the full resolve of the result
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa;
     mr::AoParams ao_params;
     mr::DofParams dof_params;
-    mr::MotionParams motion_params;
-    bool post() const { return ao || dof || motion; }
+    mr::MotionParams motion_params, taa_vel;
+    mr::TaaParams taa_params;
+    bool post() const { return ao || dof || motion || taa; }
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -380,12 +387,17 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     if (fc.ss_mode & SS_SEPARATE) fc.flags |= MR_FRAME_KEEP_FLOAT;
     // (a post pass reads the whole z-buffer -- the motion blur the winner map as well -- and rewrites the whole float frame,
     // in place or into the second one: every tile writes its taps, as for a caller who asked for them)
-    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on;
+    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on; p.taa = sc->taa.on;
     if (p.motion && sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
         return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
     if (p.motion && sc->mfaces.on && sc->mfaces.deforming.size() != sc->model_face_off.size())
         return fail(MR_E_INVALID, "per-face velocity: the scene's models changed since mr_scene_set_motion_faces: hand the flags over again");
+    if (p.taa && sc->taa.vel.n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "temporal anti-aliasing: the scene's models changed since mr_scene_set_temporal_aa: hand the classes over again");
+    if (p.taa && p.motion && !same_velocity_tables(sc->taa.vel, sc->taa.tables, sc->motion.params, sc->motion.tables))
+        return fail(MR_E_INVALID, "temporal anti-aliasing: its velocity tables are not the motion blur's: one k_velocity serves both, hand both descriptions the same matrices");
     p.ao_params = sc->ao.params; p.dof_params = sc->dof.params; p.motion_params = sc->motion.params;
+    p.taa_params = sc->taa.params; p.taa_vel = sc->taa.vel;
     if (p.post()) fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
@@ -458,8 +470,10 @@ int grow_slot(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Frame
         { fs->d_bin_count, (size_t)(BIN_CLASSES * p.n_tiles + 1) * 4 }, { fs->d_work, (size_t)fs->work_cap * sizeof(uint2) },
         { fs->d_tile_stats, nT * TILE_REC * 4 }, { fs->d_z, kept * sizeof(double) }, { fs->d_winner, kept * sizeof(int32_t) },
         { fs->d_stencil, kept * sizeof(int32_t) }, { fs->d_frame, kept_f * 3 * sizeof(float) },
-        { fs->d_frame_b, p.dof || p.motion ? kept_f * 3 * sizeof(float) : 0 } };
+        { fs->d_frame_b, p.dof || p.motion || p.taa ? kept_f * 3 * sizeof(float) : 0 } };
     for (const auto &b : sized) HIP_TRY(b.buf.ensure(b.bytes));
+    if (p.taa)
+        if (int rc = grow_history(sc, fc.width, fc.height)) return rc;
     for (int k = 1; k < p.n_lights; ++k) HIP_TRY(fs->d_stencil_x[k - 1].ensure(kept * sizeof(int32_t)));
     if (int rc = ensure_cleared(fs->d_counters, 2 * sizeof(Counters) + sizeof(Sticky), fs->stream)) return rc;
     for (int c = 0; c < BIN_CLASSES; ++c) {
@@ -616,10 +630,10 @@ void launch_post_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, i
 
 // A pass has written the other float frame: that one is the slot's float frame from here on.  The overlay, the resolve,
 // mr_read_frame_f32 and k_accum_add read d_frame; work enqueued on the stream before this point keeps the pointers it was
-// given; the two ping-pong when k_dof and k_mblur both run.
+// given; the two ping-pong when several of k_taa, k_dof and k_mblur run.
 inline void swap_float_frames(FrameSlot *fs) { std::swap(fs->d_frame, fs->d_frame_b); }
 
-// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the depth of field, the motion blur, the overlay (exported
+// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the temporal anti-aliasing, the depth of field, the motion blur, the overlay (exported
 // by a device that owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638)
 // and the resolve of a supersampled, darkened or blurred frame
 int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
@@ -631,6 +645,12 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
                            fs->d_clips.as<TriClip>(), fs->d_z.as<double>(), fs->d_stencil.as<int32_t>(), fs->d_status.as<uint8_t>());
     if (p.ao && p.n_tiles > 0)
         if (int rc = launch_ao(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fc.width, fc.height, p.ao_params, p.env.ao_shape)) return rc;
+    if (p.taa && p.n_tiles > 0) {
+        if (int rc = launch_taa(sc, stream, fs->motion, fs->motion_faces, fs->d_z.as<double>(), fs->d_winner.as<int32_t>(), fs->d_frame.as<float>(),
+                                fs->d_frame_b.as<float>(), fc.width, fc.height, p.taa_params, p.taa_vel, p.env.taa_shape))
+            return rc;
+        swap_float_frames(fs);
+    }
     if (p.dof && p.n_tiles > 0) {
         if (int rc = launch_dof(sc, stream, fs->d_z.as<double>(), fs->d_frame.as<float>(), fs->d_frame_b.as<float>(), fc.width, fc.height, p.dof_params,
                                 p.env.dof_shape))
@@ -639,7 +659,8 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
     }
     if (p.motion && p.n_tiles > 0) {
         if (int rc = launch_motion(sc, stream, fs->motion, fs->motion_faces, fs->d_z.as<double>(), fs->d_winner.as<int32_t>(), fs->d_frame.as<float>(),
-                                   fs->d_frame_b.as<float>(), fc.width, fc.height, p.motion_params, p.env.mblur_shape))
+                                   fs->d_frame_b.as<float>(), fc.width, fc.height, p.motion_params, p.env.mblur_shape,
+                                   p.taa))
             return rc;
         swap_float_frames(fs);
     }
@@ -668,7 +689,8 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
     fs->overlay_deferred = p.deferred;
     fs->last_ss_mode = fc.ss_mode;
     fs->last_post = p.post();
-    fs->last_motion = p.motion && p.n_tiles > 0;
+    fs->last_motion = (p.motion || p.taa) && p.n_tiles > 0;
+    if (p.taa && p.n_tiles > 0) taa_enqueued(sc, fs, fc.width, fc.height);
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = p.n_tiles;
     fs->last_n_lights = p.n_lights;

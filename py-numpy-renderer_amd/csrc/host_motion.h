@@ -55,25 +55,36 @@ struct MotionSlot {
     void release() { tables.release(); d_vel.release(); }
 };
 
+// What k_velocity needs on the slot before it runs: the velocity buffer, and `tables` (a description's block) staged with
+// the models' first faces of this moment.  The motion blur's pass and the temporal anti-aliasing's (host_taa.h) share it.
+int stage_velocity(mr_scene *sc, hipStream_t stream, MotionSlot &ms, std::vector<double> &tables, const mr::MotionParams &p, int width, int height)
+{
+    // (the models' first faces are the scene's of this moment: a commit may have moved them since the description came)
+    int32_t *off = reinterpret_cast<int32_t *>(tables.data() + (size_t)p.n_classes * mr::MOTION_T + mr::MOTION_B);
+    for (int32_t m = 0; m < p.n_models; ++m) off[m] = sc->model_face_off[m];
+    HIP_TRY(ms.d_vel.ensure((size_t)width * height * 2 * sizeof(float)));
+    return ms.tables.stage(tables.data(), tables.size() * sizeof(double), stream);
+}
+
 // k_velocity and k_mblur from a frame's own z-buffer, winner map and float frame into the slot's velocity buffer and `out`,
 // on the frame's stream behind its tile kernel, marked for mr_debug_motion_times.  `p` is the copy the frame's plan took, `shape` k_mblur's (Env::mblur_shape).
 // Between the two, where the scene has flagged models and the snapshot they need (motion_faces_due), k_face_homography and
 // k_velocity_faces overwrite those models' U; k_mblur's span then starts at a mark of its own.
+// With vel_ready the slot's velocity buffer is this frame's already -- the temporal anti-aliasing ran k_velocity, and the
+// per-face pair where due, from the same tables in front of k_taa -- and the pass goes straight to k_mblur.
 int launch_motion(mr_scene *sc, hipStream_t stream, MotionSlot &ms, MotionFacesSlot &faces, const double *zbuf, const int32_t *winner, const float *frame, float *out,
-                  int width, int height, const mr::MotionParams &p, int shape)
+                  int width, int height, const mr::MotionParams &p, int shape, bool vel_ready = false)
 {
     mr_scene::Motion &a = sc->motion;
-    // (the models' first faces are the scene's of this moment: a commit may have moved them since the description came)
-    int32_t *off = reinterpret_cast<int32_t *>(a.tables.data() + (size_t)p.n_classes * mr::MOTION_T + mr::MOTION_B);
-    for (int32_t m = 0; m < p.n_models; ++m) off[m] = sc->model_face_off[m];
-    HIP_TRY(ms.d_vel.ensure((size_t)width * height * 2 * sizeof(float)));
-    if (int rc = ms.tables.stage(a.tables.data(), a.tables.size() * sizeof(double), stream)) return rc;
+    if (!vel_ready)
+        if (int rc = stage_velocity(sc, stream, ms, a.tables, p, width, height)) return rc;
     float *vel = ms.d_vel.as<float>();
+    a.vel_skipped = vel_ready;
     return marked_launch(a, stream, width, height, [&]() -> int {
-        mr_motion::launch_velocity(stream, zbuf, winner, ms.tables.d_tables.as<double>(), vel, width, height, p);
+        if (!vel_ready) mr_motion::launch_velocity(stream, zbuf, winner, ms.tables.d_tables.as<double>(), vel, width, height, p);
         if (int rc = a.marks.record(1, stream)) return rc;
         a.blur_from = 1;
-        if (motion_faces_due(sc)) {
+        if (!vel_ready && motion_faces_due(sc)) {
             if (int rc = launch_motion_faces(sc, stream, faces, winner, vel, width, height)) return rc;
             if (int rc = a.marks.record(2, stream)) return rc;
             a.blur_from = 2;

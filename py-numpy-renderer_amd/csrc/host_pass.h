@@ -7,7 +7,7 @@
 // It stands in front of host_scene.h, because mr_scene holds the records by value.
 #pragma once
 
-// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip and motion_faces.hip, the library's other translation units,
+// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip and taa.hip, the library's other translation units,
 // each declared here and nowhere else; weak, so that a library linked without one of them (the tools' ablation builds)
 // still loads: it refuses that pass instead (linked)
 namespace mr_accum {
@@ -35,6 +35,10 @@ __attribute__((weak)) void launch_homography(hipStream_t stream, const int32_t *
 __attribute__((weak)) void launch_velocity_faces(hipStream_t stream, const int32_t *winner, const int32_t *tables, const double *hom, float *vel,
                                                  int width, int height, int n_models);
 }  // namespace mr_motion_faces
+namespace mr_taa {
+__attribute__((weak)) void launch(hipStream_t stream, const float *frame, const float *vel, const float *hist, float *out, float *hist_out,
+                                  int width, int height, const mr::TaaParams &p, int shape);
+}  // namespace mr_taa
 
 namespace {
 
@@ -44,6 +48,14 @@ inline int linked(const char *refusal, Launch *...launch)
 {
     if ((... && (launch != nullptr))) return MR_OK;
     return fail(MR_E_UNSUPPORTED, refusal);
+}
+
+// k_taa is taa.hip's; its velocity is motion.hip's k_velocity; the bytes of such a frame are the accumulation's resolve of
+// its float frame (accum.hip)
+inline int taa_linked()
+{
+    return linked("this library was linked without taa.hip, motion.hip or accum.hip: no temporal anti-aliasing (build it with __graft_entry__.build())",
+                  &mr_taa::launch, &mr_motion::launch_velocity, &mr_accum::launch_resolve);
 }
 
 // ---- timing marks: N events round a pass's kernels, created by the first frame that records them and kept for the

@@ -202,7 +202,27 @@ struct mr_scene {
         mr::MotionParams params = {};
         std::vector<double> tables;
         int blur_from = 1;                    // the mark k_mblur's span starts at: 2 in a frame that ran the per-face pass; set with the marks
+        bool vel_skipped = false;             // the last frame's U was the temporal anti-aliasing's: no k_velocity of its own
     } motion;
+
+    // ---- temporal anti-aliasing (host_taa.h), marked in front of its k_velocity, behind it (and behind the per-face pass
+    // where that ran) and behind k_taa.  `tables` is the velocity's block, laid out as the motion blur's.  The history is
+    // the scene's, not a slot's: two float frames on the sample grid, `cur` the one the last frame whose mr_render or
+    // mr_render_wait returned MR_OK left (valid), the other the one a frame in flight is writing (pending, on pending_slot)
+    struct Taa : PassRecord<3> {
+        mr::TaaParams params = {};
+        mr::MotionParams vel = {};
+        std::vector<double> tables;
+        DevBuf d_hist[2];
+        int cur = 0;
+        bool valid = false;
+        int32_t hist_rows = 0, hist_cols = 0;
+        bool pending = false;
+        const FrameSlot *pending_slot = nullptr;
+        int32_t pending_rows = 0, pending_cols = 0;
+        uint64_t epoch = 0, pending_epoch = 0;    // + 1 whenever the history is forgotten: a frame issued before that adopts nothing
+        int32_t velocities = 0, adopted = 0;      // k_velocity launches in front of k_taa; histories adopted (mr_debug_taa)
+    } taa;
 
     // ---- the velocity of models that bend (host_motion_faces.h): the description every frame with motion blur reads, the
     // snapshot of the vertices as the previous pass left them and the serial of the states d_verts has held

@@ -1,7 +1,8 @@
 // mi355rast.hip -- the C ABI (include/mi355rast.h) of libmi355rast.  The library is compiled from this file, from
 // accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), from
 // ao.hip, which holds the ambient obscurance's kernel in another, from dof.hip, which holds the depth of field's, and from
-// motion.hip, which holds the motion blur's two, and from motion_faces.hip, which holds the per-face velocity's two;
+// motion.hip, which holds the motion blur's two, from motion_faces.hip, which holds the per-face velocity's two, and from
+// taa.hip, which holds the temporal anti-aliasing's;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -17,6 +18,7 @@
 //   host_dof.h          depth of field from the z-buffer: the description, k_dof's launch, the host mirror
 //   host_motion.h       motion blur from a velocity buffer: the description, the two launches, the host mirrors, mr_debug_motion_post
 //   host_motion_faces.h the velocity of models that bend: the vertex snapshot and its serial, the two launches, the mirrors
+//   host_taa.h          temporal anti-aliasing: the description, the scene's history, the launch, the host mirror, mr_debug_taa_post
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
@@ -38,7 +40,8 @@
 //                   k_accum_add behind a sub-frame of mr_accum_add, k_accum_resolve for mr_accum_resolve;
 //                   k_ao behind k_tile in a scene with mr_scene_set_ambient_occlusion, k_dof behind them in one with
 //                   mr_scene_set_depth_of_field, k_velocity and k_mblur behind those in one with
-//                   mr_scene_set_motion_blur, k_accum_resolve for the bytes of any)
+//                   mr_scene_set_motion_blur, k_velocity and k_taa between k_ao and k_dof in one with
+//                   mr_scene_set_temporal_aa, k_accum_resolve for the bytes of any)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -70,6 +73,7 @@
 #include "dof_def.h"
 #include "motion_def.h"
 #include "motion_faces_def.h"
+#include "taa_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -84,6 +88,7 @@
 #include "host_dof.h"
 #include "host_motion.h"
 #include "host_motion_faces.h"
+#include "host_taa.h"
 #include "host_frame.h"
 #include "host_accum.h"
 #include "host_post.h"
@@ -232,6 +237,7 @@ void mr_scene_destroy(mr_scene *sc)
     accum_release(sc->accum);
     release_pass(sc->ao); release_pass(sc->dof); release_pass(sc->motion);
     motion_faces_release(sc);
+    taa_release(sc);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
@@ -513,9 +519,12 @@ int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats 
     if (stats) counted.flags |= MR_FRAME_COUNTERS;         // whoever asks for the counters gets them
     fr = &counted;
     for (int attempt = 0; attempt < 6; ++attempt) {
-        if ((rc = render_and_copy(sc, fs, fr, out_rgb, stats != nullptr))) return rc;
-        HIP_TRY(hipStreamSynchronize(g_stream));
+        if ((rc = render_and_copy(sc, fs, fr, out_rgb, stats != nullptr))) { taa_settle(sc, fs, false); return rc; }
+        const hipError_t drained = hipStreamSynchronize(g_stream);
+        if (drained != hipSuccess) taa_settle(sc, fs, false);
+        HIP_TRY(drained);
         rc = collect(sc, fs, true);
+        taa_settle(sc, fs, rc == MR_OK);          // (a frame that overflowed adopts nothing: the next attempt reads the same history)
         if (rc == MR_OK) {
             if (stats) *stats = sc->stats;
             return MR_OK;
@@ -539,7 +548,7 @@ int mr_render_async(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, int
     if (!ln.stream) HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
     FrameSlot *fs = slot_for(sc, ln.stream);
     if (!fs) return fail(MR_E_DEVICE, "out of frame slots");
-    if ((rc = render_and_copy(sc, fs, fr, out_rgb, (fr->flags & MR_FRAME_COUNTERS) != 0))) return rc;
+    if ((rc = render_and_copy(sc, fs, fr, out_rgb, (fr->flags & MR_FRAME_COUNTERS) != 0))) { taa_settle(sc, fs, false); return rc; }
     ln.busy = true;
     return MR_OK;
 }
@@ -550,11 +559,14 @@ int mr_render_wait(mr_scene *sc, int32_t lane, mr_stats *stats)
     if (lane < 0 || lane >= MR_ASYNC_LANES) return fail(MR_E_INVALID, "lane out of range");
     mr_scene::Lane &ln = sc->lanes[lane];
     if (!ln.busy) return fail(MR_E_INVALID, "no frame in flight on this lane");
-    HIP_TRY(hipStreamSynchronize(ln.stream));
-    ln.busy = false;
     FrameSlot *fs = slot_for(sc, ln.stream);
+    const hipError_t drained = hipStreamSynchronize(ln.stream);
+    if (drained != hipSuccess && fs) taa_settle(sc, fs, false);
+    HIP_TRY(drained);
+    ln.busy = false;
     if (!fs) return fail(MR_E_DEVICE, "lane without a frame slot");
     const int rc = collect(sc, fs, true);
+    taa_settle(sc, fs, rc == MR_OK);
     if (stats) *stats = sc->stats;
     if (rc == MR_E_OVERFLOW) return fail(MR_E_OVERFLOW, "the frame overflowed a work list (now grown): render it again");
     return rc;
@@ -704,13 +716,76 @@ int mr_debug_motion(mr_scene *sc, int32_t *out)
 
 int mr_debug_motion_times(mr_scene *sc, float *out_ms)
 {
-    return pass_times(sc, &mr_scene::motion, "no frame with motion blur yet", out_ms, { { 0, 1 }, { sc ? sc->motion.blur_from : 1, 3 } });
+    // (a frame whose U the temporal anti-aliasing computed ran no k_velocity of its own: its velocity span is 0)
+    const int rc = pass_times(sc, &mr_scene::motion, "no frame with motion blur yet", out_ms, { { 0, 1 }, { sc ? sc->motion.blur_from : 1, 3 } });
+    if (rc == MR_OK && sc->motion.vel_skipped) out_ms[0] = 0.f;
+    return rc;
 }
 
 int mr_debug_motion_post(mr_scene *sc, const double *z, const int32_t *winner, const float *frame, const int32_t *face_off, int32_t height,
                          int32_t width, const mr_motion_desc *motion, int32_t shape, float *out_velocity, float *out_frame)
 {
     return debug_motion_post(sc, z, winner, frame, face_off, height, width, motion, shape, out_velocity, out_frame);
+}
+
+int mr_scene_set_temporal_aa(mr_scene *sc, const mr_taa_desc *taa)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (!taa) {                                                // (frames already enqueued took their copy)
+        if (sc->taa.on) taa_forget(sc);
+        sc->taa.on = false;
+        return MR_OK;
+    }
+    if (taa->n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "temporal anti-aliasing: n_models is not the number of the scene's models");
+    mr::TaaParams p;
+    mr::MotionParams vel;
+    std::vector<double> tables;
+    if (int rc = taa_params(taa, sc->model_face_off.data(), p, vel, tables)) return rc;
+    if (int rc = taa_linked()) return rc;
+    sc->taa.params = p;
+    sc->taa.vel = vel;
+    sc->taa.tables.swap(tables);
+    sc->taa.on = true;
+    return MR_OK;
+}
+
+int mr_scene_reset_history(mr_scene *sc)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    taa_forget(sc);
+    return MR_OK;
+}
+
+int mr_read_history(mr_scene *sc, float *out)
+{
+    if (!sc || !out) return fail(MR_E_INVALID, "NULL argument");
+    const mr_scene::Taa &a = sc->taa;
+    if (!a.valid) return fail(MR_E_INVALID, "no temporal anti-aliasing history yet: none adopted since it was last forgotten");
+    return read_back(a.d_hist[a.cur], out, (size_t)a.hist_rows * a.hist_cols * 3, "history");
+}
+
+int mr_host_taa(const float *frame, const float *velocity, const float *history, int32_t height, int32_t width, double blend, float *out_frame)
+{
+    return host_taa(frame, velocity, history, height, width, blend, out_frame);
+}
+
+int mr_debug_taa_post(mr_scene *sc, const float *frame, const float *velocity, const float *history, int32_t height, int32_t width, double blend,
+                      int32_t shape, float *out_frame, float *out_history, int32_t *out_guard)
+{
+    return debug_taa_post(sc, frame, velocity, history, height, width, blend, shape, out_frame, out_history, out_guard);
+}
+
+int mr_debug_taa(mr_scene *sc, int32_t *out)
+{
+    if (int rc = pass_counts(sc, &mr_scene::taa, out)) return rc;
+    out[3] = sc->taa.velocities; out[4] = sc->taa.adopted; out[5] = sc->taa.valid ? 1 : 0;
+    return MR_OK;
+}
+
+int mr_debug_taa_times(mr_scene *sc, float *out_ms)
+{
+    return pass_times(sc, &mr_scene::taa, "no frame with temporal anti-aliasing yet", out_ms, { { 0, 1 }, { 1, 2 } });
 }
 
 int mr_scene_set_motion_faces(mr_scene *sc, const mr_motion_faces_desc *d)
@@ -1001,6 +1076,8 @@ int mr_render_device(mr_scene *sc, const mr_frame_desc *fr, void *d_out_rgb, voi
     if ((rc = ensure_init())) return rc;
     FrameSlot *fs = slot_for(sc, stream ? (hipStream_t)stream : g_stream);
     if (!fs) return fail(MR_E_INVALID, "a scene can be rendered from at most 32 different streams");
+    if (sc->taa.on)
+        return fail(MR_E_INVALID, "temporal anti-aliasing: its frames are rendered by mr_render or mr_render_async, whose return hands the history over");
     return enqueue_frame(sc, fs, fr, static_cast<uint8_t *>(d_out_rgb));
 }
 
@@ -1016,7 +1093,7 @@ int mr_get_stats(mr_scene *sc, mr_stats *stats)
         if (!s->have_frame) continue;
         if (int rc = fetch_counters(s.get(), true)) return rc;
         HIP_TRY(hipStreamSynchronize(s->stream));
-        if (collect(sc, s.get(), s->last_copied) == MR_E_OVERFLOW) overflowed = true;
+        if (collect(sc, s.get(), s->last_copied) == MR_E_OVERFLOW) { overflowed = true; taa_settle(sc, s.get(), false); }
     }
     (void)collect(sc, fs, fs->last_copied);     // report the most recent frame
     *stats = sc->stats;
