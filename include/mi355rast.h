@@ -1009,6 +1009,69 @@ int mr_debug_taa_times(mr_scene *scene, float *out_ms);
 int mr_debug_taa_post(mr_scene *scene, const float *frame, const float *velocity, const float *history, int32_t height,
                       int32_t width, double blend, int32_t shape, float *out_frame, float *out_history, int32_t *out_guard);
 
+/* Bloom: a glow round the samples brighter than a threshold, gathered from a resolution pyramid on the device.  It lives on
+ * the frame's sample grid (Hs, Ws), rows bottom-up.  With F the float frame behind the motion blur and IN FRONT of the
+ * overlay, t = threshold, g = gain, L = levels, float32 throughout, every operation rounded on its own, every weight dyadic:
+ *
+ *   bright pass   m = fmaxf(fmaxf(r, g), b);  k = m > t ? (m - t) / m : 0;  B0 = F * k                      per channel
+ *   level sizes   H0, W0 = Hs, Ws;  H_l = (H_{l-1} + 1) / 2, W_l = (W_{l-1} + 1) / 2 (the ceiling; 1 x 1 halves to 1 x 1)
+ *   down          D_0 = B0;  D_l[y][x] from D_{l-1} at the taps 2x-1 .. 2x+2 by 2y-1 .. 2y+2, coordinates clamped to the
+ *                 source level; rows first, ascending: r_j = (a0 + a3) + 3*(a1 + a2); v = (r0 + r3) + 3*(r1 + r2);
+ *                 D_l = v * (1/64)
+ *   up            up(C) onto a finer grid: for a fine index i, near = i / 2, far = near - 1 (i even) or near + 1 (i odd),
+ *                 clamped to the coarse level; per coarse row h = 3*C[near_x] + C[far_x]; v = 3*h[near_y] + h[far_y];
+ *                 up = v * (1/16)
+ *   up chain      U_L = D_L;  U_l = D_l + up(U_{l+1}), l = L-1 .. 1
+ *   composite     out = F + g * up(U_1)
+ *
+ * Where no sample exceeds t every level is +0 and out == F bit for bit.  A uniform field stays uniform at every level.
+ * Frame order: the lights' sum, k_ao, k_velocity, k_taa (whose history is written before this pass and never holds
+ * glow), k_dof, k_mblur, the bloom's 2 L launches (L of k_bloom_down, the first with the bright pass; L - 1 of k_bloom_up;
+ * k_bloom_composite), the overlay (drawn over the glow, not bloomed), the finalise of the result.  The pass keeps nothing
+ * from frame to frame: it composes with accumulations, frames in flight (every frame slot owns a pyramid buffer of the
+ * sum over l = 1 .. L of 3 H_l W_l floats) and every other pass.
+ *
+ * mr_scene_set_bloom copies the description during the call (NULL: off, the default); every frame enqueued afterwards uses
+ * the copy of its moment and keeps its z-buffer, winner map and float frame (MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT
+ * are implied).  A scene without it enqueues what it always did.  MR_E_INVALID for a threshold that is not finite and
+ * >= 0 as float32, a gain that is not finite and > 0 as float32, levels outside 1 .. 8; and, from the rendering entry
+ * points, for a partial frame (row band, stripes), before any device work.  MR_E_UNSUPPORTED from a library linked without
+ * bloom.hip or accum.hip. */
+typedef struct mr_bloom_desc {
+    double threshold;              /* t: >= 0 as float32 */
+    double gain;                   /* g: > 0 as float32 */
+    int32_t levels;                /* L: 1 .. 8 */
+    int32_t pad;
+} mr_bloom_desc;
+int mr_scene_set_bloom(mr_scene *scene, const mr_bloom_desc *bloom);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what the kernels write.  frame and out_frame are
+ * (height, width, 3) float32.  out_pyramid may be NULL; else it receives D_1 .. D_L and then U_{L-1} .. U_1, packed in that
+ * order, level l being (H_l, W_l, 3): 2 * (n_1 + .. + n_L) - n_L floats with n_l = 3 H_l W_l.  MR_E_INVALID for a NULL
+ * argument, out_frame == frame, what mr_scene_set_bloom refuses, or a height or width outside 1 .. 32767. */
+int mr_host_bloom(const float *frame, int32_t height, int32_t width, const mr_bloom_desc *bloom, float *out_frame, float *out_pyramid);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued the pass, out[1], out[2] = the sample rows and columns of the last
+ * of them (0 before the first), out[3] = its levels (it made 2 * out[3] launches).  Does not wait. */
+#define MR_N_BLOOM_COUNTS 4
+int mr_debug_bloom(mr_scene *scene, int32_t *out);
+
+/* Device times in milliseconds of the last frame with the pass: its down chain (L launches), its up chain (L - 1; the span
+ * between two marks with nothing in it at L = 1) and its composite.  Waits for them.  MR_E_INVALID before the first such
+ * frame. */
+#define MR_N_BLOOM_TIMES 3
+int mr_debug_bloom_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: the three kernels on a frame the caller supplies -- no frame is rendered.  Arrays as for mr_host_bloom; shape is
+ * k_bloom_down's workgroup: 0 = 32 x 8 output samples, 1 = 64 x 4, 2 = 16 x 16, 256 threads each (never MR_BLOOM_TILE's).
+ * On the device the frame and the pyramid lie between 256 bytes of sentinel either side: MR_E_DEVICE, with a text, when one
+ * of those bytes changed.  The scene lends its error text only: its frame slots and what mr_debug_bloom reports stay as
+ * they were, and the entry's device buffers are released when it returns.  Waits for the device.  MR_E_INVALID, before any
+ * device call, for a NULL argument (out_pyramid may be NULL), a height or width outside 1 .. 32767, a shape outside 0 .. 2
+ * and what mr_scene_set_bloom refuses. */
+int mr_debug_bloom_post(mr_scene *scene, const float *frame, int32_t height, int32_t width, const mr_bloom_desc *bloom, int32_t shape,
+                        float *out_frame, float *out_pyramid);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

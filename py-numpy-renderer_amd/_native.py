@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, dof_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -112,6 +112,17 @@ def fill_dof_desc(depth_map, kf, perspective, focus):
     for i in range(4):
         d.depth_map[i] = float(depth_map[i])
     d.kf, d.focus, d.perspective = float(kf), float(focus), int(perspective)
+    return d
+
+
+class BloomDesc(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("gain", C.c_double), ("levels", C.c_int32), ("pad", C.c_int32)]
+
+
+def fill_bloom_desc(threshold, gain, levels):
+    """``mr_bloom_desc`` of a frame's constants (``_pack.bloom_constants``)."""
+    d = BloomDesc()
+    d.threshold, d.gain, d.levels = float(threshold), float(gain), int(levels)
     return d
 
 
@@ -309,6 +320,11 @@ _PROTOTYPES = {
     "mr_debug_taa_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_taa_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mr_scene_set_bloom": (C.c_int, [C.c_void_p, C.POINTER(BloomDesc)]),
+    "mr_host_bloom": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BloomDesc), C.c_void_p, C.c_void_p]),
+    "mr_debug_bloom": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_bloom_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_bloom_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BloomDesc), C.c_int32, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -496,6 +512,68 @@ def debug_motion_post(handle, z, winner, frame, face_off, desc, shape=0):
                                                      C.byref(desc), int(shape), vel.ctypes.data, out.ctypes.data),
                  "mr_debug_motion_post")
     return vel, out
+
+
+def bloom_levels(height, width, levels):
+    """The pyramid of a ``(height, width)`` sample grid: ``[(H_1, W_1), ..., (H_L, W_L)]``, every extent the ceiling of half
+    the one before."""
+    sizes = []
+    for _ in range(int(levels)):
+        height, width = (height + 1) // 2, (width + 1) // 2
+        sizes.append((height, width))
+    return sizes
+
+
+def _bloom_pyramid(flat, height, width, levels):
+    """What ``mr_host_bloom`` packs, as ``(D, U)``: ``D[l - 1]`` is ``D_l``, ``U[l - 1]`` is ``U_l`` (``U[L - 1]`` is ``D_L`` itself)."""
+    sizes = bloom_levels(height, width, levels)
+    at, down = 0, []
+    for h, w in sizes:
+        down.append(flat[at:at + h * w * 3].reshape(h, w, 3))
+        at += h * w * 3
+    up = [None] * len(sizes)
+    up[-1] = down[-1]
+    for l in range(len(sizes) - 2, -1, -1):
+        h, w = sizes[l]
+        up[l] = flat[at:at + h * w * 3].reshape(h, w, 3)
+        at += h * w * 3
+    assert at == len(flat)
+    return down, up
+
+
+def _bloom_call(entry, name, head, frame, desc, tail, pyramid, guard):
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError(f"frame must be (H, W, 3), got {frame.shape}")
+    h, w = frame.shape[:2]
+    sizes = bloom_levels(h, w, max(min(int(desc.levels), 8), 0))
+    n_pyr = 2 * sum(a * b * 3 for a, b in sizes) - (sizes[-1][0] * sizes[-1][1] * 3 if sizes else 0)
+    # (both outputs between `guard` floats of a value the library never writes: the entry fills its float counts and no more)
+    out = np.full(frame.size + 2 * guard, -7.5, dtype=np.float32)
+    pyr = np.full(n_pyr + 2 * guard, -7.5, dtype=np.float32)
+    _check_accum(entry(*head, frame.ctypes.data, h, w, C.byref(desc), *tail, out[guard:].ctypes.data,
+                       pyr[guard:].ctypes.data if pyramid else None), name)
+    touched = sum(int((a[:guard] != -7.5).sum() + (a[len(a) - guard:] != -7.5).sum()) for a in (out, pyr)) if guard else 0
+    if touched:
+        raise AssertionError(f"{name}: {touched} guard floats round the outputs changed")
+    result = out[guard:guard + frame.size].reshape(frame.shape)
+    if not pyramid:
+        return result
+    return (result,) + _bloom_pyramid(pyr[guard:guard + n_pyr], h, w, len(sizes))
+
+
+def host_bloom(frame, desc, pyramid=False, guard=16):
+    """``mr_host_bloom``: the bloom's definition on the host, no device.  *frame* ``(Hs, Ws, 3)`` float32, *desc* a
+    ``BloomDesc``; returns the frame with the glow, and with *pyramid* ``(frame, D, U)``: the levels ``D_1 .. D_L`` and ``U_1 ..
+    U_L`` as lists of ``(H_l, W_l, 3)`` arrays (``U[-1]`` is ``D[-1]``).  Both outputs are handed over between *guard* floats,
+    which must come back untouched.  ``ValueError`` with the library's text for what it refuses."""
+    return _bloom_call(load_library().mr_host_bloom, "mr_host_bloom", (), frame, desc, (), pyramid, guard)
+
+
+def debug_bloom_post(handle, frame, desc, shape=0, pyramid=False, guard=16):
+    """``mr_debug_bloom_post``: the bloom's kernels on the caller's frame, no frame rendered; *shape* 0 .. 2 is
+    ``k_bloom_down``'s workgroup.  Returns what ``host_bloom`` returns."""
+    return _bloom_call(load_library().mr_debug_bloom_post, "mr_debug_bloom_post", (handle,), frame, desc, (int(shape),), pyramid, guard)
 
 
 def _taa_arrays(frame, velocity, history):
@@ -966,13 +1044,26 @@ class DeviceRenderer:
         never had one makes no call."""
         self._sync_desc(scene, "dof", "mr_scene_set_depth_of_field", self._dof_values, lambda sc: fill_dof_desc(*dof_constants(sc)))
 
+    @staticmethod
+    def _bloom_values(scene):
+        """The scene's ``Bloom`` by value (``None`` without one), for ``_frame_key``."""
+        bloom = getattr(scene, "bloom", None)
+        return None if bloom is None else (bloom.threshold, bloom.intensity, bloom.levels)
+
+    def sync_bloom(self, scene):
+        """``mr_scene_set_bloom`` for the frames enqueued from now on, whenever the description -- the scene's ``Bloom``
+        and the levels its ``supersample`` adds -- is not the one last handed over.  A scene that never had one makes no
+        call."""
+        self._sync_desc(scene, "bloom", "mr_scene_set_bloom", self._bloom_values, lambda sc: fill_bloom_desc(*bloom_constants(sc)))
+
     def _sync_post(self, scene):
-        """The post passes of the frame being issued, in the order they run: the five descriptions in step with *scene*."""
+        """The post passes of the frame being issued, in the order they run: the six descriptions in step with *scene*."""
         self.sync_ambient_occlusion(scene)
         self.sync_temporal_aa(scene)
         self.sync_depth_of_field(scene)
         self.sync_motion_blur(scene)
         self.sync_motion_faces(scene)
+        self.sync_bloom(scene)
 
     @staticmethod
     def _motion_values(scene):
@@ -1134,7 +1225,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -1234,6 +1325,8 @@ class DeviceRenderer:
             raise ValueError("ambient occlusion takes whole frames (no row band, no stripes): its taps cross the bands")
         if getattr(scene, "depth_of_field", None) is not None and partial:
             raise ValueError("depth of field takes whole frames (no row band, no stripes): its taps cross the bands")
+        if getattr(scene, "bloom", None) is not None and partial:
+            raise ValueError("bloom takes whole frames (no row band, no stripes): its taps cross the bands")
         self._sync_post(scene)
         if overlay:
             self.sync_overlay(scene)
@@ -1340,6 +1433,17 @@ class DeviceRenderer:
     def motion_times(self):
         """Device milliseconds of the last ``k_velocity`` and the last ``k_mblur`` (``mr_debug_motion_times``)."""
         return self._times(self.lib.mr_debug_motion_times, self.MOTION_TIME_NAMES)
+
+    # -- bloom (Scene.bloom) -----------------------------------------------------------------------
+    def bloom_debug(self):
+        """``mr_debug_bloom``: (frames that enqueued the pass, the last one's sample rows, its sample columns, its levels)."""
+        return self._counts(self.lib.mr_debug_bloom, 4)
+
+    BLOOM_TIME_NAMES = ("down", "up", "composite")
+
+    def bloom_times(self):
+        """Device milliseconds of the last bloom's down chain, up chain and composite (``mr_debug_bloom_times``)."""
+        return self._times(self.lib.mr_debug_bloom_times, self.BLOOM_TIME_NAMES)
 
     # -- temporal anti-aliasing (Scene.temporal_aa) ----------------------------------------------
     def read_history(self):

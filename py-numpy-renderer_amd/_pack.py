@@ -257,6 +257,39 @@ def dof_constants(scene, camera=None):
     return depth_map(scene, camera), kf, int(P[2, 3] != 0), float(focus)
 
 
+def check_bloom(threshold, intensity, levels):
+    """The parameters of a ``Bloom`` as ``(threshold, intensity, levels)``: *threshold* a Python float that is finite and in
+    [0, 1) as float32, *intensity* one that is finite and > 0 as float32, *levels* an int in 1 .. 6."""
+    def number(value, what):
+        if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError(f"bloom: {what} must be a real number, got {value!r}")
+        with np.errstate(over="ignore"):
+            return np.float32(value)
+    t, g = number(threshold, "threshold"), number(intensity, "intensity")
+    if not np.isfinite(t) or not (0 <= t < 1):
+        raise ValueError(f"bloom: threshold must lie in [0, 1) as float32, got {threshold!r}")
+    if not np.isfinite(g) or g <= 0:
+        raise ValueError(f"bloom: intensity must be finite and > 0 as float32, got {intensity!r}")
+    if isinstance(levels, (bool, np.bool_)) or not isinstance(levels, (int, np.integer)):
+        raise TypeError(f"bloom: levels must be an int, got {levels!r}")
+    if not 1 <= levels <= 6:
+        raise ValueError(f"bloom: levels must lie in 1 .. 6, got {levels!r}")
+    return float(threshold), float(intensity), int(levels)
+
+
+def bloom_constants(scene):
+    """What ``mr_bloom_desc`` carries for a frame of *scene* (``bloom`` set): ``(threshold, gain, levels)`` with ``gain =
+    float32(intensity / levels)`` evaluated in float64 -- the glow is a sum of ``levels`` terms, so its strength does not
+    grow with its width -- and ``levels + log2(supersample)`` levels on the sample grid: the glow is as wide in output
+    pixels at any ``supersample``."""
+    bloom = scene.bloom
+    s = check_supersample(getattr(scene, "supersample", 1))
+    gain = float(np.float32(np.float64(bloom.intensity) / np.float64(bloom.levels)))
+    if not (np.isfinite(gain) and gain > 0):
+        raise ValueError(f"bloom: intensity {bloom.intensity!r} over {bloom.levels} levels gives no gain > 0 as float32")
+    return bloom.threshold, gain, bloom.levels + {1: 0, 2: 1, 4: 2}[s]
+
+
 def check_motion_blur(shutter):
     """The parameter of a ``MotionBlur``: a Python float that lies in (0, 1] as float32."""
     if isinstance(shutter, (bool, str, bytes)) or not isinstance(shutter, (int, float, np.integer, np.floating)):

@@ -186,6 +186,30 @@ class MotionBlur:
         return f"MotionBlur(shutter={self.shutter!r}, deformation={self.deformation!r})"
 
 
+class Bloom:
+    """What ``Scene.bloom`` holds: a glow round the samples brighter than a threshold, gathered on the device from a
+    resolution pyramid (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6n the reasons).  ``threshold`` (a
+    float32 in [0, 1), default 0.8) is the brightness -- the largest of a sample's three channels -- above which a sample
+    glows, with ``(m - threshold) / m`` of its colour.  ``intensity`` (finite and > 0 as float32, default 0.5) is the
+    strength of the glow whatever its width: the device adds ``intensity / levels`` times the sum of ``levels`` blurred
+    copies.  ``levels`` (an int in 1 .. 6, default 4) is the width: every level doubles the glow's reach, in output pixels at
+    any ``supersample``.  ``ValueError`` outside these ranges, ``TypeError`` for the wrong type.  A ``Bloom`` is never
+    modified: assign a new one to change it."""
+
+    __slots__ = ("threshold", "intensity", "levels")
+
+    def __init__(self, threshold=0.8, intensity=0.5, levels=4):
+        from ._pack import check_bloom
+        for name, value in zip(self.__slots__, check_bloom(threshold, intensity, levels)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Bloom is read-only: assign a new one to Scene.bloom")
+
+    def __repr__(self):
+        return f"Bloom(threshold={self.threshold!r}, intensity={self.intensity!r}, levels={self.levels!r})"
+
+
 class TemporalAA:
     """What ``Scene.temporal_aa`` holds: anti-aliasing spread over consecutive frames.  Every frame is rendered once, with a
     sub-sample offset of its sample grid, and its float colours are blended into the history -- the previous frame as this
@@ -899,6 +923,12 @@ class Scene:
       byte.  One frame of the scene at a time: ``render_async()`` refuses while another frame is pending, and
       ``render_frames()`` waits for every frame before it issues the next.  Split frames (``row_band``, ``multigpu``),
       ``accumulate()`` and ``render_mean()`` refuse it.  With ``None`` a scene enqueues exactly what it did without it.
+    * ``bloom`` (an addition; ``None`` by default, or a ``Bloom``): a glow round the samples brighter than a threshold,
+      gathered on the device from a resolution pyramid behind the motion blur and in front of the debug frustum, whose
+      lines do not glow.  A frame no sample of which exceeds the threshold is ``render()``'s byte for byte.  The pass
+      keeps nothing between frames: it composes with ``accumulate()``, ``render_mean()``, ``render_frames()``,
+      ``render_async()``, several lights and every other pass; the history of ``temporal_aa`` never holds glow.  Split
+      frames (``row_band``, ``multigpu``) refuse it.  With ``None`` a scene enqueues exactly what it did without it.
     """
 
     camera = Bound()
@@ -984,6 +1014,17 @@ class Scene:
             raise TypeError(f"temporal_aa must be None or a TemporalAA, got {type(value).__name__}")
         self.__dict__["_temporal_aa"] = value
         self.reset_motion()
+
+    @property
+    def bloom(self):
+        """``None`` (off, the default) or the scene's ``Bloom`` (see the class docstring)."""
+        return self.__dict__.get("_bloom")
+
+    @bloom.setter
+    def bloom(self, value):
+        if value is not None and not isinstance(value, Bloom):
+            raise TypeError(f"bloom must be None or a Bloom, got {type(value).__name__}")
+        self.__dict__["_bloom"] = value
 
     @property
     def last_stats(self):

@@ -24,6 +24,7 @@
 //                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B)
 //   MR_MBLUR_TILE     32x32     32x32x256 | 16x16: the other workgroup shapes of k_mblur, as for k_dof (same bits; for the A/B)
 //   MR_TAA_TILE       32x8      64x4 | 16x16: the other workgroup shapes of k_taa, 256 threads each (same bits; for the A/B)
+//   MR_BLOOM_TILE     32x8      64x4 | 16x16: the other workgroup shapes of k_bloom_down, 256 threads each (same bits; for the A/B)
 //
 // MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
 // rest are read once per process.
@@ -37,6 +38,7 @@ struct Env {
     int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
     int pair_log;                                 // 0 .. mr::PAIR_LOG_K
     int ao_shape, dof_shape, mblur_shape, taa_shape;   // 0 .. 2: the `shape` of ao.hip's, dof.hip's, motion.hip's and taa.hip's launch
+    int bloom_shape;                              // 0 .. 2: the `shape` of bloom.hip's launch_down
     unsigned split_cost, split_quads;
     const char *cluster_cull;                     // as set, or NULL
 };
@@ -64,6 +66,7 @@ Env read_env()
         e.dof_shape = shape("MR_DOF_TILE", "32x32", "32x32x256", "16x16");
         e.mblur_shape = shape("MR_MBLUR_TILE", "32x32", "32x32x256", "16x16");
         e.taa_shape = shape("MR_TAA_TILE", "32x8", "64x4", "16x16");
+        e.bloom_shape = shape("MR_BLOOM_TILE", "32x8", "64x4", "16x16");
         return e;
     }();
     Env e = once;

@@ -7,7 +7,7 @@
 // It stands in front of host_scene.h, because mr_scene holds the records by value.
 #pragma once
 
-// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip and taa.hip, the library's other translation units,
+// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip and bloom.hip, the library's other translation units,
 // each declared here and nowhere else; weak, so that a library linked without one of them (the tools' ablation builds)
 // still loads: it refuses that pass instead (linked)
 namespace mr_accum {
@@ -39,6 +39,11 @@ namespace mr_taa {
 __attribute__((weak)) void launch(hipStream_t stream, const float *frame, const float *vel, const float *hist, float *out, float *hist_out,
                                   int width, int height, const mr::TaaParams &p, int shape);
 }  // namespace mr_taa
+namespace mr_bloom {
+__attribute__((weak)) void launch_down(hipStream_t stream, const float *src, float *dst, int sw, int sh, float threshold, int first, int shape);
+__attribute__((weak)) void launch_up(hipStream_t stream, float *fine, const float *coarse, int w, int h);
+__attribute__((weak)) void launch_composite(hipStream_t stream, float *frame, const float *coarse, int w, int h, float gain);
+}  // namespace mr_bloom
 
 namespace {
 
@@ -56,6 +61,14 @@ inline int taa_linked()
 {
     return linked("this library was linked without taa.hip, motion.hip or accum.hip: no temporal anti-aliasing (build it with __graft_entry__.build())",
                   &mr_taa::launch, &mr_motion::launch_velocity, &mr_accum::launch_resolve);
+}
+
+// the bloom's three kernels are bloom.hip's; the bytes of a bloomed frame are the accumulation's resolve of its float frame
+// (accum.hip)
+inline int bloom_linked()
+{
+    return linked("this library was linked without bloom.hip or accum.hip: no bloom (build it with __graft_entry__.build())",
+                  &mr_bloom::launch_down, &mr_bloom::launch_up, &mr_bloom::launch_composite, &mr_accum::launch_resolve);
 }
 
 // ---- timing marks: N events round a pass's kernels, created by the first frame that records them and kept for the

@@ -224,6 +224,9 @@ class BandRenderer:
         if getattr(scene, "temporal_aa", None) is not None:
             raise ValueError("a frame split over devices does not support temporal_aa: its taps cross the bands "
                              "(render it on one device)")
+        if getattr(scene, "bloom", None) is not None:
+            raise ValueError("a frame split over devices does not support bloom: its taps cross the bands "
+                             "(render it on one device)")
         if partition not in ("bands", "stripes", "weighted"):
             raise ValueError(f"unknown partition {partition!r}")
         self.rank, self.world, self.partition = rank, world, partition
