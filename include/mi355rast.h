@@ -1072,6 +1072,76 @@ int mr_debug_bloom_times(mr_scene *scene, float *out_ms);
 int mr_debug_bloom_post(mr_scene *scene, const float *frame, int32_t height, int32_t width, const mr_bloom_desc *bloom, int32_t shape,
                         float *out_frame, float *out_pyramid);
 
+/* Light shafts: the sky's light streaming past occluders towards a light's place on the screen, marched on the device at a
+ * half or a quarter of the output resolution.  It lives on the frame's sample grid (Hs, Ws), rows bottom-up.  With F the
+ * float frame behind the motion blur and IN FRONT of the bloom and the overlay, Z the z-buffer, t = threshold, g = gain,
+ * d = halvings (1 .. 4), n = samples, (lx, ly) the light on level d, float32 throughout, every operation rounded on its
+ * own, no fma:
+ *
+ *   source       a sample is SKY when Z is not finite;  S_0 = F * k at a sky sample, k the bloom's bright factor
+ *                (m = fmaxf(fmaxf(r, g), b);  k = m > t ? (m - t) / m : 0), +0 elsewhere
+ *   level sizes  H_0, W_0 = Hs, Ws;  H_l = (H_{l-1} + 1) / 2, W_l = (W_{l-1} + 1) / 2
+ *   reduction    B_0 = S_0;  B_{l+1}[y][x] = ((a00 + a01) + (a10 + a11)) * 0.25 over B_l at (2y, 2x), (2y, 2x+1), (2y+1, 2x),
+ *                (2y+1, 2x+1), a sample outside the level counting +0;  S = B_d
+ *   fetch        fetch(A, qx, qy), A of (H, W): for -0.5 <= qx <= W - 0.5 and -0.5 <= qy <= H - 0.5 (tested on the floats;
+ *                a position outside fetches nothing and its tap contributes +0): qx clamped to [0, W - 1], x0 = (int)qx,
+ *                x1 = min(x0 + 1, W - 1), fx = qx - (float)x0, likewise y; per channel h0 = a00 + fx*(a01 - a00),
+ *                h1 = a10 + fx*(a11 - a10), v = h0 + fy*(h1 - h0)
+ *   march        for the coarse sample (x, y), cx = (float)x, cy = (float)y: dx = (lx - cx) * step, dy = (ly - cy) * step;
+ *                q_i = (cx + dx*(float)i, cy + dy*(float)i), i = 0 .. n-1;  R = sum_i weights[i] * fetch(S, q_i), summed in
+ *                ascending i as acc = acc + w_i * v from +0
+ *   composite    out = F + g * fetch(R, (x + 0.5) * 2^-d - 0.5, (y + 0.5) * 2^-d - 0.5)
+ *
+ * Where no sky sample exceeds t, S = R = +0 and out == F bit for bit.  Frame order: the lights' sum, k_ao, k_velocity,
+ * k_taa (whose history never holds shafts), k_dof, k_mblur, k_shaft_source, k_shaft_march, k_shaft_composite, the bloom's
+ * launches (a bright shaft may glow), the overlay (neither a source nor brightened), the finalise of the result.  The pass
+ * keeps nothing from frame to frame: it composes with accumulations, frames in flight (every frame slot owns S and R, 16
+ * bytes a sample each) and every other pass.
+ *
+ * mr_scene_set_light_shafts copies the description during the call (NULL: off, the default); every frame enqueued
+ * afterwards uses the copy of its moment and keeps its z-buffer, winner map and float frame (MR_FRAME_KEEP_BUFFERS |
+ * MR_FRAME_KEEP_FLOAT are implied).  A scene without it enqueues what it always did.  MR_E_INVALID for a light position,
+ * threshold, gain or step that is not finite, a threshold < 0, a gain or step <= 0, samples outside 1 .. 128, halvings
+ * outside 1 .. 4, one of the first `samples` weights not finite or < 0; and, from the rendering entry points, for a partial
+ * frame (row band, stripes), before any device work.  MR_E_UNSUPPORTED from a library linked without shafts.hip or
+ * accum.hip. */
+typedef struct mr_light_shafts_desc {
+    float light_x, light_y;        /* the light on level d: (screen x + 0.5) / 2^d - 0.5, likewise y */
+    float threshold;               /* t: >= 0 */
+    float gain;                    /* g: > 0 */
+    float step;                    /* density / samples: > 0; 1 / samples reaches the light with tap n */
+    int32_t samples;               /* n: 1 .. 128 */
+    int32_t halvings;              /* d: 1 .. 4, the halvings of the sample grid (a supersampled grid's own included) */
+    float weights[128];            /* w_i, i < n: finite and >= 0; the others are not read */
+} mr_light_shafts_desc;
+int mr_scene_set_light_shafts(mr_scene *scene, const mr_light_shafts_desc *shafts);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what the kernels write.  frame and out_frame are
+ * (height, width, 3) float32, zbuf (height, width) float64.  out_source and out_march may be NULL; else they receive S and R,
+ * (H_d, W_d, 3) float32 each.  MR_E_INVALID for a NULL argument, out_frame == frame, what mr_scene_set_light_shafts
+ * refuses, or a height or width outside 1 .. 32767. */
+int mr_host_light_shafts(const float *frame, const double *zbuf, int32_t height, int32_t width, const mr_light_shafts_desc *shafts,
+                         float *out_frame, float *out_source, float *out_march);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued the pass, out[1], out[2] = the sample rows and columns of the last
+ * of them (0 before the first), out[3] = its halvings d.  Does not wait. */
+#define MR_N_LIGHT_SHAFTS_COUNTS 4
+int mr_debug_light_shafts(mr_scene *scene, int32_t *out);
+
+/* Device times in milliseconds of the last frame with the pass: k_shaft_source, k_shaft_march, k_shaft_composite.  Waits
+ * for them.  MR_E_INVALID before the first such frame. */
+#define MR_N_LIGHT_SHAFTS_TIMES 3
+int mr_debug_light_shafts_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: the three kernels on a frame and a z-buffer the caller supplies -- no frame is rendered.  Arrays as for
+ * mr_host_light_shafts.  On the device the frame, the z-buffer, S and R each lie between 256 bytes of sentinel either side:
+ * MR_E_DEVICE, with a text, when one of those bytes changed.  The scene lends its error text only: its frame slots and what
+ * mr_debug_light_shafts reports stay as they were, and the entry's device buffers are released when it returns.  Waits for
+ * the device.  MR_E_INVALID, before any device call, for a NULL argument (out_source and out_march may be NULL), a height or
+ * width outside 1 .. 32767 and what mr_scene_set_light_shafts refuses. */
+int mr_debug_light_shafts_post(mr_scene *scene, const float *frame, const double *zbuf, int32_t height, int32_t width,
+                               const mr_light_shafts_desc *shafts, float *out_frame, float *out_source, float *out_march);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

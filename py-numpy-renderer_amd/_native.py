@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, light_shafts_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -123,6 +123,22 @@ def fill_bloom_desc(threshold, gain, levels):
     """``mr_bloom_desc`` of a frame's constants (``_pack.bloom_constants``)."""
     d = BloomDesc()
     d.threshold, d.gain, d.levels = float(threshold), float(gain), int(levels)
+    return d
+
+
+class LightShaftsDesc(C.Structure):
+    _fields_ = [("light_x", C.c_float), ("light_y", C.c_float), ("threshold", C.c_float), ("gain", C.c_float), ("step", C.c_float),
+                ("samples", C.c_int32), ("halvings", C.c_int32), ("weights", C.c_float * 128)]
+
+
+def fill_light_shafts_desc(light_x, light_y, threshold, gain, step, samples, levels, weights):
+    """``mr_light_shafts_desc`` of a frame's constants (``_pack.light_shafts_constants``); *levels* is the library's
+    ``halvings``, those of a supersampled grid included.  At most the first 128 of *weights* are taken."""
+    d = LightShaftsDesc()
+    d.light_x, d.light_y, d.threshold, d.gain, d.step = (float(v) for v in (light_x, light_y, threshold, gain, step))
+    d.samples, d.halvings = int(samples), int(levels)
+    for i, w in enumerate(np.asarray(weights, dtype=np.float32).ravel()[:128]):
+        d.weights[i] = float(w)
     return d
 
 
@@ -325,6 +341,12 @@ _PROTOTYPES = {
     "mr_debug_bloom": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_bloom_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_bloom_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BloomDesc), C.c_int32, C.c_void_p, C.c_void_p]),
+    "mr_scene_set_light_shafts": (C.c_int, [C.c_void_p, C.POINTER(LightShaftsDesc)]),
+    "mr_host_light_shafts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(LightShaftsDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mr_debug_light_shafts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_light_shafts_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_light_shafts_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(LightShaftsDesc), C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -574,6 +596,50 @@ def debug_bloom_post(handle, frame, desc, shape=0, pyramid=False, guard=16):
     """``mr_debug_bloom_post``: the bloom's kernels on the caller's frame, no frame rendered; *shape* 0 .. 2 is
     ``k_bloom_down``'s workgroup.  Returns what ``host_bloom`` returns."""
     return _bloom_call(load_library().mr_debug_bloom_post, "mr_debug_bloom_post", (handle,), frame, desc, (int(shape),), pyramid, guard)
+
+
+def shafts_level(height, width, levels):
+    """``(H_d, W_d)``: a ``(height, width)`` sample grid halved *levels* times, every extent the ceiling of half the one before."""
+    for _ in range(int(levels)):
+        height, width = (height + 1) // 2, (width + 1) // 2
+    return height, width
+
+
+def _shafts_call(entry, name, head, frame, zbuf, desc, fields, guard):
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    zbuf = np.ascontiguousarray(zbuf, dtype=np.float64)
+    if frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError(f"frame must be (H, W, 3), got {frame.shape}")
+    if zbuf.shape != frame.shape[:2]:
+        raise ValueError(f"zbuf must be (H, W) = {frame.shape[:2]}, got {zbuf.shape}")
+    h, w = frame.shape[:2]
+    ch, cw = shafts_level(h, w, max(min(int(desc.halvings), 4), 0))
+    # (every output between `guard` floats of a value the library never writes: the entry fills its float counts and no more)
+    arrays = [np.full(n + 2 * guard, -7.5, dtype=np.float32) for n in (frame.size, ch * cw * 3, ch * cw * 3)]
+    out, src, march = arrays
+    _check_accum(entry(*head, frame.ctypes.data, zbuf.ctypes.data, h, w, C.byref(desc), out[guard:].ctypes.data,
+                       src[guard:].ctypes.data if fields else None, march[guard:].ctypes.data if fields else None), name)
+    touched = sum(int((a[:guard] != -7.5).sum() + (a[len(a) - guard:] != -7.5).sum()) for a in arrays) if guard else 0
+    if touched:
+        raise AssertionError(f"{name}: {touched} guard floats round the outputs changed")
+    result = out[guard:guard + frame.size].reshape(frame.shape)
+    if not fields:
+        return result
+    return result, src[guard:guard + ch * cw * 3].reshape(ch, cw, 3), march[guard:guard + ch * cw * 3].reshape(ch, cw, 3)
+
+
+def host_light_shafts(frame, zbuf, desc, fields=False, guard=16):
+    """``mr_host_light_shafts``: the light shafts' definition on the host, no device.  *frame* ``(Hs, Ws, 3)`` float32, *zbuf*
+    ``(Hs, Ws)`` float64, *desc* a ``LightShaftsDesc``; returns the frame with the shafts, and with *fields* ``(frame, S, R)``,
+    the march's source and result as ``(H_d, W_d, 3)`` arrays.  Every output is handed over between *guard* floats, which
+    must come back untouched.  ``ValueError`` with the library's text for what it refuses."""
+    return _shafts_call(load_library().mr_host_light_shafts, "mr_host_light_shafts", (), frame, zbuf, desc, fields, guard)
+
+
+def debug_light_shafts_post(handle, frame, zbuf, desc, fields=False, guard=16):
+    """``mr_debug_light_shafts_post``: the light shafts' kernels on the caller's frame and z-buffer, no frame rendered.
+    Returns what ``host_light_shafts`` returns."""
+    return _shafts_call(load_library().mr_debug_light_shafts_post, "mr_debug_light_shafts_post", (handle,), frame, zbuf, desc, fields, guard)
 
 
 def _taa_arrays(frame, velocity, history):
@@ -1019,9 +1085,9 @@ class DeviceRenderer:
         if getattr(self, packed_name, None) == packed:
             return
         desc = fill(scene)
-        key = bytes(desc)
+        key = None if desc is None else bytes(desc)           # (None: this view has no use for the pass -- off for this frame)
         if getattr(self, key_name, None) != key:
-            _check_accum(setter(self.handle, C.byref(desc)), entry)
+            _check_accum(setter(self.handle, None if desc is None else C.byref(desc)), entry)
             setattr(self, key_name, key)
         setattr(self, packed_name, packed)
 
@@ -1056,13 +1122,38 @@ class DeviceRenderer:
         call."""
         self._sync_desc(scene, "bloom", "mr_scene_set_bloom", self._bloom_values, lambda sc: fill_bloom_desc(*bloom_constants(sc)))
 
+    @staticmethod
+    def _light_shafts_values(scene):
+        """The scene's ``LightShafts`` by value and what it takes from its light (``None`` without one), for ``_frame_key``.
+        ``ValueError`` for a ``light`` index the scene does not have."""
+        shafts = getattr(scene, "light_shafts", None)
+        if shafts is None:
+            return None
+        lights = list(scene.lights)
+        if shafts.light >= len(lights):
+            raise ValueError(f"light shafts: light {shafts.light} does not exist: the scene has {len(lights)}")
+        light = lights[shafts.light]
+        vec = lambda a: tuple(np.asarray(a, dtype=np.float64).ravel().tolist())
+        return (tuple(getattr(shafts, name) for name in shafts.__slots__), id(light), vec(light.position), vec(light.center), str(light.light_type))
+
+    def sync_light_shafts(self, scene):
+        """``mr_scene_set_light_shafts`` for the frames enqueued from now on, whenever the description -- the scene's
+        ``LightShafts``, its light's place on this view's sample grid, the levels its ``supersample`` adds -- is not the
+        one last handed over; a view whose light lies behind the camera hands over NULL.  A scene that never had one
+        makes no call."""
+        def fill(sc):
+            constants = light_shafts_constants(sc)
+            return None if constants is None else fill_light_shafts_desc(*constants)
+        self._sync_desc(scene, "shafts", "mr_scene_set_light_shafts", self._light_shafts_values, fill)
+
     def _sync_post(self, scene):
-        """The post passes of the frame being issued, in the order they run: the six descriptions in step with *scene*."""
+        """The post passes of the frame being issued, in the order they run: the seven descriptions in step with *scene*."""
         self.sync_ambient_occlusion(scene)
         self.sync_temporal_aa(scene)
         self.sync_depth_of_field(scene)
         self.sync_motion_blur(scene)
         self.sync_motion_faces(scene)
+        self.sync_light_shafts(scene)
         self.sync_bloom(scene)
 
     @staticmethod
@@ -1225,7 +1316,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), DeviceRenderer._light_shafts_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -1327,6 +1418,8 @@ class DeviceRenderer:
             raise ValueError("depth of field takes whole frames (no row band, no stripes): its taps cross the bands")
         if getattr(scene, "bloom", None) is not None and partial:
             raise ValueError("bloom takes whole frames (no row band, no stripes): its taps cross the bands")
+        if getattr(scene, "light_shafts", None) is not None and partial:
+            raise ValueError("light shafts takes whole frames (no row band, no stripes): its taps cross the bands")
         self._sync_post(scene)
         if overlay:
             self.sync_overlay(scene)
@@ -1444,6 +1537,18 @@ class DeviceRenderer:
     def bloom_times(self):
         """Device milliseconds of the last bloom's down chain, up chain and composite (``mr_debug_bloom_times``)."""
         return self._times(self.lib.mr_debug_bloom_times, self.BLOOM_TIME_NAMES)
+
+    # -- light shafts (Scene.light_shafts) -----------------------------------------------------------
+    def light_shafts_debug(self):
+        """``mr_debug_light_shafts``: (frames that enqueued the pass, the last one's sample rows, its sample columns, its halvings)."""
+        return self._counts(self.lib.mr_debug_light_shafts, 4)
+
+    LIGHT_SHAFTS_TIME_NAMES = ("source", "march", "composite")
+
+    def light_shafts_times(self):
+        """Device milliseconds of the last frame's ``k_shaft_source``, ``k_shaft_march`` and ``k_shaft_composite``
+        (``mr_debug_light_shafts_times``)."""
+        return self._times(self.lib.mr_debug_light_shafts_times, self.LIGHT_SHAFTS_TIME_NAMES)
 
     # -- temporal anti-aliasing (Scene.temporal_aa) ----------------------------------------------
     def read_history(self):

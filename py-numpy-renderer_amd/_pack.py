@@ -290,6 +290,93 @@ def bloom_constants(scene):
     return bloom.threshold, gain, bloom.levels + {1: 0, 2: 1, 4: 2}[s]
 
 
+def check_light_shafts(light, intensity, density, decay, samples, threshold, halvings):
+    """The parameters of a ``LightShafts`` as ``(light, intensity, density, decay, samples, threshold, halvings)``: *light* an
+    int >= 0 (an index into ``scene.lights``, looked up when a frame is issued), *intensity* and *density* Python floats
+    that are finite and > 0 as float32, *decay* one in (0, 1] as float32, *samples* an int in 1 .. 128, *threshold* a float
+    in [0, 1) as float32, *halvings* 1 or 2."""
+    def number(value, what):
+        if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError(f"light shafts: {what} must be a real number, got {value!r}")
+        with np.errstate(over="ignore"):
+            return np.float32(value)
+
+    def integer(value, what, lo, hi):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+            raise TypeError(f"light shafts: {what} must be an int, got {value!r}")
+        if not lo <= value <= hi:
+            raise ValueError(f"light shafts: {what} must lie in {lo} .. {hi}, got {value!r}")
+        return int(value)
+
+    light = integer(light, "light", 0, 2 ** 31 - 1)
+    for value, what in ((intensity, "intensity"), (density, "density")):
+        v = number(value, what)
+        if not np.isfinite(v) or v <= 0:
+            raise ValueError(f"light shafts: {what} must be finite and > 0 as float32, got {value!r}")
+    d = number(decay, "decay")
+    if not np.isfinite(d) or not (0 < d <= 1):
+        raise ValueError(f"light shafts: decay must lie in (0, 1] as float32, got {decay!r}")
+    samples = integer(samples, "samples", 1, 128)
+    t = number(threshold, "threshold")
+    if not np.isfinite(t) or not (0 <= t < 1):
+        raise ValueError(f"light shafts: threshold must lie in [0, 1) as float32, got {threshold!r}")
+    halvings = integer(halvings, "halvings", 1, 2)
+    return light, float(intensity), float(density), float(decay), samples, float(threshold), halvings
+
+
+def light_shafts_weights(decay, samples):
+    """The march's weights: ``w_0 = 1``, ``w_{i+1} = w_i * decay`` in float64 -- a running product, no ``pow``: every host
+    sends the same table -- divided by their sum and rounded to float32.  They sum to 1: more samples is not more light."""
+    w = np.empty(int(samples), dtype=np.float64)
+    value = np.float64(1.0)
+    for i in range(int(samples)):
+        w[i] = value
+        value = value * np.float64(decay)
+    return (w / w.sum()).astype(np.float32)
+
+
+def light_shafts_position(scene, light):
+    """Where *light* stands on the un-jittered sample grid of *scene*'s frame: ``(x_u, y_u, w)`` float64, the row vector of
+    its ``position`` -- for a directional light of the point at infinity it shines from, ``(position - center, 0)`` --
+    through ``S = MVP @ viewport``, the matrix ``MotionState`` uses: the rays stand still under ``temporal_aa``."""
+    kind = light.light_type.value if hasattr(light.light_type, "value") else int(light.light_type)
+    position = np.asarray(light.position, dtype=np.float64).ravel()[:3]
+    if kind == 0:
+        point = np.append(position - np.asarray(light.center, dtype=np.float64).ravel()[:3], 0.0)
+    else:
+        point = np.append(position, 1.0)
+    viewport = sample_grid(scene)[3]
+    S = np.asarray(scene.camera.MVP, dtype=np.float64) @ np.asarray(viewport, dtype=np.float64)
+    x, y, _, w = (float(v) for v in point @ S)
+    return x, y, w
+
+
+def light_shafts_constants(scene):
+    """What ``mr_light_shafts_desc`` carries for a frame of *scene* (``light_shafts`` set): ``(light_x, light_y, threshold,
+    gain, step, samples, levels, weights)``, or ``None`` where the light has no place on the screen -- it lies in or behind
+    the camera's plane (``w <= 0``), or something is not finite -- and the frame runs without the pass.  ``levels =
+    halvings + log2(supersample)``: the march runs at the same share of the OUTPUT resolution at any ``supersample``.  The
+    light on that level is ``((x_u / w + 0.5) / 2^levels - 0.5, ...)`` rounded to float32, ``step = float32(density /
+    samples)``, ``gain = float32(intensity)``.  ``ValueError`` for a ``light`` index the scene does not have."""
+    shafts = scene.light_shafts
+    lights = list(scene.lights)
+    if shafts.light >= len(lights):
+        raise ValueError(f"light shafts: light {shafts.light} does not exist: the scene has {len(lights)}")
+    s = check_supersample(getattr(scene, "supersample", 1))
+    levels = shafts.halvings + {1: 0, 2: 1, 4: 2}[s]
+    with np.errstate(all="ignore"):
+        x, y, w = light_shafts_position(scene, lights[shafts.light])
+        if not (np.isfinite(x) and np.isfinite(y) and np.isfinite(w)) or w <= 0:
+            return None
+        lx = np.float32((x / w + 0.5) / 2.0 ** levels - 0.5)
+        ly = np.float32((y / w + 0.5) / 2.0 ** levels - 0.5)
+        step = np.float32(np.float64(shafts.density) / np.float64(shafts.samples))
+    if not (np.isfinite(lx) and np.isfinite(ly) and np.isfinite(step) and step > 0):
+        return None
+    return (float(lx), float(ly), shafts.threshold, float(np.float32(shafts.intensity)), float(step), shafts.samples, levels,
+            light_shafts_weights(shafts.decay, shafts.samples))
+
+
 def check_motion_blur(shutter):
     """The parameter of a ``MotionBlur``: a Python float that lies in (0, 1] as float32."""
     if isinstance(shutter, (bool, str, bytes)) or not isinstance(shutter, (int, float, np.integer, np.floating)):

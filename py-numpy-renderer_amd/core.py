@@ -210,6 +210,32 @@ class Bloom:
         return f"Bloom(threshold={self.threshold!r}, intensity={self.intensity!r}, levels={self.levels!r})"
 
 
+class LightShafts:
+    """What ``Scene.light_shafts`` holds: crepuscular rays, the bright sky streaming past the models towards a light's place
+    on the screen, marched on the device (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6o the reasons).
+    ``light`` (an int, default 0) is an index into ``scene.lights``; an index that does not exist when a frame is issued
+    raises there.  ``intensity`` (finite and > 0 as float32, default 0.5) is the gain of the rays over the frame.
+    ``density`` (finite and > 0, default 0.9) is how far towards the light a sample marches: 1 reaches it, more overshoots.
+    ``decay`` (in (0, 1], default 0.97) makes tap ``i`` weigh ``decay^i``; the weights are normalised, so more samples is not
+    more light.  ``samples`` (an int in 1 .. 128, default 64) is the number of taps.  ``threshold`` (a float32 in [0, 1),
+    default 0) is the bloom's bright factor, applied to the sky only.  ``halvings`` (1 or 2, default 2): the march runs at
+    1/2 or 1/4 of the output resolution per axis.  ``ValueError`` outside these ranges, ``TypeError`` for the wrong type.
+    A ``LightShafts`` is never modified: assign a new one to change it."""
+
+    __slots__ = ("light", "intensity", "density", "decay", "samples", "threshold", "halvings")
+
+    def __init__(self, light=0, intensity=0.5, density=0.9, decay=0.97, samples=64, threshold=0.0, halvings=2):
+        from ._pack import check_light_shafts
+        for name, value in zip(self.__slots__, check_light_shafts(light, intensity, density, decay, samples, threshold, halvings)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a LightShafts is read-only: assign a new one to Scene.light_shafts")
+
+    def __repr__(self):
+        return "LightShafts(" + ", ".join(f"{name}={getattr(self, name)!r}" for name in self.__slots__) + ")"
+
+
 class TemporalAA:
     """What ``Scene.temporal_aa`` holds: anti-aliasing spread over consecutive frames.  Every frame is rendered once, with a
     sub-sample offset of its sample grid, and its float colours are blended into the history -- the previous frame as this
@@ -929,6 +955,12 @@ class Scene:
       keeps nothing between frames: it composes with ``accumulate()``, ``render_mean()``, ``render_frames()``,
       ``render_async()``, several lights and every other pass; the history of ``temporal_aa`` never holds glow.  Split
       frames (``row_band``, ``multigpu``) refuse it.  With ``None`` a scene enqueues exactly what it did without it.
+    * ``light_shafts`` (an addition; ``None`` by default, or a ``LightShafts``): the sky's light streaming past the models
+      towards one of the scene's lights, marched on the device behind the motion blur and in front of the bloom, which
+      may make a bright shaft glow; the debug frustum's lines are neither sources nor brightened.  A frame whose light
+      lies behind the camera, or without sky above the threshold, is ``render()``'s byte for byte.  The pass keeps nothing
+      between frames and composes like ``bloom``; the history of ``temporal_aa`` never holds shafts.  Split frames
+      (``row_band``, ``multigpu``) refuse it.  With ``None`` a scene enqueues exactly what it did without it.
     """
 
     camera = Bound()
@@ -1025,6 +1057,17 @@ class Scene:
         if value is not None and not isinstance(value, Bloom):
             raise TypeError(f"bloom must be None or a Bloom, got {type(value).__name__}")
         self.__dict__["_bloom"] = value
+
+    @property
+    def light_shafts(self):
+        """``None`` (off, the default) or the scene's ``LightShafts`` (see the class docstring)."""
+        return self.__dict__.get("_light_shafts")
+
+    @light_shafts.setter
+    def light_shafts(self, value):
+        if value is not None and not isinstance(value, LightShafts):
+            raise TypeError(f"light_shafts must be None or a LightShafts, got {type(value).__name__}")
+        self.__dict__["_light_shafts"] = value
 
     @property
     def last_stats(self):

@@ -17,6 +17,7 @@ struct FrameSlot {
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
     DevBuf d_frame_b;                             // the float frame k_taa, k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
     DevBuf d_bloom;                               // the pyramid of a frame with bloom: levels 1 .. L, three floats a sample (host_bloom.h, bloom_pyramid)
+    DevBuf d_shafts;                              // S and R of a frame with light shafts, 16 bytes a sample (host_shafts.h, shafts_level)
     MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur or temporal anti-aliasing (host_motion.h)
     MotionFacesSlot motion_faces;                 // the face records and the tables of its per-face pass (host_motion_faces.h)
     bool last_motion = false;                     // the last frame ran k_velocity: mr_read_velocity has something to read
@@ -51,7 +52,7 @@ struct FrameSlot {
     void release()
     {
         for (DevBuf *b : { &d_vout, &d_vclip, &d_count_list, &d_tris, &d_clips, &d_status, &d_quads, &d_sil, &d_counters,
-                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_bloom, &d_out })
+                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_bloom, &d_shafts, &d_out })
             b->release();
         for (DevBuf &b : d_items) b.release();
         for (DevBuf &b : d_stencil_x) b.release();
@@ -164,7 +165,7 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
     const struct { bool on; const char *name; } passes[] = { { sc->ao.on, "ambient occlusion" }, { sc->dof.on, "depth of field" }, { sc->motion.on, "motion blur" },
-                                                         { sc->taa.on, "temporal anti-aliasing" }, { sc->bloom.on, "bloom" } };
+                                                         { sc->taa.on, "temporal anti-aliasing" }, { sc->bloom.on, "bloom" }, { sc->shafts.on, "light shafts" } };
     for (const auto &pass : passes)
         if (pass.on && is_partial(fr))
             return fail(MR_E_INVALID, std::string(pass.name) + " takes whole frames (no row band, no stripes): its taps cross the bands");
@@ -342,16 +343,18 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   taa          the scene has temporal anti-aliasing on: k_velocity and k_taa behind k_ao, in front of k_dof, with taa_params and
 //                taa_vel (the velocity's scalars), likewise
 //   bloom        the scene has bloom on: its 2 L launches behind k_mblur, in front of the overlay, with bloom_params, likewise
+//   shafts       the scene has light shafts on: their three launches behind k_mblur, in front of the bloom, with shafts_params, likewise
 //   post()       a pass rewrites the float frame behind the tile kernel: the bytes are the full resolve of the result
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa, bloom;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa, bloom, shafts;
     mr::AoParams ao_params;
     mr::DofParams dof_params;
     mr::MotionParams motion_params, taa_vel;
     mr::TaaParams taa_params;
     mr::BloomParams bloom_params;
-    bool post() const { return ao || dof || motion || taa || bloom; }
+    mr::ShaftsParams shafts_params;
+    bool post() const { return ao || dof || motion || taa || bloom || shafts; }
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -390,7 +393,7 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     if (fc.ss_mode & SS_SEPARATE) fc.flags |= MR_FRAME_KEEP_FLOAT;
     // (a post pass reads the whole z-buffer -- the motion blur the winner map as well -- and rewrites the whole float frame,
     // in place or into the second one: every tile writes its taps, as for a caller who asked for them)
-    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on; p.taa = sc->taa.on; p.bloom = sc->bloom.on;
+    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on; p.taa = sc->taa.on; p.bloom = sc->bloom.on; p.shafts = sc->shafts.on;
     if (p.motion && sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
         return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
     if (p.motion && sc->mfaces.on && sc->mfaces.deforming.size() != sc->model_face_off.size())
@@ -402,6 +405,7 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     p.ao_params = sc->ao.params; p.dof_params = sc->dof.params; p.motion_params = sc->motion.params;
     p.taa_params = sc->taa.params; p.taa_vel = sc->taa.vel;
     p.bloom_params = sc->bloom.params;
+    p.shafts_params = sc->shafts.params;
     if (p.post()) fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
@@ -476,7 +480,9 @@ int grow_slot(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Frame
         { fs->d_stencil, kept * sizeof(int32_t) }, { fs->d_frame, kept_f * 3 * sizeof(float) },
         { fs->d_frame_b, p.dof || p.motion || p.taa ? kept_f * 3 * sizeof(float) : 0 },
         // (one pyramid per slot: frames in flight keep their own)
-        { fs->d_bloom, p.bloom ? bloom_pyramid(fc.width, fc.height, p.bloom_params.levels).floats * sizeof(float) : 0 } };
+        { fs->d_bloom, p.bloom ? bloom_pyramid(fc.width, fc.height, p.bloom_params.levels).floats * sizeof(float) : 0 },
+        // (S and R per slot: two frames in flight under two cameras keep their own light position)
+        { fs->d_shafts, p.shafts ? 2 * shafts_level(fc.width, fc.height, p.shafts_params.levels).device_floats() * sizeof(float) : 0 } };
     for (const auto &b : sized) HIP_TRY(b.buf.ensure(b.bytes));
     if (p.taa)
         if (int rc = grow_history(sc, fc.width, fc.height)) return rc;
@@ -639,7 +645,7 @@ void launch_post_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, i
 // given; the two ping-pong when several of k_taa, k_dof and k_mblur run.
 inline void swap_float_frames(FrameSlot *fs) { std::swap(fs->d_frame, fs->d_frame_b); }
 
-// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the temporal anti-aliasing, the depth of field, the motion blur, the bloom, the overlay (exported
+// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the temporal anti-aliasing, the depth of field, the motion blur, the light shafts, the bloom, the overlay (exported
 // by a device that owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638)
 // and the resolve of a supersampled, darkened or blurred frame
 int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
@@ -670,6 +676,11 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
             return rc;
         swap_float_frames(fs);
     }
+    // (the lens and the blur key on the z of the surface behind a ray and would treat the rays as paint on it: the shafts
+    // are added behind them; the bloom comes after, so a bright shaft may glow)
+    if (p.shafts && p.n_tiles > 0)
+        if (int rc = launch_light_shafts(sc, stream, fs->d_frame.as<float>(), fs->d_z.as<double>(), fs->d_shafts.as<float>(), fc.width, fc.height, p.shafts_params))
+            return rc;
     // (the glow forms in the lens, behind the blur; k_taa's history was written in front of it and never holds glow; the
     // overlay's lines are drawn over it and do not glow)
     if (p.bloom && p.n_tiles > 0)

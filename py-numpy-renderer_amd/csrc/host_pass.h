@@ -7,7 +7,7 @@
 // It stands in front of host_scene.h, because mr_scene holds the records by value.
 #pragma once
 
-// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip and bloom.hip, the library's other translation units,
+// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip, bloom.hip and shafts.hip, the library's other translation units,
 // each declared here and nowhere else; weak, so that a library linked without one of them (the tools' ablation builds)
 // still loads: it refuses that pass instead (linked)
 namespace mr_accum {
@@ -44,6 +44,12 @@ __attribute__((weak)) void launch_down(hipStream_t stream, const float *src, flo
 __attribute__((weak)) void launch_up(hipStream_t stream, float *fine, const float *coarse, int w, int h);
 __attribute__((weak)) void launch_composite(hipStream_t stream, float *frame, const float *coarse, int w, int h, float gain);
 }  // namespace mr_bloom
+namespace mr_shafts {
+__attribute__((weak)) void launch_source(hipStream_t stream, const float *frame, const double *zbuf, float *dst, int w, int h, int dw, int dh,
+                                         float threshold, int levels);
+__attribute__((weak)) void launch_march(hipStream_t stream, const float *src, float *dst, int w, int h, const mr::ShaftsParams &p);
+__attribute__((weak)) void launch_composite(hipStream_t stream, float *frame, const float *coarse, int w, int h, int cw, int ch, int levels, float gain);
+}  // namespace mr_shafts
 
 namespace {
 
@@ -69,6 +75,14 @@ inline int bloom_linked()
 {
     return linked("this library was linked without bloom.hip or accum.hip: no bloom (build it with __graft_entry__.build())",
                   &mr_bloom::launch_down, &mr_bloom::launch_up, &mr_bloom::launch_composite, &mr_accum::launch_resolve);
+}
+
+// the light shafts' three kernels are shafts.hip's; the bytes of such a frame are the accumulation's resolve of its float
+// frame (accum.hip)
+inline int shafts_linked()
+{
+    return linked("this library was linked without shafts.hip or accum.hip: no light shafts (build it with __graft_entry__.build())",
+                  &mr_shafts::launch_source, &mr_shafts::launch_march, &mr_shafts::launch_composite, &mr_accum::launch_resolve);
 }
 
 // ---- timing marks: N events round a pass's kernels, created by the first frame that records them and kept for the

@@ -196,6 +196,8 @@ struct mr_scene {
     struct Dof : PassRecord<2> { mr::DofParams params = {}; } dof;
     // ... bloom (host_bloom.h), marked in front of its down chain, behind it, behind the up chain and behind the composite
     struct Bloom : PassRecord<4> { mr::BloomParams params = {}; int32_t last_levels = 0; } bloom;      // (the levels of the last frame enqueued)
+    // ... light shafts (host_shafts.h), marked in front of the source, behind it, behind the march and behind the composite
+    struct Shafts : PassRecord<4> { mr::ShaftsParams params = {}; int32_t last_levels = 0; } shafts;   // (likewise)
 
     // ... and motion blur (host_motion.h), marked in front of k_velocity, behind it, behind k_velocity_faces in a frame that
     // ran the per-face pass, and behind k_mblur; the tables are the class matrices, the background's, the models' first

@@ -2,7 +2,8 @@
 // accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), from
 // ao.hip, which holds the ambient obscurance's kernel in another, from dof.hip, which holds the depth of field's, and from
 // motion.hip, which holds the motion blur's two, from motion_faces.hip, which holds the per-face velocity's two, from
-// taa.hip, which holds the temporal anti-aliasing's, and from bloom.hip, which holds the bloom's three;
+// taa.hip, which holds the temporal anti-aliasing's, from bloom.hip, which holds the bloom's three, and from shafts.hip,
+// which holds the light shafts' three;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -20,6 +21,7 @@
 //   host_motion_faces.h the velocity of models that bend: the vertex snapshot and its serial, the two launches, the mirrors
 //   host_taa.h          temporal anti-aliasing: the description, the scene's history, the launch, the host mirror, mr_debug_taa_post
 //   host_bloom.h        bloom from a resolution pyramid: the description, the pyramid's layout, the launches, the host mirror, mr_debug_bloom_post
+//   host_shafts.h       light shafts marched towards a light: the description, S and R, the launches, the host mirror, mr_debug_light_shafts_post
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
@@ -43,7 +45,8 @@
 //                   mr_scene_set_depth_of_field, k_velocity and k_mblur behind those in one with
 //                   mr_scene_set_motion_blur, k_velocity and k_taa between k_ao and k_dof in one with
 //                   mr_scene_set_temporal_aa, k_bloom_down, k_bloom_up and k_bloom_composite behind k_mblur in one with
-//                   mr_scene_set_bloom, k_accum_resolve for the bytes of any)
+//                   mr_scene_set_bloom, k_shaft_source, k_shaft_march and k_shaft_composite in front of those in one with
+//                   mr_scene_set_light_shafts, k_accum_resolve for the bytes of any)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -77,6 +80,7 @@
 #include "motion_faces_def.h"
 #include "taa_def.h"
 #include "bloom_def.h"
+#include "shafts_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -93,6 +97,7 @@
 #include "host_motion_faces.h"
 #include "host_taa.h"
 #include "host_bloom.h"
+#include "host_shafts.h"
 #include "host_frame.h"
 #include "host_accum.h"
 #include "host_post.h"
@@ -239,7 +244,7 @@ void mr_scene_destroy(mr_scene *sc)
     for (auto &fs : sc->slots) fs->release();
     sc->sil.release();
     accum_release(sc->accum);
-    release_pass(sc->ao); release_pass(sc->dof); release_pass(sc->motion); release_pass(sc->bloom);
+    release_pass(sc->ao); release_pass(sc->dof); release_pass(sc->motion); release_pass(sc->bloom); release_pass(sc->shafts);
     motion_faces_release(sc);
     taa_release(sc);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
@@ -818,6 +823,35 @@ int mr_debug_bloom_post(mr_scene *sc, const float *frame, int32_t height, int32_
                         float *out_frame, float *out_pyramid)
 {
     return debug_bloom_post(sc, frame, height, width, bloom, shape, out_frame, out_pyramid);
+}
+
+int mr_scene_set_light_shafts(mr_scene *sc, const mr_light_shafts_desc *shafts)
+{
+    return set_pass(sc, &mr_scene::shafts, shafts, shafts_params, shafts_linked);
+}
+
+int mr_host_light_shafts(const float *frame, const double *zbuf, int32_t height, int32_t width, const mr_light_shafts_desc *shafts, float *out_frame,
+                         float *out_source, float *out_march)
+{
+    return host_light_shafts(frame, zbuf, height, width, shafts, out_frame, out_source, out_march);
+}
+
+int mr_debug_light_shafts(mr_scene *sc, int32_t *out)
+{
+    if (int rc = pass_counts(sc, &mr_scene::shafts, out)) return rc;
+    out[3] = sc->shafts.last_levels;
+    return MR_OK;
+}
+
+int mr_debug_light_shafts_times(mr_scene *sc, float *out_ms)
+{
+    return pass_times(sc, &mr_scene::shafts, "no frame with light shafts yet", out_ms, { { 0, 1 }, { 1, 2 }, { 2, 3 } });
+}
+
+int mr_debug_light_shafts_post(mr_scene *sc, const float *frame, const double *zbuf, int32_t height, int32_t width, const mr_light_shafts_desc *shafts,
+                               float *out_frame, float *out_source, float *out_march)
+{
+    return debug_light_shafts_post(sc, frame, zbuf, height, width, shafts, out_frame, out_source, out_march);
 }
 
 int mr_scene_set_motion_faces(mr_scene *sc, const mr_motion_faces_desc *d)
