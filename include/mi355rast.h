@@ -1142,6 +1142,104 @@ int mr_debug_light_shafts_times(mr_scene *scene, float *out_ms);
 int mr_debug_light_shafts_post(mr_scene *scene, const float *frame, const double *zbuf, int32_t height, int32_t width,
                                const mr_light_shafts_desc *shafts, float *out_frame, float *out_source, float *out_march);
 
+/* Tone mapping: an exposure metered from a luminance histogram of the frame, and a tone curve, on the device.  It lives on
+ * the frame's sample grid, behind the bloom and IN FRONT of the overlay, whose lines keep their colours.  With F the float
+ * frame there (F >= 0 and finite), all arithmetic float32 with every operation rounded on its own, or integer:
+ *
+ *   luminance   Y = (0.2126f*r + 0.7152f*g) + 0.0722f*b
+ *   bin         b = clamp((bits(Y) >> 20) - ((127 - 24) << 3), 0, 255)     8 bins a stop over 32 stops from 2^-24
+ *   histogram   n[i] = samples in bin i (uint32); n[0] (black) is metered out: n[0] := 0
+ *   trim        N = sum n;  lo = N*low_pm / 1000;  hi = N*high_pm / 1000;  C_i = n[1] + .. + n[i-1];
+ *               u_i = max(0, min(C_i + n[i], hi) - max(C_i, lo))
+ *   centre      c_i = ((i >> 3) - 24) * 256 + FRAC[i & 7],  FRAC = {22, 63, 100, 134, 165, 193, 220, 244}     1/256 stops
+ *   mean        S = sum u_i*c_i;  M = sum u_i (int64);  q = floor((2S + M) / (2M))
+ *   target      -q = 256*a + f, 0 <= f < 256;  e_t = clamp(ldexpf(key * exp2[f], a), min_exposure, max_exposure)
+ *   adapt       e = e_prev + speed * (e_t - e_prev) where the scene has a previous exposure, else e_t;
+ *               M == 0 (nothing metered): e = e_prev, else 1.0f
+ *   curve       x = F * e per channel;  linear: x;  reinhard: (x * (1 + x / (white*white))) / (1 + x);
+ *               aces: min((x*(2.51f*x + 0.03f)) / (x*(2.43f*x + 0.59f) + 0.14f), 1)
+ *
+ * exp2[f] = float32(2^(f/256)) comes with the description, so that kernel, mirror and caller read the same bits.  With
+ * `fixed` nothing is metered and e = float32(exposure).  Every count and sum is an integer: the result does not depend on
+ * the order in which the device counts the samples.  Frame order: ... k_mblur, the light shafts, the bloom, k_lum_hist,
+ * k_exposure, k_tone_apply (the last alone where the exposure is fixed), the overlay, the finalise of the result; k_taa's
+ * history was written in front of the pass and never holds tone-mapped colours.
+ *
+ * A scene has a previous exposure only while it is ADAPTIVE (metered with speed < 1): then a frame's e becomes the scene's
+ * previous exposure when that frame's mr_render or mr_render_wait returns MR_OK (a frame rendered again after an overflow
+ * reads the same e_prev), one frame of the scene is in flight at a time (MR_E_INVALID from the rendering entry points while
+ * an earlier one has not been waited for), and mr_render_device and the sub-frames of an accumulation refuse the scene.
+ * mr_scene_set_tone_map (every call, NULL included) and mr_scene_reset_exposure forget the previous exposure.  Metered with
+ * speed == 1, or fixed, the pass keeps nothing from frame to frame and composes with accumulations (sub-frames are tone-
+ * mapped before they are summed), frames in flight (every frame slot owns its slab, histogram and exposure cell) and every
+ * other pass.
+ *
+ * mr_scene_set_tone_map copies the description during the call (NULL: off, the default); every frame enqueued afterwards
+ * uses the copy of its moment and keeps its z-buffer, winner map and float frame (MR_FRAME_KEEP_BUFFERS |
+ * MR_FRAME_KEEP_FLOAT are implied).  A scene without it enqueues what it always did.  MR_E_INVALID for an operator outside
+ * 0 .. 2, a fixed flag that is not 0 or 1, key, white, exposure, min_exposure or max_exposure not finite and > 0 as float32,
+ * min_exposure > max_exposure, speed outside (0, 1] as float32, low_pm and high_pm not 0 <= low_pm < high_pm <= 1000, a
+ * table with exp2[0] != 1, not strictly increasing or not < 2; and, from the rendering entry points, for a partial frame
+ * (row band, stripes), before any device work.  MR_E_UNSUPPORTED from a library linked without tonemap.hip or accum.hip. */
+#define MR_TONE_LINEAR 0
+#define MR_TONE_REINHARD 1
+#define MR_TONE_ACES 2
+typedef struct mr_tone_map_desc {
+    int32_t op;                    /* MR_TONE_* */
+    int32_t fixed;                 /* 1: e = exposure, nothing is metered; 0: metered */
+    double exposure;               /* > 0 as float32 (checked in either case) */
+    double key;                    /* the luminance the metered mean is brought to: > 0 as float32 */
+    double white;                  /* reinhard's white point: > 0 as float32 */
+    double speed;                  /* in (0, 1] as float32; 1: no adaptation, no state */
+    double min_exposure, max_exposure;
+    int32_t low_pm, high_pm;       /* the trims in permille of the metered samples */
+    float exp2[256];               /* float32(2^(f/256)) */
+} mr_tone_map_desc;
+int mr_scene_set_tone_map(mr_scene *scene, const mr_tone_map_desc *tone_map);
+
+/* Forgets the scene's previous exposure: the next adaptive frame takes e = e_t, and a frame in flight hands nothing over. */
+int mr_scene_reset_exposure(mr_scene *scene);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what the kernels write.  frame and out_frame are
+ * (height, width, 3) float32 (out_frame may be the frame); out_hist receives the 256 counts n (n[0] = 0; all 0 where the
+ * exposure is fixed), out_exposure e.  has_prev != 0: e_prev is the scene's previous exposure.  out_hist and out_exposure may
+ * be NULL.  MR_E_INVALID for a NULL argument, what mr_scene_set_tone_map refuses, a height or width outside 1 .. 32767, or
+ * has_prev with an e_prev that is not finite and > 0. */
+int mr_host_tone_map(const float *frame, int32_t height, int32_t width, const mr_tone_map_desc *tone_map, int32_t has_prev, float e_prev,
+                     float *out_frame, uint32_t *out_hist, float *out_exposure);
+
+/* The exposure e of the last frame enqueued, where it ran the pass (waits for it), and its 256 counts n.  MR_E_INVALID
+ * where the last frame ran without the pass; the histogram also where that frame's exposure was fixed: nothing was metered. */
+int mr_read_exposure(mr_scene *scene, float *out);
+int mr_read_luminance_histogram(mr_scene *scene, uint32_t *out);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued the pass, out[1], out[2] = the sample rows and columns of the last
+ * of them (0 before the first), out[3] = the workgroups of its k_lum_hist (0: fixed exposure, not metered), out[4] = exposures
+ * handed over as the scene's previous one, out[5] = 1 while the scene holds a previous exposure.  Does not wait. */
+#define MR_N_TONE_MAP_COUNTS 6
+int mr_debug_tone_map(mr_scene *scene, int32_t *out);
+
+/* Device times in milliseconds of the last frame with the pass: k_lum_hist, k_exposure (the spans between two marks with
+ * nothing in them where the exposure is fixed), k_tone_apply.  Waits for them.  MR_E_INVALID before the first such frame. */
+#define MR_N_TONE_MAP_TIMES 3
+int mr_debug_tone_map_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: the kernels on a frame the caller supplies -- no frame is rendered.  Arrays as for mr_host_tone_map, none
+ * may be NULL; out_exposure receives TWO floats, the exposure cell and the state cell a scene would adopt (both e; the fixed
+ * exposure where nothing is metered).  grid_cap is the cap of k_lum_hist's grid: 0 for the library's default, else 1 ..
+ * 1024 -- a small field then walks the stride loop, or fills many slab rows, or one; form is k_lum_hist's: 0 an LDS add a
+ * sample, 1 an add per distinct bin of a wavefront, -1 the library's default.  On the device the frame, the block of
+ * histogram, cell and slab, and the two state cells each lie between 256 bytes of sentinel either side, and the slab is
+ * sentinel too before k_lum_hist writes it: MR_E_DEVICE, with a text, when a guard byte changed.  The scene lends its error
+ * text only: its frame slots, its previous exposure and what mr_debug_tone_map reports stay as they were, and the entry's
+ * device buffers are released when it returns.  Waits for the device.  MR_E_INVALID, before any device call, for a NULL
+ * argument (but out_ms), a height or width outside 1 .. 32767, a grid_cap outside 0 .. 1024, a form outside -1 .. 1 and what
+ * mr_host_tone_map refuses.  out_ms may be NULL; else it receives the device milliseconds of k_lum_hist, k_exposure and
+ * k_tone_apply between events of the entry's own (the first two spans hold no kernel where the exposure is fixed). */
+int mr_debug_tone_map_post(mr_scene *scene, const float *frame, int32_t height, int32_t width, const mr_tone_map_desc *tone_map,
+                           int32_t has_prev, float e_prev, int32_t grid_cap, int32_t form, float *out_frame, uint32_t *out_hist,
+                           float *out_exposure, float *out_ms);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, light_shafts_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, light_shafts_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter, tone_map_constants
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -139,6 +139,24 @@ def fill_light_shafts_desc(light_x, light_y, threshold, gain, step, samples, lev
     d.samples, d.halvings = int(samples), int(levels)
     for i, w in enumerate(np.asarray(weights, dtype=np.float32).ravel()[:128]):
         d.weights[i] = float(w)
+    return d
+
+
+class ToneMapDesc(C.Structure):
+    _fields_ = [("op", C.c_int32), ("fixed", C.c_int32), ("exposure", C.c_double), ("key", C.c_double), ("white", C.c_double),
+                ("speed", C.c_double), ("min_exposure", C.c_double), ("max_exposure", C.c_double), ("low_pm", C.c_int32),
+                ("high_pm", C.c_int32), ("exp2", C.c_float * 256)]
+
+
+def fill_tone_map_desc(op, fixed, exposure, key, white, speed, min_exposure, max_exposure, low_pm, high_pm, table):
+    """``mr_tone_map_desc`` of a frame's constants (``_pack.tone_map_constants``); *table* is ``EXP2``, 256 float32."""
+    d = ToneMapDesc()
+    d.op, d.fixed, d.low_pm, d.high_pm = int(op), int(fixed), int(low_pm), int(high_pm)
+    d.exposure, d.key, d.white, d.speed, d.min_exposure, d.max_exposure = (float(v) for v in (exposure, key, white, speed, min_exposure, max_exposure))
+    table = np.ascontiguousarray(table, dtype=np.float32).ravel()
+    if table.size != 256:
+        raise ValueError(f"the exp2 table has 256 entries, got {table.size}")
+    C.memmove(d.exp2, table.ctypes.data, 1024)
     return d
 
 
@@ -347,6 +365,15 @@ _PROTOTYPES = {
     "mr_debug_light_shafts_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_light_shafts_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(LightShaftsDesc), C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+    "mr_scene_set_tone_map": (C.c_int, [C.c_void_p, C.POINTER(ToneMapDesc)]),
+    "mr_scene_reset_exposure": (C.c_int, [C.c_void_p]),
+    "mr_host_tone_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ToneMapDesc), C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mr_read_exposure": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_read_luminance_histogram": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_tone_map": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_tone_map_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_tone_map_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ToneMapDesc), C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -640,6 +667,47 @@ def debug_light_shafts_post(handle, frame, zbuf, desc, fields=False, guard=16):
     """``mr_debug_light_shafts_post``: the light shafts' kernels on the caller's frame and z-buffer, no frame rendered.
     Returns what ``host_light_shafts`` returns."""
     return _shafts_call(load_library().mr_debug_light_shafts_post, "mr_debug_light_shafts_post", (handle,), frame, zbuf, desc, fields, guard)
+
+
+def _tone_map_call(entry, name, head, frame, desc, e_prev, tail, n_exposure, guard):
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError(f"frame must be (H, W, 3), got {frame.shape}")
+    h, w = frame.shape[:2]
+    # (every output between `guard` words of a value the library never writes: the entry fills its counts and no more)
+    out = np.full(frame.size + 2 * guard, -7.5, dtype=np.float32)
+    hist = np.full(256 + 2 * guard, 0xfeedbeef, dtype=np.uint32)
+    exposure = np.full(n_exposure + 2 * guard, -7.5, dtype=np.float32)
+    _check_accum(entry(*head, frame.ctypes.data, h, w, C.byref(desc), int(e_prev is not None), 0.0 if e_prev is None else float(e_prev), *tail,
+                       out[guard:].ctypes.data, hist[guard:].ctypes.data, exposure[guard:].ctypes.data), name)
+    touched = sum(int((a[:guard] != fill).sum() + (a[len(a) - guard:] != fill).sum())
+                  for a, fill in ((out, -7.5), (hist, 0xfeedbeef), (exposure, -7.5))) if guard else 0
+    if touched:
+        raise AssertionError(f"{name}: {touched} guard words round the outputs changed")
+    return out[guard:guard + frame.size].reshape(frame.shape), hist[guard:guard + 256].copy(), exposure[guard:guard + n_exposure].copy()
+
+
+def host_tone_map(frame, desc, e_prev=None, guard=16):
+    """``mr_host_tone_map``: the tone mapping's definition on the host, no device.  *frame* ``(Hs, Ws, 3)`` float32, *desc* a
+    ``ToneMapDesc``, *e_prev* the scene's previous exposure or ``None``; returns ``(frame, histogram, exposure)``: the
+    tone-mapped frame, the 256 uint32 counts and ``e`` as a float32.  Every output is handed over between *guard* words,
+    which must come back untouched.  ``ValueError`` with the library's text for what it refuses."""
+    out, hist, e = _tone_map_call(load_library().mr_host_tone_map, "mr_host_tone_map", (), frame, desc, e_prev, (), 1, guard)
+    return out, hist, e[0]
+
+
+def debug_tone_map_post(handle, frame, desc, e_prev=None, grid_cap=0, form=-1, guard=16, times=False):
+    """``mr_debug_tone_map_post``: the tone mapping's kernels on the caller's frame, no frame rendered; *grid_cap* caps
+    ``k_lum_hist``'s grid (0: the library's default), *form* is its form (0, 1; -1: the default).  Returns ``(frame,
+    histogram, exposure, state)``: what ``host_tone_map`` returns and the state cell a scene would adopt; with *times* a
+    fifth item, the device milliseconds of the three kernels as a dict (``DeviceRenderer.TONE_MAP_TIME_NAMES``)."""
+    ms = np.zeros(3, dtype=np.float32)
+    entry = load_library().mr_debug_tone_map_post
+    out, hist, e = _tone_map_call(lambda *a: entry(*a, ms.ctypes.data if times else None), "mr_debug_tone_map_post", (handle,), frame, desc, e_prev,
+                                  (int(grid_cap), int(form)), 2, guard)
+    if times:
+        return out, hist, e[0], e[1], dict(zip(DeviceRenderer.TONE_MAP_TIME_NAMES, (float(v) for v in ms)))
+    return out, hist, e[0], e[1]
 
 
 def _taa_arrays(frame, velocity, history):
@@ -1146,8 +1214,31 @@ class DeviceRenderer:
             return None if constants is None else fill_light_shafts_desc(*constants)
         self._sync_desc(scene, "shafts", "mr_scene_set_light_shafts", self._light_shafts_values, fill)
 
-    def _sync_post(self, scene):
-        """The post passes of the frame being issued, in the order they run: the seven descriptions in step with *scene*."""
+    @staticmethod
+    def _tone_map_values(scene):
+        """The scene's ``ToneMap`` by value (``None`` without one), for ``_frame_key``."""
+        tm = getattr(scene, "tone_map", None)
+        return None if tm is None else tuple(getattr(tm, name) for name in tm.__slots__)
+
+    def sync_tone_map(self, scene, accumulating=False):
+        """``mr_scene_set_tone_map`` for the frames enqueued from now on, whenever the description is not the one last handed
+        over, and ``mr_scene_reset_exposure`` after ``reset_motion()``.  An adaptive ``ToneMap`` takes one frame of the scene
+        at a time and no sub-frame of an accumulation.  A scene that never had one makes no call."""
+        tm = getattr(scene, "tone_map", None)
+        if tm is not None and tm.adaptive:
+            if accumulating:
+                raise ValueError("an adaptive tone_map (speed < 1) is not available inside accumulate() / render_mean(): its "
+                                 "sub-frames have no previous frame (speed=1 or a fixed exposure is)")
+            if scene.__dict__.get("_pending"):
+                raise ValueError("an adaptive tone_map (speed < 1) takes one frame of the scene at a time: another frame is "
+                                 "pending, take its result() first (every frame reads the exposure the frame before it left)")
+        forget = scene.__dict__.pop("_tone_forget", False)
+        self._sync_desc(scene, "tone", "mr_scene_set_tone_map", self._tone_map_values, lambda sc: fill_tone_map_desc(*tone_map_constants(sc)))
+        if forget and getattr(self, "_tone_key", None) is not None:
+            _check_accum(self.lib.mr_scene_reset_exposure(self.handle), "mr_scene_reset_exposure")
+
+    def _sync_post(self, scene, accumulating=False):
+        """The post passes of the frame being issued, in the order they run: the eight descriptions in step with *scene*."""
         self.sync_ambient_occlusion(scene)
         self.sync_temporal_aa(scene)
         self.sync_depth_of_field(scene)
@@ -1155,6 +1246,7 @@ class DeviceRenderer:
         self.sync_motion_faces(scene)
         self.sync_light_shafts(scene)
         self.sync_bloom(scene)
+        self.sync_tone_map(scene, accumulating)
 
     @staticmethod
     def _motion_values(scene):
@@ -1316,7 +1408,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), DeviceRenderer._light_shafts_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), DeviceRenderer._light_shafts_values(scene), DeviceRenderer._tone_map_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -1420,7 +1512,9 @@ class DeviceRenderer:
             raise ValueError("bloom takes whole frames (no row band, no stripes): its taps cross the bands")
         if getattr(scene, "light_shafts", None) is not None and partial:
             raise ValueError("light shafts takes whole frames (no row band, no stripes): its taps cross the bands")
-        self._sync_post(scene)
+        if getattr(scene, "tone_map", None) is not None and partial:
+            raise ValueError("tone mapping takes whole frames (no row band, no stripes): its exposure is metered from the whole frame")
+        self._sync_post(scene, accumulating)
         if overlay:
             self.sync_overlay(scene)
         if keep_buffers is None:
@@ -1550,6 +1644,34 @@ class DeviceRenderer:
         (``mr_debug_light_shafts_times``)."""
         return self._times(self.lib.mr_debug_light_shafts_times, self.LIGHT_SHAFTS_TIME_NAMES)
 
+    # -- tone mapping (Scene.tone_map) ------------------------------------------------------------
+    def read_exposure(self):
+        """``mr_read_exposure``: the exposure ``e`` of the last frame, which ran the pass, as a float32.  ``ValueError`` with
+        the library's text where it did not."""
+        out = np.zeros(1, dtype=np.float32)
+        _check_accum(self.lib.mr_read_exposure(self.handle, out.ctypes.data), "mr_read_exposure")
+        return out[0]
+
+    def read_luminance_histogram(self):
+        """``mr_read_luminance_histogram``: the 256 uint32 counts the last frame's exposure was metered from (bin 0, black,
+        is metered out and reads 0).  ``ValueError`` with the library's text where nothing was metered."""
+        out = np.zeros(256, dtype=np.uint32)
+        _check_accum(self.lib.mr_read_luminance_histogram(self.handle, out.ctypes.data), "mr_read_luminance_histogram")
+        return out
+
+    def tone_map_debug(self):
+        """``mr_debug_tone_map``: (frames that enqueued the pass, the last one's sample rows, its sample columns, the
+        workgroups of its ``k_lum_hist`` -- 0 with a fixed exposure --, exposures handed over, 1 while the scene holds a
+        previous exposure)."""
+        return self._counts(self.lib.mr_debug_tone_map, 6)
+
+    TONE_MAP_TIME_NAMES = ("lum_hist", "exposure", "tone_apply")
+
+    def tone_map_times(self):
+        """Device milliseconds of the last tone-mapped frame's ``k_lum_hist``, ``k_exposure`` and ``k_tone_apply``
+        (``mr_debug_tone_map_times``)."""
+        return self._times(self.lib.mr_debug_tone_map_times, self.TONE_MAP_TIME_NAMES)
+
     # -- temporal anti-aliasing (Scene.temporal_aa) ----------------------------------------------
     def read_history(self):
         """``mr_read_history``: the history as the scene holds it now -- the last complete temporal-AA frame as ``k_taa`` left
@@ -1632,6 +1754,10 @@ class DeviceRenderer:
         if getattr(scene, "temporal_aa", None) is not None:
             raise ValueError("temporal_aa frames are rendered by render() / render_async(): their return hands the history "
                              "over, and a frame enqueued on a caller's stream has none")
+        tm = getattr(scene, "tone_map", None)
+        if tm is not None and tm.adaptive:
+            raise ValueError("frames of an adaptive tone_map (speed < 1) are rendered by render() / render_async(): their return "
+                             "hands the exposure over, and a frame enqueued on a caller's stream has none")
         self.issue_motion(scene, partial=self._is_partial(scene, row_band, stripe))
         self.sync_scene(scene)
         self.sync_skybox(scene)

@@ -377,6 +377,63 @@ def light_shafts_constants(scene):
             light_shafts_weights(shafts.decay, shafts.samples))
 
 
+TONE_OPERATORS = ("linear", "reinhard", "aces")
+
+
+def permille(fraction):
+    """A trim as the device takes it: ``round(1000 * fraction)``, halves away from zero, evaluated in float64."""
+    return int(np.floor(1000.0 * float(fraction) + 0.5))
+
+
+def tone_map_table():
+    """``EXP2[f] = float32(2 ** (f / 256))`` for f in 0 .. 255, computed in float64: the table the kernels, the mirror and the
+    reference read -- no ``exp2`` runs on the device."""
+    return np.exp2(np.arange(256, dtype=np.float64) / 256.0).astype(np.float32)
+
+
+def check_tone_map(operator, exposure, key, low, high, speed, white, min_exposure, max_exposure):
+    """The parameters of a ``ToneMap``, in that order: *operator* one of ``TONE_OPERATORS``; *exposure* ``None`` (metered) or
+    a real number that is finite and > 0 as float32; *key*, *white*, *min_exposure* and *max_exposure* finite and > 0 as
+    float32 with ``min_exposure <= max_exposure``; *speed* in (0, 1] as float32; *low* and *high* fractions whose permille
+    satisfy ``0 <= low < high <= 1000``."""
+    def number(value, what):
+        if isinstance(value, (bool, str, bytes)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise TypeError(f"tone_map: {what} must be a real number, got {value!r}")
+        with np.errstate(over="ignore"):
+            return np.float32(value)
+
+    def positive(value, what):
+        v = number(value, what)
+        if not np.isfinite(v) or v <= 0:
+            raise ValueError(f"tone_map: {what} must be finite and > 0 as float32, got {value!r}")
+        return float(value)
+    if not isinstance(operator, str):
+        raise TypeError(f"tone_map: operator must be a str, got {operator!r}")
+    if operator not in TONE_OPERATORS:
+        raise ValueError(f"tone_map: operator must be one of {TONE_OPERATORS}, got {operator!r}")
+    if exposure is not None:
+        exposure = positive(exposure, "exposure")
+    key, white = positive(key, "key"), positive(white, "white")
+    min_exposure, max_exposure = positive(min_exposure, "min_exposure"), positive(max_exposure, "max_exposure")
+    if np.float32(min_exposure) > np.float32(max_exposure):
+        raise ValueError(f"tone_map: min_exposure {min_exposure!r} exceeds max_exposure {max_exposure!r}")
+    s = number(speed, "speed")
+    if not np.isfinite(s) or not (0 < s <= 1):
+        raise ValueError(f"tone_map: speed must lie in (0, 1] as float32, got {speed!r}")
+    lo, hi = number(low, "low"), number(high, "high")
+    if not (np.isfinite(lo) and np.isfinite(hi)) or not (0 <= permille(low) < permille(high) <= 1000):
+        raise ValueError(f"tone_map: the trims must satisfy 0 <= low < high <= 1 in permille, got {low!r}, {high!r}")
+    return operator, exposure, key, float(low), float(high), float(speed), white, min_exposure, max_exposure
+
+
+def tone_map_constants(scene):
+    """What ``mr_tone_map_desc`` carries for a frame of *scene* (``tone_map`` set): ``(op, fixed, exposure, key, white, speed,
+    min_exposure, max_exposure, low_pm, high_pm, table)``; a metered description carries exposure 1."""
+    tm = scene.tone_map
+    return (TONE_OPERATORS.index(tm.operator), int(tm.exposure is not None), 1.0 if tm.exposure is None else tm.exposure, tm.key, tm.white,
+            tm.speed, tm.min_exposure, tm.max_exposure, permille(tm.low), permille(tm.high), tone_map_table())
+
+
 def check_motion_blur(shutter):
     """The parameter of a ``MotionBlur``: a Python float that lies in (0, 1] as float32."""
     if isinstance(shutter, (bool, str, bytes)) or not isinstance(shutter, (int, float, np.integer, np.floating)):

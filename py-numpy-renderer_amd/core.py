@@ -236,6 +236,39 @@ class LightShafts:
         return "LightShafts(" + ", ".join(f"{name}={getattr(self, name)!r}" for name in self.__slots__) + ")"
 
 
+class ToneMap:
+    """What ``Scene.tone_map`` holds: the frame's last stage, an exposure and a tone curve applied on the device behind the
+    bloom and in front of the debug frustum (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6p the
+    reasons).  ``operator`` is the curve: ``"linear"`` (x), ``"reinhard"`` (extended, with the ``white`` point that maps to 1)
+    or ``"aces"`` (the fitted filmic curve, the default).  ``exposure`` is a fixed factor (finite and > 0 as float32), or
+    ``None`` (the default): the exposure is metered from a histogram of the frame's log luminance -- 8 bins a stop -- and
+    brings the geometric mean of the samples between the ``low`` and ``high`` fractions (black excluded) to ``key``, clamped
+    to ``min_exposure .. max_exposure``.  ``speed`` in (0, 1] is how far a frame's exposure moves from the previous frame's
+    towards its own meter: 1 (the default) meters every frame on its own and keeps nothing between frames; below 1 the scene
+    adapts over frames, one frame at a time.  ``ValueError`` outside these ranges, ``TypeError`` for the wrong type.  A
+    ``ToneMap`` is never modified: assign a new one to change it."""
+
+    __slots__ = ("operator", "exposure", "key", "low", "high", "speed", "white", "min_exposure", "max_exposure")
+
+    def __init__(self, operator="aces", exposure=None, key=0.18, low=0.0, high=1.0, speed=1.0, white=4.0, min_exposure=2.0 ** -6,
+                 max_exposure=2.0 ** 6):
+        from ._pack import check_tone_map
+        checked = check_tone_map(operator, exposure, key, low, high, speed, white, min_exposure, max_exposure)
+        for name, value in zip(self.__slots__, checked):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a ToneMap is read-only: assign a new one to Scene.tone_map")
+
+    @property
+    def adaptive(self):
+        """Whether the scene carries an exposure from frame to frame: metered with ``speed`` below 1 as float32."""
+        return self.exposure is None and np.float32(self.speed) < 1
+
+    def __repr__(self):
+        return "ToneMap(" + ", ".join(f"{name}={getattr(self, name)!r}" for name in self.__slots__) + ")"
+
+
 class TemporalAA:
     """What ``Scene.temporal_aa`` holds: anti-aliasing spread over consecutive frames.  Every frame is rendered once, with a
     sub-sample offset of its sample grid, and its float colours are blended into the history -- the previous frame as this
@@ -961,6 +994,15 @@ class Scene:
       lies behind the camera, or without sky above the threshold, is ``render()``'s byte for byte.  The pass keeps nothing
       between frames and composes like ``bloom``; the history of ``temporal_aa`` never holds shafts.  Split frames
       (``row_band``, ``multigpu``) refuse it.  With ``None`` a scene enqueues exactly what it did without it.
+    * ``tone_map`` (an addition; ``None`` by default, or a ``ToneMap``): the frame's last stage on the device, behind the
+      bloom and in front of the debug frustum, whose lines keep their colours -- an exposure, fixed or metered from a
+      luminance histogram of the frame, and a tone curve, so that what bloom and light shafts add does not burn out to
+      white.  ``ToneMap("linear", exposure=1.0)`` is ``render()``'s frame byte for byte.  Metered with ``speed=1`` or fixed,
+      the pass keeps nothing between frames and composes like ``bloom`` (sub-frames of ``accumulate()`` are tone-mapped
+      before they are summed).  With ``speed`` below 1 the scene adapts: a frame's exposure becomes the previous one when
+      the frame is complete, one frame is issued at a time (as under ``temporal_aa``), ``accumulate()`` refuses, and the
+      exposure is forgotten by ``reset_motion()`` and whenever ``tone_map`` is assigned.  The history of ``temporal_aa``
+      never holds tone-mapped colours.  Split frames (``row_band``, ``multigpu``) refuse it.
     """
 
     camera = Bound()
@@ -1030,10 +1072,11 @@ class Scene:
         self.reset_motion()
 
     def reset_motion(self):
-        """Forgets the previous frame's camera and poses, and the history of ``temporal_aa``: the next frame has identity
-        motion and no history, its bytes are ``render()``'s."""
+        """Forgets the previous frame's camera and poses, the history of ``temporal_aa`` and the exposure an adaptive
+        ``tone_map`` carried: the next frame has identity motion, no history and no previous exposure."""
         self.__dict__["_motion_prev"] = None
         self.__dict__["_taa_forget"] = True
+        self.__dict__["_tone_forget"] = True
 
     @property
     def temporal_aa(self):
@@ -1068,6 +1111,18 @@ class Scene:
         if value is not None and not isinstance(value, LightShafts):
             raise TypeError(f"light_shafts must be None or a LightShafts, got {type(value).__name__}")
         self.__dict__["_light_shafts"] = value
+
+    @property
+    def tone_map(self):
+        """``None`` (off, the default) or the scene's ``ToneMap`` (see the class docstring)."""
+        return self.__dict__.get("_tone_map")
+
+    @tone_map.setter
+    def tone_map(self, value):
+        if value is not None and not isinstance(value, ToneMap):
+            raise TypeError(f"tone_map must be None or a ToneMap, got {type(value).__name__}")
+        self.__dict__["_tone_map"] = value
+        self.__dict__["_tone_forget"] = True      # (the exposure another description adapted is not this one's)
 
     @property
     def last_stats(self):
@@ -1152,6 +1207,9 @@ class Scene:
         if self.temporal_aa is not None and pending:
             raise ValueError("temporal_aa takes one frame of the scene at a time: another frame is pending, take its "
                              "result() first (every frame reads the history the frame before it left)")
+        if self.tone_map is not None and self.tone_map.adaptive and pending:
+            raise ValueError("an adaptive tone_map (speed < 1) takes one frame of the scene at a time: another frame is pending, "
+                             "take its result() first (every frame reads the exposure the frame before it left)")
         backend = self._backend()
         lane = next((k for k in range(backend.ASYNC_LANES) if k not in pending), None)
         if lane is None:
@@ -1164,9 +1222,10 @@ class Scene:
     def render_frames(self, views, shadows=True, depth=2):
         """Frames of a sequence: for every ``(camera, debug_camera)`` pair of *views* the scene's cameras are set
         and a frame is rendered; yields the uint8 arrays in order, *depth* frames in flight (``render_async``).  Under
-        a ``temporal_aa`` every frame reads the history the frame before it left: one frame is issued at a time, and its
-        verdict is waited for before the next is issued, whatever *depth* says."""
-        if self.temporal_aa is not None:
+        a ``temporal_aa`` every frame reads the history the frame before it left (under an adaptive ``tone_map``, its
+        exposure): one frame is issued at a time, and its verdict is waited for before the next is issued, whatever
+        *depth* says."""
+        if self.temporal_aa is not None or (self.tone_map is not None and self.tone_map.adaptive):
             depth = 1
         queue = []
         try:
@@ -1195,6 +1254,9 @@ class Scene:
         if self.temporal_aa is not None:
             raise ValueError("temporal_aa is not available inside accumulate() / render_mean(): the accumulation is the "
                              "other way to spread samples over frames, and its sub-frames have no history")
+        if self.tone_map is not None and self.tone_map.adaptive:
+            raise ValueError("an adaptive tone_map (speed < 1) is not available inside accumulate() / render_mean(): its "
+                             "sub-frames have no previous frame (speed=1 or a fixed exposure is)")
         acc = self.__dict__["_accumulation"] = Accumulation(self)
         return acc
 

@@ -25,6 +25,8 @@
 //   MR_MBLUR_TILE     32x32     32x32x256 | 16x16: the other workgroup shapes of k_mblur, as for k_dof (same bits; for the A/B)
 //   MR_TAA_TILE       32x8      64x4 | 16x16: the other workgroup shapes of k_taa, 256 threads each (same bits; for the A/B)
 //   MR_BLOOM_TILE     32x8      64x4 | 16x16: the other workgroup shapes of k_bloom_down, 256 threads each (same bits; for the A/B)
+//   MR_TONEMAP_HIST   atomic    ballot: k_lum_hist adds once per distinct bin of a wavefront, not once a sample (same bits; for the A/B)
+//   MR_TONEMAP_GRID   256       1 .. 1024: the cap of k_lum_hist's grid, the rows of a frame slot's slab (same bits; for the A/B)
 //
 // MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
 // rest are read once per process.
@@ -39,6 +41,7 @@ struct Env {
     int pair_log;                                 // 0 .. mr::PAIR_LOG_K
     int ao_shape, dof_shape, mblur_shape, taa_shape;   // 0 .. 2: the `shape` of ao.hip's, dof.hip's, motion.hip's and taa.hip's launch
     int bloom_shape;                              // 0 .. 2: the `shape` of bloom.hip's launch_down
+    int tone_form, tone_grid;                     // the `form` and the grid cap of tonemap.hip's launch_hist
     unsigned split_cost, split_quads;
     const char *cluster_cull;                     // as set, or NULL
 };
@@ -67,6 +70,8 @@ Env read_env()
         e.mblur_shape = shape("MR_MBLUR_TILE", "32x32", "32x32x256", "16x16");
         e.taa_shape = shape("MR_TAA_TILE", "32x8", "64x4", "16x16");
         e.bloom_shape = shape("MR_BLOOM_TILE", "32x8", "64x4", "16x16");
+        e.tone_form = is("MR_TONEMAP_HIST", "ballot") ? 1 : 0;
+        e.tone_grid = std::min(std::max(number("MR_TONEMAP_GRID", (int)mr::TONE_HIST_BLOCKS), 1), (int)mr::TONE_MAX_BLOCKS);
         return e;
     }();
     Env e = once;

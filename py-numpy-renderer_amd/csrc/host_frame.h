@@ -18,6 +18,9 @@ struct FrameSlot {
     DevBuf d_frame_b;                             // the float frame k_taa, k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
     DevBuf d_bloom;                               // the pyramid of a frame with bloom: levels 1 .. L, three floats a sample (host_bloom.h, bloom_pyramid)
     DevBuf d_shafts;                              // S and R of a frame with light shafts, 16 bytes a sample (host_shafts.h, shafts_level)
+    DevBuf d_tone;                                // the words of a frame with tone mapping: histogram, exposure cell, slab (host_tonemap.h, tone_slot_bytes)
+    int last_tone = 0;                            // the last frame ran the tone mapping: 1 metered, 2 with a fixed exposure ...
+    float last_tone_exposure = 0.f;               // ... which was this
     MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur or temporal anti-aliasing (host_motion.h)
     MotionFacesSlot motion_faces;                 // the face records and the tables of its per-face pass (host_motion_faces.h)
     bool last_motion = false;                     // the last frame ran k_velocity: mr_read_velocity has something to read
@@ -52,7 +55,7 @@ struct FrameSlot {
     void release()
     {
         for (DevBuf *b : { &d_vout, &d_vclip, &d_count_list, &d_tris, &d_clips, &d_status, &d_quads, &d_sil, &d_counters,
-                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_bloom, &d_shafts, &d_out })
+                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_bloom, &d_shafts, &d_tone, &d_out })
             b->release();
         for (DevBuf &b : d_items) b.release();
         for (DevBuf &b : d_stencil_x) b.release();
@@ -165,13 +168,15 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
     const struct { bool on; const char *name; } passes[] = { { sc->ao.on, "ambient occlusion" }, { sc->dof.on, "depth of field" }, { sc->motion.on, "motion blur" },
-                                                         { sc->taa.on, "temporal anti-aliasing" }, { sc->bloom.on, "bloom" }, { sc->shafts.on, "light shafts" } };
+                                                         { sc->taa.on, "temporal anti-aliasing" }, { sc->bloom.on, "bloom" }, { sc->shafts.on, "light shafts" }, { sc->tone.on, "tone mapping" } };
     for (const auto &pass : passes)
         if (pass.on && is_partial(fr))
             return fail(MR_E_INVALID, std::string(pass.name) + " takes whole frames (no row band, no stripes): its taps cross the bands");
     // (host order is the only ordering between the frames that write the history and those that read it)
     if (sc->taa.on && sc->taa.pending)
         return fail(MR_E_INVALID, "temporal anti-aliasing: an earlier frame of the scene has not been waited for (mr_render_wait): its history is not there yet");
+    if (sc->tone.on && sc->tone.params.adaptive() && sc->tone.pending)
+        return fail(MR_E_INVALID, "tone mapping: an earlier frame of the adaptive scene has not been waited for (mr_render_wait): its exposure is not there yet");
     if (sc->n_extra_lights > 0) {
         if (fr->flags & MR_FRAME_FACE_STATUS)
             return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available with extra lights: the per-face status reads the one stencil buffer");
@@ -344,17 +349,19 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //                taa_vel (the velocity's scalars), likewise
 //   bloom        the scene has bloom on: its 2 L launches behind k_mblur, in front of the overlay, with bloom_params, likewise
 //   shafts       the scene has light shafts on: their three launches behind k_mblur, in front of the bloom, with shafts_params, likewise
+//   tone         the scene has tone mapping on: its launches behind the bloom, in front of the overlay, with tone_params, likewise
 //   post()       a pass rewrites the float frame behind the tile kernel: the bytes are the full resolve of the result
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa, bloom, shafts;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa, bloom, shafts, tone;
     mr::AoParams ao_params;
     mr::DofParams dof_params;
     mr::MotionParams motion_params, taa_vel;
     mr::TaaParams taa_params;
     mr::BloomParams bloom_params;
     mr::ShaftsParams shafts_params;
-    bool post() const { return ao || dof || motion || taa || bloom || shafts; }
+    mr::ToneParams tone_params;
+    bool post() const { return ao || dof || motion || taa || bloom || shafts || tone; }
     int n_lights, n_tiles;
     uint64_t serial;
     unsigned split_cost, split_quads, split_max, edge_spread, face_blocks, count_blocks;
@@ -393,7 +400,7 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     if (fc.ss_mode & SS_SEPARATE) fc.flags |= MR_FRAME_KEEP_FLOAT;
     // (a post pass reads the whole z-buffer -- the motion blur the winner map as well -- and rewrites the whole float frame,
     // in place or into the second one: every tile writes its taps, as for a caller who asked for them)
-    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on; p.taa = sc->taa.on; p.bloom = sc->bloom.on; p.shafts = sc->shafts.on;
+    p.ao = sc->ao.on; p.dof = sc->dof.on; p.motion = sc->motion.on; p.taa = sc->taa.on; p.bloom = sc->bloom.on; p.shafts = sc->shafts.on; p.tone = sc->tone.on;
     if (p.motion && sc->motion.params.n_models != (int32_t)sc->model_face_off.size())
         return fail(MR_E_INVALID, "motion blur: the scene's models changed since mr_scene_set_motion_blur: hand the classes over again");
     if (p.motion && sc->mfaces.on && sc->mfaces.deforming.size() != sc->model_face_off.size())
@@ -406,6 +413,7 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     p.taa_params = sc->taa.params; p.taa_vel = sc->taa.vel;
     p.bloom_params = sc->bloom.params;
     p.shafts_params = sc->shafts.params;
+    p.tone_params = sc->tone.params;
     if (p.post()) fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
@@ -482,7 +490,9 @@ int grow_slot(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Frame
         // (one pyramid per slot: frames in flight keep their own)
         { fs->d_bloom, p.bloom ? bloom_pyramid(fc.width, fc.height, p.bloom_params.levels).floats * sizeof(float) : 0 },
         // (S and R per slot: two frames in flight under two cameras keep their own light position)
-        { fs->d_shafts, p.shafts ? 2 * shafts_level(fc.width, fc.height, p.shafts_params.levels).device_floats() * sizeof(float) : 0 } };
+        { fs->d_shafts, p.shafts ? 2 * shafts_level(fc.width, fc.height, p.shafts_params.levels).device_floats() * sizeof(float) : 0 },
+        // (likewise: every slot its histogram, its exposure cell and its slab)
+        { fs->d_tone, p.tone ? tone_slot_bytes(tone_grid(fc.width, fc.height, p.env)) : 0 } };
     for (const auto &b : sized) HIP_TRY(b.buf.ensure(b.bytes));
     if (p.taa)
         if (int rc = grow_history(sc, fc.width, fc.height)) return rc;
@@ -645,7 +655,7 @@ void launch_post_resolve(mr_scene *sc, FrameSlot *fs, const mr_frame_desc &fr, i
 // given; the two ping-pong when several of k_taa, k_dof and k_mblur run.
 inline void swap_float_frames(FrameSlot *fs) { std::swap(fs->d_frame, fs->d_frame_b); }
 
-// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the temporal anti-aliasing, the depth of field, the motion blur, the light shafts, the bloom, the overlay (exported
+// ---- 4. behind the tile kernel: the per-face verdicts, the ambient obscurance, the temporal anti-aliasing, the depth of field, the motion blur, the light shafts, the bloom, the tone mapping, the overlay (exported
 // by a device that owns part of the frame, else drawn: after the lit pass' per-face verdicts, as in obj/core.py:624-638)
 // and the resolve of a supersampled, darkened or blurred frame
 int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr::FrameConst &fc, const FramePlan &p, uint8_t *d_out)
@@ -686,6 +696,10 @@ int launch_after_tile(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, cons
     if (p.bloom && p.n_tiles > 0)
         if (int rc = launch_bloom(sc, stream, fs->d_frame.as<float>(), fs->d_bloom.as<float>(), fc.width, fc.height, p.bloom_params, p.env.bloom_shape))
             return rc;
+    // (the exposure is metered from everything that adds light, the glow and the rays included; the overlay's lines are
+    // drawn over the result and keep their colours)
+    if (p.tone && p.n_tiles > 0)
+        if (int rc = launch_tone_map(sc, stream, fs->d_frame.as<float>(), fs->d_tone.as<uint32_t>(), fc.width, fc.height, p.tone_params, p.env)) return rc;
     if (p.overlay && p.partial) {
         const int world = fr->stripe_count > 1 ? fr->stripe_count : fr->height / (fr->row_end - fr->row_begin);
         const int rank = fr->stripe_count > 1 ? fr->stripe_index : fr->row_begin / (fr->row_end - fr->row_begin);
@@ -713,6 +727,9 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
     fs->last_post = p.post();
     fs->last_motion = (p.motion || p.taa) && p.n_tiles > 0;
     if (p.taa && p.n_tiles > 0) taa_enqueued(sc, fs, fc.width, fc.height);
+    fs->last_tone = p.tone && p.n_tiles > 0 ? (p.tone_params.fixed ? 2 : 1) : 0;
+    fs->last_tone_exposure = p.tone_params.exposure;
+    if (fs->last_tone && p.tone_params.adaptive()) tone_enqueued(sc, fs);
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = p.n_tiles;
     fs->last_n_lights = p.n_lights;

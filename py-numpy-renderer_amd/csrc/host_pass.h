@@ -7,7 +7,7 @@
 // It stands in front of host_scene.h, because mr_scene holds the records by value.
 #pragma once
 
-// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip, bloom.hip and shafts.hip, the library's other translation units,
+// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip, bloom.hip, shafts.hip and tonemap.hip, the library's other translation units,
 // each declared here and nowhere else; weak, so that a library linked without one of them (the tools' ablation builds)
 // still loads: it refuses that pass instead (linked)
 namespace mr_accum {
@@ -50,6 +50,13 @@ __attribute__((weak)) void launch_source(hipStream_t stream, const float *frame,
 __attribute__((weak)) void launch_march(hipStream_t stream, const float *src, float *dst, int w, int h, const mr::ShaftsParams &p);
 __attribute__((weak)) void launch_composite(hipStream_t stream, float *frame, const float *coarse, int w, int h, int cw, int ch, int levels, float gain);
 }  // namespace mr_shafts
+namespace mr_tonemap {
+__attribute__((weak)) unsigned hist_grid(size_t n_samples, unsigned cap);
+__attribute__((weak)) void launch_hist(hipStream_t stream, const float *frame, size_t n_samples, uint32_t *slab, unsigned grid, int form);
+__attribute__((weak)) void launch_exposure(hipStream_t stream, const uint32_t *slab, unsigned rows, const mr::ToneMeter &meter, const float *e_prev,
+                                           uint32_t *hist, float *e_cell, float *e_next);
+__attribute__((weak)) void launch_apply(hipStream_t stream, float *frame, size_t n_floats, int op, const float *e_cell, float e_fixed, float white2);
+}  // namespace mr_tonemap
 
 namespace {
 
@@ -83,6 +90,14 @@ inline int shafts_linked()
 {
     return linked("this library was linked without shafts.hip or accum.hip: no light shafts (build it with __graft_entry__.build())",
                   &mr_shafts::launch_source, &mr_shafts::launch_march, &mr_shafts::launch_composite, &mr_accum::launch_resolve);
+}
+
+// the tone mapping's three kernels are tonemap.hip's; the bytes of such a frame are the accumulation's resolve of its float
+// frame (accum.hip)
+inline int tonemap_linked()
+{
+    return linked("this library was linked without tonemap.hip or accum.hip: no tone mapping (build it with __graft_entry__.build())",
+                  &mr_tonemap::hist_grid, &mr_tonemap::launch_hist, &mr_tonemap::launch_exposure, &mr_tonemap::launch_apply, &mr_accum::launch_resolve);
 }
 
 // ---- timing marks: N events round a pass's kernels, created by the first frame that records them and kept for the

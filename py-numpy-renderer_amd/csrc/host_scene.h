@@ -199,6 +199,21 @@ struct mr_scene {
     // ... light shafts (host_shafts.h), marked in front of the source, behind it, behind the march and behind the composite
     struct Shafts : PassRecord<4> { mr::ShaftsParams params = {}; int32_t last_levels = 0; } shafts;   // (likewise)
 
+    // ... tone mapping (host_tonemap.h), marked in front of k_lum_hist, behind it, behind k_exposure and behind k_tone_apply.
+    // The previous exposure is the scene's, not a slot's, and only an adaptive scene has one: two cells, `cur` the one the
+    // last frame whose mr_render or mr_render_wait returned MR_OK left (valid), the other the one a frame in flight is
+    // writing (pending, on pending_slot) -- the hand-over rule of the temporal anti-aliasing's history
+    struct Tone : PassRecord<4> {
+        mr::ToneParams params = {};
+        DevBuf d_state;
+        int cur = 0;
+        bool valid = false;
+        bool pending = false;
+        const FrameSlot *pending_slot = nullptr;
+        uint64_t epoch = 0, pending_epoch = 0;    // + 1 whenever the exposure is forgotten: a frame issued before that hands nothing over
+        int32_t adopted = 0, last_grid = 0;       // exposures handed over; the workgroups of the last k_lum_hist (mr_debug_tone_map)
+    } tone;
+
     // ... and motion blur (host_motion.h), marked in front of k_velocity, behind it, behind k_velocity_faces in a frame that
     // ran the per-face pass, and behind k_mblur; the tables are the class matrices, the background's, the models' first
     // faces and their classes as one block (motion_params)

@@ -2,8 +2,8 @@
 // accum.hip, which holds the accumulation's two kernels in a code object of their own (kernels_accum.h says why), from
 // ao.hip, which holds the ambient obscurance's kernel in another, from dof.hip, which holds the depth of field's, and from
 // motion.hip, which holds the motion blur's two, from motion_faces.hip, which holds the per-face velocity's two, from
-// taa.hip, which holds the temporal anti-aliasing's, from bloom.hip, which holds the bloom's three, and from shafts.hip,
-// which holds the light shafts' three;
+// taa.hip, which holds the temporal anti-aliasing's, from bloom.hip, which holds the bloom's three, from shafts.hip,
+// which holds the light shafts' three, and from tonemap.hip, which holds the tone mapping's three;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -22,6 +22,7 @@
 //   host_taa.h          temporal anti-aliasing: the description, the scene's history, the launch, the host mirror, mr_debug_taa_post
 //   host_bloom.h        bloom from a resolution pyramid: the description, the pyramid's layout, the launches, the host mirror, mr_debug_bloom_post
 //   host_shafts.h       light shafts marched towards a light: the description, S and R, the launches, the host mirror, mr_debug_light_shafts_post
+//   host_tonemap.h      tone mapping from a luminance histogram: the description, the slot's words, the scene's exposure, the launches, the host mirror, mr_debug_tone_map_post
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
@@ -46,7 +47,8 @@
 //                   mr_scene_set_motion_blur, k_velocity and k_taa between k_ao and k_dof in one with
 //                   mr_scene_set_temporal_aa, k_bloom_down, k_bloom_up and k_bloom_composite behind k_mblur in one with
 //                   mr_scene_set_bloom, k_shaft_source, k_shaft_march and k_shaft_composite in front of those in one with
-//                   mr_scene_set_light_shafts, k_accum_resolve for the bytes of any)
+//                   mr_scene_set_light_shafts, k_lum_hist, k_exposure and k_tone_apply behind the bloom in one with
+//                   mr_scene_set_tone_map, k_accum_resolve for the bytes of any)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -81,6 +83,7 @@
 #include "taa_def.h"
 #include "bloom_def.h"
 #include "shafts_def.h"
+#include "tonemap_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -98,6 +101,7 @@
 #include "host_taa.h"
 #include "host_bloom.h"
 #include "host_shafts.h"
+#include "host_tonemap.h"
 #include "host_frame.h"
 #include "host_accum.h"
 #include "host_post.h"
@@ -247,6 +251,7 @@ void mr_scene_destroy(mr_scene *sc)
     release_pass(sc->ao); release_pass(sc->dof); release_pass(sc->motion); release_pass(sc->bloom); release_pass(sc->shafts);
     motion_faces_release(sc);
     taa_release(sc);
+    tone_release(sc);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
@@ -528,12 +533,12 @@ int mr_render(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, mr_stats 
     if (stats) counted.flags |= MR_FRAME_COUNTERS;         // whoever asks for the counters gets them
     fr = &counted;
     for (int attempt = 0; attempt < 6; ++attempt) {
-        if ((rc = render_and_copy(sc, fs, fr, out_rgb, stats != nullptr))) { taa_settle(sc, fs, false); return rc; }
+        if ((rc = render_and_copy(sc, fs, fr, out_rgb, stats != nullptr))) { frame_settled(sc, fs, false); return rc; }
         const hipError_t drained = hipStreamSynchronize(g_stream);
-        if (drained != hipSuccess) taa_settle(sc, fs, false);
+        if (drained != hipSuccess) frame_settled(sc, fs, false);
         HIP_TRY(drained);
         rc = collect(sc, fs, true);
-        taa_settle(sc, fs, rc == MR_OK);          // (a frame that overflowed adopts nothing: the next attempt reads the same history)
+        frame_settled(sc, fs, rc == MR_OK);          // (a frame that overflowed adopts nothing: the next attempt reads the same history)
         if (rc == MR_OK) {
             if (stats) *stats = sc->stats;
             return MR_OK;
@@ -557,7 +562,7 @@ int mr_render_async(mr_scene *sc, const mr_frame_desc *fr, uint8_t *out_rgb, int
     if (!ln.stream) HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
     FrameSlot *fs = slot_for(sc, ln.stream);
     if (!fs) return fail(MR_E_DEVICE, "out of frame slots");
-    if ((rc = render_and_copy(sc, fs, fr, out_rgb, (fr->flags & MR_FRAME_COUNTERS) != 0))) { taa_settle(sc, fs, false); return rc; }
+    if ((rc = render_and_copy(sc, fs, fr, out_rgb, (fr->flags & MR_FRAME_COUNTERS) != 0))) { frame_settled(sc, fs, false); return rc; }
     ln.busy = true;
     return MR_OK;
 }
@@ -570,12 +575,12 @@ int mr_render_wait(mr_scene *sc, int32_t lane, mr_stats *stats)
     if (!ln.busy) return fail(MR_E_INVALID, "no frame in flight on this lane");
     FrameSlot *fs = slot_for(sc, ln.stream);
     const hipError_t drained = hipStreamSynchronize(ln.stream);
-    if (drained != hipSuccess && fs) taa_settle(sc, fs, false);
+    if (drained != hipSuccess && fs) frame_settled(sc, fs, false);
     HIP_TRY(drained);
     ln.busy = false;
     if (!fs) return fail(MR_E_DEVICE, "lane without a frame slot");
     const int rc = collect(sc, fs, true);
-    taa_settle(sc, fs, rc == MR_OK);
+    frame_settled(sc, fs, rc == MR_OK);
     if (stats) *stats = sc->stats;
     if (rc == MR_E_OVERFLOW) return fail(MR_E_OVERFLOW, "the frame overflowed a work list (now grown): render it again");
     return rc;
@@ -852,6 +857,68 @@ int mr_debug_light_shafts_post(mr_scene *sc, const float *frame, const double *z
                                float *out_frame, float *out_source, float *out_march)
 {
     return debug_light_shafts_post(sc, frame, zbuf, height, width, shafts, out_frame, out_source, out_march);
+}
+
+int mr_scene_set_tone_map(mr_scene *sc, const mr_tone_map_desc *tone_map)
+{
+    const int rc = set_pass(sc, &mr_scene::tone, tone_map, tone_params, tonemap_linked);
+    if (rc == MR_OK) tone_forget(sc);                          // (off, or another description: the exposure it adapted is not this one's)
+    return rc;
+}
+
+int mr_scene_reset_exposure(mr_scene *sc)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    tone_forget(sc);
+    return MR_OK;
+}
+
+int mr_host_tone_map(const float *frame, int32_t height, int32_t width, const mr_tone_map_desc *tone_map, int32_t has_prev, float e_prev,
+                     float *out_frame, uint32_t *out_hist, float *out_exposure)
+{
+    return host_tone_map(frame, height, width, tone_map, has_prev, e_prev, out_frame, out_hist, out_exposure);
+}
+
+// the words of the last frame's slot where that frame ran the pass, from word `first`
+static int read_tone_words(mr_scene *sc, size_t first, size_t count, void *out, bool metered_only)
+{
+    if (!out) return fail(MR_E_INVALID, "NULL argument");
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (!fs->last_tone) return fail(MR_E_INVALID, "the last frame was rendered without tone mapping");
+    if (fs->last_tone == 2 && metered_only) return fail(MR_E_INVALID, "the last frame's exposure was fixed: nothing was metered");
+    if (fs->last_tone == 2) { std::memcpy(out, &fs->last_tone_exposure, sizeof(float)); return MR_OK; }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, fs->d_tone.as<uint32_t>() + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MR_OK;
+}
+
+int mr_read_exposure(mr_scene *sc, float *out)
+{
+    return read_tone_words(sc, TONE_SLOT_CELL, 1, out, false);
+}
+
+int mr_read_luminance_histogram(mr_scene *sc, uint32_t *out)
+{
+    return read_tone_words(sc, TONE_SLOT_HIST, mr::TONE_BINS, out, true);
+}
+
+int mr_debug_tone_map(mr_scene *sc, int32_t *out)
+{
+    if (int rc = pass_counts(sc, &mr_scene::tone, out)) return rc;
+    out[3] = sc->tone.last_grid; out[4] = sc->tone.adopted; out[5] = sc->tone.valid ? 1 : 0;
+    return MR_OK;
+}
+
+int mr_debug_tone_map_times(mr_scene *sc, float *out_ms)
+{
+    return pass_times(sc, &mr_scene::tone, "no frame with tone mapping yet", out_ms, { { 0, 1 }, { 1, 2 }, { 2, 3 } });
+}
+
+int mr_debug_tone_map_post(mr_scene *sc, const float *frame, int32_t height, int32_t width, const mr_tone_map_desc *tone_map, int32_t has_prev,
+                           float e_prev, int32_t grid_cap, int32_t form, float *out_frame, uint32_t *out_hist, float *out_exposure, float *out_ms)
+{
+    return debug_tone_map_post(sc, frame, height, width, tone_map, has_prev, e_prev, grid_cap, form, out_frame, out_hist, out_exposure, out_ms);
 }
 
 int mr_scene_set_motion_faces(mr_scene *sc, const mr_motion_faces_desc *d)
@@ -1144,6 +1211,8 @@ int mr_render_device(mr_scene *sc, const mr_frame_desc *fr, void *d_out_rgb, voi
     if (!fs) return fail(MR_E_INVALID, "a scene can be rendered from at most 32 different streams");
     if (sc->taa.on)
         return fail(MR_E_INVALID, "temporal anti-aliasing: its frames are rendered by mr_render or mr_render_async, whose return hands the history over");
+    if (sc->tone.on && sc->tone.params.adaptive())
+        return fail(MR_E_INVALID, "adaptive tone mapping: its frames are rendered by mr_render or mr_render_async, whose return hands the exposure over");
     return enqueue_frame(sc, fs, fr, static_cast<uint8_t *>(d_out_rgb));
 }
 
@@ -1159,7 +1228,7 @@ int mr_get_stats(mr_scene *sc, mr_stats *stats)
         if (!s->have_frame) continue;
         if (int rc = fetch_counters(s.get(), true)) return rc;
         HIP_TRY(hipStreamSynchronize(s->stream));
-        if (collect(sc, s.get(), s->last_copied) == MR_E_OVERFLOW) { overflowed = true; taa_settle(sc, s.get(), false); }
+        if (collect(sc, s.get(), s->last_copied) == MR_E_OVERFLOW) { overflowed = true; frame_settled(sc, s.get(), false); }
     }
     (void)collect(sc, fs, fs->last_copied);     // report the most recent frame
     *stats = sc->stats;
