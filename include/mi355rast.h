@@ -392,6 +392,13 @@ int mr_debug_quad_walks(mr_scene *scene, uint32_t *out);
  * sample is then walked again; the frames do not depend on it. */
 int mr_debug_pair_log(mr_scene *scene, uint32_t *out);
 
+/* Diagnostic: how many (large triangle, tile) pairs the last frame's k_bin_work left out of the tile lists because the
+ * triangle can cover no sample of the tile (frames with MR_FRAME_COUNTERS; 0 otherwise).  Such a pair added nothing but
+ * work: the frame, z, winner, stencil and every statistic but tri_bin_entries, which is smaller by this number, do not
+ * depend on it.  MR_BIG_TRI_REJECT=0 in the environment (looked up for every frame) lists every tile of a large
+ * triangle's box as before. */
+int mr_debug_big_tri_rejects(mr_scene *scene);
+
 /* The set-up and tile kernels exist in two variants of one source: the frame-only ones, which count nothing, and the
  * general ones.  A frame takes the general kernels when it carries MR_FRAME_COUNTERS or MR_FRAME_FACE_STATUS or the
  * scene has a model with depth_test == 0; every other frame the frame-only ones.  The frame, z, winner and stencil do

@@ -283,6 +283,7 @@ _PROTOTYPES = {
     "mr_debug_clusters_culled": (C.c_int, [C.c_void_p]),
     "mr_debug_quad_walks": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mr_debug_pair_log": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_big_tri_rejects": (C.c_int, [C.c_void_p]),
     "mr_host_camera_constants": (None, [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 3),
     "mr_debug_read_tile_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "mr_debug_sil_cache": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1886,6 +1887,11 @@ class DeviceRenderer:
         out = (C.c_uint32 * 2)()
         _check(self.lib.mr_debug_pair_log(self.handle, out), "mr_debug_pair_log")
         return tuple(int(x) for x in out)
+
+    def big_tri_rejects(self):
+        """``mr_debug_big_tri_rejects`` of the last (counted) frame: (large triangle, tile) pairs ``k_bin_work`` left out of
+        the tile lists because the triangle can cover no sample of the tile (``MR_BIG_TRI_REJECT=0``: none)."""
+        return int(_check(self.lib.mr_debug_big_tri_rejects(self.handle), "mr_debug_big_tri_rejects"))
 
     def sil_cache(self):
         """Silhouette cache: (path of the last frame with shadows: 0 fused / 1 captured / 2 cached / -1 none, entries it

@@ -19,6 +19,8 @@
 //   MR_CLUSTER_CULL   (auto)    0 | 1 | box | count: cluster culling off / on / boxes only / on and counted (auto: see
 //                               cluster_cull_mode)
 //   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
+//   MR_BIG_TRI_REJECT 1         0: k_bin_work lists a large triangle in every tile of its box again, not only in those it can
+//                               cover (tri_touches_tile; same frames, for the A/B and the tests)
 //   MR_AO_TILE        64x64     32x32 | 64x16: the other workgroup shapes of k_ao (same bits; for the A/B)
 //   MR_DOF_TILE       32x32     32x32x256 | 16x16: the other workgroup shapes of k_dof -- 32 x 32 samples with 256 threads, not
 //                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B)
@@ -28,14 +30,14 @@
 //   MR_TONEMAP_HIST   atomic    ballot: k_lum_hist adds once per distinct bin of a wavefront, not once a sample (same bits; for the A/B)
 //   MR_TONEMAP_GRID   256       1 .. 1024: the cap of k_lum_hist's grid, the rows of a frame slot's slab (same bits; for the A/B)
 //
-// MR_CLUSTER_CULL and MR_SIL_CACHE are looked up for every frame, because the tests switch them inside one process; the
-// rest are read once per process.
+// MR_CLUSTER_CULL, MR_SIL_CACHE and MR_BIG_TRI_REJECT are looked up for every frame, because the tests switch them inside
+// one process; the rest are read once per process.
 #pragma once
 
 namespace {
 
 struct Env {
-    bool vertex_mfma, resolve_separate, sil_cache;
+    bool vertex_mfma, resolve_separate, sil_cache, big_tri_reject;
     int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
     int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
     int pair_log;                                 // 0 .. mr::PAIR_LOG_K
@@ -78,6 +80,8 @@ Env read_env()
     e.cluster_cull = getenv("MR_CLUSTER_CULL");
     const char *sil = getenv("MR_SIL_CACHE");
     e.sil_cache = !(sil && !strcmp(sil, "0"));
+    const char *rej = getenv("MR_BIG_TRI_REJECT");
+    e.big_tri_reject = !(rej && !strcmp(rej, "0"));
     return e;
 }
 

@@ -589,7 +589,8 @@ void launch_bin_work(FrameSlot *fs, const mr::FrameConst &fc, const FramePlan &p
 {
     using namespace mr;
     hipLaunchKernelGGL(k_bin_work, dim3(p.count_blocks + WORK_BLOCKS), dim3(256), 0, fs->stream, fc, bin_args(fs), fs->d_count_list.as<uint32_t>(),
-                       fs->d_tris.as<TriRec>(), fs->d_clips.as<TriClip>(), fs->d_status.as<uint8_t>(), fs->ctr(fs->frames_enqueued), p.count_blocks);
+                       fs->d_tris.as<TriRec>(), fs->d_clips.as<TriClip>(), fs->d_status.as<uint8_t>(), fs->ctr(fs->frames_enqueued), p.count_blocks,
+                       p.env.big_tri_reject ? 1u : 0u);
 }
 
 // ---- 3. tiles: coverage, z, stencil, shading, finalise

@@ -13,6 +13,7 @@
 #pragma once
 
 #include "rast_math.h"
+#include "tri_reject.h"       // tri_touches_tile, quad_touches_tile's counterpart for a large triangle (plain C++: the CPU check compiles it too)
 
 namespace mr {
 
@@ -241,8 +242,13 @@ __device__ __forceinline__ uint32_t quad_chunks(const FrameConst &fc, int x0, in
     return (uint32_t)((sp.tx1 - sp.tx0) * (sp.ty1 - sp.ty0) + WAVE - 1) / WAVE;
 }
 
-// The work items: one wavefront per item, one tile per lane.
-__device__ __forceinline__ void bin_work_body(const FrameConst &fc, const BinArgs &a, uint32_t block, uint32_t n_blocks)
+// The work items: one wavefront per item, one tile per lane.  A shadow quad is listed only in the tiles it can
+// touch (quad_touches_tile, exact) and, with big_tri_reject (MR_BIG_TRI_REJECT, default on), so is a triangle
+// (tri_touches_tile, conservative): c4's two floor triangles are otherwise listed in every tile of their boxes, the
+// wrong side of their shared diagonal included, and a tile that lists something runs the whole listed-tile chain of
+// k_tile to write background.  A rejected pair held no covered sample, so nothing but the lists' lengths depends on it.
+__device__ __forceinline__ void bin_work_body(const FrameConst &fc, const BinArgs &a, uint32_t block, uint32_t n_blocks,
+                                              uint32_t big_tri_reject)
 {
     const int lane = threadIdx.x & (WAVE - 1);
     // the list is WORK_SHARDS stretches (reserve_work_items): lane s knows how many items stretch s holds and where
@@ -280,8 +286,18 @@ __device__ __forceinline__ void bin_work_body(const FrameConst &fc, const BinArg
         const int j = (int)item.y * WAVE + lane;
         if (j >= total) continue;
         const int tx = sp.tx0 + j % bw, ty = sp.ty0 + j / bw;
-        if (!is_quad || quad_touches_tile(a.quads[id], tx, tile_row_frame(fc, ty)))
-            bin_emit(fc, a, pair_class(fc, is_quad, clip, pb, tx, ty), id, tx, ty);
+        bool touches;
+        if (is_quad) {
+            touches = quad_touches_tile(a.quads[id], tx, tile_row_frame(fc, ty));
+        } else {
+            // tile origin as pair_class computes it: device-local, the same for bands, stripes and the supersampled grid
+            touches = !big_tri_reject || tri_touches_tile(a.tris[id], tx * TILE_W, tile_row_frame(fc, ty) * TILE_H);
+            if (fc.flags & MR_FRAME_COUNTERS) {                 // mr_debug_big_tri_rejects: one add per wavefront, not one per
+                const unsigned long long out = __ballot(!touches);     // lane (4 000 adds to one address were 8 % of a counted c4 frame)
+                if (out && lane == __ffsll((long long)out) - 1) atomicAdd(&a.ctr->pad0[7], (unsigned int)__popcll(out));
+            }
+        }
+        if (touches) bin_emit(fc, a, pair_class(fc, is_quad, clip, pb, tx, ty), id, tx, ty);
     }
 }
 

@@ -1122,12 +1122,12 @@ k_setup_full(const SetupKernArgs)
 __global__ void __launch_bounds__(256)
 k_bin_work(const FrameConst fc, const BinArgs bins, const uint32_t *__restrict__ count_list,
            TriRec *__restrict__ tris, const TriClip *__restrict__ clips,
-           uint8_t *__restrict__ status, Counters *__restrict__ ctr, uint32_t count_blocks)
+           uint8_t *__restrict__ status, Counters *__restrict__ ctr, uint32_t count_blocks, uint32_t big_tri_reject)
 {
     if (blockIdx.x < count_blocks)
         tri_count_body(fc, count_list, tris, clips, status, ctr, blockIdx.x, count_blocks);
     else
-        bin_work_body(fc, bins, blockIdx.x - count_blocks, gridDim.x - count_blocks);
+        bin_work_body(fc, bins, blockIdx.x - count_blocks, gridDim.x - count_blocks, big_tri_reject);
 }
 
 }  // namespace mr

@@ -1384,6 +1384,16 @@ int mr_debug_pair_log(mr_scene *sc, uint32_t *out)
     return MR_OK;
 }
 
+int mr_debug_big_tri_rejects(mr_scene *sc)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = fetch_counters(fs, false)) return rc;
+    HIP_TRY(hipStreamSynchronize(fs->stream));
+    return (int)fs->h_counters->pad0[7];
+}
+
 int mr_debug_force_full(mr_scene *sc, int32_t on)
 {
     if (!sc) return fail(MR_E_INVALID, "NULL argument");

@@ -227,7 +227,7 @@ struct alignas(128) Counters {
     unsigned int n_valid_tris, tri_bin_total, bin_total;
     unsigned int overflow;       // bit0-2: a tile's small / big / quad list, bit3: work list, bit4: quad list
     unsigned int max_list[BIN_CLASSES];       // longest list seen by an overflowing tile, per class
-    unsigned int pad0[15];       // diagnostics: [0] clusters culled (MR_CLUSTER_CULL=count), [1..4] mr_debug_quad_walks, [5..6] mr_debug_pair_log
+    unsigned int pad0[15];       // diagnostics: [0] clusters culled (MR_CLUSTER_CULL=count), [1..4] mr_debug_quad_walks, [5..6] mr_debug_pair_log, [7] mr_debug_big_tri_rejects
     unsigned int n_quads;        unsigned int pad1[31];     // silhouette edges
     unsigned int n_quads_drawn;  unsigned int pad2[31];     // quads that got a record
     unsigned int n_count;        unsigned int pad3[31];     // faces whose survivor count is left to k_bin_work
