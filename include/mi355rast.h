@@ -1247,6 +1247,81 @@ int mr_debug_tone_map_post(mr_scene *scene, const float *frame, int32_t height, 
                            int32_t has_prev, float e_prev, int32_t grid_cap, int32_t form, float *out_frame, uint32_t *out_hist,
                            float *out_exposure, float *out_ms);
 
+/* Data layers: per-sample ids, barycentrics, depth, position, normals and texture coordinates of what a frame shows, on the
+ * device, for callers who render frames as data (ground truth for depth, normals, segmentation, correspondence).  One
+ * kernel, k_layers, right behind k_tile and in front of every post pass, from the winner map and the scene's static face
+ * records alone: it reads no z-buffer and never touches the float frame, so the frame's bytes are what they are without
+ * it.  csrc/layers_def.h states the definition; on the sample grid, rows bottom-up, for winner face w of sample (x, y):
+ *
+ *   bit  layer        type         w >= 0                                                          w < 0
+ *   0    model        int32        the model that owns w (the last m with face_off[m] <= w)          -1
+ *   1    face         int32        w - face_off[model]                                               -1
+ *   2    material     int32        the face record's global material index                           -1
+ *   3    barycentric  float32 x3   perspective-correct barycentrics lambda on the face's plane         0
+ *   4    depth        float32      eye depth sum lambda_k E_k, > 0 in front of the camera            +inf
+ *   5    position     float32 x3   world position sum lambda_k V_k                                     0
+ *   6    face_normal  float32 x3   unit normal (V_1 - V_0) x (V_2 - V_0) of the world-space triangle   0
+ *   7    normal       float32 x3   the vertex normals blended with lambda, normalised; the face        0
+ *                                  normal where the face has none or the blend has no length
+ *   8    uv           float32 x2   sum lambda_k uv_k; 0 where the face has no texture coordinates      0
+ *
+ * lambda comes from the adjugate of the corners' (x, y, w) under `s`, the 4 x 4 matrix of the description (row vectors,
+ * row-major): columns 0, 1, 2 are x, y, w of view . projection . viewport on the sample grid as the frame is rendered (a
+ * sub-sample offset included), column 3 maps a world point to its eye depth.  A sample whose lambda is not finite is
+ * degenerate: it keeps its ids and takes the w < 0 column elsewhere.
+ *
+ * mr_scene_set_layers copies the description during the call (NULL: off, the default); every frame enqueued afterwards
+ * computes the layers of `mask` into buffers its frame slot owns -- frames in flight keep their own -- and keeps its winner
+ * map (MR_FRAME_KEEP_BUFFERS is implied).  A scene without it enqueues what it always did.  MR_E_INVALID for a mask that
+ * is 0 or has a bit above 8, an entry of s that is not finite, an n_models that is not the number of the scene's models;
+ * and, from the rendering entry points, for a partial frame (row band, stripes), for mr_render_device and for the
+ * sub-frames of an accumulation, before any device work.  MR_E_UNSUPPORTED from a library linked without layers.hip. */
+#define MR_N_LAYERS 9
+typedef struct mr_layers_desc {
+    double s[16];
+    int32_t mask;                  /* bit i: layer i */
+    int32_t n_models;              /* the scene's models (mr_scene_set_layers), or the entries of face_off (the host mirror) */
+} mr_layers_desc;
+int mr_scene_set_layers(mr_scene *scene, const mr_layers_desc *layers);
+
+/* Layer `layer` (0 .. 8) of the last frame enqueued, which computed it: height x width samples of 1, 2 or 3 32-bit words as
+ * in the table.  Waits for the device.  MR_E_INVALID where that frame ran without the pass or without this layer. */
+int mr_read_layers(mr_scene *scene, int32_t layer, void *out);
+
+/* Host arithmetic, no device needed: the definition above, bit for bit what k_layers writes.  winner is (height, width)
+ * int32; face_pos holds n_faces records of 64 bytes (pos32 != 0: float32 corners [3][4], int32 material, uint32 flags, 8
+ * bytes of padding) or 112 bytes (float64 corners likewise); face_attr n_faces records of 16 float32 (uv [3][2], normals
+ * [3][3], one of padding); face_off the n_models first faces, ascending from 0.  out[i] receives layer i where the mask
+ * names it and is not read otherwise; out_degenerate, unless NULL, the number of degenerate samples.  MR_E_INVALID for a
+ * NULL argument, what mr_scene_set_layers refuses of the description, a height or width outside 1 .. 32767, first faces
+ * that do not ascend from 0 to at most n_faces, or a winner >= n_faces. */
+int mr_host_layers(const int32_t *winner, int32_t height, int32_t width, const void *face_pos, int32_t pos32, const float *face_attr,
+                   int32_t n_faces, const int32_t *face_off, const mr_layers_desc *layers, void *const *out, int64_t *out_degenerate);
+
+/* Diagnostics: out[0] = frames of this scene that enqueued the pass, out[1], out[2] = the sample rows and columns of the last
+ * of them (0 before the first), out[3] = its mask.  Does not wait. */
+#define MR_N_LAYERS_COUNTS 4
+int mr_debug_layers(mr_scene *scene, int32_t *out);
+
+/* Device time in milliseconds of the last frame's k_layers.  Waits for it.  MR_E_INVALID before the first such frame. */
+int mr_debug_layers_times(mr_scene *scene, float *out_ms);
+
+/* Diagnostics: k_layers on arrays the caller supplies -- no frame is rendered.  Arguments as for mr_host_layers; EVERY out[i]
+ * must be given, named by the mask or not.  On the device every layer's buffer lies between 256 bytes of sentinel either
+ * side and is filled with the sentinel byte 0xa5 before the kernel runs, so a layer the mask does not name comes back as
+ * sentinel; out_guard receives the number of guard bytes that changed.  The scene lends its error text only, and the
+ * entry's device buffers are released when it returns.  Waits for the device.  out_ms, unless NULL, receives the kernel's
+ * device milliseconds between events of the entry's own. */
+int mr_debug_layers_post(mr_scene *scene, const int32_t *winner, int32_t height, int32_t width, const void *face_pos, int32_t pos32,
+                         const float *face_attr, int32_t n_faces, const int32_t *face_off, const mr_layers_desc *layers, void *const *out,
+                         int32_t *out_guard, float *out_ms);
+
+/* Diagnostics: the scene's static face records as the device holds them now, after the last commit and pose pass -- what
+ * k_layers and the shading read.  out_info receives { number of faces, pos32 }; out_pos (faces x 64 or 112 bytes) and
+ * out_attr (faces x 64 bytes) may both be NULL to ask for out_info alone.  Waits for the device.  MR_E_INVALID for a scene
+ * that has uncommitted changes (render a frame first). */
+int mr_debug_read_face_records(mr_scene *scene, void *out_pos, void *out_attr, int32_t *out_info);
+
 /* Diagnostics: the scene's per-cluster records as the set-up kernel reads them, one per 64 consecutive faces, 16 32-bit
  * words each: float32 lo[3], hi[3] (the faces' bounding box, rounded outwards; NaN = no box), float32 axis[3] (the unit
  * axis of the cone the faces' unit normals lie in), float32 cos_half, sin_half (every normal n has n . axis >= cos_half;

@@ -11,7 +11,7 @@ import zlib
 
 import numpy as np
 
-from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, light_shafts_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter, tone_map_constants
+from ._pack import active_morph, active_skin, ao_constants, auto_normals_active, bloom_constants, dof_constants, layer_mask, layer_matrix, light_shafts_constants, morph_csr, motion_matrices, motion_vertices, normal_owners, pack_frame, pack_model, pose_normal_matrix, sample_grid, taa_jitter, tone_map_constants
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libmi355rast.so"
@@ -157,6 +157,21 @@ def fill_tone_map_desc(op, fixed, exposure, key, white, speed, min_exposure, max
     if table.size != 256:
         raise ValueError(f"the exp2 table has 256 entries, got {table.size}")
     C.memmove(d.exp2, table.ctypes.data, 1024)
+    return d
+
+
+class LayersDesc(C.Structure):
+    _fields_ = [("s", C.c_double * 16), ("mask", C.c_int32), ("n_models", C.c_int32)]
+
+
+def fill_layers_desc(S, mask, n_models):
+    """``mr_layers_desc``: *S* float64 ``(4, 4)`` (``_pack.layer_matrix``), the layers' bit mask and the number of models."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    if S.shape != (4, 4):
+        raise ValueError(f"S must be (4, 4), got {S.shape}")
+    d = LayersDesc()
+    C.memmove(d.s, S.ctypes.data, 128)
+    d.mask, d.n_models = int(mask), int(n_models)
     return d
 
 
@@ -375,6 +390,15 @@ _PROTOTYPES = {
     "mr_debug_tone_map_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "mr_debug_tone_map_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(ToneMapDesc), C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mr_scene_set_layers": (C.c_int, [C.c_void_p, C.POINTER(LayersDesc)]),
+    "mr_read_layers": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "mr_host_layers": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(LayersDesc),
+                                  C.c_void_p, C.c_void_p]),
+    "mr_debug_layers": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mr_debug_layers_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "mr_debug_layers_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.POINTER(LayersDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mr_debug_read_face_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mr_last_error": (C.c_char_p, []),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
@@ -830,6 +854,65 @@ def debug_motion_faces_post(handle, verts_now, verts_prev, faces, face_off, defo
     return h[:hom_offsets(face_off, deforming, len(faces))[1]], out, int(guard.value)
 
 
+FACE_POS_DTYPES = {True: np.dtype([("v", np.float32, (3, 4)), ("material", np.int32), ("flags", np.uint32), ("pad", np.uint32, (2,))]),
+                   False: np.dtype([("v", np.float64, (3, 4)), ("material", np.int32), ("flags", np.uint32), ("pad", np.uint32, (2,))])}
+FACE_ATTR_DTYPE = np.dtype([("uv", np.float32, (3, 2)), ("n", np.float32, (3, 3)), ("pad", np.float32)])
+FF_HAS_NORMALS, FF_HAS_UV = 4, 8
+LAYERS_SENTINEL = 0xa5
+
+
+def _layers_arrays(winner, face_pos, face_attr, face_off):
+    winner = np.ascontiguousarray(winner, dtype=np.int32)
+    face_off = np.ascontiguousarray(face_off, dtype=np.int32).ravel()
+    face_pos, face_attr = np.ascontiguousarray(face_pos), np.ascontiguousarray(face_attr)
+    if winner.ndim != 2:
+        raise ValueError(f"winner must be (H, W), got {winner.shape}")
+    if face_pos.dtype not in FACE_POS_DTYPES.values() or face_attr.dtype != FACE_ATTR_DTYPE or face_pos.shape != face_attr.shape or face_pos.ndim != 1:
+        raise ValueError("face_pos and face_attr must be record arrays of FACE_POS_DTYPES and FACE_ATTR_DTYPE, one record a face")
+    return winner, face_pos, face_attr, face_off, int(face_pos.dtype == FACE_POS_DTYPES[True])
+
+
+def _layers_outputs(shape, fill_byte=None):
+    """One array a layer, on the sample grid *shape*, and the table of their addresses."""
+    from ._pack import LAYER_CHANNELS, LAYER_DTYPES
+    arrays = []
+    for dtype, channels in zip(LAYER_DTYPES, LAYER_CHANNELS):
+        a = np.zeros(tuple(shape) + ((channels,) if channels > 1 else ()), dtype=dtype)
+        if fill_byte is not None:
+            a.view(np.uint8)[...] = fill_byte
+        arrays.append(a)
+    return arrays, (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def host_layers(winner, face_pos, face_attr, face_off, desc):
+    """``mr_host_layers``: the data layers' definition on the host, no device.  *winner* ``(Hs, Ws)`` int32, *face_pos* and
+    *face_attr* record arrays (``FACE_POS_DTYPES``, ``FACE_ATTR_DTYPE``), *face_off* the models' first faces, *desc* a
+    ``LayersDesc`` whose ``n_models`` is ``len(face_off)``.  Returns ``(layers, degenerate)``: a dict name -> array of the
+    layers the mask names, and the number of degenerate samples.  ``ValueError`` with the library's text for what it refuses."""
+    from ._pack import LAYER_NAMES
+    winner, face_pos, face_attr, face_off, pos32 = _layers_arrays(winner, face_pos, face_attr, face_off)
+    arrays, table = _layers_outputs(winner.shape)
+    degenerate = C.c_int64(-1)
+    _check_accum(load_library().mr_host_layers(winner.ctypes.data, winner.shape[0], winner.shape[1], face_pos.ctypes.data, pos32, face_attr.ctypes.data,
+                                               len(face_pos), face_off.ctypes.data, C.byref(desc), table, C.byref(degenerate)), "mr_host_layers")
+    return {name: a for i, (name, a) in enumerate(zip(LAYER_NAMES, arrays)) if desc.mask >> i & 1}, int(degenerate.value)
+
+
+def debug_layers_post(handle, winner, face_pos, face_attr, face_off, desc, times=False):
+    """``mr_debug_layers_post``: ``k_layers`` on the caller's arrays, no frame rendered.  Returns ``(layers, guard)``: a dict
+    name -> array of ALL nine layers -- one the mask does not name comes back as the sentinel byte ``LAYERS_SENTINEL`` -- and
+    the guard bytes the kernel changed; with *times* a third item, the kernel's device milliseconds."""
+    from ._pack import LAYER_NAMES
+    winner, face_pos, face_attr, face_off, pos32 = _layers_arrays(winner, face_pos, face_attr, face_off)
+    arrays, table = _layers_outputs(winner.shape, fill_byte=0x3c)
+    guard, ms = C.c_int32(-1), C.c_float(0)
+    _check_accum(load_library().mr_debug_layers_post(handle, winner.ctypes.data, winner.shape[0], winner.shape[1], face_pos.ctypes.data, pos32,
+                                                     face_attr.ctypes.data, len(face_pos), face_off.ctypes.data, C.byref(desc), table,
+                                                     C.byref(guard), C.byref(ms) if times else None), "mr_debug_layers_post")
+    out = dict(zip(LAYER_NAMES, arrays))
+    return (out, int(guard.value), float(ms.value)) if times else (out, int(guard.value))
+
+
 def stripe_out_rows(height, stripe_count):
     """Rows of a device's output buffer in the striped layout (``mr_frame_desc.stripe_count``)."""
     tile_rows = -(-int(height) // 16)
@@ -1238,8 +1321,25 @@ class DeviceRenderer:
         if forget and getattr(self, "_tone_key", None) is not None:
             _check_accum(self.lib.mr_scene_reset_exposure(self.handle), "mr_scene_reset_exposure")
 
+    @staticmethod
+    def _layers_values(scene):
+        """The scene's ``Layers`` by value (``None`` without one), for ``_frame_key``."""
+        layers = getattr(scene, "layers", None)
+        return None if layers is None else (layers.names, len(scene.models))
+
+    def sync_layers(self, scene, accumulating=False):
+        """``mr_scene_set_layers`` for the frames enqueued from now on, whenever the description -- the scene's ``Layers``,
+        the view's ``layer_matrix`` with the frame's sub-sample offset, the number of models -- is not the one last handed
+        over.  A scene that never had one makes no call."""
+        if getattr(scene, "layers", None) is not None and accumulating:
+            raise ValueError("layers is not available inside accumulate() / render_mean(): a sum of frames has no one winner a sample")
+        self._sync_desc(scene, "layers", "mr_scene_set_layers", self._layers_values,
+                        lambda sc: fill_layers_desc(layer_matrix(sc), layer_mask(sc.layers.names), len(sc.models)))
+
     def _sync_post(self, scene, accumulating=False):
-        """The post passes of the frame being issued, in the order they run: the eight descriptions in step with *scene*."""
+        """The passes behind the tile kernel of the frame being issued, in the order they run: the nine descriptions in step
+        with *scene*."""
+        self.sync_layers(scene, accumulating)
         self.sync_ambient_occlusion(scene)
         self.sync_temporal_aa(scene)
         self.sync_depth_of_field(scene)
@@ -1409,7 +1509,7 @@ class DeviceRenderer:
                 float(cam.far), cam.x_offset, cam.y_offset, vec(cam.position), id(light), vec(light.position),
                 vec(light.center), vec(light.color), vec(light.ambient), str(light.light_type),
                 float(light.specular_strength), float(light.constant), float(light.linear), float(light.quadratic),
-                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), DeviceRenderer._light_shafts_values(scene), DeviceRenderer._tone_map_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
+                getattr(scene, "supersample", 1), DeviceRenderer._ao_values(scene), DeviceRenderer._dof_values(scene), DeviceRenderer._motion_values(scene), DeviceRenderer._taa_values(scene), DeviceRenderer._bloom_values(scene), DeviceRenderer._light_shafts_values(scene), DeviceRenderer._tone_map_values(scene), DeviceRenderer._layers_values(scene), scene.__dict__.get("_sample_jitter"), id(scene.skybox) if scene.skybox is None or hasattr(scene.skybox, "textures") else vec(scene.skybox))
 
     def packed_frame(self, scene, shadows):
         """``pack_frame`` with a one-entry cache: a render loop that changes nothing between two frames does
@@ -1515,6 +1615,8 @@ class DeviceRenderer:
             raise ValueError("light shafts takes whole frames (no row band, no stripes): its taps cross the bands")
         if getattr(scene, "tone_map", None) is not None and partial:
             raise ValueError("tone mapping takes whole frames (no row band, no stripes): its exposure is metered from the whole frame")
+        if getattr(scene, "layers", None) is not None and partial:
+            raise ValueError("data layers takes whole frames (no row band, no stripes): its taps cross the bands")
         self._sync_post(scene, accumulating)
         if overlay:
             self.sync_overlay(scene)
@@ -1645,6 +1747,39 @@ class DeviceRenderer:
         (``mr_debug_light_shafts_times``)."""
         return self._times(self.lib.mr_debug_light_shafts_times, self.LIGHT_SHAFTS_TIME_NAMES)
 
+    # -- data layers (Scene.layers) ---------------------------------------------------------------
+    def read_layers(self):
+        """``mr_read_layers`` for every layer the last frame computed: a dict name -> array on the sample grid ``(Hs, Ws[, c])``,
+        rows bottom-up.  ``ValueError`` with the library's text where the last frame ran without the pass."""
+        from ._pack import LAYER_CHANNELS, LAYER_DTYPES, LAYER_NAMES
+        mask = self.layers_debug()[3]
+        h, w = self._frame
+        out = {}
+        for i, name in enumerate(LAYER_NAMES):
+            if mask >> i & 1 or not out and i == len(LAYER_NAMES) - 1:      # (no layer at all: the library says why)
+                a = np.empty((h, w) + ((LAYER_CHANNELS[i],) if LAYER_CHANNELS[i] > 1 else ()), dtype=LAYER_DTYPES[i])
+                _check_accum(self.lib.mr_read_layers(self.handle, i, a.ctypes.data), "mr_read_layers")
+                out[name] = a
+        return out
+
+    def layers_debug(self):
+        """``mr_debug_layers``: (frames that enqueued ``k_layers``, the last one's sample rows, its sample columns, its mask)."""
+        return self._counts(self.lib.mr_debug_layers, 4)
+
+    def layers_time(self):
+        """Device milliseconds of the last ``k_layers`` (``mr_debug_layers_times``)."""
+        return self._times(self.lib.mr_debug_layers_times, ("layers",))["layers"]
+
+    def read_face_records(self):
+        """``mr_debug_read_face_records``: the scene's static face records as the device holds them now, ``(face_pos,
+        face_attr)`` as record arrays (``FACE_POS_DTYPES``, ``FACE_ATTR_DTYPE``): what ``host_layers`` takes."""
+        info = (C.c_int32 * 2)()
+        _check_accum(self.lib.mr_debug_read_face_records(self.handle, None, None, info), "mr_debug_read_face_records")
+        pos = np.zeros(info[0], dtype=FACE_POS_DTYPES[bool(info[1])])
+        attr = np.zeros(info[0], dtype=FACE_ATTR_DTYPE)
+        _check_accum(self.lib.mr_debug_read_face_records(self.handle, pos.ctypes.data, attr.ctypes.data, info), "mr_debug_read_face_records")
+        return pos, attr
+
     # -- tone mapping (Scene.tone_map) ------------------------------------------------------------
     def read_exposure(self):
         """``mr_read_exposure``: the exposure ``e`` of the last frame, which ran the pass, as a float32.  ``ValueError`` with
@@ -1759,6 +1894,9 @@ class DeviceRenderer:
         if tm is not None and tm.adaptive:
             raise ValueError("frames of an adaptive tone_map (speed < 1) are rendered by render() / render_async(): their return "
                              "hands the exposure over, and a frame enqueued on a caller's stream has none")
+        if getattr(scene, "layers", None) is not None:
+            raise ValueError("layers frames are rendered by render() / render_async(): their return says which frame "
+                             "read_layers() reads, and a frame enqueued on a caller's stream has none")
         self.issue_motion(scene, partial=self._is_partial(scene, row_band, stripe))
         self.sync_scene(scene)
         self.sync_skybox(scene)

@@ -195,12 +195,7 @@ def depth_map(scene, camera):
     to_screen = np.array([[V[2, 2], V[3, 2]], [0.0, 1.0]])
     linearize = np.array([[0.0, 2 * n * f], [-(f - n), f + n]])
     (a, b), (c, d) = linearize @ to_screen @ project
-    if P[2, 3] != 0:
-        sign = 1.0 if P[2, 3] > 0 else -1.0
-    else:
-        mid = 0.5 * (n + f)
-        ndc = lambda z: abs((z * P[2, 2] + P[3, 2]) / P[3, 3])
-        sign = 1.0 if ndc(mid) <= ndc(-mid) else -1.0
+    sign = depth_sign(camera)
     m = np.array([sign * d, -sign * b, -c, a], dtype=np.float64)
     largest = np.abs(m).max()
     if not np.isfinite(m).all() or largest == 0:
@@ -432,6 +427,62 @@ def tone_map_constants(scene):
     tm = scene.tone_map
     return (TONE_OPERATORS.index(tm.operator), int(tm.exposure is not None), 1.0 if tm.exposure is None else tm.exposure, tm.key, tm.white,
             tm.speed, tm.min_exposure, tm.max_exposure, permille(tm.low), permille(tm.high), tone_map_table())
+
+
+LAYER_NAMES = ("model", "face", "material", "barycentric", "depth", "position", "face_normal", "normal", "uv")
+LAYER_DTYPES = (np.int32, np.int32, np.int32, np.float32, np.float32, np.float32, np.float32, np.float32, np.float32)
+LAYER_CHANNELS = (1, 1, 1, 3, 1, 3, 3, 3, 2)
+
+
+def check_layers(names):
+    """The names of a ``Layers``: a non-empty tuple (or list) of distinct strings out of ``LAYER_NAMES``; returned as a tuple
+    in the order given."""
+    if isinstance(names, (str, bytes)) or not isinstance(names, (tuple, list)):
+        raise TypeError(f"layers: the names must be a tuple of str, got {names!r}")
+    names = tuple(names)
+    if not names:
+        raise ValueError("layers: at least one layer must be named")
+    for name in names:
+        if not isinstance(name, str):
+            raise TypeError(f"layers: a name must be a str, got {name!r}")
+        if name not in LAYER_NAMES:
+            raise ValueError(f"layers: unknown layer {name!r}: the layers are {LAYER_NAMES}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"layers: a layer is named twice in {names!r}")
+    return names
+
+
+def layer_mask(names):
+    """The bit mask ``mr_layers_desc`` carries for these names: bit i is ``LAYER_NAMES[i]``."""
+    return sum(1 << LAYER_NAMES.index(name) for name in names)
+
+
+def depth_sign(camera):
+    """+1 or -1: the sign under which the view-space z of a point in front of *camera* is its eye depth -- ``depth_map``'s
+    rule (its docstring has the reasons)."""
+    P = np.asarray(camera.projection, dtype=np.float64)
+    n, f = float(camera.near), float(camera.far)
+    if P[2, 3] != 0:
+        return 1.0 if P[2, 3] > 0 else -1.0
+    mid = 0.5 * (n + f)
+    ndc = lambda z: abs((z * P[2, 2] + P[3, 2]) / P[3, 3])
+    return 1.0 if ndc(mid) <= ndc(-mid) else -1.0
+
+
+def layer_matrix(scene):
+    """``S`` of ``mr_layers_desc`` for a frame of *scene*, float64 ``(4, 4)``, row vectors: columns 0, 1, 2 are x, y and w of
+    ``MVP . viewport`` on the sample grid as ``pack_frame`` hands it to the frame -- ``sample_grid(scene, jittered=True)``,
+    the sub-sample offset of a ``temporal_aa`` included -- and column 3 is the view matrix's z column times ``depth_sign``:
+    a world point's eye depth, > 0 in front of the camera, for orthographic cameras too."""
+    cam = scene.camera
+    viewport = np.asarray(sample_grid(scene, jittered=True)[3], dtype=np.float64)
+    full = np.asarray(cam.MVP, dtype=np.float64) @ viewport
+    S = np.empty((4, 4), dtype=np.float64)
+    S[:, :3] = full[:, (0, 1, 3)]
+    S[:, 3] = depth_sign(cam) * np.asarray(cam.lookat, dtype=np.float64)[:, 2]
+    if not np.isfinite(S).all():
+        raise ValueError("layers: the camera's matrices are not finite")
+    return S
 
 
 def check_motion_blur(shutter):

@@ -210,6 +210,28 @@ class Bloom:
         return f"Bloom(threshold={self.threshold!r}, intensity={self.intensity!r}, levels={self.levels!r})"
 
 
+class Layers:
+    """What ``Scene.layers`` holds: the names of the per-sample data layers every frame also produces on the device, for
+    ``Scene.read_layers()`` (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6q the reasons).  ``names`` is
+    a non-empty tuple of distinct names out of ``"model"``, ``"face"``, ``"material"`` (int32; -1 where no face shows),
+    ``"barycentric"``, ``"position"``, ``"face_normal"``, ``"normal"`` (float32 x 3), ``"depth"`` (float32 eye depth, ``+inf``
+    where no face shows) and ``"uv"`` (float32 x 2).  Only the named layers are computed, stored and copied.  ``ValueError``
+    for an empty tuple, an unknown name or a name given twice, ``TypeError`` for the wrong type.  A ``Layers`` is never
+    modified: assign a new one to change it."""
+
+    __slots__ = ("names",)
+
+    def __init__(self, names):
+        from ._pack import check_layers
+        object.__setattr__(self, "names", check_layers(names))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a Layers is read-only: assign a new one to Scene.layers")
+
+    def __repr__(self):
+        return f"Layers({self.names!r})"
+
+
 class LightShafts:
     """What ``Scene.light_shafts`` holds: crepuscular rays, the bright sky streaming past the models towards a light's place
     on the screen, marched on the device (``include/mi355rast.h`` has the definition, ``DESIGN.md`` section 6o the reasons).
@@ -1003,6 +1025,13 @@ class Scene:
       the frame is complete, one frame is issued at a time (as under ``temporal_aa``), ``accumulate()`` refuses, and the
       exposure is forgotten by ``reset_motion()`` and whenever ``tone_map`` is assigned.  The history of ``temporal_aa``
       never holds tone-mapped colours.  Split frames (``row_band``, ``multigpu``) refuse it.
+    * ``layers`` (an addition; ``None`` by default, or a ``Layers``): every frame also produces the named per-sample data
+      layers on the device -- model, face and material ids, perspective-correct barycentrics, eye depth, world position,
+      face and shading normals, texture coordinates -- right behind the tile kernel, from the winner map and the face
+      records alone; ``read_layers()`` returns them for the last frame.  The frame's bytes are what they are without it.
+      It composes with ``supersample`` (the layers live on the sample grid), poses, skins, morphs, ``temporal_aa`` (the
+      layers follow the jittered grid the frame was rendered on) and every post pass.  Split frames (``row_band``,
+      ``multigpu``) and ``accumulate()`` refuse it.
     """
 
     camera = Bound()
@@ -1123,6 +1152,26 @@ class Scene:
             raise TypeError(f"tone_map must be None or a ToneMap, got {type(value).__name__}")
         self.__dict__["_tone_map"] = value
         self.__dict__["_tone_forget"] = True      # (the exposure another description adapted is not this one's)
+
+    @property
+    def layers(self):
+        """``None`` (off, the default) or the scene's ``Layers`` (see the class docstring)."""
+        return self.__dict__.get("_layers")
+
+    @layers.setter
+    def layers(self, value):
+        if value is not None and not isinstance(value, Layers):
+            raise TypeError(f"layers must be None or a Layers, got {type(value).__name__}")
+        self.__dict__["_layers"] = value
+
+    def read_layers(self):
+        """The data layers of the last frame, which was rendered with ``layers`` set: a dict name -> NumPy array on the sample
+        grid, ``(s*H, s*W)`` or ``(s*H, s*W, c)``, rows bottom-up like ``read_velocity()``, and like it of the frame enqueued
+        last -- with frames in flight (``render_async``, ``render_frames``) that is the newest one issued.  ``ValueError``
+        where that frame computed none."""
+        if self._renderer is None:
+            raise ValueError("read_layers: nothing rendered yet")
+        return self._renderer.read_layers()
 
     @property
     def last_stats(self):
@@ -1257,6 +1306,8 @@ class Scene:
         if self.tone_map is not None and self.tone_map.adaptive:
             raise ValueError("an adaptive tone_map (speed < 1) is not available inside accumulate() / render_mean(): its "
                              "sub-frames have no previous frame (speed=1 or a fixed exposure is)")
+        if self.layers is not None:
+            raise ValueError("layers is not available inside accumulate() / render_mean(): a sum of frames has no one winner a sample")
         acc = self.__dict__["_accumulation"] = Accumulation(self)
         return acc
 

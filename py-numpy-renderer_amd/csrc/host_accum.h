@@ -34,6 +34,7 @@ int accum_add(mr_scene *sc, const mr_frame_desc *fr, double weight)
     if (fr->flags & MR_FRAME_FACE_STATUS) return fail(MR_E_INVALID, "MR_FRAME_FACE_STATUS is not available for the sub-frames of an accumulation");
     if (sc->motion.on) return fail(MR_E_INVALID, "motion blur is not available for the sub-frames of an accumulation: the sum is the other way to blur motion");
     if (sc->taa.on) return fail(MR_E_INVALID, "temporal anti-aliasing is not available for the sub-frames of an accumulation: the sum is the other way to spread samples over frames");
+    if (sc->layers.on) return fail(MR_E_INVALID, "data layers are not available for the sub-frames of an accumulation: a sum of frames has no one winner a sample");
     if (sc->tone.on && sc->tone.params.adaptive())
         return fail(MR_E_INVALID, "adaptive tone mapping (speed < 1) is not available for the sub-frames of an accumulation: they have no previous frame (speed = 1 or a fixed exposure is)");
     float w;

@@ -23,6 +23,8 @@ struct FrameSlot {
     float last_tone_exposure = 0.f;               // ... which was this
     MotionSlot motion;                            // the velocity buffer and the tables of a frame with motion blur or temporal anti-aliasing (host_motion.h)
     MotionFacesSlot motion_faces;                 // the face records and the tables of its per-face pass (host_motion_faces.h)
+    LayersSlot layers;                            // the data layers of a frame that computes some, one buffer a layer (host_layers.h)
+    int last_layers = 0;                          // the mask of the layers the last frame computed: mr_read_layers has those to read
     bool last_motion = false;                     // the last frame ran k_velocity: mr_read_velocity has something to read
     DevBuf d_stencil_x[mr::MAX_LIGHTS - 1];       // stencil taps of lights 1.. of a frame with several lights
     static_assert(mr::MAX_LIGHTS == MR_MAX_LIGHTS, "the ABI's light count is the kernels'");
@@ -61,6 +63,7 @@ struct FrameSlot {
         for (DevBuf &b : d_stencil_x) b.release();
         motion.release();
         motion_faces.release();
+        layers.release();
         ov.release();
         if (events_ok) {
             for (auto &set : ev_ring) for (auto &e : set) (void)hipEventDestroy(e);
@@ -168,7 +171,8 @@ int validate_frame(const mr_scene *sc, const mr_frame_desc *fr)
         if (fr->stripe_count > 1) return fail(MR_E_INVALID, "supersampling is not available on striped frames");
     }
     const struct { bool on; const char *name; } passes[] = { { sc->ao.on, "ambient occlusion" }, { sc->dof.on, "depth of field" }, { sc->motion.on, "motion blur" },
-                                                         { sc->taa.on, "temporal anti-aliasing" }, { sc->bloom.on, "bloom" }, { sc->shafts.on, "light shafts" }, { sc->tone.on, "tone mapping" } };
+                                                         { sc->taa.on, "temporal anti-aliasing" }, { sc->bloom.on, "bloom" }, { sc->shafts.on, "light shafts" }, { sc->tone.on, "tone mapping" },
+                                                         { sc->layers.on, "data layers" } };
     for (const auto &pass : passes)
         if (pass.on && is_partial(fr))
             return fail(MR_E_INVALID, std::string(pass.name) + " takes whole frames (no row band, no stripes): its taps cross the bands");
@@ -350,10 +354,13 @@ constexpr unsigned SPLIT_MAX_BIG = 64;      // tiles of a whole frame shared out
 //   bloom        the scene has bloom on: its 2 L launches behind k_mblur, in front of the overlay, with bloom_params, likewise
 //   shafts       the scene has light shafts on: their three launches behind k_mblur, in front of the bloom, with shafts_params, likewise
 //   tone         the scene has tone mapping on: its launches behind the bloom, in front of the overlay, with tone_params, likewise
+//   layers       the scene has data layers on: k_layers right behind the tile kernel, in front of every pass above, with layers_params,
+//                likewise; it rewrites nothing, so it is no part of post()
 //   post()       a pass rewrites the float frame behind the tile kernel: the bytes are the full resolve of the result
 struct FramePlan {
     Env env;
-    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa, bloom, shafts, tone;
+    bool partial, deferred, overlay, taps_asked, keep, shadows, timing, all_marks, ml, ss, ordered, split, full, ao, dof, motion, taa, bloom, shafts, tone, layers;
+    mr::LayersParams layers_params;
     mr::AoParams ao_params;
     mr::DofParams dof_params;
     mr::MotionParams motion_params, taa_vel;
@@ -414,6 +421,10 @@ int plan_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, bool may_de
     p.bloom_params = sc->bloom.params;
     p.shafts_params = sc->shafts.params;
     p.tone_params = sc->tone.params;
+    p.layers = sc->layers.on; p.layers_params = sc->layers.params;
+    if (p.layers && p.layers_params.n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "data layers: the scene's models changed since mr_scene_set_layers: hand the description over again");
+    if (p.layers) fc.flags |= MR_FRAME_KEEP_BUFFERS;        // (the winner map, as for k_velocity)
     if (p.post()) fc.flags |= MR_FRAME_KEEP_BUFFERS | MR_FRAME_KEEP_FLOAT;
     // (The overlay needs z and colour too, but only at the pixels its lines touch: then only the tiles that hold such a
     // pixel write them, TileArgs::tap_mask.)
@@ -731,6 +742,7 @@ void record_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, const mr
     fs->last_tone = p.tone && p.n_tiles > 0 ? (p.tone_params.fixed ? 2 : 1) : 0;
     fs->last_tone_exposure = p.tone_params.exposure;
     if (fs->last_tone && p.tone_params.adaptive()) tone_enqueued(sc, fs);
+    fs->last_layers = p.layers && p.n_tiles > 0 ? p.layers_params.mask : 0;
     fs->last_frame = *fr; fs->last_frame.flags = fc.flags;
     fs->last_n_tiles = p.n_tiles;
     fs->last_n_lights = p.n_lights;
@@ -766,6 +778,9 @@ int enqueue_frame(mr_scene *sc, FrameSlot *fs, const mr_frame_desc *fr, uint8_t 
     if (p.timing) HIP_TRY(hipEventRecord(fs->ev[3], stream));
     if ((rc = launch_tile(sc, fs, fc, p, lights, d_out))) return rc;
     if (p.timing) HIP_TRY(hipEventRecord(fs->ev[4], stream));
+    // the data layers: from the winner map alone, in front of every pass that rewrites the float frame
+    if (p.layers && p.n_tiles > 0)
+        if ((rc = launch_layers(sc, stream, fs->layers, fs->d_winner.as<int32_t>(), fc.width, fc.height, p.layers_params))) return rc;
     if ((rc = launch_after_tile(sc, fs, fr, fc, p, d_out))) return rc;
     HIP_TRY(hipGetLastError());
     record_frame(sc, fs, fr, fc, p);

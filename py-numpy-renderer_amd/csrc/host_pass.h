@@ -7,7 +7,7 @@
 // It stands in front of host_scene.h, because mr_scene holds the records by value.
 #pragma once
 
-// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip, bloom.hip, shafts.hip and tonemap.hip, the library's other translation units,
+// ---- the launches of accum.hip, ao.hip, dof.hip, motion.hip, motion_faces.hip, taa.hip, bloom.hip, shafts.hip, tonemap.hip and layers.hip, the library's other translation units,
 // each declared here and nowhere else; weak, so that a library linked without one of them (the tools' ablation builds)
 // still loads: it refuses that pass instead (linked)
 namespace mr_accum {
@@ -57,6 +57,9 @@ __attribute__((weak)) void launch_exposure(hipStream_t stream, const uint32_t *s
                                            uint32_t *hist, float *e_cell, float *e_next);
 __attribute__((weak)) void launch_apply(hipStream_t stream, float *frame, size_t n_floats, int op, const float *e_cell, float e_fixed, float white2);
 }  // namespace mr_tonemap
+namespace mr_layers {
+__attribute__((weak)) void launch(hipStream_t stream, const mr::LayersArgs &a, const mr::LayersParams &p, int pos32);
+}  // namespace mr_layers
 
 namespace {
 

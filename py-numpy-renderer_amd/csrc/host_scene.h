@@ -214,6 +214,14 @@ struct mr_scene {
         int32_t adopted = 0, last_grid = 0;       // exposures handed over; the workgroups of the last k_lum_hist (mr_debug_tone_map)
     } tone;
 
+    // ... the data layers (host_layers.h), marked round k_layers: the description every frame takes a copy of, and the
+    // models' first faces on the device, uploaded once per commit
+    struct Layers : PassRecord<2> {
+        mr::LayersParams params = {};
+        DevBuf d_face_off;
+        int32_t table_commits = -1, last_mask = 0;    // the commit the table was uploaded for; the mask of the last frame enqueued
+    } layers;
+
     // ... and motion blur (host_motion.h), marked in front of k_velocity, behind it, behind k_velocity_faces in a frame that
     // ran the per-face pass, and behind k_mblur; the tables are the class matrices, the background's, the models' first
     // faces and their classes as one block (motion_params)

@@ -3,7 +3,8 @@
 // ao.hip, which holds the ambient obscurance's kernel in another, from dof.hip, which holds the depth of field's, and from
 // motion.hip, which holds the motion blur's two, from motion_faces.hip, which holds the per-face velocity's two, from
 // taa.hip, which holds the temporal anti-aliasing's, from bloom.hip, which holds the bloom's three, from shafts.hip,
-// which holds the light shafts' three, and from tonemap.hip, which holds the tone mapping's three;
+// which holds the light shafts' three, from tonemap.hip, which holds the tone mapping's three, and from layers.hip, which
+// holds the data layers' one;
 // the host code behind the entry points lives in the host_*.h headers beside it, one subject each:
 //
 //   host_device.h       error text, the library's stream, growable device buffers
@@ -23,6 +24,7 @@
 //   host_bloom.h        bloom from a resolution pyramid: the description, the pyramid's layout, the launches, the host mirror, mr_debug_bloom_post
 //   host_shafts.h       light shafts marched towards a light: the description, S and R, the launches, the host mirror, mr_debug_light_shafts_post
 //   host_tonemap.h      tone mapping from a luminance histogram: the description, the slot's words, the scene's exposure, the launches, the host mirror, mr_debug_tone_map_post
+//   host_layers.h       data layers from the winner map and the face records: the description, a slot's buffers, the launch, the host mirror, mr_debug_layers_post
 //   host_frame.h        the frame slot, the frame's constants and enqueue_frame()
 //   host_accum.h        the accumulation: sub-frames summed with weights on the device, finalised once
 //   host_post.h         mr_debug_post: k_ao, k_dof and the accumulation's kernels on buffers a caller supplies
@@ -48,7 +50,8 @@
 //                   mr_scene_set_temporal_aa, k_bloom_down, k_bloom_up and k_bloom_composite behind k_mblur in one with
 //                   mr_scene_set_bloom, k_shaft_source, k_shaft_march and k_shaft_composite in front of those in one with
 //                   mr_scene_set_light_shafts, k_lum_hist, k_exposure and k_tone_apply behind the bloom in one with
-//                   mr_scene_set_tone_map, k_accum_resolve for the bytes of any)
+//                   mr_scene_set_tone_map, k_accum_resolve for the bytes of any; k_layers right behind k_tile in one with
+//                   mr_scene_set_layers)
 //
 // Per-frame work buffers live in a "frame slot".  Every stream a caller renders on gets its own slot, so frames
 // enqueued on different streams are independent and may overlap on the device.
@@ -84,6 +87,7 @@
 #include "bloom_def.h"
 #include "shafts_def.h"
 #include "tonemap_def.h"
+#include "layers_def.h"
 
 #include "host_device.h"
 #include "host_env.h"
@@ -102,6 +106,7 @@
 #include "host_bloom.h"
 #include "host_shafts.h"
 #include "host_tonemap.h"
+#include "host_layers.h"
 #include "host_frame.h"
 #include "host_accum.h"
 #include "host_post.h"
@@ -252,6 +257,7 @@ void mr_scene_destroy(mr_scene *sc)
     motion_faces_release(sc);
     taa_release(sc);
     tone_release(sc);
+    layers_release(sc);
     for (auto &ln : sc->lanes) if (ln.stream) (void)hipStreamDestroy(ln.stream);
     sc->marks_pose.release(); sc->marks_normals.release(); sc->marks_skin.release(); sc->marks_morph.release(); sc->marks_auto.release();
     delete sc;
@@ -921,6 +927,68 @@ int mr_debug_tone_map_post(mr_scene *sc, const float *frame, int32_t height, int
     return debug_tone_map_post(sc, frame, height, width, tone_map, has_prev, e_prev, grid_cap, form, out_frame, out_hist, out_exposure, out_ms);
 }
 
+int mr_scene_set_layers(mr_scene *sc, const mr_layers_desc *layers)
+{
+    if (!sc) return fail(MR_E_INVALID, "scene is NULL");
+    if (!layers) { sc->layers.on = false; return MR_OK; }      // (frames already enqueued took their copy)
+    mr::LayersParams p;
+    if (int rc = layers_params(layers, 0, p)) return rc;
+    if (layers->n_models != (int32_t)sc->model_face_off.size())
+        return fail(MR_E_INVALID, "data layers: n_models is not the number of the scene's models");
+    if (int rc = layers_linked()) return rc;
+    sc->layers.params = p;
+    sc->layers.on = true;
+    return MR_OK;
+}
+
+int mr_read_layers(mr_scene *sc, int32_t layer, void *out)
+{
+    FrameSlot *fs = last_slot(sc);
+    if (!fs) return MR_E_INVALID;
+    if (layer < 0 || layer >= mr::N_LAYERS) return fail(MR_E_INVALID, "data layers: no such layer");
+    if (!fs->last_layers) return fail(MR_E_INVALID, "the last frame was rendered without data layers");
+    if (!(fs->last_layers & (1 << layer))) return fail(MR_E_INVALID, "the last frame was rendered without this layer");
+    return read_back(fs->layers.d[layer], static_cast<uint32_t *>(out),
+                     (size_t)fs->last_frame.width * fs->last_frame.height * mr::layer_words(layer), "data layers");
+}
+
+int mr_host_layers(const int32_t *winner, int32_t height, int32_t width, const void *face_pos, int32_t pos32, const float *face_attr,
+                   int32_t n_faces, const int32_t *face_off, const mr_layers_desc *layers, void *const *out, int64_t *out_degenerate)
+{
+    return host_layers(winner, height, width, face_pos, pos32, face_attr, n_faces, face_off, layers, out, out_degenerate);
+}
+
+int mr_debug_layers(mr_scene *sc, int32_t *out)
+{
+    if (int rc = pass_counts(sc, &mr_scene::layers, out)) return rc;
+    out[3] = sc->layers.last_mask;
+    return MR_OK;
+}
+
+int mr_debug_layers_times(mr_scene *sc, float *out_ms)
+{
+    return pass_times(sc, &mr_scene::layers, "no frame with data layers yet", out_ms, { { 0, 1 } });
+}
+
+int mr_debug_layers_post(mr_scene *sc, const int32_t *winner, int32_t height, int32_t width, const void *face_pos, int32_t pos32,
+                         const float *face_attr, int32_t n_faces, const int32_t *face_off, const mr_layers_desc *layers, void *const *out,
+                         int32_t *out_guard, float *out_ms)
+{
+    return debug_layers_post(sc, winner, height, width, face_pos, pos32, face_attr, n_faces, face_off, layers, out, out_guard, out_ms);
+}
+
+int mr_debug_read_face_records(mr_scene *sc, void *out_pos, void *out_attr, int32_t *out_info)
+{
+    if (!sc || !out_info) return fail(MR_E_INVALID, "NULL argument");
+    if ((out_pos == nullptr) != (out_attr == nullptr)) return fail(MR_E_INVALID, "mr_debug_read_face_records: out_pos and out_attr go together");
+    if (sc->dirty || sc->pose_dirty) return fail(MR_E_INVALID, "the scene has uncommitted changes: render a frame first");
+    const size_t nf = sc->faces.size() / 12;
+    out_info[0] = (int32_t)nf; out_info[1] = sc->pos32 ? 1 : 0;
+    if (!out_pos || nf == 0) return MR_OK;
+    if (int rc = read_back(sc->d_face_pos, static_cast<unsigned char *>(out_pos), nf * (sc->pos32 ? sizeof(mr::FacePos32) : sizeof(mr::FacePos64)), "face records")) return rc;
+    return read_back(sc->d_face_attr, static_cast<unsigned char *>(out_attr), nf * sizeof(mr::FaceAttr), "face records");
+}
+
 int mr_scene_set_motion_faces(mr_scene *sc, const mr_motion_faces_desc *d)
 {
     if (!sc) return fail(MR_E_INVALID, "scene is NULL");
@@ -1213,6 +1281,8 @@ int mr_render_device(mr_scene *sc, const mr_frame_desc *fr, void *d_out_rgb, voi
         return fail(MR_E_INVALID, "temporal anti-aliasing: its frames are rendered by mr_render or mr_render_async, whose return hands the history over");
     if (sc->tone.on && sc->tone.params.adaptive())
         return fail(MR_E_INVALID, "adaptive tone mapping: its frames are rendered by mr_render or mr_render_async, whose return hands the exposure over");
+    if (sc->layers.on)
+        return fail(MR_E_INVALID, "data layers: its frames are rendered by mr_render or mr_render_async, whose return says which frame mr_read_layers reads");
     return enqueue_frame(sc, fs, fr, static_cast<uint8_t *>(d_out_rgb));
 }
 

@@ -233,6 +233,9 @@ class BandRenderer:
         if getattr(scene, "tone_map", None) is not None:
             raise ValueError("a frame split over devices does not support tone_map: its exposure is metered from the whole frame "
                              "(render it on one device)")
+        if getattr(scene, "layers", None) is not None:
+            raise ValueError("a frame split over devices does not support layers: its taps cross the bands "
+                             "(render it on one device)")
         if partition not in ("bands", "stripes", "weighted"):
             raise ValueError(f"unknown partition {partition!r}")
         self.rank, self.world, self.partition = rank, world, partition
