@@ -21,6 +21,10 @@
 //   MR_SIL_CACHE      1         0: no frame reads or fills the silhouette cache
 //   MR_BIG_TRI_REJECT 1         0: k_bin_work lists a large triangle in every tile of its box again, not only in those it can
 //                               cover (tri_touches_tile; same frames, for the A/B and the tests)
+//   MR_QUAD_TILE_CULL 1         0: k_tile's frame-only single-light kernels stage and classify every shadow quad a tile lists again, not
+//                               only those that k_bin_work's bound lets pass against the tile's z (quad_reject.h; same frames,
+//                               for the A/B and the tests).  count | count0: on | off, and those kernels leave the number of
+//                               quads a tile staged in word 8 of its record (mr_debug_read_tile_records; zero otherwise)
 //   MR_AO_TILE        64x64     32x32 | 64x16: the other workgroup shapes of k_ao (same bits; for the A/B)
 //   MR_DOF_TILE       32x32     32x32x256 | 16x16: the other workgroup shapes of k_dof -- 32 x 32 samples with 256 threads, not
 //                               1 024, or 16 x 16 samples with 256 (same bits; for the A/B)
@@ -30,7 +34,7 @@
 //   MR_TONEMAP_HIST   atomic    ballot: k_lum_hist adds once per distinct bin of a wavefront, not once a sample (same bits; for the A/B)
 //   MR_TONEMAP_GRID   256       1 .. 1024: the cap of k_lum_hist's grid, the rows of a frame slot's slab (same bits; for the A/B)
 //
-// MR_CLUSTER_CULL, MR_SIL_CACHE and MR_BIG_TRI_REJECT are looked up for every frame, because the tests switch them inside
+// MR_CLUSTER_CULL, MR_SIL_CACHE, MR_BIG_TRI_REJECT and MR_QUAD_TILE_CULL are looked up for every frame, because the tests switch them inside
 // one process; the rest are read once per process.
 #pragma once
 
@@ -39,6 +43,7 @@ namespace {
 struct Env {
     bool vertex_mfma, resolve_separate, sil_cache, big_tri_reject;
     int edge_spread, tile_split, tile_order;      // tile_order: 0 auto, 1 row-major, 2 heaviest first
+    int quad_tile_cull;                           // bit 0: on; bit 1: the tile records count (mr::TileArgs::quad_cull)
     int quad_walk;                                // 0 auto, 1 strips, 2 spans (mr::QUAD_WALK_*)
     int pair_log;                                 // 0 .. mr::PAIR_LOG_K
     int ao_shape, dof_shape, mblur_shape, taa_shape;   // 0 .. 2: the `shape` of ao.hip's, dof.hip's, motion.hip's and taa.hip's launch
@@ -82,6 +87,8 @@ Env read_env()
     e.sil_cache = !(sil && !strcmp(sil, "0"));
     const char *rej = getenv("MR_BIG_TRI_REJECT");
     e.big_tri_reject = !(rej && !strcmp(rej, "0"));
+    const char *cull = getenv("MR_QUAD_TILE_CULL");
+    e.quad_tile_cull = !cull ? 1 : !strcmp(cull, "0") ? 0 : !strcmp(cull, "count") ? 3 : !strcmp(cull, "count0") ? 2 : 1;
     return e;
 }
 

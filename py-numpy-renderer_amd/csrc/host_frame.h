@@ -13,7 +13,7 @@ struct FrameSlot {
     hipStream_t stream = nullptr;                 // the stream this slot serves
     int id = 0;                                   // its index among the scene's slots
     DevBuf d_vout, d_vclip, d_tris, d_clips, d_status, d_count_list, d_quads, d_sil, d_counters;
-    DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_work, d_tile_stats, d_hist, d_split;
+    DevBuf d_bin_count, d_items[mr::BIN_CLASSES], d_quad_bound, d_work, d_tile_stats, d_hist, d_split;
     DevBuf d_z, d_winner, d_stencil, d_frame, d_out;
     DevBuf d_frame_b;                             // the float frame k_taa, k_dof or k_mblur writes; then swapped with d_frame, which stays THE float frame
     DevBuf d_bloom;                               // the pyramid of a frame with bloom: levels 1 .. L, three floats a sample (host_bloom.h, bloom_pyramid)
@@ -57,7 +57,7 @@ struct FrameSlot {
     void release()
     {
         for (DevBuf *b : { &d_vout, &d_vclip, &d_count_list, &d_tris, &d_clips, &d_status, &d_quads, &d_sil, &d_counters,
-                           &d_bin_count, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_bloom, &d_shafts, &d_tone, &d_out })
+                           &d_bin_count, &d_quad_bound, &d_work, &d_tile_stats, &d_hist, &d_split, &d_z, &d_winner, &d_stencil, &d_frame, &d_frame_b, &d_bloom, &d_shafts, &d_tone, &d_out })
             b->release();
         for (DevBuf &b : d_items) b.release();
         for (DevBuf &b : d_stencil_x) b.release();
@@ -515,6 +515,8 @@ int grow_slot(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Frame
             return fail(MR_E_OVERFLOW, "more primitives in one 16x16 tile than the tile lists are allowed to grow to (48 GB per class)");
         HIP_TRY(fs->d_items[c].ensure(bytes));
     }
+    HIP_TRY(fs->d_quad_bound.ensure(nT * fs->bin_cap[2] * sizeof(float)));      // one float beside every entry of the quad lists
+
     if (!fs->events_ok) {
         for (auto &set : fs->ev_ring) for (auto &e : set) HIP_TRY(hipEventCreate(&e));
         HIP_TRY(hipHostMalloc((void **)&fs->h_counters, sizeof(Counters) + sizeof(Sticky), hipHostMallocDefault));
@@ -531,9 +533,9 @@ int grow_tile_state(FrameSlot *fs, const FramePlan &p)
 {
     using namespace mr;
     HIP_TRY(fs->d_hist.ensure(p.order_bytes + (size_t)std::max(p.n_tiles, 1) + 16));     // class bytes: 16-byte aligned, padded
-    // split tiles: HEAVY0_MAX arrival counters (zero between frames), then the parts' stencil counts
+    // split tiles: HEAVY0_MAX arrival counters (zero between frames), then the parts' stencil counts, then their counts of staged quads
     constexpr size_t arrive_bytes = (size_t)HEAVY0_MAX * 4;
-    if (int rc = ensure_cleared(fs->d_split, arrive_bytes + arrive_bytes * HEAVY_SPLIT * TILE_PX, fs->stream, arrive_bytes)) return rc;
+    if (int rc = ensure_cleared(fs->d_split, arrive_bytes + arrive_bytes * HEAVY_SPLIT * TILE_PX + arrive_bytes * HEAVY_SPLIT, fs->stream, arrive_bytes)) return rc;
     if (fs->bins_zeroed_for != BIN_CLASSES * p.n_tiles + 1) {
         HIP_TRY(hipMemsetAsync(fs->d_bin_count.p, 0, fs->d_bin_count.cap, fs->stream));
         HIP_TRY(hipMemsetAsync(fs->d_hist.p, 0, fs->d_hist.cap, fs->stream));       // no history for a new tile grid
@@ -550,6 +552,7 @@ mr::BinArgs bin_args(const FrameSlot *fs)
     ba.bin_count = fs->d_bin_count.as<uint32_t>();
     for (int c = 0; c < mr::BIN_CLASSES; ++c) { ba.items[c] = fs->d_items[c].as<uint32_t>(); ba.cap[c] = fs->bin_cap[c]; }
     ba.work = fs->d_work.as<uint2>(); ba.work_cap = fs->work_cap;
+    ba.quad_bound = fs->d_quad_bound.as<float>();
     return ba;
 }
 
@@ -626,6 +629,7 @@ int launch_tile(mr_scene *sc, FrameSlot *fs, const mr::FrameConst &fc, const Fra
     ta.split_arrive = fs->d_split.as<uint32_t>(); ta.split_sten = fs->d_split.as<int32_t>() + HEAVY0_MAX;
     ta.split_cost = p.split_cost; ta.split_quads = p.split_quads; ta.split_max = p.split_max;
     ta.quad_walk = (uint32_t)p.env.quad_walk;
+    ta.quad_bound = fs->d_quad_bound.as<float>(); ta.quad_cull = (uint32_t)p.env.quad_tile_cull;
     ta.pair_log = (uint32_t)fc.n_faces <= PAIR_LOG_MAX_FACE ? (uint32_t)p.env.pair_log : 0u;   // (a log entry holds 24 bits of the face)
     ShadeArgs &sh = tka.sh;
     sh.tris = fs->d_tris.as<TriRec>(); sh.face_pos = sc->d_face_pos.p; sh.face_attr = sc->d_face_attr.as<FaceAttr>();

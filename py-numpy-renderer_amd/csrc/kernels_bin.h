@@ -14,6 +14,7 @@
 
 #include "rast_math.h"
 #include "tri_reject.h"       // tri_touches_tile, quad_touches_tile's counterpart for a large triangle (plain C++: the CPU check compiles it too)
+#include "quad_reject.h"      // a shadow quad's depth rules: per sample, per strip, per tile (plain C++ likewise)
 
 namespace mr {
 
@@ -76,6 +77,7 @@ struct BinArgs {
     uint32_t cap[BIN_CLASSES];
     uint2 *work;                  // (primitive, chunk of 64 tiles); primitive = face, or WORK_QUAD | quad
     uint32_t work_cap;
+    float *quad_bound;            // [n_tiles * cap[2]] beside items[2]: quad_tile_bound of the listed (quad, tile) pair (quad_reject.h)
 };
 
 constexpr int TILE_STATS = 5;     // per-tile partial counters written by the tile kernel
@@ -243,7 +245,8 @@ __device__ __forceinline__ uint32_t quad_chunks(const FrameConst &fc, int x0, in
 }
 
 // The work items: one wavefront per item, one tile per lane.  A shadow quad is listed only in the tiles it can
-// touch (quad_touches_tile, exact) and, with big_tri_reject (MR_BIG_TRI_REJECT, default on), so is a triangle
+// touch (quad_touches_tile, exact), each time with the bound of its depth over the tile (quad_tile_bound: by it k_tile
+// drops the quads that lie behind everything the tile shows before it stages them) and, with big_tri_reject (MR_BIG_TRI_REJECT, default on), so is a triangle
 // (tri_touches_tile, conservative): c4's two floor triangles are otherwise listed in every tile of their boxes, the
 // wrong side of their shared diagonal included, and a tile that lists something runs the whole listed-tile chain of
 // k_tile to write background.  A rejected pair held no covered sample, so nothing but the lists' lengths depends on it.
@@ -297,7 +300,18 @@ __device__ __forceinline__ void bin_work_body(const FrameConst &fc, const BinArg
                 if (out && lane == __ffsll((long long)out) - 1) atomicAdd(&a.ctr->pad0[7], (unsigned int)__popcll(out));
             }
         }
-        if (touches) bin_emit(fc, a, pair_class(fc, is_quad, clip, pb, tx, ty), id, tx, ty);
+        if (touches && is_quad) {
+            const QuadRec &q = a.quads[id];
+            const uint32_t tile = (uint32_t)ty * fc.tiles_x + tx;
+            const uint32_t pos = atomicAdd(&a.bin_count[2u * (uint32_t)(fc.tiles_x * fc.tiles_y) + tile], 1u);
+            if (pos < a.cap[2]) {
+                a.items[2][(size_t)tile * a.cap[2] + pos] = id;
+                a.quad_bound[(size_t)tile * a.cap[2] + pos] = quad_tile_bound(q.nx, q.ny, q.nz, q.d, tx * TILE_W, tile_row_frame(fc, ty) * TILE_H,
+                                                                             TILE_W, TILE_H, fc.f_plus_n, fc.f_minus_n, fc.two_nf, fc.system == 1);
+            }
+        } else if (touches) {
+            bin_emit(fc, a, pair_class(fc, false, clip, pb, tx, ty), id, tx, ty);
+        }
     }
 }
 

@@ -20,8 +20,10 @@
 //      (MR_PAIR_LOG=0 .. 4 sets the log's capacity, 0 for none; mr_debug_pair_log counts both).  The reference's
 //      sequential rule (a fragment writes when zbuf >= z, so the last face in order wins ties) is reproduced
 //      order-free: smallest z, and among equal z the largest face index;
-//   3. the tile's shadow quads against the final z, QUAD_BATCH records staged in LDS per round; lane j of every
-//      wavefront classifies quad j against the wavefront's 16x4 strip.  A survivor is then walked in one of two ways
+//   3. the tile's shadow quads against the final z, QUAD_BATCH records staged in LDS per round -- in the frame-only
+//      single-light kernels only the quads that k_bin_work's depth bound lets pass against the tile's most favourable
+//      covered z (quad_tile_none, quad_reject.h; MR_QUAD_TILE_CULL=0 stages them all), and a tile none of whose quads
+//      can pass skips the phase; lane j of every wavefront classifies quad j against the wavefront's 16x4 strip.  A survivor is then walked in one of two ways
 //      (obj/triangular.py:335-368): the STRIP walk, one quad at a time, every lane its own pixel, stencil +-1 in the
 //      lane's register; or -- single light, where enough of the strip's quads are crossed by an edge -- the SPAN walk:
 //      (quad, row) items dealt to the lanes, sixteen quads to a round, the row's samples found as one interval by
@@ -262,37 +264,7 @@ enum : uint32_t { QUAD_WALK_AUTO = 0, QUAD_WALK_STRIPS = 1, QUAD_WALK_SPANS = 2 
 #define MR_SPAN_MIN_QUADS 6
 #endif
 
-// The depth rule of a shadow quad's sample (obj/triangular.py:351-360), the one copy both walks of phase 3 call: does
-// the sample (dpx, dpy) of the quad with plane (q_nx, q_ny, nzq, q_d) pass against the pixel's final z?
-// zq = two_nf / (f_plus_n + (t / nz) * f_minus_n) with t the plane's value at the sample.  The reference's value needs
-// two IEEE divisions; the DECISION needs none: multiplied through by nz, zbest - zq has the sign of E / D with
-// D = f_plus_n * nz + t * f_minus_n and E = zbest * D - two_nf * nz (a0 = f_plus_n * nz and b0 = two_nf * nz come with
-// the staged record).  That settles it unless z-buffer and quad depth agree to nine digits or D is close to its pole
-// (or something is not finite); only then is the exactly rounded expression evaluated.  t itself is computed exactly
-// as the reference does.  Decisions stay bit-exact.  `in`: the lane holds a sample of the quad (the others' verdicts
-// are not used).
-__device__ __forceinline__ bool quad_depth_pass(double q_nx, double q_ny, double nzq, double q_d, double a0, double b0,
-                                                double dpx, double dpy, double zbest, bool rh, bool in,
-                                                double f_plus_n, double f_minus_n, double two_nf)
-{
-    const double t = (q_nx * dpx + q_ny * dpy) + q_d;
-    const double tf = t * f_minus_n;
-    const double den = a0 + tf;
-    const double prod = zbest * den;
-    const double e = prod - b0;
-    // an empty z-buffer entry (+-inf) beats or loses against every finite depth
-    const bool zinf = fabs(zbest) == INFINITY;
-    bool pass = zinf ? (rh ? zbest > 0 : zbest < 0) : (rh ? ((e > 0) == (den > 0)) : ((e < 0) == (den > 0)));
-    const bool clear = zinf || fabs(e) > 1e-9 * (fabs(prod) + fabs(b0));
-    const bool unsure = in && !(clear && fabs(den) > 2e-4 * (fabs(a0) + fabs(tf)));
-    if (__ballot(unsure)) {
-        if (unsure) {
-            const double z = two_nf / (f_plus_n - (-t / nzq) * f_minus_n);     // linearize_z (obj/core.py:226-228)
-            pass = rh ? (zbest >= z) : (zbest <= z);
-        }
-    }
-    return pass;
-}
+// (quad_depth_pass, the depth rule of a shadow quad's sample both walks of phase 3 call: quad_reject.h)
 
 constexpr int MAT_LDS = 8;            // scenes with up to this many materials keep them in LDS
 static_assert(sizeof(Material) % 8 == 0 && MAT_LDS * sizeof(Material) / 8 <= TILE_PX, "material staging");
@@ -367,13 +339,16 @@ struct TileArgs {
     uint32_t *tile_stats;
     Counters *ctr, *next_ctr;     // this frame's counters; the next frame's (cleared here)
     Sticky *sticky;               // overflow verdicts of the slot's earlier frames (see Sticky)
-    int32_t *split_sten;          // [HEAVY0_MAX][HEAVY_SPLIT][TILE_PX] stencil counts of a split tile's parts
+    int32_t *split_sten;          // [HEAVY0_MAX][HEAVY_SPLIT][TILE_PX] stencil counts of a split tile's parts, then [HEAVY0_MAX][HEAVY_SPLIT] counts of the quads they staged
     uint32_t *split_arrive;       // [HEAVY0_MAX] parts that have left theirs (zero between frames)
     const uint32_t *order;        // ORDER_HEAD words, then the tiles in the order to render them (k_bin_work); null: row-major
     uint8_t *tile_class;          // [n_tiles] what this frame leaves for the next: 1 + the tile's cost class
     uint32_t split_cost, split_quads;   // k_tile<true>: a tile this costly, with this many shadow quads, is shared out next frame ...
     uint32_t split_max;                 // ... if no more than this many are (<= HEAVY0_MAX)
     uint32_t quad_walk;                 // QUAD_WALK_*: MR_QUAD_WALK (single-light instantiations, phase 3)
+    const float *quad_bound;            // [n_tiles * cap[2]] beside items[2]: k_bin_work's quad_tile_bound of every listed quad
+    uint32_t quad_cull;                 // MR_QUAD_TILE_CULL: bit 0, the frame-only single-light kernels drop a tile's quads by that bound (phase 3);
+                                        // bit 1, they leave the number they staged in word 8 of the tile's record
 };
 
 // A frame with several lights (k_tile<., ., true>): the lights (all of them, FrameLights) and the stencil taps of
@@ -417,6 +392,11 @@ __device__ __forceinline__ void tile_body()
     __shared__ uint32_t s_id[QUAD_BATCH];
     __shared__ float s_gamma[GAMMA_LUT_SIZE];
     __shared__ unsigned long long s_mat[MAT_LDS * sizeof(Material) / 8];
+    // CULL: the frame-only single-light kernels drop the shadow quads that lie behind everything the tile shows before
+    // they stage them (phase 3).  The multi-light kernel is at its 96 registers with scratch and the general ones count
+    // every fragment or are at their budgets: they keep the strip-level rule alone.
+    constexpr bool CULL = !FULL && !ML;
+    __shared__ unsigned long long s_zt;                   // (CULL only) key of the tile's most favourable covered z
 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int lp = tid;                                   // pixel of this thread inside the tile
@@ -548,6 +528,7 @@ __device__ __forceinline__ void tile_body()
         // pair of scalar registers through every phase, and the multi-light general kernel spilled it)
         if (FULL && tid == 0) ta.tile_stats[(size_t)tile * TILE_REC + 8] = (uint32_t)t_start;
         if (FULL && tid < TILE_STATS) s_cnt[tid] = 0;
+        if (CULL && tid == 0) s_zt = rh ? 0ull : ~0ull;   // below (above) the key of every z: "nothing covered" (read behind phase 3's entry barrier)
         s_gamma[tid] = sh.gamma_lut[tid];
         if (tid == 0) s_gamma[GAMMA_LUT_SIZE - 1] = sh.gamma_lut[GAMMA_LUT_SIZE - 1];
         mat_lds = fc.n_materials <= MAT_LDS;
@@ -726,7 +707,23 @@ __device__ __forceinline__ void tile_body()
     int sten_x[MAX_LIGHTS - 1] = { 0, 0, 0 };             // ML: lights 1.. (always indexed by constants: registers)
     unsigned int qfrags = 0, qupd = 0;
     // without the counters only the frame is the contract: the stencil matters where a triangle was drawn
-    if (n_quad && (counters || __syncthreads_or(covered))) {
+    unsigned int q_kept = 0;                              // CULL: the quads this workgroup staged (word 8 of the tile's record)
+    // CULL (the frame-only single-light kernels): the tile's most favourable covered z is the extreme of its strips',
+    // one LDS atomic per wavefront that covers anything, in front of the entry barrier; a word nobody touched says what
+    // __syncthreads_or(covered) says in the other kernels.
+    int zt_seen = 0;
+    if (CULL && n_quad) {
+        if (__ballot(covered)) {
+            // (the wavefront's extreme again below, where the strip's two limits are worked out together)
+            double zw = covered ? zbest : (rh ? -INFINITY : INFINITY);
+#pragma unroll
+            for (int off = WAVE / 2; off; off >>= 1) { const double o = __shfl_xor(zw, off); zw = rh ? fmax(zw, o) : fmin(zw, o); }
+            if (lane == 0) { if (rh) atomicMax(&s_zt, z_key(zw)); else atomicMin(&s_zt, z_key(zw)); }
+        }
+        __syncthreads();
+        zt_seen = __builtin_amdgcn_readfirstlane(s_zt != (rh ? 0ull : ~0ull) ? 1 : 0);
+    }
+    if (n_quad && (CULL ? zt_seen != 0 : (counters || __syncthreads_or(covered)))) {
         const TileKernArgs &ka = kernargs<TileKernArgs>();
         const FrameConst &fc = ka.fc;
         const TileArgs &ta = ka.ta;
@@ -749,40 +746,95 @@ __device__ __forceinline__ void tile_body()
             zlim = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(zlim)), __builtin_amdgcn_readfirstlane(__double2loint(zlim)));
             zhard = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(zhard)), __builtin_amdgcn_readfirstlane(__double2loint(zhard)));
         }
+        // (CULL: set up in front of the first batch that is staged, if any is -- the key from a copy of z the compiler
+        // cannot trace, or it is worked out in front of the batch loop and spilled)
+        auto span_words = [&]() {
+            if (ta.quad_walk != QUAD_WALK_STRIPS) {
+                double zb = zbest;
+                asm volatile("" : "+v"(zb));
+                if (!n_small) s_key[lp] = z_key(zb);
+                s_win[lp] = 0;
+            }
+        };
         // The span walk (single light): the final z in LDS (the keys are there already wherever the tile had small
         // pairs), and the stencil words it adds to in s_win, dead since `best` was read.  Each thread writes its own
         // pixel's; the batch's staging barrier stands between these stores and the first span.
         // (the walk's few arguments are read where they are used, batch by batch: kept in scalar registers from here
         // on they cost the kernel its sixth wavefront)
-        if (!ML && ta.quad_walk != QUAD_WALK_STRIPS) {
+        if (!CULL && !ML && ta.quad_walk != QUAD_WALK_STRIPS) {
             if (!n_small) s_key[lp] = z_key(zbest);
             s_win[lp] = 0;
         }
         const uint32_t q_begin = SPLIT ? (uint32_t)((unsigned long long)part * n_quad / n_parts) : 0u,
                        q_end = SPLIT ? (uint32_t)((unsigned long long)(part + 1) * n_quad / n_parts) : n_quad;    // this part's share
         for (uint32_t qbase = q_begin; qbase < q_end; qbase += QUAD_BATCH) {
-            const int n = (int)min((uint32_t)QUAD_BATCH, q_end - qbase);
-            if (qbase != q_begin) __syncthreads();        // the previous batch has been read
+            int n = (int)min((uint32_t)QUAD_BATCH, q_end - qbase);
             // Staging also folds two per-quad facts into the copy: a back-facing quad's edge vectors are
             // negated (the rounded cross product changes sign exactly, so "inner side" is "> 0" for every
             // staged quad), and the last 16 bytes of the header, unused here, receive f_plus_n * nz and
             // two_nf * nz of the depth test below.
-            for (int i = tid; i < n * QUAD_STAGE_U4; i += TILE_PX) {
-                const int q = i / QUAD_STAGE_U4, piece = i - q * QUAD_STAGE_U4;
-                const uint32_t id = quad_items[qbase + q];
-                const QuadRec *src = quads + id;
-                uint4 val = reinterpret_cast<const uint4 *>(src)[piece];
-                if (piece == 3) {
-                    const double a0 = f_plus_n * src->nz, b0 = two_nf * src->nz;
-                    val = make_uint4((uint32_t)__double2loint(a0), (uint32_t)__double2hiint(a0),
-                                     (uint32_t)__double2loint(b0), (uint32_t)__double2hiint(b0));
-                } else if (piece >= 5 && (piece & 1) && !src->is_front) {
-                    val.y ^= 0x80000000u; val.w ^= 0x80000000u;
-                } else if (ML && piece == 2) {
-                    val.w |= src->light << 1;               // beside is_front (0 / 1): the header's last 16 bytes are overwritten above
+            if (CULL) {
+                // Lane j of every wavefront takes entry j of the batch and the bound k_bin_work left beside it, and drops
+                // the quad when no sample of the tile can pass against the tile's z (quad_tile_none, quad_reject.h: the
+                // strip rule below would reject it in all four wavefronts).  Every wavefront reads the same values, so
+                // the ballot is the same in all four: an empty one skips the batch with its two barriers in the whole
+                // workgroup, otherwise the survivors move to the lanes 0 .. n-1 in order and only they are staged and
+                // classified.  (The tile's z is read per batch: held in scalar registers it was spilled.)
+                bool keep = lane < n;
+                uint32_t my_id = 0;
+                if (keep) {
+                    my_id = quad_items[qbase + lane];
+                    if (ta.quad_cull & 1u) {
+                        double tnf = two_nf;                // (an untraceable copy again: see the strip's verdicts below)
+                        asm volatile("" : "+v"(tnf));
+                        keep = !quad_tile_none(ta.quad_bound[(size_t)tile * ta.cap[2] + qbase + lane], z_unkey(s_zt), tnf, rh);
+                    }
                 }
-                s_quad[i] = val;
-                if (piece == 0) s_id[q] = id;
+                const unsigned long long km = __ballot(keep);
+                n = __popcll(km);
+                if (!n) continue;
+                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
+                const int ids = __builtin_amdgcn_ds_permute((keep ? rank : n + (lane - rank)) << 2, (int)my_id);
+                if (q_kept) __syncthreads();              // the previous batch has been read
+                else span_words();
+                q_kept += (unsigned int)n;
+                // (staged as below, the survivor's id from the wavefront's own copy of the list: every lane takes part)
+                for (int i0 = 0; i0 < n * QUAD_STAGE_U4; i0 += TILE_PX) {
+                    const int i = i0 + tid, q = i / QUAD_STAGE_U4, piece = i - q * QUAD_STAGE_U4;
+                    const uint32_t id = (uint32_t)__builtin_amdgcn_ds_bpermute(q << 2, ids);
+                    if (i < n * QUAD_STAGE_U4) {
+                        const QuadRec *src = quads + id;
+                        uint4 val = reinterpret_cast<const uint4 *>(src)[piece];
+                        if (piece == 3) {
+                            const double a0 = f_plus_n * src->nz, b0 = two_nf * src->nz;
+                            val = make_uint4((uint32_t)__double2loint(a0), (uint32_t)__double2hiint(a0),
+                                             (uint32_t)__double2loint(b0), (uint32_t)__double2hiint(b0));
+                        } else if (piece >= 5 && (piece & 1) && !src->is_front) {
+                            val.y ^= 0x80000000u; val.w ^= 0x80000000u;
+                        }
+                        s_quad[i] = val;
+                        if (piece == 0) s_id[q] = id;
+                    }
+                }
+            } else {
+                if (qbase != q_begin) __syncthreads();    // the previous batch has been read
+                for (int i = tid; i < n * QUAD_STAGE_U4; i += TILE_PX) {
+                    const int q = i / QUAD_STAGE_U4, piece = i - q * QUAD_STAGE_U4;
+                    const uint32_t id = quad_items[qbase + q];
+                    const QuadRec *src = quads + id;
+                    uint4 val = reinterpret_cast<const uint4 *>(src)[piece];
+                    if (piece == 3) {
+                        const double a0 = f_plus_n * src->nz, b0 = two_nf * src->nz;
+                        val = make_uint4((uint32_t)__double2loint(a0), (uint32_t)__double2hiint(a0),
+                                         (uint32_t)__double2loint(b0), (uint32_t)__double2hiint(b0));
+                    } else if (piece >= 5 && (piece & 1) && !src->is_front) {
+                        val.y ^= 0x80000000u; val.w ^= 0x80000000u;
+                    } else if (ML && piece == 2) {
+                        val.w |= src->light << 1;               // beside is_front (0 / 1): the header's last 16 bytes are overwritten above
+                    }
+                    s_quad[i] = val;
+                    if (piece == 0) s_id[q] = id;
+                }
             }
             __syncthreads();
 
@@ -817,44 +869,23 @@ __device__ __forceinline__ void tile_body()
                     }
                 }
             }
-            // Depth verdicts for the whole strip.  The quad's plane depth is affine over the screen, so
-            // over the strip -t/nz is extreme at a corner, and linearize_z is monotone while its
-            // denominator stays positive: with 0 < den_lo <= den <= den_hi over the strip (bounds pushed
-            // outwards by a slack that dwarfs the rounding of the per-pixel expression and of the
-            // approximate reciprocal used here) the depth two_nf / den lies in [two_nf / den_hi,
-            // two_nf / den_lo], and comparisons against it are decided without dividing.
-            //   all pass: even the quad's least favourable depth passes against the least favourable
-            //             covered z of the strip (uncovered pixels pass anyway: their z is +-inf) ->
-            //             the per-pixel depth arithmetic is skipped, the verdict is the same;
-            //   none can: (only when the frame is all that is asked for, no MR_FRAME_COUNTERS: the
-            //             stencil matters where a triangle was drawn) even its most favourable depth
-            //             loses against the most favourable covered z -> the quad is skipped.
+            // Depth verdicts for the whole strip (quad_rect_bounds / quad_rect_sane / quad_rect_verdict, quad_reject.h): `all pass` skips
+            // the per-pixel depth arithmetic; `none can` (only when the frame is all that is asked for, no
+            // MR_FRAME_COUNTERS: the stencil matters where a triangle was drawn) skips the quad.
             bool q_allpass = false;
             if (!q_reject) {
                 const QuadHead &h = *reinterpret_cast<const QuadHead *>(s_quad + lane * QUAD_STAGE_U4);
                 const double xa = (double)gx, xb = (double)(gx + TILE_W - 1);
                 const double ya = (double)(gy + (tid / WAVE) * (WAVE / TILE_W)), yb = ya + (double)(WAVE / TILE_W - 1);
-                const double t00 = (h.nx * xa + h.ny * ya) + h.d, t10 = (h.nx * xb + h.ny * ya) + h.d;
-                const double t01 = (h.nx * xa + h.ny * yb) + h.d, t11 = (h.nx * xb + h.ny * yb) + h.d;
-                const double tmin = fmin(fmin(t00, t10), fmin(t01, t11)), tmax = fmax(fmax(t00, t10), fmax(t01, t11));
-                const double inz = approx_rcp(h.nz);
-                const double za = -tmin * inz, zb = -tmax * inz;
-                const double slack = 1e-12 * fmax(fabs(za), fabs(zb)) +
-                                     1e-15 * ((fabs(h.nx) * xb + fabs(h.ny) * yb) + fabs(h.d)) * fabs(inz);
-                const double zs_lo = fmin(za, zb) - slack, zs_hi = fmax(za, zb) + slack;
-                const double den_lo = f_plus_n - zs_hi * f_minus_n, den_hi = f_plus_n - zs_lo * f_minus_n;
+                const QuadRectBounds b = quad_rect_bounds(h.nx, h.ny, h.nz, h.d, xa, xb, ya, yb, f_plus_n, f_minus_n);
                 // (single light: three products of frame constants, worked out here per batch from copies the compiler
                 // cannot trace -- hoisted out of the batch loop they held six registers through the span walk)
                 double fpn = f_plus_n, tnf = two_nf;
                 if (!ML) asm volatile("" : "+v"(fpn), "+v"(tnf));
-                const bool sane = two_nf > 0 && f_minus_n > 0 && den_lo > 1e-9 * fpn && h.nz != 0 &&
-                                  fabs(inz) < 1e300 && den_hi < 1e300;
-                const double lo = tnf * (1.0 - 1e-12), hi = tnf * (1.0 + 1e-12);
-                // rh: a pixel passes when zbuf >= zq; lh: when zbuf <= zq
-                const bool none = rh ? lo > zlim * den_hi : hi < zlim * den_lo;
-                const bool all = rh ? hi <= zhard * den_lo : lo >= zhard * den_hi;
-                if (sane && !counters && none) q_reject = true;
-                q_allpass = sane && all;
+                const bool sane = quad_rect_sane(b, h.nz, f_minus_n, two_nf, fpn);
+                const QuadRectVerdict v = quad_rect_verdict(b, tnf, zlim, zhard, rh);
+                if (sane && !counters && v.none) q_reject = true;
+                q_allpass = sane && v.all;
             }
             unsigned long long todo = __ballot(!q_reject);
             const unsigned long long allpass = __ballot(q_allpass);
@@ -1017,7 +1048,7 @@ __device__ __forceinline__ void tile_body()
                 }
             }
         }
-        if (!ML && kernargs<TileKernArgs>().ta.quad_walk != QUAD_WALK_STRIPS) {
+        if (!ML && (!CULL || q_kept) && kernargs<TileKernArgs>().ta.quad_walk != QUAD_WALK_STRIPS) {
             __syncthreads();                              // every wavefront's spans are in
             sten += s_win[lp];
         }
@@ -1035,6 +1066,9 @@ __device__ __forceinline__ void tile_body()
         int l = lp;                                       // (frame-only: an untraceable copy like my_pixel's, or 4 * lp is held -- and spilled -- from phase 2 to here)
         if (!FULL) asm volatile("" : "+v"(l));
         mine[l] = sten;
+        // (CULL: the part's count of staged quads behind the stencil counts, handed over the same way)
+        uint32_t *kept = reinterpret_cast<uint32_t *>(ta.split_sten + (size_t)HEAVY0_MAX * HEAVY_SPLIT * TILE_PX) + (size_t)entry * HEAVY_SPLIT;
+        if (CULL && tid == 0) kept[part] = q_kept;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) {
@@ -1052,6 +1086,9 @@ __device__ __forceinline__ void tile_body()
         __syncthreads();
         for (int k = 0; k < n_parts; ++k)
             if (k != part) sten += ta.split_sten[((size_t)entry * HEAVY_SPLIT + k) * TILE_PX + l];
+        if (CULL)
+            for (int k = 0; k < n_parts; ++k)
+                if (k != part) q_kept += __atomic_load_n(&kept[k], __ATOMIC_RELAXED);
     }
     const unsigned long long t_quads = stamp();
 
@@ -1183,7 +1220,9 @@ __device__ __forceinline__ void tile_body()
     if (FULL && tid < TILE_STATS) rec[tid] = s_cnt[tid];
     if (tid == 0) {                                       // list lengths; timing for mr_debug_read_tile_records
         rec[5] = n_small_raw; rec[6] = n_big_raw; rec[7] = n_quad_raw;
-        if (!FULL) rec[8] = 0;                            // (the general kernel stored its first stamp when it took it)
+        // (frame-only: no stamp; with MR_QUAD_TILE_CULL=count the shadow quads the tile staged -- CULL, 0 elsewhere.  The general
+        // kernel stored its first stamp when it took it)
+        if (!FULL) rec[8] = (ta.quad_cull & 2u) ? q_kept : 0u;
         rec[9] = (uint32_t)stamp();
         rec[10] = (uint32_t)t_raster; rec[11] = (uint32_t)t_quads;
         if (n_small_raw > ta.cap[0]) { atomicOr(&ta.ctr->overflow, 1u); atomicMax(&ta.ctr->max_list[0], n_small_raw); }
